@@ -18,10 +18,21 @@ Prints ONE JSON line on rank 0.  `value` = reference-schedule GFLOP (SURVEY 8d: 
 BLAS calls the reference would issue for the iterations performed -- counted per logical operation
 at the library's entry points, dla_stats.ref_flops, so that a fused / pending / skipped sweep raises
 it; `value_launched` is the per-launch count of what the engine ran) / wall time of the solves,
-inputs resident in HBM.  `roofline` is the dominant kernel class measured with HIP events on the
-engine's stream during the timed region; `cpu_baseline` times the UNMODIFIED reference
-(oracle/_ref, flang+MKL) -- or the oracle's C port when that library cannot be loaded -- on this
-box's host cores on the same workload (one solve at n = 2e6 rows, about 10 s of CPU work).
+inputs resident in HBM.  `ms_per_step` = wall time of one timed solve.
+
+A plain run does only what that headline needs: set-up, --warmup solves, --steps timed solves, the
+line.  With --full it also records HIP events on the engine's stream during the first --event-steps
+timed steps and reports `roofline` (the dominant kernel class), `kernel_classes` / `kernels`, a stream
+triad, the residual check of the returned pairs, the seed-2 random-guess leg and `cpu_baseline`,
+which times the UNMODIFIED reference (oracle/_ref, flang+MKL) -- or the oracle's C port when that
+library cannot be loaded -- on the host cores on the same workload (one solve at n = 2e6 rows, about
+10 s of CPU work).
+
+--dump-outputs DIR writes what the last timed solve returned to its caller, in float64:
+DIR/eigenvalues.npy (all n_max values) and DIR/eigenvectors_sample.npy (the eigenvector block at a
+fixed, seeded sample of rows, ascending: np.random.default_rng(DUMP_SEED).choice(n, k, replace=False),
+k = min(n, DUMP_ROWS, what fits in DUMP_BYTES)).  The inputs depend on the arguments only, so two
+builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -59,6 +70,9 @@ import numpy as np  # noqa: E402
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 TB/s achievable)
 MFMA_F64_PEAK_TFLOPS = 78.6  # dense FP64 matrix peak (256 CUs x 4 SIMDs x one 16x16x4 MFMA = 2048 flop per 64 cycles
                              # at 2.4 GHz; tools/mfma_probe.hip measures the 64 cycles); balance = 9.8 flop per HBM byte
+DUMP_SEED = 20240607         # --dump-outputs: the row sample of the eigenvector block
+DUMP_ROWS = 1 << 16
+DUMP_BYTES = 48 << 20
 
 
 def shard_rows(n: int, nranks: int, rank: int):
@@ -67,6 +81,30 @@ def shard_rows(n: int, nranks: int, rank: int):
     r0 = min(n, rank * per)
     r1 = min(n, r0 + per)
     return r0, r1 - r0
+
+
+def dump_rows(n: int, n_max: int) -> np.ndarray:
+    """The global rows of the eigenvector block that --dump-outputs writes (ascending; a function of n and n_max only)."""
+    k = min(n, DUMP_ROWS, DUMP_BYTES // (8 * n_max))
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+
+
+def dump_outputs(dirname: str, eig: np.ndarray, x_loc: np.ndarray, n: int, row0: int, world: int, rank: int) -> None:
+    """Write what the last timed solve returned (eigenvalues + the sampled rows of the eigenvectors) under dirname on rank 0.
+    x_loc is this rank's shard of the eigenvector block (rows row0 .. row0 + len - 1)."""
+    rows = dump_rows(n, x_loc.shape[1])
+    mine = rows[(rows >= row0) & (rows < row0 + x_loc.shape[0])]
+    part = np.ascontiguousarray(x_loc[mine - row0, :], dtype=np.float64)
+    if world > 1:
+        import torch.distributed as dist
+        parts = [None] * world
+        dist.all_gather_object(parts, part)       # shards are contiguous and in rank order: the concatenation is ascending
+        part = np.concatenate(parts, axis=0)
+    if rank == 0:
+        assert part.shape[0] == rows.size, (part.shape, rows.size)
+        os.makedirs(dirname, exist_ok=True)
+        np.save(os.path.join(dirname, "eigenvalues.npy"), np.asarray(eig, dtype=np.float64))
+        np.save(os.path.join(dirname, "eigenvectors_sample.npy"), part)
 
 
 class _CaptureStdout:
@@ -163,6 +201,81 @@ def cpu_baseline(n_sample: int, n_targ: int, n_max: int, max_dav: int, tol: floa
     return res
 
 
+def full_figures(ctx, capi, args, main: dict, kst: dict, ev_stats: dict, stats: dict, ev_steps: int, dt: float,
+                 workload_key: str, world: int, rank: int, classes: list) -> dict:
+    """--full: roofline of the dominant kernel, per-class and per-kernel figures from the HIP events of the first
+    ev_steps timed steps, and a stream triad of its own."""
+    dom = max(main, key=lambda k: main[k]["ms"])
+    dk = main[dom]
+    cls_of = "gram" if dom.startswith("gram") else "ritz" if dom.startswith("ritz") else \
+             ("trmm" if re.match(r"gemm_kernel<\d+, \d+, 2,", dom) else "gemm")
+    # (kernel names carry every template argument, exactly as rocprofv3 prints them in profiles/r01/kernel_stats_*.csv)
+    kern = {c: {"launches": ev_stats[c]["launches"], "ms": round(ev_stats[c]["ms"], 3),
+                "GBps": round(ev_stats[c]["alg_bytes"] / max(ev_stats[c]["ms"], 1e-9) / 1e6, 1)}
+            for c in classes + ["matvec", "precnd"]}
+    per_kernel = {k: {"launches": v["launches"], "avg_us": round(v["ms"] / max(1, v["launches"]) * 1e3, 1),
+                      "GBps": round(v["alg_bytes"] / max(v["ms"], 1e-9) / 1e6, 1) if v["alg_bytes"] > 0 else None}
+                  for k, v in sorted(kst.items(), key=lambda kv: -kv[1]["ms"])[:10]}
+    ach = dk["alg_bytes"] / max(dk["ms"], 1e-9) / 1e6
+    # HBM bytes per launch from the PMC passes (tools/pmc_traffic.py): only a figure collected for THIS workload and THIS
+    # kernel symbol is quoted -- profiles/pmc_traffic.json is keyed by the workload string; anything else stays null
+    traffic = None
+    tfile = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+    traffic_source = None
+    if os.path.exists(tfile) and world == 1:      # the PMC passes were taken at N = 1 (whole problem on one GPU)
+        try:
+            tj = json.load(open(tfile))
+            traffic = tj.get(workload_key, {}).get(dom)
+            if traffic is not None:       # (a separate rocprofv3 --pmc pass of this workload, not a counter of THIS run)
+                traffic_source = "profiles/pmc_traffic.json (" + str(tj.get("_source", "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, tools/pmc_traffic.py")) + ")"
+        except Exception:
+            traffic = None
+    roofline = {"bound": "hbm", "kernel": dom, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                "launches": dk["launches"], "event_steps": ev_steps,
+                "avg_launch_ms": round(dk["ms"] / max(1, dk["launches"]), 4),
+                "alg_bytes_per_launch": round(dk["alg_bytes"] / max(1, dk["launches"]), 1)}
+    # the wide-block sweeps of the other BASELINE shapes (n_max = 37: 74 output columns in the Ritz + P sweep) do more than the
+    # machine balance of flops per byte: their roofline is the dense FP64 MFMA peak, not HBM
+    intensity = dk.get("flops", 0.0) / max(dk["alg_bytes"], 1.0)
+    roofline["flop_per_byte"] = round(intensity, 2)
+    if intensity > MFMA_F64_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9):
+        tf = dk["flops"] / max(dk["ms"], 1e-9) / 1e9
+        roofline.update({"bound": "mfma", "achieved": round(tf, 2), "peak": MFMA_F64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                         "frac": round(tf / MFMA_F64_PEAK_TFLOPS, 4), "hbm_GBps": round(ach, 1)})
+    # the north star's "ortho/matvec step": every O(n) launch of ortho_vs_x (Gram, projection update, triangular update,
+    # their reductions and k x k tail kernels, which move no panel bytes but take time) plus the operator; and the
+    # whole solve: all algorithmic bytes over the wall time of the solve, host work included
+    step_cls = ["gram", "gemm", "trmm", "matvec"]
+    step_b = sum(ev_stats[c]["alg_bytes"] for c in step_cls)
+    step_ms = sum(ev_stats[c]["ms"] for c in step_cls)
+    all_cls = classes + ["matvec", "precnd"]
+    all_b = sum(stats[c]["alg_bytes"] for c in all_cls) / args.steps
+    # ... and the same classes without the launches that move no panel bytes (reductions of per-block partials, the k x k
+    # steps of the device-driven chains, the cross-rank exchange): the rate of the sweeps themselves
+    small_ms = sum(v["ms"] for k, v in kst.items()
+                   if k.startswith(("gram_reduce_kernel", "ortho_tail_kernel", "ortho_tail16_kernel", "p2p_allreduce_kernel")))
+    roofline["step"] = {"what": "ortho/matvec step = classes " + "+".join(step_cls) + " (HIP-event time, reductions included)",
+                        "achieved": round(step_b / max(step_ms, 1e-9) / 1e6, 1),
+                        "frac": round(step_b / max(step_ms, 1e-9) / 1e6 / HBM_PEAK_GBS, 4),
+                        "sweeps_only": {"what": "the same without the reduction / k x k / exchange launches (no panel bytes)",
+                                        "ms_excluded": round(small_ms, 3),
+                                        "achieved": round(step_b / max(step_ms - small_ms, 1e-9) / 1e6, 1),
+                                        "frac": round(step_b / max(step_ms - small_ms, 1e-9) / 1e6 / HBM_PEAK_GBS, 4)}}
+    roofline["solve"] = {"what": "all algorithmic bytes of one solve / wall time of the solve",
+                         "alg_GB": round(all_b / 1e9, 2),
+                         "achieved": round(all_b / (dt / args.steps) / 1e9, 1),
+                         "frac": round(all_b / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 4)}
+    if rank == 0 and world == 1:
+        try:
+            triad = ctx.stream_triad(1 << 27, 5)    # 3 x 1 GiB, far beyond the 256 MiB Infinity Cache
+            roofline["triad_GBps"] = round(triad, 1)
+            roofline["frac_of_triad"] = round(ach / max(triad, 1e-9), 4)
+        except capi.DlaError:
+            roofline["triad_GBps"] = None
+    return {"roofline": roofline, "kernel_classes": kern, "kernels": per_kernel}
+
+
 def _launch_ranks(n_ranks: int) -> int:
     """`python bench.py --gpus N` started without a launcher: run the N ranks under torch.distributed.run as a child
     process of this one (which has initialised neither torch nor the GPU, and is never replaced by exec), pass the child's
@@ -212,7 +325,15 @@ def main() -> None:
                          "hipIpc (falls back to RCCL when the mailboxes cannot be shared) or RCCL all-reduce")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-n", type=int, default=2_000_000)
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel events, roofline, stream triad, residual check, random-guess leg and CPU "
+                         "baseline (a plain run times the headline solves only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the eigenvalues and a seeded row sample of the eigenvectors of the last timed step as "
+                         "DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -341,10 +462,11 @@ def main() -> None:
 
     for _ in range(args.warmup):
         solve()
-    # Kernel durations come from HIP events recorded on the engine's stream around every launch.  Each event is a
+    # Kernel durations (--full) come from HIP events recorded on the engine's stream around every launch.  Each event is a
     # barrier packet (about 3.6 us; ~500 of them per solve = 1.8 ms of a 20 ms solve, measured), so they are recorded
-    # during the first --event-steps timed steps only; the remaining timed steps run the same work without them.
-    ev_steps = 0 if os.environ.get("DIAGLIB_BENCH_NOPROFILE") else max(1, min(args.event_steps, args.steps))
+    # during the first --event-steps timed steps only; the remaining timed steps run the same work without them.  A plain
+    # run records none.
+    ev_steps = 0 if os.environ.get("DIAGLIB_BENCH_NOPROFILE") or not args.full else max(1, min(args.event_steps, args.steps))
     ctx.reset_stats()
     ctx.set_option(capi.OPT_PROFILE, 1 if ev_steps else 0)
     ev_stats, ctx_kernel_stats = None, {}
@@ -366,16 +488,24 @@ def main() -> None:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt[0])
 
-    # ---- residual check of the returned pairs: ||A x - lambda x||_2 / |lambda| (north star <= 1e-10)
-    ax = ctx.panel(n_loc, n_max)
-    ctx.synth_matvec(ev, ax)
-    x_h, ax_h = ev.download(), ax.download()
-    r2 = ((ax_h - x_h * eig[None, :]) ** 2).sum(0)
-    if world > 1:
-        rt = torch.from_numpy(r2.copy())
-        dist.all_reduce(rt)
-        r2 = rt.numpy()
-    rel_res = float((np.sqrt(r2[:n_targ]) / np.abs(eig[:n_targ])).max())
+    # ---- what the last timed step returned (eig, and the eigenvector block ev still holds)
+    x_h = ev.download() if (args.full or args.dump_outputs) else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eig, x_h, n, row0, world, rank)
+
+    ax, rel_res = None, None
+    if args.full:
+        # ---- residual check of the returned pairs: ||A x - lambda x||_2 / |lambda| (north star <= 1e-10)
+        ax = ctx.panel(n_loc, n_max)
+        ctx.synth_matvec(ev, ax)
+        ax_h = ax.download()
+        r2 = ((ax_h - x_h * eig[None, :]) ** 2).sum(0)
+        if world > 1:
+            rt = torch.from_numpy(r2.copy())
+            dist.all_reduce(rt)
+            r2 = rt.numpy()
+        rel_res = float((np.sqrt(r2[:n_targ]) / np.abs(eig[:n_targ])).max())
+    x_h = None
 
     rows_per_rank = [n_loc]
     if world > 1:
@@ -393,7 +523,7 @@ def main() -> None:
     kst = ctx_kernel_stats
     # dominant kernel = the single kernel symbol with the largest HIP-event time in the timed region
     main = {k: v for k, v in kst.items() if v["alg_bytes"] > 0 and v["ms"] > 0}
-    if not main:                                    # DIAGLIB_BENCH_NOPROFILE: wall time only
+    if os.environ.get("DIAGLIB_BENCH_NOPROFILE") or (args.full and not main):     # wall time only
         if rank == 0:
             print(json.dumps({"ms_per_step": round(dt / args.steps * 1e3, 3), "value": round(value, 2), "n_gpus": world,
                               "iters": info["iters"], "allreduces": stats["allreduces"], "host_syncs": stats["host_syncs"],
@@ -402,74 +532,6 @@ def main() -> None:
         if os.environ.get("DIAGLIB_AMD_HOSTTIME") and world == 1:
             ctx.destroy()                # prints the host time spent inside every entry point
         return
-    dom = max(main, key=lambda k: main[k]["ms"])
-    dk = main[dom]
-    cls_of = "gram" if dom.startswith("gram") else "ritz" if dom.startswith("ritz") else \
-             ("trmm" if re.match(r"gemm_kernel<\d+, \d+, 2,", dom) else "gemm")
-    # (kernel names carry every template argument, exactly as rocprofv3 prints them in profiles/r01/kernel_stats_*.csv)
-    kern = {c: {"launches": ev_stats[c]["launches"], "ms": round(ev_stats[c]["ms"], 3),
-                "GBps": round(ev_stats[c]["alg_bytes"] / max(ev_stats[c]["ms"], 1e-9) / 1e6, 1)}
-            for c in classes + ["matvec", "precnd"]}
-    per_kernel = {k: {"launches": v["launches"], "avg_us": round(v["ms"] / max(1, v["launches"]) * 1e3, 1),
-                      "GBps": round(v["alg_bytes"] / max(v["ms"], 1e-9) / 1e6, 1) if v["alg_bytes"] > 0 else None}
-                  for k, v in sorted(kst.items(), key=lambda kv: -kv[1]["ms"])[:10]}
-    ach = dk["alg_bytes"] / max(dk["ms"], 1e-9) / 1e6
-    # HBM bytes per launch from the PMC passes (tools/pmc_traffic.py): only a figure collected for THIS workload and THIS
-    # kernel symbol is quoted -- profiles/pmc_traffic.json is keyed by the workload string; anything else stays null
-    traffic = None
-    tfile = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    traffic_source = None
-    if os.path.exists(tfile) and world == 1:      # the PMC passes were taken at N = 1 (whole problem on one GPU)
-        try:
-            tj = json.load(open(tfile))
-            traffic = tj.get(workload_key, {}).get(dom)
-            if traffic is not None:       # (a separate rocprofv3 --pmc pass of this workload, not a counter of THIS run)
-                traffic_source = "profiles/pmc_traffic.json (" + str(tj.get("_source", "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, tools/pmc_traffic.py")) + ")"
-        except Exception:
-            traffic = None
-    roofline = {"bound": "hbm", "kernel": dom, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                "launches": dk["launches"], "event_steps": ev_steps,
-                "avg_launch_ms": round(dk["ms"] / max(1, dk["launches"]), 4),
-                "alg_bytes_per_launch": round(dk["alg_bytes"] / max(1, dk["launches"]), 1)}
-    # the wide-block sweeps of the other BASELINE shapes (n_max = 37: 74 output columns in the Ritz + P sweep) do more than the
-    # machine balance of flops per byte: their roofline is the dense FP64 MFMA peak, not HBM
-    intensity = dk.get("flops", 0.0) / max(dk["alg_bytes"], 1.0)
-    roofline["flop_per_byte"] = round(intensity, 2)
-    if intensity > MFMA_F64_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9):
-        tf = dk["flops"] / max(dk["ms"], 1e-9) / 1e9
-        roofline.update({"bound": "mfma", "achieved": round(tf, 2), "peak": MFMA_F64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(tf / MFMA_F64_PEAK_TFLOPS, 4), "hbm_GBps": round(ach, 1)})
-    # the north star's "ortho/matvec step": every O(n) launch of ortho_vs_x (Gram, projection update, triangular update,
-    # their reductions and k x k tail kernels, which move no panel bytes but take time) plus the operator; and the
-    # whole solve: all algorithmic bytes over the wall time of the solve, host work included
-    step_cls = ["gram", "gemm", "trmm", "matvec"]
-    step_b = sum(ev_stats[c]["alg_bytes"] for c in step_cls)
-    step_ms = sum(ev_stats[c]["ms"] for c in step_cls)
-    all_cls = classes + ["matvec", "precnd"]
-    all_b = sum(stats[c]["alg_bytes"] for c in all_cls) / args.steps
-    # ... and the same classes without the launches that move no panel bytes (reductions of per-block partials, the k x k
-    # steps of the device-driven chains, the cross-rank exchange): the rate of the sweeps themselves
-    small_ms = sum(v["ms"] for k, v in kst.items()
-                   if k.startswith(("gram_reduce_kernel", "ortho_tail_kernel", "ortho_tail16_kernel", "p2p_allreduce_kernel")))
-    roofline["step"] = {"what": "ortho/matvec step = classes " + "+".join(step_cls) + " (HIP-event time, reductions included)",
-                        "achieved": round(step_b / max(step_ms, 1e-9) / 1e6, 1),
-                        "frac": round(step_b / max(step_ms, 1e-9) / 1e6 / HBM_PEAK_GBS, 4),
-                        "sweeps_only": {"what": "the same without the reduction / k x k / exchange launches (no panel bytes)",
-                                        "ms_excluded": round(small_ms, 3),
-                                        "achieved": round(step_b / max(step_ms - small_ms, 1e-9) / 1e6, 1),
-                                        "frac": round(step_b / max(step_ms - small_ms, 1e-9) / 1e6 / HBM_PEAK_GBS, 4)}}
-    roofline["solve"] = {"what": "all algorithmic bytes of one solve / wall time of the solve",
-                         "alg_GB": round(all_b / 1e9, 2),
-                         "achieved": round(all_b / (dt / args.steps) / 1e9, 1),
-                         "frac": round(all_b / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 4)}
-    if rank == 0 and world == 1:
-        try:
-            triad = ctx.stream_triad(1 << 27, 5)    # 3 x 1 GiB, far beyond the 256 MiB Infinity Cache
-            roofline["triad_GBps"] = round(triad, 1)
-            roofline["frac_of_triad"] = round(ach / max(triad, 1e-9), 4)
-        except capi.DlaError:
-            roofline["triad_GBps"] = None
 
     out = {
         "metric": "eigensolver GFLOP/s + iters-to-converge, n=2e6 m=8 Davidson, 1/2/4/8 GPU",
@@ -481,17 +543,16 @@ def main() -> None:
                                f"operator=diag(i+1)+0.5*W*W^T(rank 4) guess={args.guess} callbacks=device",
                    "workload_key": workload_key,
                    "iters": info["iters"], "matvec_cols": info["matvec_cols"], "restarts": info["restarts"],
-                   "converged": bool(ok), "max_rel_residual": rel_res, "rows_per_gpu": n_loc,
+                   "converged": bool(ok), **({"max_rel_residual": rel_res} if args.full else {}), "rows_per_gpu": n_loc,
                    "eig": [round(float(e), 9) for e in eig[:n_targ]]},
-        "roofline": roofline,
-        "kernel_classes": kern,
-        "kernels": per_kernel,
-        "host": {"allreduces": stats["allreduces"], "host_syncs": stats["host_syncs"], "nproc": HOST_CPUS,
-                 "allreduce_transport": (transport if world > 1 and not rehearsal else ("gloo hook (rehearsal)" if rehearsal else None)),
-                 "p2p_selftest": p2p_selftest, "rows_per_rank": rows_per_rank,
-                 "usable_cpus": CPU_THREADS},
     }
-    if args.guess == "unit" and not args.no_random_leg:
+    if args.full:
+        out.update(full_figures(ctx, capi, args, main, kst, ev_stats, stats, ev_steps, dt, workload_key, world, rank, classes))
+    out["host"] = {"allreduces": stats["allreduces"], "host_syncs": stats["host_syncs"], "nproc": HOST_CPUS,
+                   "allreduce_transport": (transport if world > 1 and not rehearsal else ("gloo hook (rehearsal)" if rehearsal else None)),
+                   "p2p_selftest": p2p_selftest, "rows_per_rank": rows_per_rank,
+                   "usable_cpus": CPU_THREADS}
+    if args.full and args.guess == "unit" and not args.no_random_leg:
         # second leg (SURVEY 8d guess (b)): the seed-2 random guess confined to the leading rows -- the run that restarts
         # and locks roots one by one.  Timed on its own (outside the K timed steps), reported beside the headline.
         args.guess = "seed2"
@@ -519,7 +580,7 @@ def main() -> None:
             "max_rel_residual": float((np.sqrt(r2[:n_targ]) / np.abs(eig2[:n_targ])).max()),
             "max_eig_diff_vs_unit_guess": float(np.abs(eig2[:n_targ] - eig[:n_targ]).max())}
         args.guess = "unit"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample_n, n_targ, n_max, args.max_dav, args.tol,
                                                flops_total / args.steps / n)
@@ -535,7 +596,8 @@ def main() -> None:
         dist.destroy_process_group()
     if os.environ.get("DIAGLIB_AMD_HOSTTIME"):
         for p_ in (ax, ev, g_dev):
-            p_.free()
+            if p_ is not None:
+                p_.free()
         ctx.destroy()                    # prints the engine's host-wait totals
 
 

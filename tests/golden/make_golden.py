@@ -27,6 +27,17 @@ import numpy as np  # noqa: E402
 ROW = re.compile(r"^\s+(\d+)\s+(\d+)\s+(-?\d+\.\d+)\s+([0-9.DE+-]+)\s+([0-9.DE+-]+)\s+([TF])\s*$")
 
 
+
+def save_npz_lzma(path, **arrays):
+    """np.savez with LZMA-compressed members: np.load reads it like any .npz, and reference_fixtures.npz stays under the 1 MiB
+    limit of a committed file (deflate leaves it above)."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            z.writestr(k + ".npy", buf.getvalue())
+
 def fnum(s):
     return float(s.replace("D", "E"))
 
@@ -193,7 +204,7 @@ def main():
     out["driver_specs"] = json.dumps(drv)
     out["provenance"] = ("reference: Molecolab-Pisa/diaglib @ /root/reference (unmodified), flang 22 (ROCm 7.2) -O2 -fopenmp, "
                          "MKL LP64 /opt/conda/lib (mkl_gf_lp64 + mkl_gnu_thread + mkl_core), 8 threads")
-    np.savez_compressed(os.path.join(HERE, "reference_fixtures.npz"), **out)
+    save_npz_lzma(os.path.join(HERE, "reference_fixtures.npz"), **out)
     for f in os.listdir(tmp):
         os.remove(os.path.join(tmp, f))
     os.rmdir(tmp)

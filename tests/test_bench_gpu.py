@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -37,7 +38,7 @@ def _check(d: dict, n_gpus: int, steps: int, warmup: int, n: int) -> None:
 
 def test_bench_one_gpu_small():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "200000", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-random-leg"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--no-random-leg"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     d = _line(p.stdout)
     _check(d, 1, 2, 1, 200000)
@@ -66,7 +67,7 @@ def test_bench_two_ranks_started_without_a_launcher():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n", "200000", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-random-leg"],
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-random-leg"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     d = _line(p.stdout)
@@ -105,8 +106,8 @@ def test_headline_line_finds_its_counters():
     """On the headline workload the dominant kernel's HBM traffic must come from profiles/pmc_traffic.json: the file is keyed by
     workload and by the kernel name with every template argument, so a kernel whose template list changed without a new PMC
     pass shows up here as traffic = null."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-random-leg"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full",
+                        "--no-cpu-baseline", "--no-random-leg"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     d = _line(p.stdout)
     _check(d, 1, 2, 1, 2000000)
@@ -169,3 +170,60 @@ def test_bench_four_ranks_full_row_count_with_a_short_last_shard():
     rows = d["rows_per_rank"]
     assert sum(rows) == n and rows[:3] == [500032] * 3 and rows[3] == n - 3 * 500032
     assert d["iters"] in (9, 10) and d["allreduces"] > 0    # the 1-rank headline solve takes 9 (BENCH_r05); summation order differs
+
+
+def test_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line without the figures that take events or runs of their own, runs exactly
+    --steps timed solves, and --dump-outputs writes what the last of them returned; the inputs depend on the arguments only, so a
+    second run with another step count returns the same outputs (repeated solves are bit-identical)."""
+    n = 200000
+    lines, dumps = [], []
+    for steps, tag in ((3, "a"), (2, "b")):
+        out = tmp_path / tag
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--n", str(n), "--steps", str(steps),
+                            "--warmup", "1", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-3000:]
+        d = _line(p.stdout)
+        base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+        assert d["metric"] == base["metric"] and d["unit"] == "GFLOP/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert d["steps"] == steps and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["value"] * d["ms_per_step"] == pytest.approx(d["gflop_per_solve"] * 1e3, rel=1e-3)
+        assert not {"roofline", "kernel_classes", "kernels", "cpu_baseline"} & set(d)
+        cfg = d["config"]
+        assert cfg["converged"] is True and cfg["iters"] > 0 and "random_guess_leg" not in cfg
+        files = {f.name: f for f in out.iterdir()}
+        assert set(files) == {"eigenvalues.npy", "eigenvectors_sample.npy"}
+        assert sum(f.stat().st_size for f in files.values()) <= 64 << 20
+        eig, vec = np.load(files["eigenvalues.npy"]), np.load(files["eigenvectors_sample.npy"])
+        n_max = min(2 * 8, 8 + 5)
+        assert eig.dtype == np.float64 and eig.shape == (n_max,)
+        assert vec.dtype == np.float64 and vec.shape == (min(n, 1 << 16), n_max) and np.isfinite(vec).all()
+        assert np.allclose(eig[:8], cfg["eig"], rtol=0, atol=1e-8)
+        lines.append(d)
+        dumps.append((eig, vec))
+    # the flops of the timed region are counted solve by solve: per step they agree only if each run timed --steps solves
+    assert lines[0]["config"]["iters"] == lines[1]["config"]["iters"]
+    assert lines[0]["gflop_per_solve"] == pytest.approx(lines[1]["gflop_per_solve"], rel=1e-4)
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
+
+
+def test_two_ranks_dump_the_sampled_rows_of_every_shard(tmp_path):
+    """--dump-outputs of a 2-rank run: rank 0 writes the same row sample a 1-rank run writes, gathered from both shards; the
+    converged pairs agree with the 1-rank run's (the cross-rank sums are added in another order)."""
+    n, t = 200000, 8
+    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", str(n), "--steps", "1", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "one")], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert one.returncode == 0, one.stderr[-3000:]
+    env = dict(os.environ, DIAGLIB_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
+                          "127.0.0.1", "--master-port", "29553", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", str(n),
+                          "--steps", "1", "--warmup", "1", "--dump-outputs", str(tmp_path / "two")],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+    assert two.returncode == 0, two.stderr[-3000:]
+    assert _line(two.stdout)["n_gpus"] == 2
+    e1, v1 = np.load(tmp_path / "one" / "eigenvalues.npy"), np.load(tmp_path / "one" / "eigenvectors_sample.npy")
+    e2, v2 = np.load(tmp_path / "two" / "eigenvalues.npy"), np.load(tmp_path / "two" / "eigenvectors_sample.npy")
+    assert v1.shape == v2.shape and e1.shape == e2.shape
+    assert np.allclose(e1[:t], e2[:t], rtol=1e-11, atol=0)
+    sgn = np.sign((v1[:, :t] * v2[:, :t]).sum(0))
+    assert np.abs(v1[:, :t] - v2[:, :t] * sgn).max() < 1e-7

@@ -77,13 +77,13 @@ if [[ $PART == *D* ]]; then
 # projected block's Gram matrix), 15 (the same with the first factor from U^T U), 14 (dla_expand_project mode 5 behaves like mode 4: the
 # round's earlier state, tight bounds on what stays pending), 12 (five-sweep schedule) -- headline + random-guess leg, LOBPCG cfg 3, cfg 5 shape
 for r in 1 2 3; do for t in 0 15 14 12; do
-  DIAGLIB_BENCH_TUNE="6=$t" python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('davidson n=2e6 8 roots  knob6=$t:', d['ms_per_step'], 'ms,', d['config']['iters'], 'iterations,', d['roofline']['solve']['alg_GB'], 'GB, step', d['roofline']['step']['frac'], '| random-guess leg', d['config']['random_guess_leg']['ms'], 'ms,', d['config']['random_guess_leg']['iters'], 'iterations')"
+  DIAGLIB_BENCH_TUNE="6=$t" python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('davidson n=2e6 8 roots  knob6=$t:', d['ms_per_step'], 'ms,', d['config']['iters'], 'iterations,', d['roofline']['solve']['alg_GB'], 'GB, step', d['roofline']['step']['frac'], '| random-guess leg', d['config']['random_guess_leg']['ms'], 'ms,', d['config']['random_guess_leg']['iters'], 'iterations')"
 done; done > $OUT/schedule_ab.txt 2>&1 || true
 for r in 1 2; do for t in 0 15 12; do
-  DIAGLIB_BENCH_TUNE="6=$t" python3 bench.py --solver lobpcg --steps 10 --warmup 3 --no-cpu-baseline --no-random-leg 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('lobpcg n=2e6 8 roots    knob6=$t:', d['ms_per_step'], 'ms,', d['config']['iters'], 'iterations,', d['roofline']['solve']['alg_GB'], 'GB')"
+  DIAGLIB_BENCH_TUNE="6=$t" python3 bench.py --solver lobpcg --steps 10 --warmup 3 --full --no-cpu-baseline --no-random-leg 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('lobpcg n=2e6 8 roots    knob6=$t:', d['ms_per_step'], 'ms,', d['config']['iters'], 'iterations,', d['roofline']['solve']['alg_GB'], 'GB')"
 done; done >> $OUT/schedule_ab.txt 2>&1 || true
 for r in 1 2; do for t in 0 12; do
-  DIAGLIB_BENCH_TUNE="6=$t" python3 bench.py --solver lobpcg --n 10000000 --roots 32 --tol 1e-12 --steps 3 --warmup 1 --no-cpu-baseline --no-random-leg 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('lobpcg n=1e7 32 roots   knob6=$t:', d['ms_per_step'], 'ms,', d['config']['iters'], 'iterations,', d['roofline']['solve']['alg_GB'], 'GB')"
+  DIAGLIB_BENCH_TUNE="6=$t" python3 bench.py --solver lobpcg --n 10000000 --roots 32 --tol 1e-12 --steps 3 --warmup 1 --full --no-cpu-baseline --no-random-leg 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('lobpcg n=1e7 32 roots   knob6=$t:', d['ms_per_step'], 'ms,', d['config']['iters'], 'iterations,', d['roofline']['solve']['alg_GB'], 'GB')"
 done; done >> $OUT/schedule_ab.txt 2>&1 || true
 python3 tools/solve_jitter.py 30 > $OUT/solve_jitter.txt 2>/dev/null || true
 python3 tools/solve_jitter.py 30 14 >> $OUT/solve_jitter.txt 2>/dev/null || true

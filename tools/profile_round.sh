@@ -11,7 +11,7 @@ OUT=gpurun_out/profile_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 B="python3 bench.py $EXTRA"
-$B > $OUT/bench_default.json 2> $OUT/bench_default.err
+$B --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 echo "bench done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o run -- $B --steps 5 --warmup 1 --no-cpu-baseline --no-random-leg > $OUT/kt.log 2>&1
 echo "kernel trace done"

@@ -20,6 +20,66 @@ struct OrthoReport {
   int clean = 1;        // ortho_chain_finish: 1 when the launches enqueued by ortho_chain_begin were the whole chain
 };
 
+// What the caller of an orthogonalisation wants from the chain.  One value, held in BlockOps::policy and installed for the length of
+// a call by PolicyScope below; one named constructor per treatment that exists.
+struct ChainPolicy {
+  // set by a caller that B-orthonormalises the block by Cholesky-QR right behind ortho_vs_x (dla_expand_project_metric): a device
+  // chain may then end without applying its last pending triangular factor (OrthoTailArgs::drop_final in hip_engine.hip)
+  bool drop_final = false;
+  // ... and with publish_pending the chain hands what it left undone to the host instead (BlockOps::pending_block): for a caller that
+  // folds it into its small matrices and coefficient blocks (dla_expand_project modes 3 and 4)
+  bool publish_pending = false;
+  // basis_exact (dla_expand_project mode 5): the stored columns X are not a finished basis but X D is, with the caller's upper-
+  // triangular D kept on the device block by block (BlockOps::basis_sync).  Device chains then project with X (D D^T) X^T, and a block
+  // may stay pending however far the stored columns are from orthonormal.
+  bool basis_exact = false;
+  // the device-driven chain must not take the next calls: the host-driven loop runs (dla_expand_project mode 5 on a shape the device
+  // cannot project exactly, mode 6)
+  bool chain_off = false;
+  double drop_tol = 0.0;      // > 0: the block stays pending only when the closing pass found max |U^T U - I| below it
+  double drop_stol = 1.0e-4;  // ... and max |X^T U| of the stored block below this (three-pass schedule)
+
+  // the intents the engine and the host-driven loop ask about:
+  // the caller takes the closing block on its small matrices without a bound on the factor (mode 3, exact mode 5)
+  bool rebuilt() const { return drop_final && publish_pending && drop_tol <= 0.0; }
+  // what the chain leaves undone goes to pending_block
+  bool publishes() const { return drop_final && publish_pending; }
+  // the block stays in a basis that is orthonormal to drop_tol per block only (mode 4)
+  bool tight() const { return drop_final && drop_tol > 0.0; }
+
+  // default: the chain applies everything to the block in memory
+  static ChainPolicy finish() { return ChainPolicy(); }
+  // dla_expand_project_metric: b_ortho follows b_ortho_vs_x at once (reference :2170 / :2185, :523-529): its Cholesky-QR gives the same
+  // block whether the chain's last pending factor -- upper triangular, positive diagonal -- has been applied or not, so the chain may
+  // end without the sweep U <- U W (the host-driven loop has nothing pending and is not affected)
+  static ChainPolicy metric_drop() { ChainPolicy p; p.drop_final = true; return p; }
+  // mode 3 = mode 1 for a block that is used once and rebuilt (LOBPCG's W, reference diaglib.f90:518-529, 394-403): what the chain
+  // left undone -- its last triangular factor T (near the identity) and, with the three-pass schedule, the closing projection E --
+  // is not applied to the block; the projection of the stored blocks is corrected on the host, H <- D^T H D with D = [I E ; 0 T], and
+  // the caller folds D into every coefficient block it multiplies the panel with (dla_pending_block): the closing sweeps are never run
+  static ChainPolicy rebuild() { ChainPolicy p; p.drop_final = true; p.publish_pending = true; return p; }
+  // mode 4 = mode 0 for a block that STAYS in the basis (Davidson, reference diaglib.f90:1790 + 1685 + 1691): what the chain
+  // left undone stays pending only when the closing pass found the block orthonormal to 1e-8 -- later blocks are projected
+  // against the stored block as if it were orthonormal, twice, the second time on a measured product.  h_host comes back RAW,
+  // for the stored block: the caller keeps the pending blocks of its whole basis (an upper-triangular D, dla_basis_admit) and
+  // multiplies the rows of its coefficient blocks by D before any product with the panel (dla_basis_fold)
+  // (1e-8 / 1e-9: a later block's first projection against the stored columns leaves that share of what it removes, and the block
+  //  that comes out of it can be as ill-conditioned as 1e7 -- the leftover must stay below its smallest directions)
+  // exact: mode 5 = mode 4 with the caller's pending blocks kept on the device as well (dla_basis_sync after every block): the chain's
+  // projections are exact against the FINISHED basis X D, so what a block leaves pending is bounded only by what keeps the host
+  // algebra well conditioned (max |S| < 0.05, Gram matrix factorable in one step) -- not by what later projections could absorb
+  static ChainPolicy stay(bool exact)
+  {
+    ChainPolicy p = rebuild();
+    p.drop_tol = exact ? 0.0 : 1.0e-8; p.drop_stol = exact ? 5.0e-2 : 1.0e-9; p.basis_exact = exact;
+    return p;
+  }
+  // mode 6, and mode 5 where the device cannot project with a D that is not the identity: the block is finished in memory by the
+  // host-driven loop, which multiplies every X^T U with D D^T (BlockOps::basis_dd) -- exact against the finished basis X D, nothing
+  // stays pending
+  static ChainPolicy host_loop_exact() { ChainPolicy p; p.basis_exact = true; p.chain_off = true; return p; }
+};
+
 // The block operations the orthogonalisation control flow (ortho_cd / ortho_vs_x / ortho in host_logic.cpp) is written
 // over.  The device engine implements them on n-length panels in HBM; get_coeffs runs the same control flow on
 // host-size coefficient blocks through a plain-loop implementation (CoeffOps in host_logic.cpp) -- it implements these
@@ -75,16 +135,10 @@ struct BlockOps {
     }
     return 0;
   }
-  // set by a caller that B-orthonormalises the block by Cholesky-QR right behind ortho_vs_x (dla_expand_project_metric): a device
-  // chain may then end without applying its last pending triangular factor (OrthoTailArgs::drop_final in hip_engine.hip)
-  bool drop_final = false;
-  // ... and with publish_pending the chain hands what it left undone to the host instead (pending_block): for a caller that folds it
-  // into its small matrices and coefficient blocks (dla_expand_project modes 3 and 4).  p = [E ; T] is (m + k) x k: the finished
-  // block is [X | U_stored] p -- T the upper-triangular factor that was not applied, E the closing projection that was not run
-  // (only the three-pass schedule of the device chain leaves one).  Default: [0 ; I] (nothing is ever pending in the host-driven loops).
-  bool publish_pending = false;
-  double drop_final_tol = 0.0;     // > 0: the block stays pending only when the closing pass found max |U^T U - I| below it
-  double drop_final_stol = 1.0e-4; // ... and max |X^T U| of the stored block below this (three-pass schedule)
+  ChainPolicy policy = ChainPolicy::finish();   // what the current caller wants from a chain (PolicyScope)
+  // The block a chain with policy.publishes() left pending.  p = [E ; T] is (m + k) x k: the finished block is [X | U_stored] p -- T the
+  // upper-triangular factor that was not applied, E the closing projection that was not run (only the three-pass schedule of the
+  // device chain leaves one).  Default: [0 ; I] (nothing is ever pending in the host-driven loops).
   // *applied = 1: the chain's closing sweep HAS applied p to the block in memory (it ran without measuring anything): the block in
   // memory is [X | U_measured] p, and what the caller still owes it is the k x k factor of its Gram matrix I - E^T E
   virtual int pending_block(int m, int k, double* p, int ldp, int* applied)
@@ -94,13 +148,10 @@ struct BlockOps {
     if (applied) *applied = 0;
     return 0;
   }
-  // basis_exact (dla_expand_project mode 5): the stored columns X are not a finished basis but X D is, with the caller's upper-
-  // triangular D kept on the device block by block (basis_sync; m = columns in front of the block, k <= 0: forget everything).
-  // Device chains then project with X (D D^T) X^T, and a block may stay pending however far the stored columns are from orthonormal.
-  bool basis_exact = false;
+  // policy.basis_exact: the caller's upper-triangular D, block by block (m = columns in front of the block, k <= 0: forget everything)
   virtual int basis_sync(int /*m*/, int /*k*/, const double* /*dmat*/, int /*ld*/) { return 0; }
   virtual bool basis_exact_ok() const { return false; }   // the device-driven chain takes one-tile blocks on this context
-  // xu <- D D^T xu (m x k, leading dimension ld) while basis_exact is set: what the host-driven loop multiplies X^T U with before a
+  // xu <- D D^T xu (m x k, leading dimension ld) while policy.basis_exact is set: what the host-driven loop multiplies X^T U with before a
   // projection, so that it projects with X (D D^T) X^T as the device chain does (a chain that stopped half way -- ortho_cd out of
   // iterations, Householder fallback -- is continued there)
   virtual int basis_dd(int /*m*/, int /*k*/, double* /*xu*/, int /*ld*/) { return 0; }
@@ -111,11 +162,17 @@ struct BlockOps {
   virtual int basis_state(int /*m*/) const { return 0; }
   // basis columns (block included) up to which the device-driven chain can project with the caller's D (0: not at all)
   virtual int basis_capacity() const { return 0; }
-  // the device-driven chain must not take the next calls: the host-driven loop runs (dla_expand_project mode 5 on a shape the device
-  // cannot project exactly, mode 6)
-  bool chain_off = false;
   int ortho_maxit = 10;      // maxit of ortho_cd / ortho_vs_x (diaglib.f90:3224,3521); DLA_OPT_ORTHO_MAXIT lowers it in tests
   std::string err;
+};
+
+// installs a policy for the length of a call and puts back what was there before
+struct PolicyScope {
+  BlockOps* o; ChainPolicy saved;
+  PolicyScope(BlockOps* o_, const ChainPolicy& p) : o(o_), saved(o_->policy) { o->policy = p; }
+  ~PolicyScope() { o->policy = saved; }
+  PolicyScope(const PolicyScope&) = delete;
+  PolicyScope& operator=(const PolicyScope&) = delete;
 };
 
 // What the host logic needs from a device.  All panel pointers are device addresses,

@@ -4439,13 +4439,13 @@ struct HipEngine : dla::Engine {
     //  but such a block's weakest columns then depend on the schedule, and the reference's dense test matrix with unit guesses takes
     //  another history (tests/test_trace_text.py::dav_n1000_unit fails with it, also when only the drivers' chains use it): not shipped)
     pending_tail.gp = tune[6] == 15 ? 0 : tune[6] == 16 ? 2 : 1;
-    pending_tail.dmat = (basis_exact && fold && m > 0 && dmat_nontrivial && dmat_cols == m && m <= DMAT_LD) ? d_dmat : nullptr;
+    pending_tail.dmat = (policy.basis_exact && fold && m > 0 && dmat_nontrivial && dmat_cols == m && m <= DMAT_LD) ? d_dmat : nullptr;
     pending_tail.dmat_ld = DMAT_LD;
-    pending_tail.drop_final = (drop_final && m > 0) ? 1 : 0;
-    pending_tail.t_host = (pending_tail.drop_final && publish_pending && m + k <= PEND_ROWS) ? h_tpend_dev : nullptr;
+    pending_tail.drop_final = (policy.drop_final && m > 0) ? 1 : 0;
+    pending_tail.t_host = (pending_tail.drop_final && policy.publish_pending && m + k <= PEND_ROWS) ? h_tpend_dev : nullptr;
     pending_tail.t_seq = t_seq;
-    pending_tail.drop_tol = drop_final_tol;
-    pending_tail.drop_stol = drop_final_stol;
+    pending_tail.drop_tol = policy.drop_tol;
+    pending_tail.drop_stol = policy.drop_stol;
     fuse_tail = p2p.on ? tune[6] != 4 : (nranks <= 1 && !comm);     // (knob 6 = 4: the exchange as a launch of its own)
     tail_fused = false;
     pred_phase = &d_ost->phase;
@@ -4631,7 +4631,7 @@ struct HipEngine : dla::Engine {
   bool basis_exact_ok() const override { return !hook && !local_only && tune[6] != 3 && tune[6] != 5 && tune[6] != 14 && lds_limit > (size_t)128 * 1024; }   // (knob 6 = 14: A/B, mode 5 behaves like mode 4)
   int basis_dd(int m, int k, double* xu, int ld) override
   {
-    if (!basis_exact || m <= 0) return DLA_OK;
+    if (!policy.basis_exact || m <= 0) return DLA_OK;
     if (dmat_cols != m) { err = "ortho_vs_x: the copy of the caller's pending blocks does not describe this basis (dla_basis_sync after every block)"; return DLA_ERR_ARG; }
     if (!dmat_nontrivial) return DLA_OK;
     std::vector<double> y(m);
@@ -4685,7 +4685,7 @@ struct HipEngine : dla::Engine {
     return stage_commit(slot, bytes, d_dmat + (size_t)m * DMAT_LD);
   }
 
-  // the block the last chain left pending (drop_final + publish_pending): p = [E ; T], (m + k) x k -- the finished block is
+  // the block the last chain left pending (policy.publishes()): p = [E ; T], (m + k) x k -- the finished block is
   // [X | U_stored] p -- or [0 ; I] when nothing is pending; fetching it clears it
   int pending_block(int m, int k, double* p, int ldp, int* applied) override
   {
@@ -4716,14 +4716,14 @@ struct HipEngine : dla::Engine {
     rep->handled = 0;
     t_pending_k = 0;                 // (whatever an earlier chain left: nobody fetched it, it belongs to no later call)
     if (run.active) { err = "ortho_chain: a chain is already in flight"; return DLA_ERR_RUNTIME; }
-    // (basis_exact: the stored columns are not orthonormal, only the device chain projects with the caller's D -- the host-driven
+    // (policy.basis_exact: the stored columns are not orthonormal, only the device chain projects with the caller's D -- the host-driven
     //  loop, which ends on the reference's growth test, must not take such a block)
     auto not_handled = [&]() {
-      if (!(basis_exact && m > 0) || dmat_cols == m) return (int)DLA_OK;     // (the host-driven loop projects with D as well: basis_dd)
+      if (!(policy.basis_exact && m > 0) || dmat_cols == m) return (int)DLA_OK;     // (the host-driven loop projects with D as well: basis_dd)
       err = "ortho_chain: dla_expand_project mode 5 needs the caller's pending blocks (dla_basis_sync after every block of the basis)";
       return (int)DLA_ERR_ARG;
     };
-    if (tune[6] == 3 || chain_off) return not_handled();                  // A/B / the caller's request: host-driven loop
+    if (tune[6] == 3 || policy.chain_off) return not_handled();                  // A/B / the caller's request: host-driven loop
     if (hook || local_only || k <= 0 || k > 48) return not_handled();     // hook reductions need the host between sweeps
     const bool vsx = m > 0;
     if (vsx && !(u == x + (size_t)n * m && can_combo(m, k))) return not_handled();
@@ -4741,14 +4741,14 @@ struct HipEngine : dla::Engine {
     // and the closing projection only needs its Gram matrix (measured r05, interleaved: 17.0 against 16.35 ms per benchmark solve;
     // 138.5 against 144.3 ms on the random-guess leg, which never shifts).  A chain that reports a level shift switches the schedule
     // off for the next 16 chains, and every solve starts with two chains of the five-sweep schedule (on the benchmark the first one
-    // shifts).  Callers that take the closing block on their small matrices (modes 3 and 5) always run it: `rebuilt`, `basis_exact`.
+    // shifts).  Callers that take the closing block on their small matrices (modes 3 and 5) always run it: `rebuilt`, `policy.basis_exact`.
     // (A block that is used once and rebuilt -- LOBPCG's W, dla_expand_project mode 3: pending blocks without a bound on the Gram
     //  matrix -- leaves nothing in a basis: the three-pass schedule always; measured r05, n = 2e6, 8 roots: 15.99 against 17.07 ms.)
-    const bool rebuilt = drop_final && publish_pending && drop_final_tol <= 0.0;
-    // (basis_exact: the caller keeps its pending blocks on the device (dla_basis_sync) and every projection of this chain is exact
+    const bool rebuilt = policy.rebuilt();
+    // (policy.basis_exact: the caller keeps its pending blocks on the device (dla_basis_sync) and every projection of this chain is exact
     //  against the FINISHED basis -- a loose stored basis costs later chains nothing, so the schedule that ends soonest always)
-    if (basis_exact && vsx && (fold == 0 || dmat_cols != m || (dmat_nontrivial && m > DMAT_LD))) return not_handled();
-    const bool x3 = fold == 1 && bx == x && tune[6] != 12 && (x3_cooldown <= 0 || tune[6] == 13 || rebuilt || basis_exact);
+    if (policy.basis_exact && vsx && (fold == 0 || dmat_cols != m || (dmat_nontrivial && m > DMAT_LD))) return not_handled();
+    const bool x3 = fold == 1 && bx == x && tune[6] != 12 && (x3_cooldown <= 0 || tune[6] == 13 || rebuilt || policy.basis_exact);
     // wider blocks (LDS-loop tail): X^T U and U^T U in ONE sweep when [X | U] fits one pass of the Gram kernel (the plain
     // product with the contiguous panel [X | U] on the left: U follows X, bx == x) and the leading ortho_cd takes one step
     const int ktw = (k + 15) / 16;
@@ -4808,7 +4808,7 @@ struct HipEngine : dla::Engine {
     h_ost->nops = 0;
 
     // the schedule depends on how much of the new block already lies in span(X): remembered per basis width
-    const bool dropf = drop_final && vsx;
+    const bool dropf = policy.drop_final && vsx;
     t_pending_k = 0;
     t_seq = t_seq >= 1000000 ? 1 : t_seq + 1;
     const long long key = (long long)k * 1000000 + m + fold * 500000000000LL + (wide_gramx ? 250000000000LL : 0LL) + (wide_xw ? 125000000000LL : 0LL) +
@@ -4835,7 +4835,7 @@ struct HipEngine : dla::Engine {
     // last planned sweep reports where the machine stands whether or not it was that sweep's turn (gram_reduce_kernel<true>).  Two
     // predicated-off sweeps and two k x k launches less per chain: 19 us (r05 trace: 0.15 ms per benchmark solve, 0.23 per LOBPCG solve).
     const bool fused_steps = p2p.on ? (tune[6] != 4 && (m + k) * k <= P2P_MAX_DOUBLES) : (nranks <= 1 && !comm);
-    const bool lean = vsx && drop_final && publish_pending && drop_final_tol <= 0.0 && m + k <= PEND_ROWS && fused_steps && tune[6] != 17;
+    const bool lean = vsx && rebuilt && m + k <= PEND_ROWS && fused_steps && tune[6] != 17;
     if (lean) {
       while (plan.size() > 1 && (plan.back() == OP_FINAL || plan.back() == OP_CLOSE)) plan.pop_back();
     } else
@@ -5014,7 +5014,7 @@ struct HipEngine : dla::Engine {
       if (sres.status == OST_DONE && sres.nops <= 48) { hist.assign(sres.log, sres.log + nlog); last_k = hist; }
     }
     // a chain that ended with its last factor pending has left it in the pinned buffer (the tail wrote the sequence number last)
-    if (sres.status == OST_DONE && drop_final && publish_pending && vsx && h_tpend[PEND_HDR] == (double)t_seq) t_pending_k = k;
+    if (sres.status == OST_DONE && policy.publishes() && vsx && h_tpend[PEND_HDR] == (double)t_seq) t_pending_k = k;
     rep->handled = 1;
     rep->status = sres.status;
     rep->growth = sres.growth;

@@ -862,11 +862,10 @@ int dla_ortho_qr(dla_ctx* c, int n, int k, double* u)
 static int ortho_vs_x_after_chain(dla_ctx* c, dla::BlockOps* ops, long long row0, long long n_rows_global, int n, int m, int k,
                                   const double* x, const double* bx, double* u, const dla::OrthoReport* chain);
 
-// dla_expand_project mode 4: the stored basis is orthonormal to 1e-8 per block only, and a projection against it leaves that share of
-// what it removes.  The device chains know (TIGHT_REMOVES in hip_engine.hip); the host-driven loop follows the reference, whose
+// dla_expand_project mode 4 (ChainPolicy::tight()): the stored basis is orthonormal to 1e-8 per block only, and a projection against
+// it leaves that share of what it removes.  The device chains know (TIGHT_REMOVES in hip_engine.hip); the host-driven loop follows the reference, whose
 // growth test ends after one projection -- there the whole ortho_vs_x runs a second time: its first product X^T U is then what the
 // first run left, 1e-8 |S|, and what the second run leaves of it is below rounding (tools/fuzz_pending_basis.py, FUZZ_WIDE).
-static bool tight_basis(const dla_ctx* c) { return c && c->eng && c->eng->drop_final && c->eng->drop_final_tol > 0.0; }
 
 static int ortho_vs_x_impl(dla_ctx* c, dla::BlockOps* ops, long long row0, long long n_rows_global, int n, int m, int k,
                            const double* x, const double* bx, double* u)
@@ -877,7 +876,7 @@ static int ortho_vs_x_impl(dla_ctx* c, dla::BlockOps* ops, long long row0, long 
   int stc = ops->ortho_chain(n, m, k, x, bx, u, &rep);
   if (stc) return opsfail(c, ops, stc);
   int st = ortho_vs_x_after_chain(c, ops, row0, n_rows_global, n, m, k, x, bx, u, rep.handled ? &rep : nullptr);
-  if (st == DLA_OK && m > 0 && tight_basis(c) && !(rep.handled && rep.status == 1))
+  if (st == DLA_OK && m > 0 && c->eng->policy.tight() && !(rep.handled && rep.status == 1))
     st = ortho_vs_x_after_chain(c, ops, row0, n_rows_global, n, m, k, x, bx, u, nullptr);
   return st;
 }
@@ -1268,6 +1267,16 @@ static int expand_apply_project(dla_ctx* c, int mode, int n, int m, int k, doubl
 static int expand_project_impl(dla_ctx* c, int mode, int n, int m, int k, double* basis, double* abasis, dla_matvec_fn fn,
                                double shift, double* h, int ldh);
 
+// dot product with four partial sums, so that the compiler may keep them in one vector register
+static inline double dot4(const double* a, const double* b, int n)
+{
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  int i = 0;
+  for (; i + 4 <= n; i += 4) { s0 += a[i] * b[i]; s1 += a[i + 1] * b[i + 1]; s2 += a[i + 2] * b[i + 2]; s3 += a[i + 3] * b[i + 3]; }
+  for (; i < n; ++i) s0 += a[i] * b[i];
+  return (s0 + s1) + (s2 + s3);
+}
+
 // The closing pass of ortho_vs_x on the small side.  A device chain that ends with a pending block hands over p = [E' ; T]: the
 // stored block U_c has the measured products S = X_c^T U_c and G = U_c^T U_c, T is the inverse Cholesky factor of G
 // (T^T G T = I) and E' = -S T -- the reference's closing pass (diaglib.f90:3543-3544, then one macro-iteration of ortho_cd,
@@ -1280,18 +1289,6 @@ static int expand_project_impl(dla_ctx* c, int mode, int n, int m, int k, double
 // measured with.  E' = 0 (nothing but a triangular factor pending) is left alone.
 // applied: the chain's closing sweep has already applied [E' ; T] to the block in memory (it measured nothing behind it); what is
 // still owed is the difference, [E - E' ; I] R.
-// y(0:rows) += D(0:rows, 0:rows)^T-or-not times x, for the upper-triangular D = I + N of a basis with pending blocks, in the
-// cache- and SIMD-friendly order: column q of D is contiguous.  trans: y_q += D(0:q, q) . x(0:q)  (dot products: four partial
-// sums, so that the compiler may keep them in one vector register); otherwise y(0:q) += D(0:q, q) x_q.
-static inline double dot4(const double* a, const double* b, int n)
-{
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-  int i = 0;
-  for (; i + 4 <= n; i += 4) { s0 += a[i] * b[i]; s1 += a[i + 1] * b[i + 1]; s2 += a[i + 2] * b[i + 2]; s3 += a[i + 3] * b[i + 3]; }
-  for (; i < n; ++i) s0 += a[i] * b[i];
-  return (s0 + s1) + (s2 + s3);
-}
-
 static int close_pending_block(int m, int k, double* p, int ldp, const double* dmat, int ld, int applied)
 {
   double emax = 0.0;
@@ -1361,26 +1358,20 @@ static int close_pending_block(int m, int k, double* p, int ldp, const double* d
   return DLA_OK;
 }
 
-int dla_expand_project(dla_ctx* c, int mode, int n, int m, int k, double* basis, double* abasis, dla_matvec_fn fn,
-                       double shift, double* h, int ldh)
+// What a call of dla_expand_project gets, from the mode it asked for and what the context and the engine can do
+enum class Treatment { Plain0, Plain1, Rebuild, Stay, StayExact, HostLoopExact, Refused };
+
+// bs = basis_state(m), exact_ok = basis_exact_ok(), capacity = basis_capacity() of the engine
+static Treatment resolve_treatment(int mode, bool pending_blocks, int bs, bool exact_ok, int k, int m, int capacity)
 {
-  DLA_T("dla_expand_project");
-  // ortho_vs_x (:1790 / 523-529) + the projection (:1691 / 401-403) [+ daxpy :397]; the operator is the caller's
-  RefFlops rf(c, c && n > 0 && k > 0 ? ortho_vs_x_flops(n, m, k) + (shift != 0.0 ? 2.0 * n * (double)k : 0.0) +
-                                       ((mode == 0 || mode >= 4) ? 2.0 * n * (double)(m + k) * k : 2.0 * n * (double)(m + k) * (m + k)) : 0.0);
-  if (!c || !basis || !abasis || !h || !fn || mode < 0 || mode == 2 || mode > 6 || n <= 0 || m < 0 || k <= 0 || ldh < m + k)
-    return fail(c, DLA_ERR_ARG, "dla_expand_project: bad argument (n > 0, m >= 0, k > 0, ldh >= m + k)");
-  c->pending_k = 0; c->pending_m = 0; c->pending_applied = 0;
   // (DLA_OPT_PENDING_BLOCKS = 0 makes modes 3 / 4 / 5 behave like 1 / 0 / 0: the chain finishes the block in memory)
-  if (mode == 3 && !c->pending_blocks) mode = 1;
-  if ((mode == 4 || mode == 5) && !c->pending_blocks && c->eng->basis_state(m) <= 0) mode = 0;
-  // mode 5 = mode 4 with the caller's pending blocks kept on the device as well (dla_basis_sync after every block): the chain's
-  // projections are exact against the FINISHED basis X D, so what a block leaves pending is bounded only by what keeps the host
-  // algebra well conditioned (max |S| < 0.05, Gram matrix factorable in one step) -- not by what later projections could absorb
-  // (where the device cannot project with D -- wider blocks, a wider basis, an all-reduce hook -- the block is finished in memory,
-  //  mode 0: nothing of it stays pending in a basis that later blocks are projected against)
-  const bool exact = mode == 5 && c->pending_blocks && c->eng->basis_exact_ok() && k <= 16 && m + k <= c->eng->basis_capacity();
+  if (mode == 3 && !pending_blocks) return Treatment::Plain1;
+  if ((mode == 4 || mode == 5) && !pending_blocks && bs <= 0) return Treatment::Plain0;
   if (mode == 5 || mode == 6) {
+    // mode 5 = mode 4 with the caller's pending blocks kept on the device as well (ChainPolicy::stay(true))
+    // (where the device cannot project with D -- wider blocks, a wider basis, an all-reduce hook -- the block is finished in memory,
+    //  mode 0: nothing of it stays pending in a basis that later blocks are projected against)
+    const bool exact = mode == 5 && pending_blocks && exact_ok && k <= 16 && m + k <= capacity;
     // What the copy of the caller's D says about the m stored columns decides what a call that cannot be exact may do (round-5
     // advisor: the device's ability can change between two calls of one solve -- a refused LDS request lowers the engine's limit --
     // and earlier blocks of the basis may already be pending with max |S| up to 0.05, i.e. the stored columns are not orthonormal):
@@ -1390,71 +1381,43 @@ int dla_expand_project(dla_ctx* c, int mode, int n, int m, int k, double* basis,
     //   no copy of these m:  refused -- a plain projection against unfinished columns would lose orthogonality without a word.
     // mode 6 asks for the second treatment outright: a block whose closing algebra the caller could not complete (dla_basis_admit
     // answered DLA_ERR_ORTHO: I - F^T F not positive definite) is finished in memory from what the chain stored.
-    const int bs = c->eng->basis_state(m);
-    if (bs < 0)
-      return fail(c, DLA_ERR_ARG, "dla_expand_project: the engine's copy of the caller's pending blocks does not describe the columns in front of "
-                                  "this block (dla_basis_sync after every block of the basis, identity ones included)");
-    if (mode == 6 || (!exact && bs > 0)) {
-      struct Flags { dla::Engine* e; explicit Flags(dla::Engine* e_) : e(e_) { e->basis_exact = true; e->chain_off = true; }
-                     ~Flags() { e->basis_exact = false; e->chain_off = false; } } flags(c->eng);
-      return expand_project_impl(c, 0, n, m, k, basis, abasis, fn, shift, h, ldh);
-    }
-    mode = exact ? 4 : 0;
+    if (bs < 0) return Treatment::Refused;
+    if (mode == 6 || (!exact && bs > 0)) return Treatment::HostLoopExact;
+    return exact ? Treatment::StayExact : Treatment::Plain0;
   }
-  // a chain that failed behind a finished orthogonalisation must not leave its block to the next call (round-4 advisor)
-  struct Forget { dla_ctx* c; int m, k; bool keep = false; ~Forget() { if (!keep) { std::vector<double> junk((size_t)(m + k) * k); (void)c->eng->pending_block(m, k, junk.data(), m + k, nullptr); } } };
-  if (mode == 4) {
-    // mode 4 = mode 0 for a block that STAYS in the basis (Davidson, reference diaglib.f90:1790 + 1685 + 1691): what the chain
-    // left undone stays pending only when the closing pass found the block orthonormal to 1e-8 -- later blocks are projected
-    // against the stored block as if it were orthonormal, twice, the second time on a measured product.  h_host comes back RAW,
-    // for the stored block: the caller keeps the pending blocks of its whole basis (an upper-triangular D, dla_basis_admit) and
-    // multiplies the rows of its coefficient blocks by D before any product with the panel (dla_basis_fold)
-    // (1e-8 / 1e-9: a later block's first projection against the stored columns leaves that share of what it removes, and the block
-    //  that comes out of it can be as ill-conditioned as 1e7 -- the leftover must stay below its smallest directions)
-    struct Flags { dla::Engine* e; Flags(dla::Engine* e_, bool ex) : e(e_) { e->drop_final = true; e->publish_pending = true; e->drop_final_tol = ex ? 0.0 : 1.0e-8; e->drop_final_stol = ex ? 5.0e-2 : 1.0e-9; e->basis_exact = ex; }
-                   ~Flags() { e->drop_final = false; e->publish_pending = false; e->drop_final_tol = 0.0; e->drop_final_stol = 1.0e-4; e->basis_exact = false; } } flags(c->eng, exact);
-    Forget forget{c, m, k};
-    const int st = expand_project_impl(c, 0, n, m, k, basis, abasis, fn, shift, h, ldh);
-    if (st) return st;
-    forget.keep = true;
-    c->pending_p.assign((size_t)(m + k) * k, 0.0);
-    const int stp = c->eng->pending_block(m, k, c->pending_p.data(), m + k, &c->pending_applied);
-    if (stp) return engfail(c, stp);
-    c->pending_k = k; c->pending_m = m;
-    return DLA_OK;
-  }
-  if (mode != 3) return expand_project_impl(c, mode, n, m, k, basis, abasis, fn, shift, h, ldh);
-  // mode 3 = mode 1 for a block that is used once and rebuilt (LOBPCG's W, reference diaglib.f90:518-529, 394-403): what the chain
-  // left undone -- its last triangular factor T (near the identity) and, with the three-pass schedule, the closing projection E --
-  // is not applied to the block; the projection of the stored blocks is corrected here, H <- D^T H D with D = [I E ; 0 T], and the
-  // caller folds D into every coefficient block it multiplies the panel with (dla_pending_block): the closing sweeps are never run
-  {
-    struct Flags { dla::Engine* e; explicit Flags(dla::Engine* e_) : e(e_) { e->drop_final = true; e->publish_pending = true; }
-                   ~Flags() { e->drop_final = false; e->publish_pending = false; } } flags(c->eng);
-    Forget forget{c, m, k};
-    const int st = expand_project_impl(c, 1, n, m, k, basis, abasis, fn, shift, h, ldh);
-    if (st) return st;
-    forget.keep = true;
-  }
-  const int l = m + k;
-  c->pending_p.assign((size_t)l * k, 0.0);
-  int st = c->eng->pending_block(m, k, c->pending_p.data(), l, &c->pending_applied);
-  if (st) return engfail(c, st);
+  return mode == 4 ? Treatment::Stay : mode == 3 ? Treatment::Rebuild : mode == 1 ? Treatment::Plain1 : Treatment::Plain0;
+}
+
+// a chain that failed behind a finished orthogonalisation must not leave its block to the next call (round-4 advisor)
+namespace {
+struct Forget { dla_ctx* c; int m, k; bool keep = false; ~Forget() { if (!keep) { std::vector<double> junk((size_t)(m + k) * k); (void)c->eng->pending_block(m, k, junk.data(), m + k, nullptr); } } };
+}  // namespace
+
+// expand_project_impl under a policy that publishes; on success what the chain left pending becomes the context's pending block
+static int run_and_take_pending(dla_ctx* c, const dla::ChainPolicy& policy, int impl_mode, int n, int m, int k, double* basis,
+                                double* abasis, dla_matvec_fn fn, double shift, double* h, int ldh)
+{
+  dla::PolicyScope scope(c->eng, policy);
+  Forget forget{c, m, k};
+  const int st = expand_project_impl(c, impl_mode, n, m, k, basis, abasis, fn, shift, h, ldh);
+  if (st) return st;
+  forget.keep = true;
+  c->pending_p.assign((size_t)(m + k) * k, 0.0);
+  const int stp = c->eng->pending_block(m, k, c->pending_p.data(), m + k, &c->pending_applied);
+  if (stp) return engfail(c, stp);
   c->pending_k = k; c->pending_m = m;
-  st = close_pending_block(m, k, c->pending_p.data(), l, nullptr, 0, c->pending_applied);       // ([X P] is a finished block: D = I)
-  c->pending_applied = 0;
-  if (st) {
-    // I - (S T)^T (S T) is not positive definite: nothing bounds |T| where the chain ended (round-5 advisor).  The block in memory
-    // is intact -- what the chain stored -- so it is finished there: the orthogonalisation runs again on it, without anything left
-    // pending, and the operator and the projection are repeated on the finished block (p = [0 ; I]).
-    c->pending_k = 0; c->pending_m = 0;
-    return expand_project_impl(c, 1, n, m, k, basis, abasis, fn, shift, h, ldh);
-  }
-  const double* p = c->pending_p.data();
+  return DLA_OK;
+}
+
+// mode 3: the projection of the stored blocks is corrected for the closed pending block p ((m + k) x k, ld m + k),
+// H <- D^T H D with D = [I E ; 0 T] = [I_x | p]
+static void fold_pending_into_projection(int m, int k, const double* p, double* h, int ldh)
+{
+  const int l = m + k;
   bool ident = true;
   for (int j = 0; j < k && ident; ++j)
     for (int i = 0; i < l; ++i) if (p[(size_t)i + (size_t)j * l] != (i == m + j ? 1.0 : 0.0)) { ident = false; break; }
-  if (ident) return DLA_OK;
+  if (ident) return;
   // lower triangle of H (l x l): the W rows become  p^T H_full [I_x | p]  (H_xx is untouched)
   std::vector<double> hf((size_t)l * l), g((size_t)l * k);
   for (int j = 0; j < l; ++j)
@@ -1478,6 +1441,44 @@ int dla_expand_project(dla_ctx* c, int mode, int n, int m, int k, double* basis,
       h[(size_t)(m + i) + (size_t)(m + j) * ldh] = acc;
     }
   }
+}
+
+int dla_expand_project(dla_ctx* c, int mode, int n, int m, int k, double* basis, double* abasis, dla_matvec_fn fn,
+                       double shift, double* h, int ldh)
+{
+  DLA_T("dla_expand_project");
+  // ortho_vs_x (:1790 / 523-529) + the projection (:1691 / 401-403) [+ daxpy :397]; the operator is the caller's
+  RefFlops rf(c, c && n > 0 && k > 0 ? ortho_vs_x_flops(n, m, k) + (shift != 0.0 ? 2.0 * n * (double)k : 0.0) +
+                                       ((mode == 0 || mode >= 4) ? 2.0 * n * (double)(m + k) * k : 2.0 * n * (double)(m + k) * (m + k)) : 0.0);
+  if (!c || !basis || !abasis || !h || !fn || mode < 0 || mode == 2 || mode > 6 || n <= 0 || m < 0 || k <= 0 || ldh < m + k)
+    return fail(c, DLA_ERR_ARG, "dla_expand_project: bad argument (n > 0, m >= 0, k > 0, ldh >= m + k)");
+  c->pending_k = 0; c->pending_m = 0; c->pending_applied = 0;
+  switch (resolve_treatment(mode, c->pending_blocks != 0, c->eng->basis_state(m), c->eng->basis_exact_ok(), k, m, c->eng->basis_capacity())) {
+  case Treatment::Refused:
+    return fail(c, DLA_ERR_ARG, "dla_expand_project: the engine's copy of the caller's pending blocks does not describe the columns in front of "
+                                "this block (dla_basis_sync after every block of the basis, identity ones included)");
+  case Treatment::Plain0: return expand_project_impl(c, 0, n, m, k, basis, abasis, fn, shift, h, ldh);
+  case Treatment::Plain1: return expand_project_impl(c, 1, n, m, k, basis, abasis, fn, shift, h, ldh);
+  case Treatment::HostLoopExact: {
+    dla::PolicyScope scope(c->eng, dla::ChainPolicy::host_loop_exact());
+    return expand_project_impl(c, 0, n, m, k, basis, abasis, fn, shift, h, ldh);
+  }
+  case Treatment::Stay: return run_and_take_pending(c, dla::ChainPolicy::stay(false), 0, n, m, k, basis, abasis, fn, shift, h, ldh);
+  case Treatment::StayExact: return run_and_take_pending(c, dla::ChainPolicy::stay(true), 0, n, m, k, basis, abasis, fn, shift, h, ldh);
+  case Treatment::Rebuild: break;
+  }
+  int st = run_and_take_pending(c, dla::ChainPolicy::rebuild(), 1, n, m, k, basis, abasis, fn, shift, h, ldh);
+  if (st) return st;
+  st = close_pending_block(m, k, c->pending_p.data(), m + k, nullptr, 0, c->pending_applied);       // ([X P] is a finished block: D = I)
+  c->pending_applied = 0;
+  if (st) {
+    // I - (S T)^T (S T) is not positive definite: nothing bounds |T| where the chain ended (round-5 advisor).  The block in memory
+    // is intact -- what the chain stored -- so it is finished there: the orthogonalisation runs again on it, without anything left
+    // pending, and the operator and the projection are repeated on the finished block (p = [0 ; I]).
+    c->pending_k = 0; c->pending_m = 0;
+    return expand_project_impl(c, 1, n, m, k, basis, abasis, fn, shift, h, ldh);
+  }
+  fold_pending_into_projection(m, k, c->pending_p.data(), h, ldh);
   return DLA_OK;
 }
 
@@ -1639,12 +1640,12 @@ static int expand_project_impl(dla_ctx* c, int mode, int n, int m, int k, double
       // the chain took more launches than planned, or stopped: what ran behind it has read an unfinished block
       st = ortho_vs_x_after_chain(c, c->eng, c->row0, nglob, n, m, k, basis, basis, u, &rep);
       if (st) return st;
-      if (tight_basis(c) && rep.status != 1) { st = ortho_vs_x_after_chain(c, c->eng, c->row0, nglob, n, m, k, basis, basis, u, nullptr); if (st) return st; }
+      if (c->eng->policy.tight() && rep.status != 1) { st = ortho_vs_x_after_chain(c, c->eng, c->row0, nglob, n, m, k, basis, basis, u, nullptr); if (st) return st; }
       return expand_apply_project(c, mode, n, m, k, basis, abasis, fn, shift, h, ldh);
     }
     st = ortho_vs_x_after_chain(c, c->eng, c->row0, nglob, n, m, k, basis, basis, u, nullptr);
     if (st) return st;
-    if (tight_basis(c)) { st = ortho_vs_x_after_chain(c, c->eng, c->row0, nglob, n, m, k, basis, basis, u, nullptr); if (st) return st; }
+    if (c->eng->policy.tight()) { st = ortho_vs_x_after_chain(c, c->eng, c->row0, nglob, n, m, k, basis, basis, u, nullptr); if (st) return st; }
     return expand_apply_project(c, mode, n, m, k, basis, abasis, fn, shift, h, ldh);
   }
   int st = ortho_vs_x_impl(c, c->eng, c->row0, nglob, n, m, k, basis, basis, u);
@@ -1700,10 +1701,7 @@ int dla_expand_project_metric(dla_ctx* c, int mode, int n, int m, int k, double*
   const int order = builtin ? 2 : c->callback_order;
   const bool ahead = (c->run_ahead == 2 || (c->run_ahead == 1 && builtin)) && c->callbacks_on_device && order != 1;
   int b_handled = 0;
-  // b_ortho follows b_ortho_vs_x at once (reference :2170 / :2185, :523-529): its Cholesky-QR gives the same block whether the
-  // chain's last pending factor -- upper triangular, positive diagonal -- has been applied or not, so the chain may end without
-  // the sweep U <- U W (the host-driven loop has nothing pending and is not affected)
-  struct DropFinal { dla::Engine* e; explicit DropFinal(dla::Engine* e_) : e(e_) { e->drop_final = true; } ~DropFinal() { e->drop_final = false; } } drop_guard(c->eng);
+  dla::PolicyScope drop_guard(c->eng, dla::ChainPolicy::metric_drop());
   if (ahead && m > 0) {
     dla::OrthoReport rep;
     int st = c->eng->ortho_chain_begin(n, m, k, basis, bbasis, u, &rep);

@@ -29,6 +29,7 @@
 #include <set>
 #include <vector>
 #include "dla_internal.h"
+#include "hip_owned.h"
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 typedef double v2d __attribute__((ext_vector_type(2)));
@@ -3600,18 +3601,17 @@ struct HipEngine : dla::Engine {
   int ncu = 256;
   hipStream_t st = nullptr;
   std::string nm;
-  // workspaces
-  double* d_partial = nullptr; size_t partial_bytes = 0;
-  double* d_small = nullptr;   size_t small_bytes = 0;    // reduced results (device)
-  double* h_small = nullptr;                              // pinned, device-mapped host mirror
-  double* h_small_dev = nullptr;                          // its device-visible address
-  double* d_lvl2 = nullptr;    size_t lvl2_bytes = 0;     // second-level partials of the Gram reduction
-  unsigned* d_ticket = nullptr;
+  // workspaces (hip_owned.h: each owner releases itself, reserve() is the one regrow primitive)
+  DeviceBuffer<double> d_partial;
+  DeviceBuffer<double> d_small;         // reduced results (device)
+  MappedHostBuffer<double> h_small;     // pinned, device-mapped host mirror
+  DeviceBuffer<double> d_lvl2;          // second-level partials of the Gram reduction
+  DeviceBuffer<unsigned> d_ticket;
   static const int RING = 8;
-  double* h_ring[RING] = {nullptr}; hipEvent_t ring_ev[RING]; size_t ring_bytes = 0; int ring_pos = 0;
-  double* d_cpk = nullptr; size_t cpk_bytes = 0;
+  MappedHostBuffer<double> h_ring[RING]; Event ring_ev[RING]; int ring_pos = 0;
+  DeviceBuffer<double> d_cpk;
     // built-in operator
-  double* d_w = nullptr; double* d_diag = nullptr; double* d_t = nullptr; double* d_wsq = nullptr;
+  DeviceBuffer<double> d_w, d_diag, d_t, d_wsq;
   long long syn_row0 = 0; int syn_n = 0, syn_rw = 0; double syn_sigma = 0.0;
   // rccl
   ncclComm_t comm = nullptr;
@@ -3660,52 +3660,19 @@ struct HipEngine : dla::Engine {
     if (std::getenv("DIAGLIB_AMD_HOSTTIME"))
       std::fprintf(stderr, "[dla] host waits: stream sync %.3f s (%ld), ring event sync %.3f s, alloc %.3f s, free %.3f s\n",
                    t_sync, n_sync, t_evsync, t_alloc, t_free);
+    // Everything queued is waited for here, so nothing below can pull memory from under a running kernel; the buffers and
+    // events are members that release themselves after this body, and once the streams are idle their order does not matter.
     if (st) (void)hipStreamSynchronize(st);
-    for (auto& b : cache) (void)hipFree(b.ptr);
-    for (auto& b : live) (void)hipFree(b.ptr);
+    if (st_down) (void)hipStreamSynchronize(st_down);
+    if (st_up) (void)hipStreamSynchronize(st_up);
     p2p_release();
     if (comm) ncclCommDestroy(comm);
+    for (auto& b : cache) (void)hipFree(b.ptr);
+    for (auto& b : live) (void)hipFree(b.ptr);
     for (auto& t : timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
     for (auto e : ev_pool) (void)hipEventDestroy(e);
-    if (d_partial) (void)hipFree(d_partial);
-    if (d_small) (void)hipFree(d_small);
-    if (h_small) (void)hipHostFree(h_small);
-    if (d_lvl2) (void)hipFree(d_lvl2);
-    if (d_ticket) (void)hipFree(d_ticket);
-    if (ev_wait) (void)hipEventDestroy(ev_wait);
-    if (ev_cb) (void)hipEventDestroy(ev_cb);
-    if (ev_cb2) (void)hipEventDestroy(ev_cb2);
-    if (d_ost) (void)hipFree(d_ost);
-    if (h_ost) (void)hipHostFree(h_ost);
-    if (h_ost_init) (void)hipHostFree(h_ost_init);
-    if (h_tpend) (void)hipHostFree(h_tpend);
-    if (d_wpk) (void)hipFree(d_wpk);
-    if (d_wfull) (void)hipFree(d_wfull);
-    if (d_cpk2) (void)hipFree(d_cpk2);
-    if (d_wst) (void)hipFree(d_wst);
-    if (d_xug) (void)hipFree(d_xug);
-    if (d_dmat) (void)hipFree(d_dmat);
-    if (d_red_small) (void)hipFree(d_red_small);
-    if (d_red_xug) (void)hipFree(d_red_xug);
-    if (d_bgo) (void)hipFree(d_bgo);
-    if (h_bstat) (void)hipHostFree(h_bstat);
-    if (d_wpk_b) (void)hipFree(d_wpk_b);
-    for (int i = 0; i < RING; ++i) if (h_ring[i]) { (void)hipHostFree(h_ring[i]); (void)hipEventDestroy(ring_ev[i]); }
-    if (d_cpk) (void)hipFree(d_cpk);
-    if (d_w) (void)hipFree(d_w);
-    if (d_diag) (void)hipFree(d_diag);
-    if (d_wsq) (void)hipFree(d_wsq);
-    if (d_t) (void)hipFree(d_t);
-    if (d_ell_col) (void)hipFree(d_ell_col);
-    if (d_ell_val) (void)hipFree(d_ell_val);
-    if (d_ell_diag) (void)hipFree(d_ell_diag);
-    if (d_halo) (void)hipFree(d_halo);
-    if (st_down) {
-      (void)hipStreamSynchronize(st_down); (void)hipStreamSynchronize(st_up);
-      (void)hipStreamDestroy(st_down); (void)hipStreamDestroy(st_up);
-      (void)hipEventDestroy(ev_stage_ready); (void)hipEventDestroy(ev_stage_done);
-      for (int i = 0; i < 16; ++i) (void)hipEventDestroy(ev_down[i]);
-    }
+    if (st_down) (void)hipStreamDestroy(st_down);
+    if (st_up) (void)hipStreamDestroy(st_up);
     if (st) (void)hipStreamDestroy(st);
   }
 
@@ -3733,11 +3700,9 @@ struct HipEngine : dla::Engine {
     ncu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
     nm = std::string("hip:") + p.gcnArchName;
     HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    small_bytes = sizeof(double) * 512 * 512;
-    HIPCHK(hipMalloc((void**)&d_small, small_bytes));
-    HIPCHK(hipHostMalloc((void**)&h_small, small_bytes, hipHostMallocMapped));
-    HIPCHK(hipHostGetDevicePointer((void**)&h_small_dev, h_small, 0));
-    HIPCHK(hipMalloc((void**)&d_ticket, sizeof(unsigned) * 4100));     // [4096] per output tile + 1 global
+    HIPCHK(d_small.reserve(512 * 512));
+    HIPCHK(h_small.reserve(512 * 512));
+    HIPCHK(d_ticket.reserve(4100));                                         // [4096] per output tile + 1 global
     HIPCHK(hipMemsetAsync(d_ticket, 0, sizeof(unsigned) * 4100, st));       // (on the engine's stream: see d_halo)
     return DLA_OK;
   }
@@ -3938,15 +3903,13 @@ struct HipEngine : dla::Engine {
   }
   int sync() override { HIPCHK(hipStreamSynchronize(st)); return DLA_OK; }
   // device-mode callbacks (dla_internal.h): order the user's stream(s) against ours
-  hipEvent_t ev_cb = nullptr, ev_cb2 = nullptr;
+  Event ev_cb, ev_cb2;
   int callback_begin(int mode) override
   {
     if (mode == 2) return DLA_OK;
     if (mode == 1) { int stw = wait_stream(); if (stw) return stw; stats.host_syncs++; return DLA_OK; }
-    if (!ev_cb) {
-      HIPCHK(hipEventCreateWithFlags(&ev_cb, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&ev_cb2, hipEventDisableTiming));
-    }
+    HIPCHK(ev_cb.ensure(hipEventDisableTiming));
+    HIPCHK(ev_cb2.ensure(hipEventDisableTiming));
     HIPCHK(hipEventRecord(ev_cb, st));
     HIPCHK(hipStreamWaitEvent(nullptr, ev_cb, 0));     // legacy null stream: every blocking stream follows it
     return DLA_OK;
@@ -3961,16 +3924,17 @@ struct HipEngine : dla::Engine {
   }
   // ---- staging pipeline of host-mode callbacks (dla_internal.h)
   hipStream_t st_down = nullptr, st_up = nullptr;
-  bool stage_pending = false;
-  hipEvent_t ev_stage_ready = nullptr, ev_stage_done = nullptr, ev_down[16] = {nullptr};
+  bool stage_pending = false, stage_ready = false;
+  Event ev_stage_ready, ev_stage_done, ev_down[16];
   int stage_init()
   {
-    if (st_down) return DLA_OK;
-    HIPCHK(hipStreamCreateWithFlags(&st_down, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&st_up, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&ev_stage_ready, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&ev_stage_done, hipEventDisableTiming));
-    for (int i = 0; i < 16; ++i) HIPCHK(hipEventCreateWithFlags(&ev_down[i], hipEventDisableTiming));
+    if (stage_ready) return DLA_OK;
+    if (!st_down) HIPCHK(hipStreamCreateWithFlags(&st_down, hipStreamNonBlocking));
+    if (!st_up) HIPCHK(hipStreamCreateWithFlags(&st_up, hipStreamNonBlocking));
+    HIPCHK(ev_stage_ready.ensure(hipEventDisableTiming));
+    HIPCHK(ev_stage_done.ensure(hipEventDisableTiming));
+    for (int i = 0; i < 16; ++i) HIPCHK(ev_down[i].ensure(hipEventDisableTiming));
+    stage_ready = true;
     return DLA_OK;
   }
   int stage_begin() override
@@ -4013,31 +3977,46 @@ struct HipEngine : dla::Engine {
   int host_alloc(size_t bytes, void** p) override { bind(); HIPCHK(hipHostMalloc(p, bytes, hipHostMallocDefault)); return DLA_OK; }
   int host_free(void* p) override { if (p) HIPCHK(hipHostFree(p)); return DLA_OK; }
 
+  // the workspaces hold doubles; their callers think in bytes
+  static size_t doubles(size_t bytes) { return (bytes + sizeof(double) - 1) / sizeof(double); }
   int ensure_partial(size_t bytes)
   {
-    if (bytes <= partial_bytes) return DLA_OK;
+    if (doubles(bytes) <= d_partial.capacity()) return DLA_OK;
     bind();
-    if (d_partial) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(d_partial)); d_partial = nullptr; }
-    HIPCHK(hipMalloc((void**)&d_partial, bytes));
-    partial_bytes = bytes;
+    if (d_partial) HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(d_partial.reserve(doubles(bytes)));
     return DLA_OK;
   }
   int ensure_small(size_t bytes)
   {
-    if (bytes <= small_bytes) return DLA_OK;
+    if (doubles(bytes) <= std::min(d_small.capacity(), h_small.capacity())) return DLA_OK;
     bind();
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipFree(d_small)); HIPCHK(hipHostFree(h_small));
-    small_bytes = bytes;
-    HIPCHK(hipMalloc((void**)&d_small, small_bytes));
-    HIPCHK(hipHostMalloc((void**)&h_small, small_bytes, hipHostMallocMapped));
-    HIPCHK(hipHostGetDevicePointer((void**)&h_small_dev, h_small, 0));
+    HIPCHK(d_small.reserve(doubles(bytes)));
+    HIPCHK(h_small.reserve(doubles(bytes)));
+    return DLA_OK;
+  }
+  // first allocation of a buffer that starts zeroed (on the engine's stream): both or nothing, so that a later call retries
+  template <class T> int reserve_zeroed(DeviceBuffer<T>& b, size_t count)
+  {
+    if (b) return DLA_OK;
+    HIPCHK(b.reserve(count));
+    const hipError_t e = hipMemsetAsync(b, 0, sizeof(T) * count, st);
+    if (e != hipSuccess) b.reset();
+    HIPCHK(e);
+    return DLA_OK;
+  }
+  int ensure_lvl2(size_t bytes)
+  {
+    if (doubles(bytes) <= d_lvl2.capacity()) return DLA_OK;
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(d_lvl2.reserve(doubles(std::max(bytes, (size_t)1 << 20))));
     return DLA_OK;
   }
   // Host wait for the stream: poll an event instead of blocking in the driver.  A blocking
   // hipStreamSynchronize sleeps on an interrupt and pays a scheduler wake-up per call (tens of
   // microseconds on an idle host, milliseconds on a busy one); a solve makes ~90 such waits.
-  hipEvent_t ev_wait = nullptr;
+  Event ev_wait;
   int wait_stream()
   {
     const double t0 = now();
@@ -4052,7 +4031,7 @@ struct HipEngine : dla::Engine {
       if (q != hipSuccess) { err = std::string("hipStreamQuery: ") + hipGetErrorString(q); return DLA_ERR_RUNTIME; }
       return DLA_OK;
     }
-    if (!ev_wait) HIPCHK(hipEventCreateWithFlags(&ev_wait, hipEventDisableTiming));
+    HIPCHK(ev_wait.ensure(hipEventDisableTiming));
     HIPCHK(hipEventRecord(ev_wait, st));
     while ((q = hipEventQuery(ev_wait)) == hipErrorNotReady) {
 #if defined(__x86_64__)
@@ -4085,18 +4064,17 @@ struct HipEngine : dla::Engine {
   // a copy kernel of the engine's own is faster -- tools/upload_probe.hip: 26 us host-to-consumer against 20 us -- but inside a
   // solve it buys nothing: interleaved A/B, knob 7 = 9, 16.88 / 16.90 ms against 16.90 / 16.88 at n = 2e6 and 3.90 / 3.90 against
   // 3.86 / 3.87 at 250 k rows.  The runtime's copy stays.)
-  double* h_ring_dev[RING] = {nullptr};
   int stage_slot(size_t bytes, double** host, int* slot_out)
   {
     bind();
-    if (bytes > ring_bytes) {
+    size_t have = h_ring[0].capacity();        // of the smallest slot: one that failed to regrow is empty, the others are not
+    for (int i = 1; i < RING; ++i) have = std::min(have, h_ring[i].capacity());
+    if (doubles(bytes) > have) {
       HIPCHK(hipStreamSynchronize(st));
       for (int i = 0; i < RING; ++i) {
-        if (h_ring[i]) { HIPCHK(hipHostFree(h_ring[i])); } else { HIPCHK(hipEventCreateWithFlags(&ring_ev[i], hipEventDisableTiming)); }
-        HIPCHK(hipHostMalloc((void**)&h_ring[i], std::max(bytes, (size_t)1 << 16), hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer((void**)&h_ring_dev[i], h_ring[i], 0));
+        HIPCHK(ring_ev[i].ensure(hipEventDisableTiming));
+        HIPCHK(h_ring[i].reserve(doubles(std::max(bytes, (size_t)1 << 16))));
       }
-      ring_bytes = std::max(bytes, (size_t)1 << 16);
     }
     const int slot = ring_pos;
     ring_pos = (ring_pos + 1) % RING;
@@ -4114,7 +4092,7 @@ struct HipEngine : dla::Engine {
     } else {                                 // A/B: a copy kernel of the engine's own reading the mapped slot
       const int cnt = (int)(bytes / sizeof(double));
       hipLaunchKernelGGL(small_copy_kernel, dim3((cnt / 2 + 255) / 256 > 0 ? (cnt / 2 + 255) / 256 : 1), dim3(256), 0, st, dev,
-                         (const double*)h_ring_dev[slot], cnt);
+                         (const double*)h_ring[slot].dev(), cnt);
       HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(ring_ev[slot], st));
@@ -4141,7 +4119,7 @@ struct HipEngine : dla::Engine {
       if (exchange_fused) { exchange_fused = false; return DLA_OK; }   // the reduction kernel did it (launch_reduce)
       P2PArgs pa = p2p_args(dev, count, op);
       // outside the device-driven chains the host reads the result next: the exchange writes the pinned mirror itself
-      if (!pred_phase && dev == d_small && host_mirror == h_small) { pa.buf_host = h_small_dev; mirror_fresh = true; }
+      if (!pred_phase && dev == d_small && host_mirror == h_small) { pa.buf_host = h_small.dev(); mirror_fresh = true; }
       Scope s(this, DLA_OP_ELEM, 0.0, 0.0, "p2p_allreduce_kernel");
       DLA_LAUNCH(p2p_allreduce_kernel, dim3(1), dim3(256), 0, st, pa);
       HIPCHK(hipGetLastError());
@@ -4174,7 +4152,7 @@ struct HipEngine : dla::Engine {
     pa.buf = dev; pa.buf_host = nullptr; pa.count = count; pa.op = op; pa.nranks = nranks; pa.rank = rank;
     pa.executed = p2p.d_executed;
     for (int r = 0; r < nranks; ++r) { pa.data[r] = p2p.data[r]; pa.flags[r] = p2p.flags[r]; }
-    pa.status = p2p.d_status; pa.phase = pred_phase; pa.want = pred_want;
+    pa.status = p2p.h_status.dev(); pa.phase = pred_phase; pa.want = pred_want;
     pa.timeout_ticks = (unsigned long long)std::max(0, p2p_timeout_ms) * 100000ULL;
     return pa;
   }
@@ -4190,11 +4168,10 @@ struct HipEngine : dla::Engine {
   // ---- one-shot peer-to-peer all-reduce (p2p_allreduce_kernel)
   struct P2P {
     bool on = false;
-    double* my_data = nullptr; unsigned long long* my_flags = nullptr;
+    DeviceBuffer<double> my_data; DeviceBuffer<unsigned long long> my_flags;     // fine-grained
     double* data[P2P_MAX_RANKS] = {nullptr}; unsigned long long* flags[P2P_MAX_RANKS] = {nullptr};
-    int* h_status = nullptr;             // pinned, device-mapped: a timed-out kernel sets it, the host reads it at its waits
-    int* d_status = nullptr;
-    unsigned long long* d_executed = nullptr;   // see P2PArgs::executed
+    MappedHostBuffer<int> h_status;      // pinned, device-mapped: a timed-out kernel sets it, the host reads it at its waits
+    DeviceBuffer<unsigned long long> d_executed;   // see P2PArgs::executed
     int slots = 0;                       // ranks the local mailbox was sized for
   } p2p;
   static size_t p2p_data_bytes(int nr) { return sizeof(double) * 2 * (size_t)nr * P2P_MAX_DOUBLES; }
@@ -4207,14 +4184,14 @@ struct HipEngine : dla::Engine {
     if (nr < 1 || nr > P2P_MAX_RANKS) { err = "p2p: 1..8 ranks"; return DLA_ERR_ARG; }
     HIPCHK(hipSetDevice(device));
     p2p_release();
-    HIPCHK(hipExtMallocWithFlags((void**)&p2p.my_data, p2p_data_bytes(nr), hipDeviceMallocFinegrained));
-    HIPCHK(hipExtMallocWithFlags((void**)&p2p.my_flags, p2p_flag_bytes(nr), hipDeviceMallocFinegrained));
+    // (everything below is a first allocation: p2p_release left the mailbox empty)
+    HIPCHK(p2p.my_data.reserve(p2p_data_bytes(nr) / sizeof(double), hipDeviceMallocFinegrained));
+    HIPCHK(p2p.my_flags.reserve(p2p_flag_bytes(nr) / sizeof(unsigned long long), hipDeviceMallocFinegrained));
     HIPCHK(hipMemset(p2p.my_data, 0, p2p_data_bytes(nr)));
     HIPCHK(hipMemset(p2p.my_flags, 0, p2p_flag_bytes(nr)));
-    HIPCHK(hipHostMalloc((void**)&p2p.h_status, sizeof(int), hipHostMallocMapped));
+    HIPCHK(p2p.h_status.reserve(1));
     *p2p.h_status = 0;
-    HIPCHK(hipHostGetDevicePointer((void**)&p2p.d_status, p2p.h_status, 0));
-    HIPCHK(hipMalloc((void**)&p2p.d_executed, sizeof(unsigned long long)));
+    HIPCHK(p2p.d_executed.reserve(1));
     HIPCHK(hipMemset(p2p.d_executed, 0, sizeof(unsigned long long)));
     HIPCHK(hipDeviceSynchronize());
     p2p.slots = nr;
@@ -4263,11 +4240,7 @@ struct HipEngine : dla::Engine {
       for (int r = 0; r < nranks && r < P2P_MAX_RANKS; ++r)
         if (r != rank) { if (p2p.data[r]) (void)hipIpcCloseMemHandle(p2p.data[r]); if (p2p.flags[r]) (void)hipIpcCloseMemHandle(p2p.flags[r]); }
     }
-    if (p2p.my_data) (void)hipFree(p2p.my_data);
-    if (p2p.my_flags) (void)hipFree(p2p.my_flags);
-    if (p2p.h_status) (void)hipHostFree(p2p.h_status);
-    if (p2p.d_executed) (void)hipFree(p2p.d_executed);
-    p2p = P2P{};
+    p2p = P2P{};      // (after the peers' handles were closed: this releases the local mailbox)
   }
   int p2p_detach() override { p2p_release(); return DLA_OK; }
   int set_p2p_timeout(int ms) override { p2p_timeout_ms = ms; return DLA_OK; }
@@ -4349,21 +4322,20 @@ struct HipEngine : dla::Engine {
   int pred_want = 0;
   std::vector<SpecRec>* spec_rec = nullptr;
   int spec_tag = 0;
-  OrthoDev* d_ost = nullptr;        // state machine (device)
-  OrthoDev* h_ost = nullptr;        // pinned mirror the tail kernels write
-  OrthoDev* h_ost_dev = nullptr;
-  OrthoDev* h_ost_init = nullptr;   // pinned source of the initial state
-  double* d_wpk = nullptr; double* d_wfull = nullptr; double* d_cpk2 = nullptr;
-  unsigned long long* d_dbg = nullptr;   // $DIAGLIB_AMD_CHAIN_DEBUG: time stamps of the chain's steps
-  double* d_wst = nullptr;          // pending factors of ortho_tail16 (3 x 256 doubles)
-  double* d_xug = nullptr;          // X^T U | U^T U of the last OP_GRAMX / OP_XW sweep: (m + k) x k
+  DeviceBuffer<OrthoDev> d_ost;             // state machine (device)
+  MappedHostBuffer<OrthoDev> h_ost;         // pinned mirror the tail kernels write
+  MappedHostBuffer<OrthoDev> h_ost_init;    // pinned (not mapped) source of the initial state
+  DeviceBuffer<double> d_wpk, d_wfull, d_cpk2;
+  DeviceBuffer<unsigned long long> d_dbg;   // $DIAGLIB_AMD_CHAIN_DEBUG: time stamps of the chain's steps (empty otherwise)
+  DeviceBuffer<double> d_wst;               // pending factors of ortho_tail16 (3 x 256 doubles)
+  DeviceBuffer<double> d_xug;               // X^T U | U^T U of the last OP_GRAMX / OP_XW sweep: (m + k) x k
   static const int XUG_DOUBLES = 640 * 16;
   // RCCL inside a device-driven chain: the collective itself cannot be predicated (it is enqueued by the host), so a launch
   // whose turn it is not still all-reduces whatever its source buffer holds.  Out of place, into these buffers, that is harmless:
   // the source is never scaled, and the tail that would read the result is predicated off like its sweep.
-  double* d_red_small = nullptr; double* d_red_xug = nullptr;
+  DeviceBuffer<double> d_red_small, d_red_xug;
   static const int RED_DOUBLES = 640 * 48;
-  double* h_tpend = nullptr; double* h_tpend_dev = nullptr;   // the factor a drop_final chain left pending (OrthoTailArgs::t_host)
+  MappedHostBuffer<double> h_tpend;  // the factor a drop_final chain left pending (OrthoTailArgs::t_host)
   int t_seq = 0;                     // sequence number of the chain being enqueued
   int t_pending_k = 0;               // > 0: the last chain ended with a k x k factor pending and nobody has fetched it yet
   std::map<long long, std::vector<int>> ortho_history;   // (k, m) -> the sweeps the last call of that shape executed
@@ -4375,25 +4347,27 @@ struct HipEngine : dla::Engine {
   bool tail_fused = false;           // ... and did
   OrthoTailArgs pending_tail{};
 
+  bool chain_buffers_ready = false;
   int ensure_chain_buffers()
   {
-    if (d_ost) return DLA_OK;
+    if (chain_buffers_ready) return DLA_OK;
     bind();
-    HIPCHK(hipMalloc((void**)&d_ost, sizeof(OrthoDev)));
-    HIPCHK(hipHostMalloc((void**)&h_ost, sizeof(OrthoDev), hipHostMallocMapped));
-    HIPCHK(hipHostGetDevicePointer((void**)&h_ost_dev, h_ost, 0));
-    HIPCHK(hipHostMalloc((void**)&h_ost_init, sizeof(OrthoDev), hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&d_wpk, sizeof(double) * 3 * 48 * 16));
-    HIPCHK(hipMalloc((void**)&d_wfull, sizeof(double) * 48 * 48));
-    HIPCHK(hipMalloc((void**)&d_cpk2, (size_t)80 * 1024));
-    HIPCHK(hipMalloc((void**)&d_wst, sizeof(double) * 768));
-    if (chain_debug) { HIPCHK(hipMalloc((void**)&d_dbg, sizeof(unsigned long long) * 48 * 16)); HIPCHK(hipMemsetAsync(d_dbg, 0, sizeof(unsigned long long) * 48 * 16, st)); }
-    HIPCHK(hipMalloc((void**)&d_xug, sizeof(double) * XUG_DOUBLES));
-    HIPCHK(hipHostMalloc((void**)&h_tpend, sizeof(double) * (PEND_HDR + 8), hipHostMallocMapped));
-    HIPCHK(hipHostGetDevicePointer((void**)&h_tpend_dev, h_tpend, 0));
-    h_tpend[PEND_HDR] = 0.0; h_tpend[PEND_HDR + 1] = 0.0; h_tpend[PEND_HDR + 2] = 0.0;
-    HIPCHK(hipMalloc((void**)&d_red_small, sizeof(double) * RED_DOUBLES));
-    HIPCHK(hipMalloc((void**)&d_red_xug, sizeof(double) * RED_DOUBLES));
+    HIPCHK(d_ost.reserve(1));
+    HIPCHK(h_ost.reserve(1));
+    HIPCHK(h_ost_init.reserve(1, false));
+    HIPCHK(d_wpk.reserve(3 * 48 * 16));
+    HIPCHK(d_wfull.reserve(48 * 48));
+    HIPCHK(d_cpk2.reserve((size_t)80 * 1024 / sizeof(double)));
+    HIPCHK(d_wst.reserve(768));
+    if (chain_debug) { const int stz = reserve_zeroed(d_dbg, 48 * 16); if (stz) return stz; }
+    HIPCHK(d_xug.reserve(XUG_DOUBLES));
+    if (!h_tpend) {
+      HIPCHK(h_tpend.reserve(PEND_HDR + 8));
+      h_tpend[PEND_HDR] = 0.0; h_tpend[PEND_HDR + 1] = 0.0; h_tpend[PEND_HDR + 2] = 0.0;
+    }
+    HIPCHK(d_red_small.reserve(RED_DOUBLES));
+    HIPCHK(d_red_xug.reserve(RED_DOUBLES));
+    chain_buffers_ready = true;
     return DLA_OK;
   }
 
@@ -4430,7 +4404,7 @@ struct HipEngine : dla::Engine {
   // come between the two, so the tail is a launch of its own.
   int launch_op(int op, int n, int m, int k, const double* x, const double* bx, double* u, bool publish, int fold)
   {
-    pending_tail = OrthoTailArgs{d_ost, h_ost_dev, d_small, d_wpk, d_wfull, d_cpk2, op, m, k, m > 0 ? 1 : 0, ortho_maxit, publish ? 1 : 0,
+    pending_tail = OrthoTailArgs{d_ost, h_ost.dev(), d_small, d_wpk, d_wfull, d_cpk2, op, m, k, m > 0 ? 1 : 0, ortho_maxit, publish ? 1 : 0,
                                  fold, tune[6] == 7 ? 0 : 1, d_xug, d_wst, d_dbg, chain_xw ? 1 : 0};
     if ((fold == 1 && op == OP_GRAMX) || op == OP_XW || op == OP_COMBOX) pending_tail.gsrc = d_xug;
     pending_tail.x3 = chain_x3 ? 1 : 0;
@@ -4442,7 +4416,7 @@ struct HipEngine : dla::Engine {
     pending_tail.dmat = (policy.basis_exact && fold && m > 0 && dmat_nontrivial && dmat_cols == m && m <= DMAT_LD) ? d_dmat : nullptr;
     pending_tail.dmat_ld = DMAT_LD;
     pending_tail.drop_final = (policy.drop_final && m > 0) ? 1 : 0;
-    pending_tail.t_host = (pending_tail.drop_final && policy.publish_pending && m + k <= PEND_ROWS) ? h_tpend_dev : nullptr;
+    pending_tail.t_host = (pending_tail.drop_final && policy.publish_pending && m + k <= PEND_ROWS) ? h_tpend.dev() : nullptr;
     pending_tail.t_seq = t_seq;
     pending_tail.drop_tol = policy.drop_tol;
     pending_tail.drop_stol = policy.drop_stol;
@@ -4581,12 +4555,7 @@ struct HipEngine : dla::Engine {
       Scope s2(this, DLA_OP_GRAM, 0.0, 0.0, "gram_reduce_kernel");
       const int groups = reduce_groups(blocks);
       const size_t need2 = sizeof(double) * (size_t)n_out * groups * 256;
-      if (need2 > lvl2_bytes) {
-        HIPCHK(hipStreamSynchronize(st));
-        if (d_lvl2) HIPCHK(hipFree(d_lvl2));
-        lvl2_bytes = std::max(need2, (size_t)1 << 20);
-        HIPCHK(hipMalloc((void**)&d_lvl2, lvl2_bytes));
-      }
+      { const int stl = ensure_lvl2(need2); if (stl) return stl; }
       GramReduceArgs ra{d_partial, d_lvl2, d_ticket, cdst, nullptr, blocks, self ? k : m, k, tlw, kt, passes,
                         pred_phase, pred_want, 0, n_out, d_ticket + 4096, OrthoTailArgs{}, P2PArgs{}, extra, self ? k : m + k};
       launch_reduce(ra, dim3(n_out, groups));
@@ -4617,7 +4586,7 @@ struct HipEngine : dla::Engine {
   // ---- the caller's pending blocks on the device (dla_basis_sync): D, upper triangular, column-major with leading dimension
   // DMAT_LD -- what the exact projection of ortho_tail16 multiplies with.  Columns arrive in order, block by block.
   static const int DMAT_LD = T16_ZS_ROWS;
-  double* d_dmat = nullptr;
+  DeviceBuffer<double> d_dmat;
   // the same on the host, column by column (column j: rows 0 .. j) -- what the host-driven loop multiplies with (basis_dd).  The host
   // copy has no width limit: a basis that outgrows the device copy (DMAT_LD columns) goes on with blocks finished in memory by the
   // host-driven loop, exactly, instead of being refused or -- before round 6 -- silently projected against unfinished columns
@@ -4671,10 +4640,7 @@ struct HipEngine : dla::Engine {
     // beyond them stays on the host only -- dla_expand_project sends such a basis through the host-driven loop (round-5 advisor)
     if (m + k > DMAT_LD) return DLA_OK;
     bind();
-    if (!d_dmat) {
-      HIPCHK(hipMalloc((void**)&d_dmat, sizeof(double) * (size_t)DMAT_LD * DMAT_LD));
-      HIPCHK(hipMemsetAsync(d_dmat, 0, sizeof(double) * (size_t)DMAT_LD * DMAT_LD, st));
-    }
+    { const int stz = reserve_zeroed(d_dmat, (size_t)DMAT_LD * DMAT_LD); if (stz) return stz; }
     double* h = nullptr;
     int slot = 0;
     const size_t bytes = sizeof(double) * (size_t)k * DMAT_LD;
@@ -5027,20 +4993,16 @@ struct HipEngine : dla::Engine {
   // ---- b_ortho behind a chain (dla_expand_project_metric): Gram sweep U^T BU, k x k step on the device, the two updates
   // predicated on its outcome; nothing waits.  b_ortho_ahead_status() after the caller's next host wait: 1 done, 0 did not run
   // (the chain in front of it had not ended well: the caller repeats everything behind the chain), -1 metric not positive definite.
-  int* d_bgo = nullptr; int* h_bstat = nullptr; int* h_bstat_dev = nullptr; double* d_wpk_b = nullptr;
+  DeviceBuffer<int> d_bgo; MappedHostBuffer<int> h_bstat; DeviceBuffer<double> d_wpk_b;
   int b_seq = 0;
   int b_ortho_ahead(int n, int k, double* u, double* bu, bool behind_chain, int* handled) override
   {
     *handled = 0;
     if (k <= 0 || k > 48 || hook || local_only || tune[6] == 11) return DLA_OK;
     bind();
-    if (!d_bgo) {
-      HIPCHK(hipMalloc((void**)&d_bgo, sizeof(int)));
-      HIPCHK(hipMemsetAsync(d_bgo, 0, sizeof(int), st));
-      HIPCHK(hipHostMalloc((void**)&h_bstat, sizeof(int), hipHostMallocMapped));
-      HIPCHK(hipHostGetDevicePointer((void**)&h_bstat_dev, h_bstat, 0));
-      HIPCHK(hipMalloc((void**)&d_wpk_b, sizeof(double) * 3 * 48 * 16));
-    }
+    { const int stz = reserve_zeroed(d_bgo, 1); if (stz) return stz; }
+    HIPCHK(h_bstat.reserve(1));
+    HIPCHK(d_wpk_b.reserve(3 * 48 * 16));
     int stc = ensure_chain_buffers();
     if (stc) return stc;
     // M = U^T (B U): every rank's share summed like any other small product
@@ -5050,7 +5012,7 @@ struct HipEngine : dla::Engine {
     *h_bstat = 0;
     {
       Scope s(this, DLA_OP_GRAM, 0.0, 0.0, "bortho_tail_kernel");
-      BOrthoTailArgs ta{d_ost, d_small, d_wpk_b, k, behind_chain ? 1 : 0, b_seq, d_bgo, h_bstat_dev};
+      BOrthoTailArgs ta{d_ost, d_small, d_wpk_b, k, behind_chain ? 1 : 0, b_seq, d_bgo, h_bstat.dev()};
       DLA_LAUNCH(bortho_tail_kernel, dim3(1), dim3(64), 0, st, ta);
       HIPCHK(hipGetLastError());
     }
@@ -5229,14 +5191,9 @@ struct HipEngine : dla::Engine {
       Scope s2(this, cls, 0.0, 0.0, "gram_reduce_kernel");
       const int groups = reduce_groups(blocks_per_pass);
       const size_t need2 = sizeof(double) * (size_t)passes * slots * groups * 256;
-      if (need2 > lvl2_bytes) {
-        HIPCHK(hipStreamSynchronize(st));
-        if (d_lvl2) HIPCHK(hipFree(d_lvl2));
-        lvl2_bytes = std::max(need2, (size_t)1 << 20);
-        HIPCHK(hipMalloc((void**)&d_lvl2, lvl2_bytes));
-      }
+      { const int stl = ensure_lvl2(need2); if (stl) return stl; }
       if (passes * slots > 4096) { err = "gram: too many output tiles"; return DLA_ERR_ARG; }
-      GramReduceArgs ra{d_partial, d_lvl2, d_ticket, d_small + small_off, pred_phase ? nullptr : h_small_dev + small_off, blocks_per_pass, l, k, tlw, kt, px,
+      GramReduceArgs ra{d_partial, d_lvl2, d_ticket, d_small + small_off, pred_phase ? nullptr : h_small.dev() + small_off, blocks_per_pass, l, k, tlw, kt, px,
                         pred_phase, pred_want, 0, passes * slots, d_ticket + 4096, OrthoTailArgs{}};
       launch_reduce(ra, dim3(passes * slots, groups));
     }
@@ -5249,7 +5206,7 @@ struct HipEngine : dla::Engine {
   // C(:, c0 : c0 + kc) = X^T U_chunk is enqueued behind the uploads issued so far and lands in its columns of the l x k result;
   // the sweep runs while the caller's routine works on the next chunk.  gram_chunks_collect waits once for all of them.
   size_t small_off = 0;              // element offset of the result of the Gram being launched inside d_small / h_small
-  hipEvent_t ev_chunk = nullptr;
+  Event ev_chunk;
   bool gram_chunks_ok(int n, int l, int k) override
   {
     (void)n;
@@ -5258,7 +5215,7 @@ struct HipEngine : dla::Engine {
   int gram_chunk(int n, int l, const double* x, int k_total, int c0, int kc, const double* u_chunk) override
   {
     if (c0 == 0) { int stc = ensure_small(sizeof(double) * (size_t)l * k_total); if (stc) return stc; }
-    if (!ev_chunk) HIPCHK(hipEventCreateWithFlags(&ev_chunk, hipEventDisableTiming));
+    HIPCHK(ev_chunk.ensure(hipEventDisableTiming));
     HIPCHK(hipEventRecord(ev_chunk, st_up));
     HIPCHK(hipStreamWaitEvent(st, ev_chunk, 0));
     small_off = (size_t)c0 * l;
@@ -5316,13 +5273,8 @@ struct HipEngine : dla::Engine {
     const int kt = (k + 15) / 16;
     const int groups = reduce_groups(fused_blocks);
     const size_t need2 = sizeof(double) * (size_t)kt * kt * groups * 256;
-    if (need2 > lvl2_bytes) {
-      HIPCHK(hipStreamSynchronize(st));
-      if (d_lvl2) HIPCHK(hipFree(d_lvl2));
-      lvl2_bytes = std::max(need2, (size_t)1 << 20);
-      HIPCHK(hipMalloc((void**)&d_lvl2, lvl2_bytes));
-    }
-    GramReduceArgs ra{d_partial, d_lvl2, d_ticket, d_small, pred_phase ? nullptr : h_small_dev, fused_blocks, k, k, kt, kt, 1,
+    { const int stl = ensure_lvl2(need2); if (stl) return stl; }
+    GramReduceArgs ra{d_partial, d_lvl2, d_ticket, d_small, pred_phase ? nullptr : h_small.dev(), fused_blocks, k, k, kt, kt, 1,
                       pred_phase, pred_want, 0, kt * kt, d_ticket + 4096, OrthoTailArgs{}};
     {
       Scope s2(this, DLA_OP_GRAM, 0.0, 0.0, "gram_reduce_kernel");
@@ -5429,11 +5381,9 @@ struct HipEngine : dla::Engine {
   {
     bind();
     const size_t cnt = (size_t)kt * l4 * 16;
-    if (sizeof(double) * cnt > cpk_bytes) {
+    if (cnt > d_cpk.capacity()) {
       HIPCHK(hipStreamSynchronize(st));
-      if (d_cpk) HIPCHK(hipFree(d_cpk));
-      cpk_bytes = std::max(sizeof(double) * cnt, (size_t)1 << 16);
-      HIPCHK(hipMalloc((void**)&d_cpk, cpk_bytes));
+      HIPCHK(d_cpk.reserve(std::max(cnt, doubles((size_t)1 << 16))));
     }
     double* pk = nullptr;                    // packed straight into the pinned slot
     int slot = 0;
@@ -5626,17 +5576,16 @@ struct HipEngine : dla::Engine {
     if (k <= 48) return gemm_cols(n, k, u, k, w_host, ld, u, 2, DLA_OP_TRMM);
     // wide block (cold path: the drivers never exceed n_max columns): W is upper triangular, so column
     // block J of U W needs columns <= max(J) only; go right to left through a scratch panel
-    double* tmp = nullptr;
+    DeviceBuffer<double> tmp;
     bind();
-    HIPCHK(hipMalloc((void**)&tmp, sizeof(double) * (size_t)n * 48));
+    HIPCHK(tmp.reserve((size_t)n * 48));
     int stc = DLA_OK;
     for (int j1 = k; j1 > 0 && stc == DLA_OK; j1 -= 48) {
       const int j0 = std::max(0, j1 - 48), kc = j1 - j0;
       stc = gemm_cols(n, j1, u, kc, w_host + (size_t)j0 * ld, ld, tmp, 0, DLA_OP_TRMM);
       if (stc == DLA_OK) stc = d2d(u + (size_t)j0 * n, tmp, sizeof(double) * (size_t)n * kc);
     }
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(tmp);
+    (void)hipStreamSynchronize(st);          // before tmp goes out of scope
     return stc;
   }
 
@@ -5833,7 +5782,7 @@ struct HipEngine : dla::Engine {
     {
       Scope s2(this, DLA_OP_RITZ, 0.0, 0.0, "ritz_reduce_kernel");
       DLA_LAUNCH(ritz_reduce_kernel, dim3(ncol), dim3(256), 0, st, (const double*)d_partial, blocks, ncol, d_small,
-                         h_small_dev, nslots, local_only ? 0 : rank);
+                         h_small.dev(), nslots, local_only ? 0 : rank);
     }
     HIPCHK(hipGetLastError());
     // sums and all ranks' maxima in one collective (reference :1730-1731 are two reductions)
@@ -5901,7 +5850,7 @@ struct HipEngine : dla::Engine {
     {
       Scope s2(this, DLA_OP_RITZ, 0.0, 0.0, "ritz_reduce_kernel");
       DLA_LAUNCH(ritz_reduce_kernel, dim3(ncol), dim3(256), 0, st, (const double*)d_partial, blocks, ncol, d_small,
-                         h_small_dev, nslots, local_only ? 0 : rank);
+                         h_small.dev(), nslots, local_only ? 0 : rank);
     }
     HIPCHK(hipGetLastError());
     exchange_fused = false;
@@ -5968,7 +5917,7 @@ struct HipEngine : dla::Engine {
     {
       Scope s(this, DLA_OP_ELEM, 8.0 * (double)len, 2.0 * (double)len);
       DLA_LAUNCH(sumsq_kernel, dim3(blocks), dim3(256), 0, st, len, x, d_partial);
-      DLA_LAUNCH(sum_partials_kernel, dim3(1), dim3(256), 0, st, (const double*)d_partial, blocks, d_small, h_small_dev);
+      DLA_LAUNCH(sum_partials_kernel, dim3(1), dim3(256), 0, st, (const double*)d_partial, blocks, d_small, h_small.dev());
     }
     HIPCHK(hipGetLastError());
     exchange_fused = false;
@@ -5991,8 +5940,21 @@ struct HipEngine : dla::Engine {
   }
 
   // ---- sample sparse operator (ELLPACK)
-  int* d_ell_col = nullptr; double* d_ell_val = nullptr; double* d_ell_diag = nullptr;
+  DeviceBuffer<int> d_ell_col; DeviceBuffer<double> d_ell_val, d_ell_diag;
   int ell_n = 0, ell_w = 0;
+  // replace the operator on the device (both set-up routines end here); the caller has bound the device.  The arrays only grow:
+  // a smaller operator after a larger one keeps the larger blocks (the kernels go by ell_n / ell_w); the same holds for synth_setup
+  int upload_ell(const std::vector<int>& col, const std::vector<double>& val, const std::vector<double>& diag)
+  {
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(d_ell_col.reserve(col.size()));
+    HIPCHK(d_ell_val.reserve(val.size()));
+    HIPCHK(d_ell_diag.reserve(diag.size()));
+    HIPCHK(hipMemcpy(d_ell_col, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_ell_val, val.data(), sizeof(double) * val.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_ell_diag, diag.data(), sizeof(double) * diag.size(), hipMemcpyHostToDevice));
+    return DLA_OK;
+  }
   int spmm_setup_csr(int n, const long long* rowptr, const int* colind, const double* values) override
   {
     if (n <= 0 || !rowptr || !colind || !values) { err = "spmm_setup_csr: bad arguments"; return DLA_ERR_ARG; }
@@ -6013,23 +5975,14 @@ struct HipEngine : dla::Engine {
       }
     }
     HIPCHK(hipSetDevice(device));
-    HIPCHK(hipStreamSynchronize(st));
-    if (d_ell_col) HIPCHK(hipFree(d_ell_col));
-    if (d_ell_val) HIPCHK(hipFree(d_ell_val));
-    if (d_ell_diag) HIPCHK(hipFree(d_ell_diag));
-    HIPCHK(hipMalloc((void**)&d_ell_col, sizeof(int) * col.size()));
-    HIPCHK(hipMalloc((void**)&d_ell_val, sizeof(double) * val.size()));
-    HIPCHK(hipMalloc((void**)&d_ell_diag, sizeof(double) * diag.size()));
-    HIPCHK(hipMemcpy(d_ell_col, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_ell_val, val.data(), sizeof(double) * val.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_ell_diag, diag.data(), sizeof(double) * diag.size(), hipMemcpyHostToDevice));
+    { const int stc = upload_ell(col, val, diag); if (stc) return stc; }
     ell_n = n; ell_w = w; ell_sharded = false; ell_halo = 0;
     return DLA_OK;
   }
   // ---- ... on a row shard (banded matrices: the columns of a shard reach at most `halo` rows into its neighbours)
   int ell_halo = 0;                  // rows exchanged with each neighbour; 0 = the operator is not sharded
   bool ell_sharded = false;
-  double* d_halo = nullptr; size_t halo_doubles = 0;
+  DeviceBuffer<double> d_halo;
   std::vector<double> h_halo;        // host mirror for the hook transport
   // all-reduce of a few host values through the engine's small-product transport (setup-time agreement between the ranks)
   bool has_transport() const override { return hook != nullptr || comm != nullptr || p2p.on; }
@@ -6091,17 +6044,8 @@ struct HipEngine : dla::Engine {
     dla::ShardedEll e;
     dla::sharded_ell_build(n, row0, rowptr, colind, values, (int)halo, e);
     bind();
-    HIPCHK(hipStreamSynchronize(st));
-    if (d_ell_col) HIPCHK(hipFree(d_ell_col));
-    if (d_ell_val) HIPCHK(hipFree(d_ell_val));
-    if (d_ell_diag) HIPCHK(hipFree(d_ell_diag));
-    d_ell_col = nullptr; d_ell_val = nullptr; d_ell_diag = nullptr;
-    HIPCHK(hipMalloc((void**)&d_ell_col, sizeof(int) * e.col.size()));
-    HIPCHK(hipMalloc((void**)&d_ell_val, sizeof(double) * e.val.size()));
-    HIPCHK(hipMalloc((void**)&d_ell_diag, sizeof(double) * e.diag.size()));
-    HIPCHK(hipMemcpy(d_ell_col, e.col.data(), sizeof(int) * e.col.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_ell_val, e.val.data(), sizeof(double) * e.val.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_ell_diag, e.diag.data(), sizeof(double) * e.diag.size(), hipMemcpyHostToDevice));
+    stc = upload_ell(e.col, e.val, e.diag);
+    if (stc) return stc;
     ell_n = n; ell_w = e.w; ell_halo = (int)halo; ell_sharded = true;
     return DLA_OK;
   }
@@ -6113,15 +6057,12 @@ struct HipEngine : dla::Engine {
     int mc = m;
     if (H > 0 && nr > 1) mc = std::max(1, std::min(m, P2P_MAX_DOUBLES / (nr * 2 * H)));
     const size_t need = (size_t)std::max(1, nr * 2 * mc * std::max(1, H));
-    if (need > halo_doubles) {
+    if (need > d_halo.capacity()) {
       HIPCHK(hipStreamSynchronize(st));
-      if (d_halo) HIPCHK(hipFree(d_halo));
-      d_halo = nullptr;
-      HIPCHK(hipMalloc((void**)&d_halo, sizeof(double) * need));
+      HIPCHK(d_halo.reserve(need));
       // (on the engine's stream: hipMemset runs on the null stream, which this non-blocking stream does not wait for -- the
       //  zeros would land in the middle of the first exchange)
       HIPCHK(hipMemsetAsync(d_halo, 0, sizeof(double) * need, st));
-      halo_doubles = need;
       h_halo.assign(need, 0.0);
     }
     for (int c0 = 0; c0 < m; c0 += mc) {
@@ -6173,13 +6114,10 @@ struct HipEngine : dla::Engine {
     if (rank_w != 4) { err = "synth operator: rank_w must be 4"; return DLA_ERR_ARG; }
     bind();
     HIPCHK(hipStreamSynchronize(st));
-    if (d_w) HIPCHK(hipFree(d_w));
-    if (d_diag) HIPCHK(hipFree(d_diag));
-    if (d_wsq) HIPCHK(hipFree(d_wsq));
-    if (!d_t) HIPCHK(hipMalloc((void**)&d_t, sizeof(double) * 4 * 64));
-    HIPCHK(hipMalloc((void**)&d_w, sizeof(double) * (size_t)n_local * rank_w));
-    HIPCHK(hipMalloc((void**)&d_diag, sizeof(double) * (size_t)n_local));
-    HIPCHK(hipMalloc((void**)&d_wsq, sizeof(double) * (size_t)n_local));
+    HIPCHK(d_t.reserve(4 * 64));
+    HIPCHK(d_w.reserve((size_t)n_local * rank_w));
+    HIPCHK(d_diag.reserve((size_t)n_local));
+    HIPCHK(d_wsq.reserve((size_t)n_local));
     syn_row0 = row0; syn_n = n_local; syn_rw = rank_w; syn_sigma = sigma;
     DLA_LAUNCH(synth_build_kernel, dim3((n_local + 255) / 256), dim3(256), 0, st, row0, n_local, rank_w, sigma, d_w, d_diag, d_wsq);
     HIPCHK(hipGetLastError());

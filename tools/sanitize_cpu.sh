@@ -16,10 +16,11 @@ out=profiles/r06/sanitizer_cpu.txt
 mkdir -p profiles/r06
 {
   echo "# $(date -u +%FT%TZ)  gcc $(gcc -dumpversion), -fsanitize=address,undefined -fno-sanitize-recover=undefined -O1 -g"
-  echo "# instrumented: diaglib_amd/csrc/host_logic.cpp, diaglib_amd/csrc/smalldense.cpp, oracle/hostsim_engine.cpp, oracle/oracle.c, oracle/oracle_ops.c"
+  echo "# instrumented: diaglib_amd/csrc/host_logic.cpp, diaglib_amd/csrc/smalldense.cpp, oracle/hostsim_engine.cpp, oracle/oracle.c, oracle/oracle_ops.c, tests/owned_buffers_driver.cpp (diaglib_amd/csrc/hip_owned.h)"
   echo "# ASAN_OPTIONS=$ASAN_OPTIONS  UBSAN_OPTIONS=$UBSAN_OPTIONS"
 } > "$out"
 python -m pytest tests/test_host_dense.py tests/test_hostsim.py tests/test_ortho_qr.py tests/test_lr.py tests/test_trace_text.py tests/test_spmm_sharded.py \
+       tests/test_owned_buffers.py \
        -q -m "not gpu" -p no:cacheprovider "$@" 2>&1 | tee -a "$out"
 rc=${PIPESTATUS[0]}
 echo "# exit code $rc; sanitizer reports in the output above: $(grep -c 'ERROR: AddressSanitizer\|runtime error:' "$out")" >> "$out"

@@ -3592,9 +3592,9 @@ __global__ __launch_bounds__(256) void gram_reduce_kernel(GramReduceArgs a)
 // host side of the engine
 // ======================================================================================
 struct TimedLaunch { hipEvent_t a, b; int cls; std::string kname; };
-// every launch of the engine goes through here: a dry run (HipEngine::dry_launch) walks the launch paths -- shape decisions,
+// every launch of the engine goes through here: a dry run (HipEngine::LaunchCtx::dry) walks the launch paths -- shape decisions,
 // workspace growth, requests for more than 64 KiB of LDS -- without launching anything
-#define DLA_LAUNCH(...) do { if (!dry_launch) hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+#define DLA_LAUNCH(...) do { if (!lc.dry) hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 
 struct HipEngine : dla::Engine {
   int device = 0;
@@ -3653,7 +3653,37 @@ struct HipEngine : dla::Engine {
 
   const char* name() const override { return nm.c_str(); }
   void* stream() override { return (void*)st; }
-  bool dry_launch = false;           // see DLA_LAUNCH
+
+  // What the launches of the current step are enqueued under.  Nothing a launch depends on is a bare engine member: a caller
+  // installs a modified copy with CtxScope, which puts back what was there before on every way out.  Outside any scope the
+  // context is this default: unpredicated, not dry, nothing fused.
+  struct LaunchCtx {
+    const int* phase = nullptr;      // predicate of the launches (device-driven chains): run only if *phase == want; nullptr = always
+    int want = 0;
+    std::vector<SpecRec>* rec = nullptr;   // speculative launches are booked here under `tag` instead of the statistics (Scope)
+    int tag = 0;
+    bool dry = false;                // see DLA_LAUNCH
+    bool fuse_tail = false;          // the reduction of this step may run `tail` in its last block (launch_reduce)
+    OrthoTailArgs tail{};
+    bool xw = false;                 // the chain may use the storing sweep OP_XW for its wide block (ortho_tail)
+    bool x3 = false;                 // the chain runs the three-pass schedule (OP_COMBOX / OP_CLOSE, ortho_tail16)
+    size_t small_off = 0;            // element offset of a Gram's result inside d_small / h_small ...
+    bool in_chunk = false;           // ... which is a column chunk of a larger result: one rank only (gram_chunk)
+  } lc;
+  struct CtxScope {
+    HipEngine* e; LaunchCtx saved;
+    CtxScope(HipEngine* e_, const LaunchCtx& c) : e(e_), saved(e_->lc) { e->lc = c; }
+    ~CtxScope() { e->lc = saved; }
+    CtxScope(const CtxScope&) = delete;
+    CtxScope& operator=(const CtxScope&) = delete;
+  };
+  // What an enqueued step reports back; it lives in the frame of whoever asked for the step.
+  struct StepOut {
+    bool tail_fused = false;         // the reduction ran the chain's tail in its last block
+    double* summed_at = nullptr;     // the cross-rank sum went out of place, to this buffer (RCCL inside a chain); nullptr: in place
+    bool mirror_fresh = false;       // the cross-rank sum already wrote the pinned mirror h_small (peer-to-peer exchange)
+    bool lower_only = false;         // a Gram formed only the lower block triangle of its result
+  };
 
   ~HipEngine() override
   {
@@ -3720,10 +3750,10 @@ struct HipEngine : dla::Engine {
     Scope(HipEngine* e_, int cls_, double bytes, double flops, const std::string& kname_ = std::string()) : e(e_), cls(cls_), kname(kname_)
     {
       e->bind();
-      if (e->dry_launch) return;
-      if (e->spec_rec) {
+      if (e->lc.dry) return;
+      if (e->lc.rec) {
         // speculative launch of a device-driven chain: counted after the read-back, if the device executed it
-        e->spec_rec->push_back({e->spec_tag, cls_, kname_, bytes, flops});
+        e->lc.rec->push_back({e->lc.tag, cls_, kname_, bytes, flops});
         if (e->profile) { a = e->get_event(); b = e->get_event(); (void)hipEventRecord(a, e->st); }
         return;
       }
@@ -3744,7 +3774,7 @@ struct HipEngine : dla::Engine {
     }
     ~Scope()
     {
-      if (e->dry_launch) return;
+      if (e->lc.dry) return;
       if (e->trace) {
         hipError_t er = hipStreamSynchronize(e->st);
         timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -4044,14 +4074,12 @@ struct HipEngine : dla::Engine {
   }
 
   // reduced small result -> host: single rank reads the pinned mirror the kernel wrote,
-  // multi-rank copies the all-reduced device buffer
-  bool mirror_fresh = false;         // the last cross-rank sum already wrote h_small (peer-to-peer exchange)
-  int small_to_host(size_t count)
+  // multi-rank copies the all-reduced device buffer, unless the cross-rank sum already wrote the mirror (StepOut::mirror_fresh)
+  int small_to_host(size_t count, bool mirror_fresh)
   {
     DLA_T("  wait for a small result");
     if (!local_only && (nranks > 1 || comm || p2p.on) && !mirror_fresh)
       HIPCHK(hipMemcpyAsync(h_small, d_small, sizeof(double) * count, hipMemcpyDeviceToHost, st));
-    mirror_fresh = false;
     int stw = wait_stream();
     if (stw) return stw;
     stats.host_syncs++;
@@ -4109,17 +4137,18 @@ struct HipEngine : dla::Engine {
   }
 
   // ---- collectives on small device buffers
-  int allreduce_dev(double* dev, int count, int op /*0 sum, 1 max*/, double* host_mirror)
+  // exchanged: the reduction kernel that produced `dev` carried the cross-rank sum already (launch_reduce)
+  int allreduce_dev(double* dev, int count, int op /*0 sum, 1 max*/, double* host_mirror, StepOut& out, bool exchanged = false)
   {
+    out.summed_at = nullptr; out.mirror_fresh = false;
     if (local_only || (nranks <= 1 && !comm && !p2p.on)) return DLA_OK;
-    if (dry_launch) return DLA_OK;
+    if (lc.dry) return DLA_OK;
     stats.allreduces++;
-    mirror_fresh = false;
     if (p2p.on && count <= P2P_MAX_DOUBLES) {
-      if (exchange_fused) { exchange_fused = false; return DLA_OK; }   // the reduction kernel did it (launch_reduce)
+      if (exchanged) return DLA_OK;
       P2PArgs pa = p2p_args(dev, count, op);
       // outside the device-driven chains the host reads the result next: the exchange writes the pinned mirror itself
-      if (!pred_phase && dev == d_small && host_mirror == h_small) { pa.buf_host = h_small.dev(); mirror_fresh = true; }
+      if (!lc.phase && dev == d_small && host_mirror == h_small) { pa.buf_host = h_small.dev(); out.mirror_fresh = true; }
       Scope s(this, DLA_OP_ELEM, 0.0, 0.0, "p2p_allreduce_kernel");
       DLA_LAUNCH(p2p_allreduce_kernel, dim3(1), dim3(256), 0, st, pa);
       HIPCHK(hipGetLastError());
@@ -4128,9 +4157,8 @@ struct HipEngine : dla::Engine {
     if (comm) {
       // inside a chain: out of place (see d_red_small), the tail reads the destination
       double* dst = dev;
-      if (pred_phase && d_red_small && count <= RED_DOUBLES && (dev == d_small || dev == d_xug)) dst = (dev == d_xug) ? d_red_xug : d_red_small;
-      chain_reduced = (dst != dev);
-      chain_red_dst = dst;
+      if (lc.phase && d_red_small && count <= RED_DOUBLES && (dev == d_small || dev == d_xug)) dst = (dev == d_xug) ? d_red_xug : d_red_small;
+      if (dst != dev) out.summed_at = dst;
       ncclResult_t r = ncclAllReduce(dev, dst, (size_t)count, ncclDouble, op == 0 ? ncclSum : ncclMax, comm, st);
       if (r != ncclSuccess) { err = std::string("ncclAllReduce: ") + ncclGetErrorString(r); return DLA_ERR_COMM; }
       return DLA_OK;
@@ -4146,21 +4174,23 @@ struct HipEngine : dla::Engine {
     err = "nranks > 1 but neither an RCCL communicator nor a reduction hook is attached";
     return DLA_ERR_COMM;
   }
+  // the cross-rank sum of d_small and its copy to the host
+  int sum_to_host(int count, int op)
+  {
+    StepOut out;
+    const int stc = allreduce_dev(d_small, count, op, h_small, out);
+    return stc ? stc : small_to_host((size_t)count, out.mirror_fresh);
+  }
   P2PArgs p2p_args(double* dev, int count, int op)
   {
     P2PArgs pa{};
     pa.buf = dev; pa.buf_host = nullptr; pa.count = count; pa.op = op; pa.nranks = nranks; pa.rank = rank;
     pa.executed = p2p.d_executed;
     for (int r = 0; r < nranks; ++r) { pa.data[r] = p2p.data[r]; pa.flags[r] = p2p.flags[r]; }
-    pa.status = p2p.h_status.dev(); pa.phase = pred_phase; pa.want = pred_want;
+    pa.status = p2p.h_status.dev(); pa.phase = lc.phase; pa.want = lc.want;
     pa.timeout_ticks = (unsigned long long)std::max(0, p2p_timeout_ms) * 100000ULL;
     return pa;
   }
-  bool exchange_fused = false;       // the reduction just enqueued carries the cross-rank sum (gram_reduce_kernel<true>)
-  bool chain_reduced = false;        // the last RCCL all-reduce of a chain went out of place (d_red_small / d_red_xug)
-  double* chain_red_dst = nullptr;   // ... to this buffer
-  bool chain_xw = false;             // the chain being enqueued may use the storing sweep OP_XW for its wide block (ortho_tail)
-  bool chain_x3 = false;             // the chain being enqueued runs the three-pass schedule (OP_COMBOX / OP_CLOSE, ortho_tail16)
   static const int X3_COOLDOWN_START = 2;
   int x3_cooldown = X3_COOLDOWN_START;   // > 0: a recent chain needed a level shift (or the solve is new: no evidence yet) -- that many
                                      // chains run the five-sweep schedule.  Reset at every driver call (begin_solve): the schedule of
@@ -4318,10 +4348,6 @@ struct HipEngine : dla::Engine {
   }
 
   // ---- device-driven orthogonalisation chain (see ortho_tail_kernel)
-  const int* pred_phase = nullptr;   // predicate of the launches being enqueued (nullptr = unconditional)
-  int pred_want = 0;
-  std::vector<SpecRec>* spec_rec = nullptr;
-  int spec_tag = 0;
   DeviceBuffer<OrthoDev> d_ost;             // state machine (device)
   MappedHostBuffer<OrthoDev> h_ost;         // pinned mirror the tail kernels write
   MappedHostBuffer<OrthoDev> h_ost_init;    // pinned (not mapped) source of the initial state
@@ -4338,14 +4364,23 @@ struct HipEngine : dla::Engine {
   MappedHostBuffer<double> h_tpend;  // the factor a drop_final chain left pending (OrthoTailArgs::t_host)
   int t_seq = 0;                     // sequence number of the chain being enqueued
   int t_pending_k = 0;               // > 0: the last chain ended with a k x k factor pending and nobody has fetched it yet
-  std::map<long long, std::vector<int>> ortho_history;   // (k, m) -> the sweeps the last call of that shape executed
-  std::set<long long> chain_verified;                    // shapes whose launch paths have been walked (see ortho_chain)
+  // What tells two chains apart.  Plans are remembered per shape with wide_gramx and dropf (vsx follows from m there); the walked
+  // launch paths depend on neither, so chain_verified keeps those two fields false; kind() forgets the basis width.
+  struct ChainShape {
+    int k = 0, m = 0, fold = 0;
+    bool vsx = false, wide_gramx = false, wide_xw = false, dropf = false, x3 = false;
+    bool operator<(const ChainShape& o) const
+    {
+      return std::tie(k, m, fold, vsx, wide_gramx, wide_xw, dropf, x3) < std::tie(o.k, o.m, o.fold, o.vsx, o.wide_gramx, o.wide_xw, o.dropf, o.x3);
+    }
+    ChainShape kind() const { ChainShape s = *this; s.m = 0; return s; }
+  };
+  std::map<ChainShape, std::vector<int>> plan_of_shape;   // the sweeps the last chain of that shape executed
+  std::map<ChainShape, std::vector<int>> plan_of_kind;    // ... the most recent chain of that kind() and width, whatever its m
+  std::set<ChainShape> chain_verified;                    // shapes whose launch paths have been walked (see ortho_chain)
 
   bool chain_armed = false;          // the device state machine stands at its initial state
   const bool chain_debug = std::getenv("DIAGLIB_AMD_CHAIN_DEBUG") != nullptr;   // print every chain's plan and outcome
-  bool fuse_tail = false;            // the reduction being enqueued may run the tail in its last block
-  bool tail_fused = false;           // ... and did
-  OrthoTailArgs pending_tail{};
 
   bool chain_buffers_ready = false;
   int ensure_chain_buffers()
@@ -4378,20 +4413,42 @@ struct HipEngine : dla::Engine {
     const int per = tune[7] == 22 ? 16 : tune[7] == 23 ? 64 : 32;
     return std::max(1, std::min(32, (nblk + per - 1) / per));
   }
-  void launch_reduce(GramReduceArgs& ra, dim3 grid)
+  struct Rode { bool tail = false, exchange = false; };   // what went along in a reduction kernel: the chain's tail, the cross-rank sum
+  Rode launch_reduce(GramReduceArgs& ra, dim3 grid)
   {
-    exchange_fused = false;
+    Rode rode;
     if (ra.ldc == 0) ra.ldc = ra.l;
     ra.fenced = tune[5] == 3 ? 1 : 0;
-    if (fuse_tail && p2p.on && ra.ldc * ra.k > P2P_MAX_DOUBLES) fuse_tail = false;   // beyond a mailbox slot: separate launches
-    if (fuse_tail) {
-      ra.do_tail = 1; ra.tail = pending_tail; tail_fused = true;
+    rode.tail = lc.fuse_tail && !(p2p.on && ra.ldc * ra.k > P2P_MAX_DOUBLES);   // beyond a mailbox slot: separate launches
+    if (rode.tail) {
+      ra.do_tail = 1; ra.tail = lc.tail;
       ra.p2p = P2PArgs{};
-      if (p2p.on) { ra.p2p = p2p_args(ra.c, ra.ldc * ra.k, 0); exchange_fused = true; }
+      if (p2p.on) { ra.p2p = p2p_args(ra.c, ra.ldc * ra.k, 0); rode.exchange = true; }
       DLA_LAUNCH(gram_reduce_kernel<true>, grid, dim3(256), 0, st, ra);
     } else {
       DLA_LAUNCH(gram_reduce_kernel<false>, grid, dim3(256), 0, st, ra);
     }
+    return rode;
+  }
+  // Second stage of every Gram: the per-block partials in d_partial -> c (l x k, leading dimension ldc, 0 = l; `extra`: see
+  // GramReduceArgs), then the cross-rank sum of c unless the kernel carried it or the result is a column chunk of one rank.
+  int reduce_and_sum(int cls, double* c, double* c_host, int nblk, int l, int k, int tlw, int kt, int px, int n_out, int extra, int ldc,
+                     StepOut& out)
+  {
+    Rode rode;
+    {
+      Scope s2(this, cls, 0.0, 0.0, "gram_reduce_kernel");
+      const int groups = reduce_groups(nblk);
+      { const int stl = ensure_lvl2(sizeof(double) * (size_t)n_out * groups * 256); if (stl) return stl; }
+      if (n_out > 4096) { err = "gram: too many output tiles"; return DLA_ERR_ARG; }     // (d_ticket holds one word per output tile)
+      GramReduceArgs ra{d_partial, d_lvl2, d_ticket, c, c_host, nblk, l, k, tlw, kt, px,
+                        lc.phase, lc.want, 0, n_out, d_ticket + 4096, OrthoTailArgs{}, P2PArgs{}, extra, ldc};
+      rode = launch_reduce(ra, dim3(n_out, groups));
+    }
+    HIPCHK(hipGetLastError());
+    out.tail_fused = rode.tail;
+    if (lc.in_chunk) return DLA_OK;
+    return allreduce_dev(c, (ldc ? ldc : l) * k, 0, h_small, out, rode.exchange);
   }
   void launch_tail_kernel(const OrthoTailArgs& ta)
   {
@@ -4404,62 +4461,65 @@ struct HipEngine : dla::Engine {
   // come between the two, so the tail is a launch of its own.
   int launch_op(int op, int n, int m, int k, const double* x, const double* bx, double* u, bool publish, int fold)
   {
-    pending_tail = OrthoTailArgs{d_ost, h_ost.dev(), d_small, d_wpk, d_wfull, d_cpk2, op, m, k, m > 0 ? 1 : 0, ortho_maxit, publish ? 1 : 0,
-                                 fold, tune[6] == 7 ? 0 : 1, d_xug, d_wst, d_dbg, chain_xw ? 1 : 0};
-    if ((fold == 1 && op == OP_GRAMX) || op == OP_XW || op == OP_COMBOX) pending_tail.gsrc = d_xug;
-    pending_tail.x3 = chain_x3 ? 1 : 0;
+    OrthoTailArgs tail{d_ost, h_ost.dev(), d_small, d_wpk, d_wfull, d_cpk2, op, m, k, m > 0 ? 1 : 0, ortho_maxit, publish ? 1 : 0,
+                       fold, tune[6] == 7 ? 0 : 1, d_xug, d_wst, d_dbg, lc.xw ? 1 : 0};
+    if ((fold == 1 && op == OP_GRAMX) || op == OP_XW || op == OP_COMBOX) tail.gsrc = d_xug;
+    tail.x3 = lc.x3 ? 1 : 0;
     // (knob 6 = 15: A/B, the first factor from U^T U as the reference's; 16: A/B, level shifts on the projected block's Gram matrix
     //  instead of the reference's order for a numerically rank-deficient block -- 14.2-14.36 against 14.37-14.46 ms on the benchmark,
     //  but such a block's weakest columns then depend on the schedule, and the reference's dense test matrix with unit guesses takes
     //  another history (tests/test_trace_text.py::dav_n1000_unit fails with it, also when only the drivers' chains use it): not shipped)
-    pending_tail.gp = tune[6] == 15 ? 0 : tune[6] == 16 ? 2 : 1;
-    pending_tail.dmat = (policy.basis_exact && fold && m > 0 && dmat_nontrivial && dmat_cols == m && m <= DMAT_LD) ? d_dmat : nullptr;
-    pending_tail.dmat_ld = DMAT_LD;
-    pending_tail.drop_final = (policy.drop_final && m > 0) ? 1 : 0;
-    pending_tail.t_host = (pending_tail.drop_final && policy.publish_pending && m + k <= PEND_ROWS) ? h_tpend.dev() : nullptr;
-    pending_tail.t_seq = t_seq;
-    pending_tail.drop_tol = policy.drop_tol;
-    pending_tail.drop_stol = policy.drop_stol;
-    fuse_tail = p2p.on ? tune[6] != 4 : (nranks <= 1 && !comm);     // (knob 6 = 4: the exchange as a launch of its own)
-    tail_fused = false;
-    pred_phase = &d_ost->phase;
-    pred_want = (op == OP_GRAMX) ? (int)OP_GRAM_UU : (chain_x3 && op == OP_COMBO) ? (int)OP_COMBOX : op;   // the first sweep answers the start phase
+    tail.gp = tune[6] == 15 ? 0 : tune[6] == 16 ? 2 : 1;
+    tail.dmat = (policy.basis_exact && fold && m > 0 && dmat_nontrivial && dmat_cols == m && m <= DMAT_LD) ? d_dmat : nullptr;
+    tail.dmat_ld = DMAT_LD;
+    tail.drop_final = (policy.drop_final && m > 0) ? 1 : 0;
+    tail.t_host = (tail.drop_final && policy.publish_pending && m + k <= PEND_ROWS) ? h_tpend.dev() : nullptr;
+    tail.t_seq = t_seq;
+    tail.drop_tol = policy.drop_tol;
+    tail.drop_stol = policy.drop_stol;
+    StepOut out;
     int stc = DLA_OK;
-    switch (op) {
-      case OP_GRAM_UU: stc = gram_dev_once(n, k, u, k, u, DLA_OP_GRAM, false); break;
-      case OP_XU:      stc = gram_dev_once(n, m, bx, k, u, DLA_OP_GRAM, false); break;
-      case OP_GRAMX:
-        // one-tile blocks: the WP kernel family; wider blocks: the plain product with [X | U] as the left panel (U follows X)
-        stc = fold == 1 ? gram_wp_once(n, m, bx, k, u, nullptr, nullptr) : gram_dev_once(n, m + k, x, k, u, DLA_OP_GRAM, false);
-        break;
-      case OP_XW:      stc = gram_wp_once(n, m, bx, k, u, d_wpk, u); break;
-      case OP_GRAMW:   stc = gram_wp_once(n, 0, nullptr, k, u, d_wpk, nullptr); break;
-      case OP_TRMMG:
-      case OP_TRMMC:
-        stc = gemm_chunk(n, 0, k, u, k, nullptr, 0, u, 2, DLA_OP_TRMM, true, d_wpk);
-        if (!stc) stc = fused_reduce(k);
-        break;
-      case OP_COMBO:
-        stc = gemm_chunk(n, 0, m + k, x, k, nullptr, 0, u, 0, DLA_OP_GEMM, true, d_cpk2);
-        if (!stc) stc = fused_reduce(k);
-        break;
-      case OP_FINAL:   stc = gemm_chunk(n, 0, k, u, k, nullptr, 0, u, 2, DLA_OP_TRMM, false, d_wpk); break;
-      // three-pass schedule: the projection that measures what it stores, and the closing one that measures nothing
-      case OP_COMBOX:  stc = gram_wp_once(n, m, bx, k, u, nullptr, u, d_cpk2); break;
-      case OP_CLOSE:   stc = gemm_chunk(n, 0, m + k, x, k, nullptr, 0, u, 0, DLA_OP_GEMM, false, d_cpk2); break;
-      default: err = "ortho_chain: bad op"; stc = DLA_ERR_ARG;
+    {
+      LaunchCtx step = lc;
+      step.fuse_tail = p2p.on ? tune[6] != 4 : (nranks <= 1 && !comm);     // (knob 6 = 4: the exchange as a launch of its own)
+      step.tail = tail;
+      step.phase = &d_ost->phase;
+      step.want = (op == OP_GRAMX) ? (int)OP_GRAM_UU : (lc.x3 && op == OP_COMBO) ? (int)OP_COMBOX : op;   // the first sweep answers the start phase
+      CtxScope scope(this, step);
+      int blocks = 0;
+      switch (op) {
+        case OP_GRAM_UU: stc = gram_dev_once(n, k, u, k, u, DLA_OP_GRAM, false, out); break;
+        case OP_XU:      stc = gram_dev_once(n, m, bx, k, u, DLA_OP_GRAM, false, out); break;
+        case OP_GRAMX:
+          // one-tile blocks: the WP kernel family; wider blocks: the plain product with [X | U] as the left panel (U follows X)
+          stc = fold == 1 ? gram_wp_once(n, m, bx, k, u, nullptr, nullptr, out) : gram_dev_once(n, m + k, x, k, u, DLA_OP_GRAM, false, out);
+          break;
+        case OP_XW:      stc = gram_wp_once(n, m, bx, k, u, d_wpk, u, out); break;
+        case OP_GRAMW:   stc = gram_wp_once(n, 0, nullptr, k, u, d_wpk, nullptr, out); break;
+        case OP_TRMMG:
+        case OP_TRMMC:
+          stc = gemm_chunk(n, 0, k, u, k, nullptr, 0, u, 2, DLA_OP_TRMM, &blocks, d_wpk);
+          if (!stc) stc = fused_reduce(k, blocks, out);
+          break;
+        case OP_COMBO:
+          stc = gemm_chunk(n, 0, m + k, x, k, nullptr, 0, u, 0, DLA_OP_GEMM, &blocks, d_cpk2);
+          if (!stc) stc = fused_reduce(k, blocks, out);
+          break;
+        case OP_FINAL:   stc = gemm_chunk(n, 0, k, u, k, nullptr, 0, u, 2, DLA_OP_TRMM, nullptr, d_wpk); break;
+        // three-pass schedule: the projection that measures what it stores, and the closing one that measures nothing
+        case OP_COMBOX:  stc = gram_wp_once(n, m, bx, k, u, nullptr, u, out, d_cpk2); break;
+        case OP_CLOSE:   stc = gemm_chunk(n, 0, m + k, x, k, nullptr, 0, u, 0, DLA_OP_GEMM, nullptr, d_cpk2); break;
+        default: err = "ortho_chain: bad op"; stc = DLA_ERR_ARG;
+      }
     }
-    pred_phase = nullptr; pred_want = 0;
-    fuse_tail = false;
-    if (stc || tail_fused) return stc;
+    if (stc || out.tail_fused) return stc;
     if (comm && !p2p.on && d_red_small) {
       // RCCL: the reduced matrices live in the out-of-place destinations of the all-reduce
-      if (chain_reduced) pending_tail.gsrc = chain_red_dst;
-      pending_tail.xug = d_red_xug;
+      if (out.summed_at) tail.gsrc = out.summed_at;
+      tail.xug = d_red_xug;
     }
-    chain_reduced = false;
     Scope s(this, DLA_OP_GRAM, 0.0, 0.0, fold ? "ortho_tail16_kernel" : "ortho_tail_kernel");
-    launch_tail_kernel(pending_tail);
+    launch_tail_kernel(tail);
     HIPCHK(hipGetLastError());
     return DLA_OK;
   }
@@ -4498,32 +4558,43 @@ struct HipEngine : dla::Engine {
   // widest X pass of the pending-factor sweeps: 12 X tiles beside one U tile, 8 beside two (16 + 3 accumulator tiles), 5 beside
   // three (15 + 6)
   static int wp_max_tlw(int kt) { return kt <= 1 ? 12 : kt == 2 ? 8 : 5; }
-  //   cx != nullptr (m > 0, uw = u, one pass): U <- [X | U] C' stored, X^T U and U^T U of the stored result (OP_COMBOX)
-  int gram_wp_once(int n, int m, const double* x, int k, const double* u, const double* wp, double* uw, const double* cx = nullptr)
+  // pass shape of a pending-factor sweep: what the kernel's name, its instance and the reduction behind it are all read from
+  struct WpPlan { int tlw, kt, R, passes, blocks, extra, slots; bool self; };
+  WpPlan wp_plan(int n, int m, int k) const
   {
-    const bool self = (m == 0);
-    if (cx != nullptr && (self || uw == nullptr || wp != nullptr || k > 16)) { err = "gram_wp: bad projection sweep"; return DLA_ERR_ARG; }
-    const int kt = (k + 15) / 16;
-    if (kt > 3 || (self && kt > 1)) { err = "gram_wp: block too wide"; return DLA_ERR_ARG; }
-    const int tx = self ? 1 : (m + 15) / 16;
-    const int passes = self ? 1 : (tx + wp_max_tlw(kt) - 1) / wp_max_tlw(kt);
-    int tlw = (tx + passes - 1) / passes;
-    if (kt == 1) {
+    WpPlan p{};
+    p.self = (m == 0);
+    p.kt = (k + 15) / 16;
+    const int tx = p.self ? 1 : (m + 15) / 16;
+    p.passes = p.self ? 1 : (tx + wp_max_tlw(p.kt) - 1) / wp_max_tlw(p.kt);
+    p.tlw = (tx + p.passes - 1) / p.passes;
+    if (p.kt == 1) {
       static const int avail[] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12};
-      for (int v : avail) if (v >= tlw) { tlw = v; break; }
+      for (int v : avail) if (v >= p.tlw) { p.tlw = v; break; }
     }
     // the staged image of the widest pass: 13 tiles of 16 rows (4 waves x 13 x 16 x 18 doubles = 117 KiB); under a refused
-    // LDS raise the chain is not taken at all (ortho_chain)
-    const int R = (kt == 1 && tlw <= 2) ? 32 : 16;
+    // LDS raise the chain is not taken at all (ortho_chain).  (A block against itself is one tile beside one: 32 rows.)
+    p.R = (p.kt == 1 && p.tlw <= 2) ? 32 : 16;
     const long long nchunks = ((long long)n + 31) / 32;
     const long long want = (nchunks + 15) / 16;
     // (one U tile beside up to five X tiles: at most 212 / 252 registers and 55 KB of LDS per block -- two blocks per CU, two waves
     //  per SIMD: measured r05 at n = 2e6, interleaved: +5 ... 11 % for the projection sweep, +3 ... 9 % for the storing one; beyond
     //  five tiles the kernels need more than 256 registers and a second block per CU only runs behind the first)
-    int blocks = (int)std::max(1LL, std::min((long long)ncu * ((self || (kt == 1 && tlw <= 5 && tune[4] != -1)) ? 2 : 1), want));   // (knob 4 = -1: A/B)
-    if (tune[4] > 0) blocks = (int)std::max(1LL, std::min((long long)tune[4], want));
-    const int extra = self ? 0 : kt * (kt + 1) / 2;          // tiles (qi >= qj) of the Gram matrix of the U block
-    const int slots = self ? 1 : tlw * kt + extra;
+    p.blocks = (int)std::max(1LL, std::min((long long)ncu * ((p.self || (p.kt == 1 && p.tlw <= 5 && tune[4] != -1)) ? 2 : 1), want));   // (knob 4 = -1: A/B)
+    if (tune[4] > 0) p.blocks = (int)std::max(1LL, std::min((long long)tune[4], want));
+    p.extra = p.self ? 0 : p.kt * (p.kt + 1) / 2;          // tiles (qi >= qj) of the Gram matrix of the U block
+    p.slots = p.self ? 1 : p.tlw * p.kt + p.extra;
+    return p;
+  }
+  //   cx != nullptr (m > 0, uw = u, one pass): U <- [X | U] C' stored, X^T U and U^T U of the stored result (OP_COMBOX)
+  int gram_wp_once(int n, int m, const double* x, int k, const double* u, const double* wp, double* uw, StepOut& out, const double* cx = nullptr)
+  {
+    out = StepOut{};
+    const bool self = (m == 0);
+    if (cx != nullptr && (self || uw == nullptr || wp != nullptr || k > 16)) { err = "gram_wp: bad projection sweep"; return DLA_ERR_ARG; }
+    if (k > 48 || (self && k > 16)) { err = "gram_wp: block too wide"; return DLA_ERR_ARG; }
+    const WpPlan p = wp_plan(n, m, k);
+    const int tlw = p.tlw, kt = p.kt, passes = p.passes, blocks = p.blocks, extra = p.extra, slots = p.slots;
     int stc = ensure_partial(sizeof(double) * (size_t)passes * blocks * slots * 256);
     if (stc) return stc;
     stc = ensure_small(sizeof(double) * (size_t)k * k);
@@ -4531,17 +4602,17 @@ struct HipEngine : dla::Engine {
     if (!self && (m + k) * k > XUG_DOUBLES) { err = "gram_wp: basis too wide for the chain's buffer"; return DLA_ERR_ARG; }
     // (written-back tiles: every pass would transform the block again, and passes run side by side)
     if (uw != nullptr && passes != 1) { err = "gram_wp: the storing sweep takes one pass"; return DLA_ERR_ARG; }
-    GramArgs a{self ? u : x, u, d_partial, (long long)n, self ? k : m, k, passes, 0, pred_phase, pred_want, 0, wp, uw, cx};
+    GramArgs a{self ? u : x, u, d_partial, (long long)n, self ? k : m, k, passes, 0, lc.phase, lc.want, 0, wp, uw, cx};
     dim3 grid(blocks, passes);
     {
       char kn[64];
-      std::snprintf(kn, sizeof kn, "gram_lds_kernel<%d, %d, 1, %d, %d, 0, 0, %d>", tlw, kt, self ? 32 : R, self ? 1 : 0, cx ? 2 : 1);
+      std::snprintf(kn, sizeof kn, "gram_lds_kernel<%d, %d, 1, %d, %d, 0, 0, %d>", tlw, kt, p.R, self ? 1 : 0, cx ? 2 : 1);
       // reference-schedule flops: the Gram matrix (2 n k^2), X^T U (2 n m k), and the triangular update the sweep applies on the fly
       // (n k^2) -- or, for the projection sweep, the update U -= X (X^T U) (2 n m k) with the pending factor (n k^2)
       Scope s(this, cx ? DLA_OP_GEMM : DLA_OP_GRAM, 8.0 * (double)n * (double)(m + k + (uw ? k : 0)),
               2.0 * (double)n * (m + k) * k + ((wp || cx) ? 1.0 * (double)n * k * k : 0.0) + (cx ? 2.0 * (double)n * m * k : 0.0), kn);
       int r_ = DLA_ERR_RUNTIME;
-#define GWP(T, K, RR) if (tlw == T && kt == K) r_ = launch_gram_wp<T, K, RR>(a, grid, self); else
+#define GWP(T, K, RR) if (tlw == T && kt == K && p.R == RR) r_ = launch_gram_wp<T, K, RR>(a, grid, self); else
       GWP(1, 1, 32) GWP(2, 1, 32) GWP(3, 1, 16) GWP(4, 1, 16) GWP(5, 1, 16) GWP(6, 1, 16) GWP(7, 1, 16) GWP(8, 1, 16) GWP(10, 1, 16) GWP(12, 1, 16)
       GWP(1, 2, 16) GWP(2, 2, 16) GWP(3, 2, 16) GWP(4, 2, 16) GWP(5, 2, 16) GWP(6, 2, 16) GWP(7, 2, 16) GWP(8, 2, 16)
       GWP(1, 3, 16) GWP(2, 3, 16) GWP(3, 3, 16) GWP(4, 3, 16) GWP(5, 3, 16)
@@ -4550,18 +4621,7 @@ struct HipEngine : dla::Engine {
       if (r_) return r_;
     }
     const int n_out = self ? 1 : passes * tlw * kt + extra;
-    double* cdst = self ? d_small : d_xug;
-    {
-      Scope s2(this, DLA_OP_GRAM, 0.0, 0.0, "gram_reduce_kernel");
-      const int groups = reduce_groups(blocks);
-      const size_t need2 = sizeof(double) * (size_t)n_out * groups * 256;
-      { const int stl = ensure_lvl2(need2); if (stl) return stl; }
-      GramReduceArgs ra{d_partial, d_lvl2, d_ticket, cdst, nullptr, blocks, self ? k : m, k, tlw, kt, passes,
-                        pred_phase, pred_want, 0, n_out, d_ticket + 4096, OrthoTailArgs{}, P2PArgs{}, extra, self ? k : m + k};
-      launch_reduce(ra, dim3(n_out, groups));
-    }
-    HIPCHK(hipGetLastError());
-    return allreduce_dev(cdst, (self ? k : m + k) * k, 0, h_small);
+    return reduce_and_sum(DLA_OP_GRAM, self ? d_small : d_xug, nullptr, blocks, self ? k : m, k, tlw, kt, passes, n_out, extra, self ? k : m + k, out);
   }
 
   // A chain runs in two halves: ortho_chain_begin enqueues the planned launches, ortho_chain_finish waits, reads what the
@@ -4575,7 +4635,7 @@ struct HipEngine : dla::Engine {
     bool vsx = false;
     const double *x = nullptr, *bx = nullptr;
     double* u = nullptr;
-    long long key = 0, key_last = 0;
+    ChainShape shape;                // of the plan: plan_of_shape[shape], plan_of_kind[shape.kind()]
     bool xw = false;                 // wide block with the storing sweep OP_XW (see ortho_chain_begin)
     bool x3 = false;                 // three-pass schedule
     bool lean = false;               // the plan carries no closing / final sweep (the machine will not ask for them: see ortho_chain_begin)
@@ -4734,27 +4794,30 @@ struct HipEngine : dla::Engine {
     // refused request for more than 64 KiB of LDS shows up before anything has touched U).  After a refusal the engine's LDS
     // limit is down and the host-driven loop, which redoes single operations under it, takes the call.
     {
-      const long long vkey = (long long)k * 1000000 + m + fold * 500000000000LL + (vsx ? 0 : 250000000000LL) + (wide_xw ? 125000000000LL : 0LL) +
-                             (x3 ? 31250000000LL : 0LL);
-      if (!chain_verified.count(vkey)) {
+      ChainShape walked;
+      walked.k = k; walked.m = m; walked.fold = fold; walked.vsx = vsx; walked.wide_xw = wide_xw; walked.x3 = x3;
+      if (!chain_verified.count(walked)) {
         static const int every_op[] = {OP_GRAM_UU, OP_GRAMX, OP_GRAMW, OP_XW, OP_XU, OP_TRMMG, OP_COMBO, OP_FINAL, OP_COMBOX, OP_CLOSE, OP_TRMMC};
-        std::vector<SpecRec> dummy;
-        dry_launch = true; spec_rec = &dummy; lds_retry = false; chain_xw = wide_xw; chain_x3 = x3;
+        lds_retry = false;
         int std_ = DLA_OK;
-        for (int op : every_op) {
-          if (!vsx && (op == OP_GRAMX || op == OP_XW || op == OP_XU || op == OP_COMBO || op == OP_GRAMW)) continue;
-          if ((op == OP_COMBOX || op == OP_CLOSE || op == OP_TRMMC) && !x3) continue;
-          if (fold != 1 && (op == OP_GRAMW || (op == OP_XW && !wide_xw))) continue;
-          if (fold != 1 && op == OP_GRAMX && !wide_gramx) continue;
-          std_ = launch_op(op, n, m, k, x, bx, u, false, fold);
-          if (std_) break;
+        {
+          LaunchCtx walk = lc;
+          walk.dry = true; walk.xw = wide_xw; walk.x3 = x3;
+          CtxScope scope(this, walk);
+          for (int op : every_op) {
+            if (!vsx && (op == OP_GRAMX || op == OP_XW || op == OP_XU || op == OP_COMBO || op == OP_GRAMW)) continue;
+            if ((op == OP_COMBOX || op == OP_CLOSE || op == OP_TRMMC) && !x3) continue;
+            if (fold != 1 && (op == OP_GRAMW || (op == OP_XW && !wide_xw))) continue;
+            if (fold != 1 && op == OP_GRAMX && !wide_gramx) continue;
+            std_ = launch_op(op, n, m, k, x, bx, u, false, fold);
+            if (std_) break;
+          }
         }
-        dry_launch = false; spec_rec = nullptr;
         if (std_) {
           if (lds_retry) { lds_retry = false; return not_handled(); }        // rep->handled stays 0: host-driven loop
           return std_;
         }
-        chain_verified.insert(vkey);
+        chain_verified.insert(walked);
       }
     }
     // the widest reductions of the chain: make sure nothing reallocates (and drains the stream) half way
@@ -4777,13 +4840,10 @@ struct HipEngine : dla::Engine {
     const bool dropf = policy.drop_final && vsx;
     t_pending_k = 0;
     t_seq = t_seq >= 1000000 ? 1 : t_seq + 1;
-    const long long key = (long long)k * 1000000 + m + fold * 500000000000LL + (wide_gramx ? 250000000000LL : 0LL) + (wide_xw ? 125000000000LL : 0LL) +
-                          (dropf ? 62500000000LL : 0LL) + (x3 ? 31250000000LL : 0LL);
-    std::vector<int>& hist = ortho_history[key];
-    std::vector<int> plan = hist;
-    const long long kind_key = -(long long)(128 * k + (vsx ? 1 : 0) + 2 * fold + (wide_gramx ? 8 : 0) + (wide_xw ? 16 : 0) + (dropf ? 32 : 0) + (x3 ? 64 : 0)) - 1;
-    std::vector<int>& last_k = ortho_history[kind_key];   // most recent call of this kind and width
-    if (plan.empty()) plan = last_k;
+    ChainShape shape;
+    shape.k = k; shape.m = m; shape.fold = fold; shape.vsx = vsx; shape.wide_gramx = wide_gramx; shape.wide_xw = wide_xw; shape.dropf = dropf; shape.x3 = x3;
+    std::vector<int> plan = plan_of_shape[shape];
+    if (plan.empty()) plan = plan_of_kind[shape.kind()];   // most recent call of this kind and width
     if (plan.empty()) {
       // the schedule measured on the reference: cd x2, [projection, cd x2], [projection, cd x1]
       if (x3) plan = {OP_GRAMX, OP_COMBOX, OP_COMBOX, OP_CLOSE, OP_FINAL};
@@ -4816,13 +4876,10 @@ struct HipEngine : dla::Engine {
     //  this context has seen before, and two identical solves would differ in their last bits.  r05: tried, 0.02 ms per shifted
     //  chain of the benchmark; tests/test_solver_gpu.py compares repeated solves bit for bit.)
     run.n = n; run.m = m; run.k = k; run.fold = fold; run.vsx = vsx; run.x = x; run.bx = bx; run.u = u;
-    run.key = key;
-    run.key_last = kind_key;
+    run.shape = shape;
     run.xw = wide_xw;
     run.x3 = x3;
     run.lean = lean;
-    chain_xw = wide_xw;
-    chain_x3 = x3;
     run.plan = plan; run.launched.clear(); run.recs.clear();
     stc = chain_enqueue();
     if (stc) return stc;
@@ -4862,17 +4919,14 @@ struct HipEngine : dla::Engine {
   // enqueue run.plan (every launch predicated on the device state machine standing where the plan expects it)
   int chain_enqueue()
   {
-    spec_rec = &run.recs;
-    chain_xw = run.xw;
-    chain_x3 = run.x3;
     int stc = DLA_OK;
-    for (size_t pi = 0; pi < run.plan.size(); ++pi) {
-      spec_tag = (int)run.launched.size();
+    for (size_t pi = 0; pi < run.plan.size() && !stc; ++pi) {
+      LaunchCtx spec = lc;
+      spec.rec = &run.recs; spec.tag = (int)run.launched.size(); spec.xw = run.xw; spec.x3 = run.x3;
+      CtxScope scope(this, spec);
       run.launched.push_back(run.plan[pi]);
       stc = launch_op(run.plan[pi], run.n, run.m, run.k, run.x, run.bx, run.u, pi + 1 == run.plan.size(), run.fold);
-      if (stc) break;
     }
-    spec_rec = nullptr;
     if (stc) { (void)hipStreamSynchronize(st); chain_armed = false; return stc; }
     return DLA_OK;
   }
@@ -4888,8 +4942,8 @@ struct HipEngine : dla::Engine {
     std::vector<int>& plan = run.plan;
     std::vector<int>& launched = run.launched;
     std::vector<SpecRec>& recs = run.recs;
-    std::vector<int>& hist = ortho_history[run.key];
-    std::vector<int>& last_k = ortho_history[run.key_last];
+    std::vector<int>& hist = plan_of_shape[run.shape];
+    std::vector<int>& last_k = plan_of_kind[run.shape.kind()];
     int stc = DLA_OK;
     rep->clean = 1;
     OrthoDev sres{};
@@ -5006,7 +5060,8 @@ struct HipEngine : dla::Engine {
     int stc = ensure_chain_buffers();
     if (stc) return stc;
     // M = U^T (B U): every rank's share summed like any other small product
-    stc = gram_dev(n, k, u, k, bu);
+    StepOut gram_out;
+    stc = gram_dev(n, k, u, k, bu, gram_out);
     if (stc) return stc;
     b_seq = b_seq >= 1000000 ? 1 : b_seq + 1;
     *h_bstat = 0;
@@ -5016,10 +5071,13 @@ struct HipEngine : dla::Engine {
       DLA_LAUNCH(bortho_tail_kernel, dim3(1), dim3(64), 0, st, ta);
       HIPCHK(hipGetLastError());
     }
-    pred_phase = d_bgo; pred_want = b_seq;
-    stc = gemm_chunk(n, 0, k, u, k, nullptr, 0, u, 2, DLA_OP_TRMM, false, d_wpk_b);
-    if (!stc) stc = gemm_chunk(n, 0, k, bu, k, nullptr, 0, bu, 2, DLA_OP_TRMM, false, d_wpk_b);
-    pred_phase = nullptr; pred_want = 0;
+    {
+      LaunchCtx behind = lc;
+      behind.phase = d_bgo; behind.want = b_seq;
+      CtxScope scope(this, behind);
+      stc = gemm_chunk(n, 0, k, u, k, nullptr, 0, u, 2, DLA_OP_TRMM, nullptr, d_wpk_b);
+      if (!stc) stc = gemm_chunk(n, 0, k, bu, k, nullptr, 0, bu, 2, DLA_OP_TRMM, nullptr, d_wpk_b);
+    }
     if (stc) return stc;
     *handled = 1;
     return DLA_OK;
@@ -5031,8 +5089,25 @@ struct HipEngine : dla::Engine {
   }
 
   // ---- Gram
+  // Pass shape of one Gram launch (gram_plan): the kernel's name for the statistics and the instance that is launched are both
+  // read from it.
+  struct GramPlan {
+    int tlw, kt;           // tile shape of one pass: KT U-tiles x TLW X-tiles
+    int px, passes;        // passes over X, passes in all
+    int rows;              // rows of a staged tile (LDS-staged kernel): 16 or 32
+    bool lds;              // the LDS-staged kernel (gram_lds_kernel), else the direct-load one (gram_kernel)
+    bool self;             // ... a block against itself in one pass: staged once (gram_lds_kernel SELF)
+    int qt;                // ... quarter tiles of its last U tile (gram_lds_kernel QT)
+    bool low_single;       // ... the lower triangle of two different panels in a single pass (gram_lds_kernel LOW)
+    bool lower;            // only the tile pairs on or below the block diagonal are formed
+    int blocks_per_pass;
+    bool vec2;             // the 16-byte path
+  };
+  // whether a pass of tlw + kt tiles can be staged 32 rows at a time at all, and the rows per step of the direct-load kernel
+  static constexpr bool gram_can32(int tlw, int kt) { return sizeof(double) * 4 * 16 * (tlw + kt) * 34 <= 150 * 1024 && tlw + kt <= 7; }
+  static constexpr int gram_rs(int tlw, int kt) { return (tlw * kt >= 6) ? 2 : 4; }
   template <int TLW, int KT, int R>
-  int launch_gram_lds(const GramArgs& a, dim3 grid)
+  int launch_gram_lds(const GramArgs& a, dim3 grid, const GramPlan& p)
   {
 #define GLK(SELF_, Q)                                                                                          \
     do {                                                                                                      \
@@ -5043,12 +5118,12 @@ struct HipEngine : dla::Engine {
       return DLA_OK;                                                                                          \
     } while (0)
     if constexpr (TLW == KT) {
-      if (cur_self) {
-        if constexpr (KT >= 2) { if (cur_qt == 1) GLK(1, 1); if (cur_qt == 2) GLK(1, 2); }
+      if (p.self) {
+        if constexpr (KT >= 2) { if (p.qt == 1) GLK(1, 1); if (p.qt == 2) GLK(1, 2); }
         GLK(1, 0);
       }
     }
-    if constexpr (KT >= 2) { if (cur_qt == 1) GLK(0, 1); if (cur_qt == 2) GLK(0, 2); }
+    if constexpr (KT >= 2) { if (p.qt == 1) GLK(0, 1); if (p.qt == 2) GLK(0, 2); }
     GLK(0, 0);
 #undef GLK
   }
@@ -5072,17 +5147,13 @@ struct HipEngine : dla::Engine {
   // (a pass narrower than one tile, e.g. the 4-column W^T x of the benchmark operator, would stage mostly
   // duplicates of its last column: it keeps the direct-load kernel)
   bool use_lds_gram(bool vec2, int l, int kt) const { return vec2 && kt <= 3 && l > 8 && tune[5] != 2; }
-  bool cur_lds = false;   // decision of the Gram being launched
-  bool cur_self = false;  // ... a block against itself in one pass: staged once (gram_lds_kernel SELF)
-  int cur_qt = 0;         // ... quarter tiles of its last U tile (gram_lds_kernel QT)
   template <int TLW, int KT>
-  int launch_gram(const GramArgs& a, dim3 grid, bool vec2)
+  int launch_gram(const GramArgs& a, dim3 grid, const GramPlan& p)
   {
     if constexpr (KT <= 3) {
-      if (cur_lds) {
-        constexpr bool can32 = sizeof(double) * 4 * 16 * (TLW + KT) * 34 <= 150 * 1024 && TLW + KT <= 7;
-        if constexpr (can32) { if (lds_rows(TLW, KT) == 32) return launch_gram_lds<TLW, KT, 32>(a, grid); }
-        return launch_gram_lds<TLW, KT, 16>(a, grid);
+      if (p.lds) {
+        if constexpr (gram_can32(TLW, KT)) { if (p.rows == 32) return launch_gram_lds<TLW, KT, 32>(a, grid, p); }
+        return launch_gram_lds<TLW, KT, 16>(a, grid, p);
       }
     }
     if constexpr (TLW == 5 || TLW == 7 || TLW == 10 || (TLW == 12 && KT > 1) || (TLW == 3 && KT >= 2 && KT <= 3) || (TLW >= 5 && KT == 3) ||
@@ -5090,29 +5161,31 @@ struct HipEngine : dla::Engine {
       err = "gram: width without a direct-load instance";
       return DLA_ERR_RUNTIME;
     } else {
-      constexpr int RS = (TLW * KT >= 6) ? 2 : 4;
-      if (vec2) DLA_LAUNCH((gram_kernel<TLW, KT, 2, RS>), grid, dim3(256), 0, st, a);
+      constexpr int RS = gram_rs(TLW, KT);
+      if (p.vec2) DLA_LAUNCH((gram_kernel<TLW, KT, 2, RS>), grid, dim3(256), 0, st, a);
       else      DLA_LAUNCH((gram_kernel<TLW, KT, 1, RS>), grid, dim3(256), 0, st, a);
       return DLA_OK;
     }
   }
 
   // result stays on the device in d_small (l x k, ld = l), reduced over ranks
-  int gram_dev(int n, int l, const double* x, int k, const double* u, int cls = DLA_OP_GRAM, bool lower = false)
+  // out.lower_only: only the lower block triangle was formed (whoever copies the result out mirrors it, see gram())
+  int gram_dev(int n, int l, const double* x, int k, const double* u, StepOut& out, int cls = DLA_OP_GRAM, bool lower = false)
   {
-    return with_lds_retry([&]() { return gram_dev_once(n, l, x, k, u, cls, lower); });
+    return with_lds_retry([&]() { return gram_dev_once(n, l, x, k, u, cls, lower, out); });
   }
-  int gram_dev_once(int n, int l, const double* x, int k, const double* u, int cls, bool lower)
+  // same: x == u; aligned: both panels start on 16 bytes
+  GramPlan gram_plan(int n, int l, int k, bool same, bool aligned, bool lower) const
   {
     const int tx = (l + 15) / 16, tu = (k + 15) / 16;
     // tile shape of one pass: KT U-tiles x TLW X-tiles, at most 12 accumulators
-    const bool vec2 = even_rows(n) && (((uintptr_t)x | (uintptr_t)u) % 16 == 0);
+    const bool vec2 = even_rows(n) && aligned;
     // (even n: at most 3 U tiles per pass, so that the LDS-staged kernel serves every pass -- the direct-load kernel a
     // fourth tile would need measured 2.6 TB/s on the 111-column S^T A S of LOBPCG at n_max = 37)
     int kt = std::min(tu, (vec2 && l > 8 && tune[5] != 2) ? 3 : 4);
     const int passes_u = (tu + kt - 1) / kt;
     kt = (tu + passes_u - 1) / passes_u;
-    const bool ldsk = cur_lds = use_lds_gram(vec2, l, kt);
+    const bool ldsk = use_lds_gram(vec2, l, kt);
     // widest pass: the direct-load kernel loses its register prefetch stage beyond 8 tiles (measured); the LDS-staged
     // one keeps all of X's columns of up to 12 tiles in one pass, so U is read once for L <= 192
     static const int maxtl[5] = {0, 8, 6, 4, 3};
@@ -5139,14 +5212,14 @@ struct HipEngine : dla::Engine {
     int passes = px * passes_u;
     // a block against itself in a single pass: one staged image serves both operands, and only the tile pairs on or
     // below the diagonal are formed (the host side mirrors, see gram())
-    cur_self = ldsk && x == u && l == k && passes == 1 && tlw == kt;
-    if (cur_self) lower = true;
-    cur_qt = (ldsk && passes_u == 1 && kt >= 2) ? quarter_tiles(k, vec2) : 0;
+    const bool self = ldsk && same && l == k && passes == 1 && tlw == kt;
+    if (self) lower = true;
+    int qt = (ldsk && passes_u == 1 && kt >= 2) ? quarter_tiles(k, vec2) : 0;
     // the lower triangle of X^T U for two different panels of 49..112 columns (S^T A S of LOBPCG at n_max = 21 / 37):
     // one pass over both panels with the 10..28 tile pairs on or below the diagonal (gram_lds_kernel LOW)
-    const bool low_single = lower && ldsk && !cur_self && l == k && tx >= 4 && tx <= 7 && passes > 1 && tune[7] != 8 &&
+    const bool low_single = lower && ldsk && !self && l == k && tx >= 4 && tx <= 7 && passes > 1 && tune[7] != 8 &&
                             sizeof(double) * 4 * 16 * (size_t)(2 * tx) * 18 <= lds_limit;
-    if (low_single) { kt = tlw = tx; px = 1; passes = 1; cur_qt = 0; }
+    if (low_single) { kt = tlw = tx; px = 1; passes = 1; qt = 0; }
     const int ch = vec2 ? 32 : 16;
     long long nchunks = ((long long)n + ch - 1) / ch;
     long long want = (nchunks + 4 * 4 - 1) / (4 * 4);   // >= 4 chunks per wave
@@ -5154,32 +5227,37 @@ struct HipEngine : dla::Engine {
     int blocks_per_pass = (int)std::max(1LL, std::min((long long)ncu, want));
     // the narrowest sweeps (a block against itself, or fewer than 8 columns against a block) have too few loads in
     // flight with one block per CU: two per CU measured +11 % / +19 % there and -1..-3 % everywhere else
-    if (tlw * kt == 1 && ((x == u && l == k) || l <= 8)) blocks_per_pass = (int)std::max(1LL, std::min(2LL * ncu, want));
+    if (tlw * kt == 1 && ((same && l == k) || l <= 8)) blocks_per_pass = (int)std::max(1LL, std::min(2LL * ncu, want));
     if (tune[4] > 0) blocks_per_pass = (int)std::max(1LL, std::min((long long)tune[4], want));
+    const int rows = (ldsk && !low_single && gram_can32(tlw, kt) && lds_rows(tlw, kt) == 32) ? 32 : 16;
+    return GramPlan{tlw, kt, px, passes, rows, ldsk, self, qt, low_single, lower, blocks_per_pass, vec2};
+  }
+  int gram_dev_once(int n, int l, const double* x, int k, const double* u, int cls, bool lower, StepOut& out)
+  {
+    out = StepOut{};
+    const GramPlan p = gram_plan(n, l, k, x == u, ((uintptr_t)x | (uintptr_t)u) % 16 == 0, lower);
+    const int tlw = p.tlw, kt = p.kt, passes = p.passes, blocks_per_pass = p.blocks_per_pass;
+    out.lower_only = p.self;
     const int slots = tlw * kt;
     int stc = ensure_partial(sizeof(double) * (size_t)passes * blocks_per_pass * slots * 256);
     if (stc) return stc;
     stc = ensure_small(sizeof(double) * (size_t)l * k);
     if (stc) return stc;
-    GramArgs a{x, u, d_partial, (long long)n, l, k, px, lower ? 1 : 0, pred_phase, pred_want, tune[7] == 2 ? 1 : 0};
+    GramArgs a{x, u, d_partial, (long long)n, l, k, p.px, p.lower ? 1 : 0, lc.phase, lc.want, tune[7] == 2 ? 1 : 0};
     dim3 grid(blocks_per_pass, passes);
     {
       const bool same = (x == u) && (l == k);
-      const int rs = (tlw * kt >= 6) ? 2 : 4;
       char kn[64];
-      if (cur_lds) {
-        const bool can32 = sizeof(double) * 4 * 16 * (tlw + kt) * 34 <= 150 * 1024 && tlw + kt <= 7;
-        std::snprintf(kn, sizeof kn, "gram_lds_kernel<%d, %d, 1, %d, %d, %d, %d, 0>", tlw, kt,
-                      (!low_single && can32 && lds_rows(tlw, kt) == 32) ? 32 : 16, cur_self ? 1 : 0, cur_qt, low_single ? 1 : 0);
-      }
-      else std::snprintf(kn, sizeof kn, "gram_kernel<%d, %d, %d, %d, 0, -1>", tlw, kt, vec2 ? 2 : 1, rs);
+      if (p.lds)
+        std::snprintf(kn, sizeof kn, "gram_lds_kernel<%d, %d, 1, %d, %d, %d, %d, 0>", tlw, kt, p.rows, p.self ? 1 : 0, p.qt, p.low_single ? 1 : 0);
+      else std::snprintf(kn, sizeof kn, "gram_kernel<%d, %d, %d, %d, 0, -1>", tlw, kt, p.vec2 ? 2 : 1, gram_rs(tlw, kt));
       Scope s(this, cls, 8.0 * (double)n * (same ? (double)k : (double)(l + k)), 2.0 * (double)n * l * k, kn);
-      if (low_single) {
-        int r_ = tx == 4 ? launch_gram_low<4>(a, grid) : tx == 5 ? launch_gram_low<5>(a, grid) : tx == 6 ? launch_gram_low<6>(a, grid)
-                                                                                                       : launch_gram_low<7>(a, grid);
+      if (p.low_single) {
+        int r_ = tlw == 4 ? launch_gram_low<4>(a, grid) : tlw == 5 ? launch_gram_low<5>(a, grid) : tlw == 6 ? launch_gram_low<6>(a, grid)
+                                                                                                          : launch_gram_low<7>(a, grid);
         if (r_) return r_;
       } else
-#define GL(T, K) if (tlw == T && kt == K) { int r_ = launch_gram<T, K>(a, grid, vec2); if (r_) return r_; } else
+#define GL(T, K) if (tlw == T && kt == K) { int r_ = launch_gram<T, K>(a, grid, p); if (r_) return r_; } else
       GL(1, 1) GL(2, 1) GL(3, 1) GL(4, 1) GL(5, 1) GL(6, 1) GL(7, 1) GL(8, 1) GL(10, 1) GL(12, 1)
       GL(1, 2) GL(2, 2) GL(3, 2) GL(4, 2) GL(5, 2) GL(6, 2) GL(7, 2) GL(8, 2)
       GL(1, 3) GL(2, 3) GL(3, 3) GL(4, 3) GL(5, 3) GL(6, 3) GL(7, 3)
@@ -5187,30 +5265,18 @@ struct HipEngine : dla::Engine {
       { err = "gram: no kernel instance"; return DLA_ERR_RUNTIME; }
 #undef GL
     }
-    {
-      Scope s2(this, cls, 0.0, 0.0, "gram_reduce_kernel");
-      const int groups = reduce_groups(blocks_per_pass);
-      const size_t need2 = sizeof(double) * (size_t)passes * slots * groups * 256;
-      { const int stl = ensure_lvl2(need2); if (stl) return stl; }
-      if (passes * slots > 4096) { err = "gram: too many output tiles"; return DLA_ERR_ARG; }
-      GramReduceArgs ra{d_partial, d_lvl2, d_ticket, d_small + small_off, pred_phase ? nullptr : h_small.dev() + small_off, blocks_per_pass, l, k, tlw, kt, px,
-                        pred_phase, pred_want, 0, passes * slots, d_ticket + 4096, OrthoTailArgs{}};
-      launch_reduce(ra, dim3(passes * slots, groups));
-    }
-    HIPCHK(hipGetLastError());
-    if (in_chunk) return DLA_OK;           // (column chunk of a larger result: one rank only, gram_chunk)
-    return allreduce_dev(d_small, l * k, 0, h_small);
+    return reduce_and_sum(cls, d_small + lc.small_off, lc.phase ? nullptr : h_small.dev() + lc.small_off, blocks_per_pass, l, k, tlw, kt, p.px,
+                          passes * slots, 0, 0, out);
   }
 
   // ---- projection of a block that arrives in column chunks (host-mode callbacks: SURVEY 8f row 4, reference README.md:34-35).
   // C(:, c0 : c0 + kc) = X^T U_chunk is enqueued behind the uploads issued so far and lands in its columns of the l x k result;
   // the sweep runs while the caller's routine works on the next chunk.  gram_chunks_collect waits once for all of them.
-  size_t small_off = 0;              // element offset of the result of the Gram being launched inside d_small / h_small
   Event ev_chunk;
   bool gram_chunks_ok(int n, int l, int k) override
   {
     (void)n;
-    return !hook && !comm && !p2p.on && (local_only || nranks <= 1) && l > 0 && k > 0 && pred_phase == nullptr;
+    return !hook && !comm && !p2p.on && (local_only || nranks <= 1) && l > 0 && k > 0 && lc.phase == nullptr;
   }
   int gram_chunk(int n, int l, const double* x, int k_total, int c0, int kc, const double* u_chunk) override
   {
@@ -5218,16 +5284,15 @@ struct HipEngine : dla::Engine {
     HIPCHK(ev_chunk.ensure(hipEventDisableTiming));
     HIPCHK(hipEventRecord(ev_chunk, st_up));
     HIPCHK(hipStreamWaitEvent(st, ev_chunk, 0));
-    small_off = (size_t)c0 * l;
-    in_chunk = true;
-    int stc = gram_dev(n, l, x, kc, u_chunk);
-    in_chunk = false; small_off = 0;
-    return stc;
+    LaunchCtx chunk = lc;
+    chunk.small_off = (size_t)c0 * l; chunk.in_chunk = true;
+    CtxScope scope(this, chunk);
+    StepOut out;
+    return gram_dev(n, l, x, kc, u_chunk, out);
   }
-  bool in_chunk = false;
   int gram_chunks_collect(int l, int k, double* c_host, int ldc) override
   {
-    int stc = small_to_host((size_t)l * k);
+    int stc = small_to_host((size_t)l * k, false);       // (one rank: no cross-rank sum has written the mirror)
     if (stc) return stc;
     for (int j = 0; j < k; ++j) std::memcpy(c_host + (size_t)j * ldc, h_small + (size_t)j * l, sizeof(double) * l);
     return DLA_OK;
@@ -5235,9 +5300,10 @@ struct HipEngine : dla::Engine {
 
   int gram_lower(int n, int l, const double* x, const double* u, double* c_host, int ldc) override
   {
-    int stc = gram_dev(n, l, x, l, u, DLA_OP_GRAM, true);
+    StepOut out;
+    int stc = gram_dev(n, l, x, l, u, out, DLA_OP_GRAM, true);
     if (stc) return stc;
-    stc = small_to_host((size_t)l * l);
+    stc = small_to_host((size_t)l * l, out.mirror_fresh);
     if (stc) return stc;
     for (int j = 0; j < l; ++j) std::memcpy(c_host + (size_t)j * ldc, h_small + (size_t)j * l, sizeof(double) * l);
     return DLA_OK;
@@ -5245,11 +5311,12 @@ struct HipEngine : dla::Engine {
 
   int gram(int n, int l, const double* x, int k, const double* u, double* c_host, int ldc) override
   {
-    int stc = gram_dev(n, l, x, k, u);
+    StepOut out;
+    int stc = gram_dev(n, l, x, k, u, out);
     if (stc) return stc;
-    stc = small_to_host((size_t)l * k);
+    stc = small_to_host((size_t)l * k, out.mirror_fresh);
     if (stc) return stc;
-    if (cur_self) {
+    if (out.lower_only) {
       // only the lower block triangle was formed: mirror it (the Gram matrix of a block is symmetric)
       for (int j = 0; j < k; ++j)
         for (int i2 = 0; i2 < k; ++i2) {
@@ -5262,34 +5329,24 @@ struct HipEngine : dla::Engine {
     return DLA_OK;
   }
 
-  int fused_blocks = 0;
-
-  // second stage of a Gram whose per-block partials a fused kernel left in d_partial: result in d_small (k x k,
-  // lower block triangle), summed over ranks
-  int fused_reduce(int k)
+  // second stage of a Gram whose per-block partials a fused kernel left in d_partial (`blocks` of them: gemm_chunk): result in
+  // d_small (k x k, lower block triangle), summed over ranks
+  int fused_reduce(int k, int blocks, StepOut& out)
   {
+    out = StepOut{};
     int stc = ensure_small(sizeof(double) * (size_t)k * k);
     if (stc) return stc;
     const int kt = (k + 15) / 16;
-    const int groups = reduce_groups(fused_blocks);
-    const size_t need2 = sizeof(double) * (size_t)kt * kt * groups * 256;
-    { const int stl = ensure_lvl2(need2); if (stl) return stl; }
-    GramReduceArgs ra{d_partial, d_lvl2, d_ticket, d_small, pred_phase ? nullptr : h_small.dev(), fused_blocks, k, k, kt, kt, 1,
-                      pred_phase, pred_want, 0, kt * kt, d_ticket + 4096, OrthoTailArgs{}};
-    {
-      Scope s2(this, DLA_OP_GRAM, 0.0, 0.0, "gram_reduce_kernel");
-      launch_reduce(ra, dim3(kt * kt, groups));
-    }
-    HIPCHK(hipGetLastError());
-    return allreduce_dev(d_small, k * k, 0, h_small);
+    return reduce_and_sum(DLA_OP_GRAM, d_small, lc.phase ? nullptr : h_small.dev(), blocks, k, k, kt, kt, 1, kt * kt, 0, 0, out);
   }
 
   // ... and its copy to the host
-  int finish_fused_gram(int k, double* g_host, int ldg)
+  int finish_fused_gram(int k, int blocks, double* g_host, int ldg)
   {
-    int stc = fused_reduce(k);
+    StepOut out;
+    int stc = fused_reduce(k, blocks, out);
     if (stc) return stc;
-    stc = small_to_host((size_t)k * k);
+    stc = small_to_host((size_t)k * k, out.mirror_fresh);
     if (stc) return stc;
     // the kernel formed the lower block triangle; mirror it (G is symmetric)
     for (int j = 0; j < k; ++j)
@@ -5315,13 +5372,14 @@ struct HipEngine : dla::Engine {
   int trmm_gram_once(int n, int k, double* u, const double* w_host, int ld, double* g_host, int ldg)
   {
     if (k > 48 || fused_lds(k, k) > lds_limit) return Engine::trmm_gram(n, k, u, w_host, ld, g_host, ldg);
+    int blocks = 0;
     {
       // accounted as TRMM traffic (16nk) -- the Gram rides along
-      int stc = gemm_chunk(n, 0, k, u, k, w_host, ld, u, 2, DLA_OP_TRMM, true);
+      int stc = gemm_chunk(n, 0, k, u, k, w_host, ld, u, 2, DLA_OP_TRMM, &blocks);
       if (stc) return stc;
     }
     stats.flops[DLA_OP_GRAM] += 2.0 * (double)n * k * k;   // reference-schedule flops of the Gram it replaces
-    return finish_fused_gram(k, g_host, ldg);
+    return finish_fused_gram(k, blocks, g_host, ldg);
   }
 
   // U <- [X | U] C' and G = U^T U of the result in one sweep; U is the last k columns of the same
@@ -5351,13 +5409,14 @@ struct HipEngine : dla::Engine {
   int combo_gram_once(int n, int m, const double* x, int k, const double* c_host, int ldc, double* u, double* g_host, int ldg)
   {
     if (!can_combo(m, k) || u != x + (size_t)n * m) { err = "combo_gram: unsupported shape"; return DLA_ERR_ARG; }
-    int stc = gemm_chunk(n, 0, m + k, x, k, c_host, ldc, u, 0, DLA_OP_GEMM, true);
+    int blocks = 0;
+    int stc = gemm_chunk(n, 0, m + k, x, k, c_host, ldc, u, 0, DLA_OP_GEMM, &blocks);
     if (stc) return stc;
     // reference-schedule flops of what was folded in: dtrmm (n k^2) + the Gram (2 n k^2); the 2 n m k of the
     // update itself were counted by gemm_chunk (it counted 2 n (m+k) k)
     stats.flops[DLA_OP_GRAM] += 2.0 * (double)n * k * k;
     stats.flops[DLA_OP_GEMM] -= 1.0 * (double)n * k * k;
-    return finish_fused_gram(k, g_host, ldg);
+    return finish_fused_gram(k, blocks, g_host, ldg);
   }
 
   // U -= X C and G = U^T U of the result, one sweep (k <= 48, C fits one LDS chunk)
@@ -5370,10 +5429,11 @@ struct HipEngine : dla::Engine {
     if (k > 48 || l == 0 || (size_t)(l + 3) * 16 * ((k + 15) / 16) * sizeof(double) > (size_t)64 * 1024 ||
         fused_lds(l, k) > lds_limit)
       return Engine::update_gram(n, l, x, k, c_host, ldc, u, g_host, ldg);
-    int stc = gemm_chunk(n, 0, l, x, k, c_host, ldc, u, 1, DLA_OP_GEMM, true);
+    int blocks = 0;
+    int stc = gemm_chunk(n, 0, l, x, k, c_host, ldc, u, 1, DLA_OP_GEMM, &blocks);
     if (stc) return stc;
     stats.flops[DLA_OP_GRAM] += 2.0 * (double)n * k * k;
-    return finish_fused_gram(k, g_host, ldg);
+    return finish_fused_gram(k, blocks, g_host, ldg);
   }
 
   // ---- packed C upload: [KT][l4][16], zero padded
@@ -5456,9 +5516,12 @@ struct HipEngine : dla::Engine {
   }
 
   // cpk_dev != nullptr: the coefficient block is already packed in device memory (ortho_tail_kernel wrote it)
+  // fused_blocks != nullptr: the fused variant, which also leaves the partials of the result's Gram matrix in d_partial -- one set per
+  // block, and their number here for fused_reduce
   int gemm_chunk(int n, int l0, int l, const double* x, int k, const double* c_host, int ldc, double* z, int mode, int cls,
-                 bool fuse = false, const double* cpk_dev = nullptr)
+                 int* fused_blocks = nullptr, const double* cpk_dev = nullptr)
   {
+    const bool fuse = fused_blocks != nullptr;
     const int kt = (k + 15) / 16;
     const int l4 = ((l + 3) / 4) * 4;
     const bool inl = (cpk_dev == nullptr && kt == 1 && l4 <= 16);
@@ -5487,11 +5550,11 @@ struct HipEngine : dla::Engine {
     if (fuse) {
       int stp = ensure_partial(sizeof(double) * (size_t)blocks * kt * kt * 256);
       if (stp) return stp;
-      fused_blocks = blocks;
+      *fused_blocks = blocks;
     }
     GemmArgs a{};
     a.x = x + (size_t)l0 * n; a.cpk = cpk_dev ? cpk_dev : d_cpk; a.z = z; a.n = n; a.l = l; a.l4 = l4; a.k = k; a.gpart = d_partial;
-    a.phase = pred_phase; a.want = pred_want; a.xpf = tune[7] == 4 ? 0 : 1;
+    a.phase = lc.phase; a.want = lc.want; a.xpf = tune[7] == 4 ? 0 : 1;
     const double rd = (mode == 0) ? 8.0 * n * (double)l : (mode == 2 ? 8.0 * n * (double)k : 8.0 * n * (double)(l + k));
     char kn[96];
     std::snprintf(kn, sizeof kn, "gemm_kernel<%d, %d, %d, %s, %s, %d, %d, 9, %d, %d>", kt, vec2 ? 2 : 1, mode, inl ? "GemmArgsInl" : "GemmArgs",
@@ -5786,10 +5849,7 @@ struct HipEngine : dla::Engine {
     }
     HIPCHK(hipGetLastError());
     // sums and all ranks' maxima in one collective (reference :1730-1731 are two reductions)
-    exchange_fused = false;
-    stc = allreduce_dev(d_small, ncol * (1 + nslots), 0, h_small);
-    if (stc) return stc;
-    stc = small_to_host((size_t)ncol * (1 + nslots));
+    stc = sum_to_host(ncol * (1 + nslots), 0);
     if (stc) return stc;
     for (int j = 0; j < n_res; ++j) {
       double mx = 0.0;
@@ -5853,10 +5913,7 @@ struct HipEngine : dla::Engine {
                          h_small.dev(), nslots, local_only ? 0 : rank);
     }
     HIPCHK(hipGetLastError());
-    exchange_fused = false;
-    stc = allreduce_dev(d_small, ncol * (1 + nslots), 0, h_small);
-    if (stc) return stc;
-    stc = small_to_host((size_t)ncol * (1 + nslots));
+    stc = sum_to_host(ncol * (1 + nslots), 0);
     if (stc) return stc;
     for (int j = 0; j < n_res; ++j) {
       double mx = 0.0;
@@ -5920,10 +5977,7 @@ struct HipEngine : dla::Engine {
       DLA_LAUNCH(sum_partials_kernel, dim3(1), dim3(256), 0, st, (const double*)d_partial, blocks, d_small, h_small.dev());
     }
     HIPCHK(hipGetLastError());
-    exchange_fused = false;
-    stc = allreduce_dev(d_small, 1, 0, h_small);
-    if (stc) return stc;
-    stc = small_to_host(1);
+    stc = sum_to_host(1, 0);
     if (stc) return stc;
     *out = h_small[0];
     return DLA_OK;
@@ -6001,9 +6055,7 @@ struct HipEngine : dla::Engine {
     int stc = ensure_small(sizeof(double) * v.size());
     if (stc) return stc;
     HIPCHK(hipMemcpyAsync(d_small, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, st));
-    stc = allreduce_dev(d_small, (int)v.size(), op, h_small);
-    if (stc) return stc;
-    stc = small_to_host(v.size());
+    stc = sum_to_host((int)v.size(), op);
     if (stc) return stc;
     std::memcpy(v.data(), h_small, sizeof(double) * v.size());
     return DLA_OK;
@@ -6072,7 +6124,8 @@ struct HipEngine : dla::Engine {
         const int total = nr * 2 * mcur * H;
         DLA_LAUNCH(halo_pack_kernel, dim3(std::max(1, std::min(64, (total + 255) / 256))), dim3(256), 0, st, n, mcur, H, nr, rank, xc, d_halo);
         HIPCHK(hipGetLastError());
-        const int stc = allreduce_dev(d_halo, total, 0, h_halo.data());
+        StepOut halo_out;
+        const int stc = allreduce_dev(d_halo, total, 0, h_halo.data(), halo_out);
         if (stc) return stc;
       }
       // (the first / last rank never index their missing neighbour: any valid address serves)
@@ -6132,7 +6185,8 @@ struct HipEngine : dla::Engine {
     if (n != syn_n) { err = "synth operator: n differs from setup"; return DLA_ERR_ARG; }
     if (m > 64) { err = "synth operator: m > 64"; return DLA_ERR_ARG; }
     if (kind < SYN_A || kind > SYN_METRIC) { err = "synth operator: unknown kind"; return DLA_ERR_ARG; }
-    int stc = gram_dev(n, syn_rw, d_w, m, x, DLA_OP_MATVEC);   // t = W^T x (4 x m), reduced over ranks, on device
+    StepOut t_out;
+    int stc = gram_dev(n, syn_rw, d_w, m, x, t_out, DLA_OP_MATVEC);   // t = W^T x (4 x m), reduced over ranks, on device
     if (stc) return stc;
     SynthCoupling cp{};
     const double tau = 0.05;

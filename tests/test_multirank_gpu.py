@@ -58,7 +58,19 @@ if spec["guess"] == "unit":
         if row0 <= j < row0 + n_loc: g[j - row0, j] = 1.0
 ev = ctx.panel(g)
 mv, pc = capi.fn_address("dla_synth_matvec"), capi.fn_address("dla_synth_precnd")
-if spec["solver"] == "check_guess":
+extra = dict()
+if spec["solver"] == "ortho_then_reduce":
+    # ortho_vs_x of a shape this context has not seen (its launch paths are walked without launching, then the chain runs) and,
+    # with no other reduction in between, the norm and the Gram matrix of the block it left
+    mm, kk = spec["m"], spec["k"]
+    rs = np.random.default_rng(7)
+    xu = np.hstack([np.linalg.qr(rs.standard_normal((n, mm)))[0], rs.standard_normal((n, kk))])
+    big = ctx.panel(np.asfortranarray(xu[row0:row0 + n_loc]))
+    pu = big.col(mm, kk)
+    ctx.ortho_vs_x(big.col(0, mm), pu)
+    extra = dict(nrm2=ctx.nrm2(pu), gram=ctx.gram(pu, pu))
+    eig, ok, info = np.zeros(m), True, dict(iters=0, matvec_cols=0)
+elif spec["solver"] == "check_guess":
     # zero guess -> library-generated random block (global row indices) + sharded ortho_cd
     ctx.check_guess(ev)
     eig, ok, info = np.zeros(m), True, dict(iters=0, matvec_cols=0)
@@ -72,7 +84,7 @@ else:
     eig, _, ok, info = ctx.lobpcg_driver(n_loc, t, m, 200, spec["tol"], 0.0, mv, pc, ev)
 st = ctx.stats()
 np.savez(os.path.join({out!r}, f"rank{{rank}}.npz"), eig=eig, ok=ok, iters=info["iters"], cols=info["matvec_cols"],
-         row0=row0, vec=ev.download(), allreduces=st["allreduces"], host_syncs=st["host_syncs"])
+         row0=row0, vec=ev.download(), allreduces=st["allreduces"], host_syncs=st["host_syncs"], **extra)
 dist.barrier()
 if world > 1 and spec.get("transport", "hook") in ("p2p", "rccl"):
     ctx.comm_finalize()
@@ -191,6 +203,24 @@ def test_two_ranks_wide_blocks_peer_to_peer(tmp_path, oracle, solver):
     assert np.abs(v2 * sgn - v1)[:, :t].max() < 1e-6
     assert np.abs(v2[:, :t].T @ v2[:, :t] - np.eye(t)).max() < 1e-12
     assert_parity_with_oracle(oracle, spec, two)
+
+
+def test_reductions_right_behind_a_first_chain_peer_to_peer(tmp_path):
+    """The first ortho_vs_x of an (m, k) shape walks its launch paths without launching and then runs the chain, whose reductions
+    carry the cross-rank sum inside the reduction kernel.  Neither may leave anything behind for the next reduction: the norm
+    (its own kernels, then the exchange as a launch) and the Gram matrix of the block must still be summed over both ranks.
+    A sum that was skipped gives each rank its own half: different bits, norm^2 and diagonal far from k and 1.
+    Tolerances: the orthonormality bound of tests/test_ortho_chain_gpu.py, 50 eps per entry of U^T U - I; norm^2 is the sum of
+    the k diagonal entries, hence k times that."""
+    eps = np.finfo(np.float64).eps
+    k = 8
+    spec = dict(n=2048, n_targ=1, n_max=1, m=16, k=k, solver="ortho_then_reduce", guess="zero", transport="p2p")
+    two = _run_world(tmp_path, spec, 2)
+    assert np.array_equal(two[0]["nrm2"], two[1]["nrm2"])          # the exchange has a fixed summation order
+    assert np.array_equal(two[0]["gram"], two[1]["gram"])
+    assert abs(float(two[0]["nrm2"]) ** 2 - k) < k * 50 * eps, float(two[0]["nrm2"]) ** 2 - k
+    assert np.abs(two[0]["gram"] - np.eye(k)).max() < 50 * eps, np.abs(two[0]["gram"] - np.eye(k)).max()
+    assert int(two[0]["allreduces"]) == int(two[1]["allreduces"]) > 0
 
 
 @pytest.mark.parametrize("world,solver", [(3, "davidson"), (4, "lobpcg"), (4, "gen_david")])

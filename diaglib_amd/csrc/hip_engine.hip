@@ -6013,7 +6013,11 @@ struct HipEngine : dla::Engine {
   {
     if (n <= 0 || !rowptr || !colind || !values) { err = "spmm_setup_csr: bad arguments"; return DLA_ERR_ARG; }
     int w = 0;
-    for (int i = 0; i < n; ++i) w = std::max(w, (int)(rowptr[i + 1] - rowptr[i]));
+    for (int i = 0; i < n; ++i) {
+      // (as sharded_ell_need: a descending pair used to pass for an empty row)
+      if (rowptr[i + 1] < rowptr[i]) { err = "spmm_setup_csr: row pointers not ascending"; return DLA_ERR_ARG; }
+      w = std::max(w, (int)(rowptr[i + 1] - rowptr[i]));
+    }
     if (w <= 0) { err = "spmm_setup_csr: empty matrix"; return DLA_ERR_ARG; }
     std::vector<int> col((size_t)w * n);
     std::vector<double> val((size_t)w * n, 0.0), diag((size_t)n, 0.0);

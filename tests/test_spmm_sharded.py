@@ -2,8 +2,8 @@
 banded symmetric matrix with global column indices; the halo rows of x travel through the same all-reduce transport as the
 small products (every rank fills its own slots of a zeroed buffer, the sum gathers).
 
-CPU leg: the host-memory engine over gloo (2 and 3 ranks).  GPU legs: two ranks sharing one GPU over the reduction hook and over
-the peer-to-peer mailboxes.  Checked: the product against scipy on every shard, a Davidson solve on the sharded operator against
+CPU leg: the host-memory engine over gloo (2 and 3 ranks, banded and ragged).  GPU legs: two ranks sharing one GPU over the
+reduction hook and over the peer-to-peer mailboxes, three ranks (a middle rank with both halos) over the hook.  Checked: the product against scipy on every shard, a Davidson solve on the sharded operator against
 the single-rank solve and against a dense eigensolver, and that a matrix with a long-range coupling is refused on every rank."""
 import json
 import os
@@ -53,6 +53,8 @@ i = np.arange(n, dtype=np.float64)
 diags, offs = [2.0 + i / 50.0], [0]
 for d in range(1, hb + 1):
     v = 0.3 / d * np.cos(i[:n - d] + d)
+    if spec.get("ragged"):                  # the reach varies with the row: (r, r + d) is present iff d <= 1 + (r mod half_band), mirrored
+        v = np.where(d <= 1 + (np.arange(n - d) % hb), v, 0.0)
     diags += [v, v]; offs += [d, -d]
 if spec.get("reach"):                       # one more pair of diagonals far out: the halo has to be that wide
     d = spec["reach"]; v = 0.01 * np.cos(i[:n - d]); diags += [v, v]; offs += [d, -d]
@@ -60,6 +62,7 @@ a = sp.diags(diags, offs, shape=(n, n), format="lil")
 if spec.get("far"):
     a[0, n - 1] = 0.1; a[n - 1, 0] = 0.1
 a = a.tocsr()
+a.eliminate_zeros()                         # (ragged: the rows really are of different lengths)
 status = "ok"
 try:
     ctx.spmm_setup_sharded(a[row0:row0 + n_loc], row0, n)
@@ -74,7 +77,9 @@ if status == "ok":
     ref = (a @ x)[row0:row0 + n_loc]
     den = a.diagonal()[row0:row0 + n_loc, None] - 1.25
     res["matvec_err"] = float(np.abs(pax.download() - ref).max() / np.abs(ref).max())
-    res["precnd_err"] = float(np.abs(ppx.download() - x[row0:row0 + n_loc] / den).max())
+    xl = x[row0:row0 + n_loc]
+    res["precnd_err"] = float(np.abs(ppx.download() - np.where(np.abs(den) > 1e-5, xl / den, xl)).max())
+    res["ell_w"] = int(np.diff(a[row0:row0 + n_loc].indptr).max())
     g = np.zeros((n_loc, m), order="F")
     for j in range(m):
         if row0 <= j < row0 + n_loc: g[j - row0, j] = 1.0
@@ -114,6 +119,8 @@ def _dense_lowest(spec):
     a = np.diag(2.0 + i / 50.0)
     for d in range(1, hb + 1):
         v = 0.3 / d * np.cos(i[:n - d] + d)
+        if spec.get("ragged"):
+            v = np.where(d <= 1 + (np.arange(n - d) % hb), v, 0.0)
         a += np.diag(v, d) + np.diag(v, -d)
     return np.linalg.eigvalsh(a)[:spec["n_targ"]]
 
@@ -138,6 +145,7 @@ def _check(tmp_path, spec, world):
     stitched = np.vstack([v["vec"] for v in vn])
     sgn = np.sign((stitched * v1["vec"]).sum(0))
     assert np.abs(stitched * sgn - v1["vec"])[:, :t].max() < 1e-6
+    return many
 
 
 @pytest.mark.parametrize("world", [2, 3])
@@ -148,6 +156,16 @@ def test_sharded_banded_operator_gloo(tmp_path, world):
     hostsim.build()
     spec = dict(backend="hostsim", transport="hook", n=3000, n_targ=4, n_max=8, half_band=6, tol=1e-9)
     _check(tmp_path, spec, world)
+
+
+def test_sharded_ragged_operator_three_ranks_gloo(tmp_path):
+    """host-memory engine, 3 ranks: a symmetric pattern whose reach depends on the row, so the ranks need halos of different widths
+    (the agreed halo is the widest) and the rows are of different lengths"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hostsim
+    hostsim.build()
+    spec = dict(backend="hostsim", transport="hook", n=3000, n_targ=4, n_max=8, half_band=6, tol=1e-9, ragged=True)
+    _check(tmp_path, spec, 3)
 
 
 def test_sharded_operator_refuses_long_range_couplings_on_every_rank(tmp_path):
@@ -164,6 +182,17 @@ def test_sharded_operator_refuses_long_range_couplings_on_every_rank(tmp_path):
 def test_sharded_banded_operator_two_ranks_on_one_gpu(tmp_path, transport):
     spec = dict(backend="hip", transport=transport, n=200_000, n_targ=6, n_max=10, half_band=6, tol=1e-9)
     _check(tmp_path, spec, 2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("half_band,ragged,ell_w", [(1, False, 3), (3, False, 7), (12, False, 25), (12, True, 20)])
+def test_sharded_banded_operator_three_ranks_on_one_gpu(tmp_path, half_band, ragged, ell_w):
+    """Three ranks share one GPU over the reduction hook: the middle rank reads a `prev` AND a `next` halo.  w = 3, 7, 25 are the
+    halo kernel's width buckets 4, 8, 32 (the two-rank legs above run w = 13: bucket 16); `ragged` gives rows of 2 .. 20 entries
+    and ranks that need halos of 8, 8 and 10 rows."""
+    spec = dict(backend="hip", transport="hook", n=30_000, n_targ=4, n_max=8, half_band=half_band, tol=1e-9, ragged=ragged)
+    many = _check(tmp_path, spec, 3)
+    assert max(r["ell_w"] for r in many) == ell_w, many
 
 
 @pytest.mark.gpu

@@ -56,9 +56,6 @@ template <int V, int NT> __device__ __forceinline__ typename VecOf<V>::type ploa
 // may_alias types so that type-based alias analysis cannot reorder them against each other
 typedef double __attribute__((may_alias)) lds_f64;
 typedef v2d __attribute__((may_alias)) lds_v2f64;
-// LDS arrays handed to device functions: address-space-3 pointers (a generic pointer may turn every access into a flat load)
-typedef __attribute__((address_space(3))) double as3_f64;
-typedef __attribute__((address_space(3))) int as3_i32;
 __device__ __forceinline__ void lds_store2(double* p, v2d v) { *(lds_v2f64*)p = v; }
 __device__ __forceinline__ void lds_store1(double* p, double v) { *(lds_f64*)p = v; }
 __device__ __forceinline__ double lds_load1(const double* p) { return *(const lds_f64*)p; }
@@ -944,11 +941,12 @@ struct RitzArgs {
 // (+6 % measured, tools/tune_ab.py)
 // XP: the coefficient block carries extra product columns behind the k Ritz columns (RitzArgs::k2); a template argument so
 // that the plain Ritz step keeps its code (the same tests as run-time branches cost the one-tile kernel 37 %)
-// SCHED (A/B, tune knob 0 = 7 / 8, wide blocks only): 1 = __builtin_amdgcn_iglp_opt(0) in the pipelined loop, 2 = an explicit
-// sched_group_barrier pipeline (four MFMAs, then one coefficient read of a later column step / one panel load of the next stage)
-template <int KT, int VEC, int NT = 3, int PIPE = (KT >= 3 ? 3 : KT >= 2 ? 2 : 0), int QT = 0, bool XP = false, int SCHED = 0>
+// RESERVED: always 0.  It once chose among hand-scheduled loops (none faster, profiles/r04/ritz_sched_ab.txt); it stays because the
+// benchmark and profiles/pmc_traffic.json key on the seven-argument kernel names
+template <int KT, int VEC, int NT = 3, int PIPE = (KT >= 3 ? 3 : KT >= 2 ? 2 : 0), int QT = 0, bool XP = false, int RESERVED = 0>
 __global__ __launch_bounds__(256) void ritz_kernel(RitzArgs a)
 {
+  static_assert(RESERVED == 0, "ritz_kernel: the seventh template argument only keeps the kernel's name");
   constexpr int RG = 16 * VEC;             // rows per wave tile (one row group)
   extern __shared__ __attribute__((aligned(16))) double cs[];  // [KT][l4][16], later reduction scratch
   typedef typename VecOf<VEC>::type vec_t;
@@ -1052,54 +1050,12 @@ __global__ __launch_bounds__(256) void ritz_kernel(RitzArgs a)
       if (PIPE <= nfull4) {
         vec_t xa[PIPE], ya[PIPE];
         load_stage(0, xa, ya);
-        if constexpr (SCHED == 5) {
-          // two stages per trip with the register sets changing roles: no copies, and a stage's loads are first read a whole
-          // stage of MFMAs after their issue
-          vec_t xc[PIPE], yc[PIPE];
-          for (; cs4 + 3 * PIPE <= nfull4; cs4 += 2 * PIPE) {
-            load_stage(cs4 + PIPE, xc, yc);
-            mfma_stage(cs4, xa, ya);
-            load_stage(cs4 + 2 * PIPE, xa, ya);
-            mfma_stage(cs4 + PIPE, xc, yc);
-          }
-        }
         for (; cs4 + 2 * PIPE <= nfull4; cs4 += PIPE) {
           vec_t xb[PIPE], yb[PIPE];
           load_stage(cs4 + PIPE, xb, yb);
           mfma_stage(cs4, xa, ya);
 #pragma unroll
           for (int u4 = 0; u4 < PIPE; ++u4) { xa[u4] = xb[u4]; ya[u4] = yb[u4]; }
-          if constexpr (SCHED == 1) __builtin_amdgcn_iglp_opt(0);
-          if constexpr (SCHED == 3) __builtin_amdgcn_iglp_opt(1);
-          if constexpr (SCHED == 4) {
-            // per column step: the coefficient reads of the NEXT step behind the first MFMAs, the panel loads of the next stage
-            // spread over the second half
-            __builtin_amdgcn_sched_group_barrier(0x100, KT, 0);
-#pragma unroll
-            for (int u4 = 0; u4 < PIPE; ++u4) {
-#pragma unroll
-              for (int q = 0; q < KT; ++q) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                if (u4 + 1 < PIPE) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-              }
-#pragma unroll
-              for (int q = 0; q < KT; ++q) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 2 * VEC - 2, 0);
-                if (q < 2) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-              }
-            }
-          }
-          if constexpr (SCHED == 2) {
-            constexpr int NG = PIPE * VEC * KT / 2;        // groups of four MFMAs
-            constexpr int ND = PIPE * KT, NV = 2 * PIPE;   // coefficient reads, panel loads of the next stage
-            __builtin_amdgcn_sched_group_barrier(0x100, KT, 0);
-#pragma unroll
-            for (int sg = 0; sg < NG; ++sg) {
-              __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-              if (sg < ND - KT) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-              if ((sg & 1) == 0 && sg / 2 < NV) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-          }
         }
         mfma_stage(cs4, xa, ya);
         cs4 += PIPE;
@@ -1212,322 +1168,6 @@ __global__ __launch_bounds__(256) void ritz_kernel(RitzArgs a)
     a.red[((size_t)blockIdx.x * 16 * KT + j) * 2 + 1] = m;
   }
 }
-
-#ifdef DLA_AB_VARIANTS
-// ---- the same sweep as a device function over a RANGE of column tiles, for ritz_pair_kernel below (A/B builds only: the shipped
-// ritz_kernel above keeps its own text -- wrapping it around this function cost the one-tile kernel 4 % on the benchmark although
-// the register counts came out equal, profiles/r06/ritz_pair_ab.txt)
-// what a sweep needs of RitzArgs, by value (a reference to the kernel's argument block -- which holds two 48-entry arrays that are
-// indexed at run time -- made the compiler keep a copy of it: 20 ... 90 registers more per kernel)
-struct RitzPanels {
-  const double* v; const double* av; double* evec; double* r; double* avy; double* p2; double* ap2;
-  long long n; int l, l4, k, k2;
-};
-__device__ __forceinline__ RitzPanels ritz_panels(const RitzArgs& a) { return RitzPanels{a.v, a.av, a.evec, a.r, a.avy, a.p2, a.ap2, a.n, a.l, a.l4, a.k, a.k2}; }
-// The sweep of one wave over its row tiles for the column tiles Q0 .. Q0 + KT - 1 of a coefficient block of KTOT tiles (Q0 = 0, KT = KTOT: the
-// whole block, as ritz_kernel does it; ritz_pair_kernel: two groups of four waves, each with a part of the tiles).  csall: the LDS
-// copy of the whole block, [KTOT][l4][16]; wave: 0 .. 3 inside the group; s_nrm: the group's norm accumulators (KT >= 4 only).
-// Ends with the wave's column sums / maxima in sred ([4][16 KTOT][2]) -- the caller synchronises around it.
-template <int KT, int VEC, int NT, int PIPE, int QT, bool XP, int SCHED, int KTOT, int Q0, bool NRM_LDS>
-__device__ __forceinline__ void ritz_sweep(const RitzPanels a, as3_f64* csall, const int wave, const as3_f64* s_theta, const as3_i32* s_active,
-                                           as3_f64* s_nrm, as3_f64* sred_all, const int blocks_x)
-{
-  // (the LDS arrays come in as address-space-3 pointers, so that their accesses stay ds_read / ds_write whatever the inliner proves;
-  //  the 20 ... 90 extra registers of this function's first version came from the argument block by reference, see RitzPanels)
-  constexpr int RG = 16 * VEC;             // rows per wave tile (one row group)
-  as3_f64* cs = csall + (size_t)Q0 * a.l4 * 16;
-  typedef typename VecOf<VEC>::type vec_t;
-  const long long n = a.n;
-  const int l = a.l, l4 = a.l4;
-  constexpr int KF = QT > 0 ? KT - 1 : KT;   // full tiles; the last tile has 4*QT live columns (see mfma_quarter)
-  constexpr int J0 = 16 * Q0;                // first column of this group's tiles
-  const int lane = threadIdx.x & 63;
-  const int i = lane & 15, g = lane >> 4;
-  const int i4 = lane & 3;
-  const long long ntiles = (n + RG - 1) / RG;
-  const int nsteps = l4 / 4;
-
-  // tiles of this group that can hold residual columns (m <= 48: tiles 0 .. 2 of the block); further tiles: extra products only
-  constexpr int KR0 = (3 - Q0) < 0 ? 0 : (3 - Q0);
-  constexpr int KR = KT < KR0 ? KT : KR0;
-  constexpr int KRA = KR > 0 ? KR : 1;    // (array extents)
-  constexpr bool TH_LDS = NRM_LDS;        // the norm accumulators (and theta / active) live in LDS, one slot per lane
-  double th[KRA][4];
-  int act[KRA][4];
-  double ssq[KRA][4], smx[KRA][4];
-  as3_f64* my_nrm = s_nrm + (TH_LDS ? (size_t)wave * 48 * 16 * 2 + i * 2 : 0);      // [col j][lane i][2], this wave
-#pragma unroll
-  for (int q = 0; q < KR; ++q)
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int j = J0 + 16 * q + g + 4 * reg;
-      th[q][reg] = s_theta[j];
-      act[q][reg] = s_active[j];
-      ssq[q][reg] = 0.0;
-      smx[q][reg] = 0.0;
-      if constexpr (TH_LDS) { my_nrm[(size_t)j * 32 + 0] = 0.0; my_nrm[(size_t)j * 32 + 1] = 0.0; }
-    }
-
-  for (long long tile = (long long)blockIdx.x * 4 + wave; tile < ntiles; tile += (long long)blocks_x * 4) {
-    long long row = tile * RG + VEC * i;
-    const bool rok = row < n;
-    if (!rok) row = 0;
-    v4d av[VEC][KT], aav[VEC][KT];
-#pragma unroll
-    for (int e = 0; e < VEC; ++e)
-#pragma unroll
-      for (int q = 0; q < KT; ++q) { av[e][q] = (v4d){0.0, 0.0, 0.0, 0.0}; aav[e][q] = (v4d){0.0, 0.0, 0.0, 0.0}; }
-    double avq[VEC][QT > 0 ? QT : 1], aavq[VEC][QT > 0 ? QT : 1];   // quarter tiles: scalars of their own (see gemm_kernel)
-#pragma unroll
-    for (int e = 0; e < VEC; ++e)
-#pragma unroll
-      for (int qq = 0; qq < (QT > 0 ? QT : 1); ++qq) { avq[e][qq] = 0.0; aavq[e][qq] = 0.0; }
-    auto avv = [&](int e, int q, int reg) -> double {
-      if (QT > 0 && q == KF) return reg < QT ? avq[e][reg < QT ? reg : 0] : 0.0;
-      return av[e][q][reg];
-    };
-    auto aavv = [&](int e, int q, int reg) -> double {
-      if (QT > 0 && q == KF) return reg < QT ? aavq[e][reg < QT ? reg : 0] : 0.0;
-      return aav[e][q][reg];
-    };
-    int cs4 = 0;
-    if constexpr (PIPE > 0) {
-      // two-stage register pipeline over column steps (see gemm_kernel)
-      const int nfull4 = l / 4;
-      auto load_stage = [&](int c0, vec_t (&xs)[PIPE], vec_t (&ys)[PIPE]) {
-#pragma unroll
-        for (int u4 = 0; u4 < PIPE; ++u4) {
-          const size_t off = (size_t)(4 * (c0 + u4) + g) * (size_t)n + row;
-          xs[u4] = pload<VEC, NT>(a.v + off);
-          ys[u4] = pload<VEC, NT>(a.av + off);
-        }
-      };
-      auto mfma_stage = [&](int c0, const vec_t (&xs)[PIPE], const vec_t (&ys)[PIPE]) {
-#pragma unroll
-        for (int u4 = 0; u4 < PIPE; ++u4) {
-          double cfu[KT];
-#pragma unroll
-          for (int q = 0; q < KF; ++q) cfu[q] = cs[(size_t)q * l4 * 16 + (size_t)(4 * (c0 + u4) + g) * 16 + i];
-          double cfq[QT > 0 ? QT : 1];
-#pragma unroll
-          for (int qq = 0; qq < QT; ++qq) cfq[qq] = cs[(size_t)KF * l4 * 16 + (size_t)(4 * (c0 + u4) + g) * 8 + 4 * qq + i4];
-#pragma unroll
-          for (int e = 0; e < VEC; ++e) {
-#pragma unroll
-            for (int q = 0; q < KF; ++q) {
-              av[e][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(cfu[q], vget<VEC>(xs[u4], e), av[e][q], 0, 0, 0);
-              aav[e][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(cfu[q], vget<VEC>(ys[u4], e), aav[e][q], 0, 0, 0);
-            }
-#pragma unroll
-            for (int qq = 0; qq < QT; ++qq) {
-              avq[e][qq] = mfma_quarter(cfq[qq], vget<VEC>(xs[u4], e), avq[e][qq]);
-              aavq[e][qq] = mfma_quarter(cfq[qq], vget<VEC>(ys[u4], e), aavq[e][qq]);
-            }
-          }
-        }
-      };
-      if (PIPE <= nfull4) {
-        vec_t xa[PIPE], ya[PIPE];
-        load_stage(0, xa, ya);
-        if constexpr (SCHED == 5) {
-          // two stages per trip with the register sets changing roles: no copies, and a stage's loads are first read a whole
-          // stage of MFMAs after their issue
-          vec_t xc[PIPE], yc[PIPE];
-          for (; cs4 + 3 * PIPE <= nfull4; cs4 += 2 * PIPE) {
-            load_stage(cs4 + PIPE, xc, yc);
-            mfma_stage(cs4, xa, ya);
-            load_stage(cs4 + 2 * PIPE, xa, ya);
-            mfma_stage(cs4 + PIPE, xc, yc);
-          }
-        }
-        for (; cs4 + 2 * PIPE <= nfull4; cs4 += PIPE) {
-          vec_t xb[PIPE], yb[PIPE];
-          load_stage(cs4 + PIPE, xb, yb);
-          mfma_stage(cs4, xa, ya);
-#pragma unroll
-          for (int u4 = 0; u4 < PIPE; ++u4) { xa[u4] = xb[u4]; ya[u4] = yb[u4]; }
-          if constexpr (SCHED == 1) __builtin_amdgcn_iglp_opt(0);
-          if constexpr (SCHED == 3) __builtin_amdgcn_iglp_opt(1);
-          if constexpr (SCHED == 4) {
-            // per column step: the coefficient reads of the NEXT step behind the first MFMAs, the panel loads of the next stage
-            // spread over the second half
-            __builtin_amdgcn_sched_group_barrier(0x100, KT, 0);
-#pragma unroll
-            for (int u4 = 0; u4 < PIPE; ++u4) {
-#pragma unroll
-              for (int q = 0; q < KT; ++q) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                if (u4 + 1 < PIPE) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-              }
-#pragma unroll
-              for (int q = 0; q < KT; ++q) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 2 * VEC - 2, 0);
-                if (q < 2) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-              }
-            }
-          }
-          if constexpr (SCHED == 2) {
-            constexpr int NG = PIPE * VEC * KT / 2;        // groups of four MFMAs
-            constexpr int ND = PIPE * KT, NV = 2 * PIPE;   // coefficient reads, panel loads of the next stage
-            __builtin_amdgcn_sched_group_barrier(0x100, KT, 0);
-#pragma unroll
-            for (int sg = 0; sg < NG; ++sg) {
-              __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-              if (sg < ND - KT) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-              if ((sg & 1) == 0 && sg / 2 < NV) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-          }
-        }
-        mfma_stage(cs4, xa, ya);
-        cs4 += PIPE;
-      }
-    }
-    for (; cs4 < nsteps; ++cs4) {
-      int col = 4 * cs4 + g;
-      const bool cok = col < l;
-      col = cok ? col : l - 1;
-      vec_t xv = pload<VEC, NT>(a.v + (size_t)col * (size_t)n + row);
-      vec_t yv = pload<VEC, NT>(a.av + (size_t)col * (size_t)n + row);
-      xv = cok ? xv : vzero<VEC>();
-      yv = cok ? yv : vzero<VEC>();
-      double cf[KT];
-#pragma unroll
-      for (int q = 0; q < KF; ++q) cf[q] = cs[(size_t)q * l4 * 16 + (size_t)(4 * cs4 + g) * 16 + i];
-      double cfq[QT > 0 ? QT : 1];
-#pragma unroll
-      for (int qq = 0; qq < QT; ++qq) cfq[qq] = cs[(size_t)KF * l4 * 16 + (size_t)(4 * cs4 + g) * 8 + 4 * qq + i4];
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) {
-#pragma unroll
-        for (int q = 0; q < KF; ++q) {
-          av[e][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(cf[q], vget<VEC>(xv, e), av[e][q], 0, 0, 0);
-          aav[e][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(cf[q], vget<VEC>(yv, e), aav[e][q], 0, 0, 0);
-        }
-#pragma unroll
-        for (int qq = 0; qq < QT; ++qq) {
-          avq[e][qq] = mfma_quarter(cfq[qq], vget<VEC>(xv, e), avq[e][qq]);
-          aavq[e][qq] = mfma_quarter(cfq[qq], vget<VEC>(yv, e), aavq[e][qq]);
-        }
-      }
-    }
-    if (rok) {
-#pragma unroll
-      for (int q = 0; q < KT; ++q)
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          const int j = J0 + 16 * q + g + 4 * reg;
-          if (j >= a.k + (XP ? a.k2 : 0)) continue;
-          const double e0 = avv(0, q, reg), e1 = avv(VEC - 1, q, reg);
-          double r0 = aavv(0, q, reg), r1 = aavv(VEC - 1, q, reg);
-          if constexpr (XP) {
-            if (j >= a.k) {                // a column of the extra block: two plain products
-              pstore<VEC, NT>(a.p2 + (size_t)(j - a.k) * (size_t)n + row, vmake<VEC>(e0, e1));
-              pstore<VEC, NT>(a.ap2 + (size_t)(j - a.k) * (size_t)n + row, vmake<VEC>(r0, r1));
-              continue;
-            }
-          }
-          constexpr int KRm = KRA - 1;
-          const int qr = q < KR ? q : KRm;  // (j < k <= 48 implies tile < 3; the clamp only keeps the unrolled indices in range)
-          if constexpr (KR == 0) continue;  // (a group without residual columns: everything it holds is an extra product)
-          if (a.avy) pstore<VEC, NT>(a.avy + (size_t)j * (size_t)n + row, vmake<VEC>(r0, r1));
-          // (the four- and five-tile kernels sit at the register limit: they read theta / active from LDS per tile)
-          const double thv = TH_LDS ? s_theta[j] : th[qr][reg];
-          const int actv = TH_LDS ? s_active[j] : act[qr][reg];
-          if (actv) {
-            r0 = r0 - thv * e0;            // daxpy(-eig), reference diaglib.f90:1729
-            if constexpr (TH_LDS) {
-              // (same order of additions as the register accumulators of the narrower kernels: same bits)
-              as3_f64* slot = my_nrm + (size_t)j * 32;
-              double sq = slot[0], mx = slot[1];
-              sq += r0 * r0; mx = fmax(mx, fabs(r0));
-              if constexpr (VEC == 2) { r1 = r1 - thv * e1; sq += r1 * r1; mx = fmax(mx, fabs(r1)); }
-              slot[0] = sq;
-              slot[1] = mx;
-            } else {
-              ssq[qr][reg] += r0 * r0;
-              smx[qr][reg] = fmax(smx[qr][reg], fabs(r0));
-              if constexpr (VEC == 2) {
-                r1 = r1 - thv * e1;
-                ssq[qr][reg] += r1 * r1;
-                smx[qr][reg] = fmax(smx[qr][reg], fabs(r1));
-              }
-            }
-          }
-          if (a.evec) pstore<VEC, NT>(a.evec + (size_t)j * (size_t)n + row, vmake<VEC>(e0, e1));     // (optional: Ritz vectors nobody reads are not written)
-          pstore<VEC, NT>(a.r + (size_t)j * (size_t)n + row, vmake<VEC>(r0, r1));
-        }
-    }
-  }
-  // reduce over the 16 lanes that share g (xor-shuffles stay inside 16-lane groups), then over waves
-  __syncthreads();   // everyone is done with cs as the copy of Y
-  as3_f64* sred = sred_all; // [4 waves][16*KTOT][2]
-#pragma unroll
-  for (int q = 0; q < KR; ++q)
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      double s = ssq[q][reg], m = smx[q][reg];
-      if constexpr (TH_LDS) { const int j = J0 + 16 * q + g + 4 * reg; s = my_nrm[(size_t)j * 32 + 0]; m = my_nrm[(size_t)j * 32 + 1]; }
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1) {
-        s += __shfl_xor(s, off, 64);
-        m = fmax(m, __shfl_xor(m, off, 64));
-      }
-      if (i == 0) {
-        const int j = J0 + 16 * q + g + 4 * reg;
-        sred[(wave * 16 * KTOT + j) * 2 + 0] = s;
-        sred[(wave * 16 * KTOT + j) * 2 + 1] = m;
-      }
-    }
-}
-
-// block partials of the column sums / maxima: the four waves that hold column j, in wave order (columns beyond the residual tiles: zero)
-template <int KTOT>
-__device__ __forceinline__ void ritz_partials_out(const RitzArgs& a, const as3_f64* sred)
-{
-  if (threadIdx.x < 16 * KTOT) {
-    const int j = threadIdx.x;
-    constexpr int KRT = KTOT < 3 ? KTOT : 3;
-    double s = 0.0, m = 0.0;
-    for (int w = 0; w < 4 && j < 16 * KRT; ++w) {
-      s += sred[(w * 16 * KTOT + j) * 2 + 0];
-      m = fmax(m, sred[(w * 16 * KTOT + j) * 2 + 1]);
-    }
-    a.red[((size_t)blockIdx.x * 16 * KTOT + j) * 2 + 0] = s;
-    a.red[((size_t)blockIdx.x * 16 * KTOT + j) * 2 + 1] = m;
-  }
-}
-
-// Two waves per SIMD for the wide sweeps (round-5 review, item 5): the one-wave-per-SIMD kernels of four and five column tiles keep
-// neither HBM nor the matrix cores busy -- a wave that waits for its loads issues no MFMAs (rocprofv3: MfmaUtil 62-65 %,
-// SQ_WAIT_INST_ANY 64 % of the wave cycles).  Here a block has EIGHT waves in two groups; both groups walk the same row tiles, group 0
-// forms the column tiles 0 .. KA - 1 and group 1 the tiles KA .. KA + KB - 1, each from its own loads of the rows (the second read of
-// a line is served by the caches; no LDS staging, no barrier inside the sweep).  Half the accumulators per wave, so two waves fit a
-// SIMD's registers.  Same contraction order per output element as ritz_kernel: bit-identical results.
-// MEASURED AND REJECTED (profiles/r06/ritz_pair_ab.txt, n = 1e7, 111 basis columns): 37 + 37 outputs 8.29 ms (pipeline depth 2 / 2; 8.9 with
-// 3 / 2, 10.3 without a pipeline) against 7.7-8.0 ms for the one-wave kernel; 30 + 30 outputs 8.85 against 6.9 ms -- every row is
-// fetched by two waves, and the second fetch is not free: it doubles the load instructions and the L2 -> CU traffic of a sweep
-// that already moves 4 TB/s.  Built only with -DDLA_AB_VARIANTS (tune knob 0 = 12 .. 15), for tools/ritz_pair_ab.py.
-template <int KA, int KB, int VEC, bool XP, int PA = (KA >= 3 ? 3 : KA >= 2 ? 2 : 0), int PB = (KB >= 3 ? 3 : KB >= 2 ? 2 : 0)>
-__global__ __launch_bounds__(512) void ritz_pair_kernel(RitzArgs a)
-{
-  constexpr int KTOT = KA + KB;
-  extern __shared__ __attribute__((aligned(16))) double cs[];  // [KTOT][l4][16], later reduction scratch
-  const int l4 = a.l4;
-  for (int idx = threadIdx.x; idx < KTOT * l4 * 16; idx += 512) cs[idx] = a.cpk[idx];
-  __shared__ double s_theta[48];
-  __shared__ int s_active[48];
-  __shared__ double s_nrm[4 * 48 * 16 * 2];      // group 0 holds every residual column (tiles 0 .. 2 when KA = 3; KA = 2: tile 2 is group 1's)
-  if (threadIdx.x < 48) { s_theta[threadIdx.x] = a.theta[threadIdx.x]; s_active[threadIdx.x] = a.active[threadIdx.x]; }
-  __syncthreads();
-  // (the reduction scratch of the two groups must not overlap the coefficient copy the other group may still read: both groups
-  //  synchronise inside ritz_sweep before they write it)
-  const int wv = (int)(threadIdx.x >> 6);
-  if (wv < 4) ritz_sweep<KA, VEC, 3, PA, 0, XP, 0, KTOT, 0, true>(ritz_panels(a), (as3_f64*)cs, wv, (const as3_f64*)s_theta, (const as3_i32*)s_active, (as3_f64*)s_nrm, (as3_f64*)cs, (int)gridDim.x);
-  else        ritz_sweep<KB, VEC, 3, PB, 0, XP, 0, KTOT, KA, false>(ritz_panels(a), (as3_f64*)cs, wv - 4, (const as3_f64*)s_theta, (const as3_i32*)s_active, (as3_f64*)s_nrm, (as3_f64*)cs, (int)gridDim.x);
-  __syncthreads();
-  ritz_partials_out<KTOT>(a, (const as3_f64*)cs);
-}
-#endif  // DLA_AB_VARIANTS
 
 // The same sweep with TWO coefficient blocks: e = V Y1 (stored when a.evec is given), r = AV Y2 - theta e for the active columns,
 // sum r^2 and max |r| -- the residual blocks of the linear-response drivers (reference diaglib.f90:872-889, 1337-1353:
@@ -3433,7 +3073,7 @@ struct GramReduceArgs {
   int ldc;             // leading dimension of c: l, or l + k with the extra tile
   int fenced;          // 1: hand the level-2 rows and C over behind agent-scope release / acquire fences (the portable form: what
                        // the HIP memory model guarantees) instead of write-through stores + drained store counter + sc1 loads
-                       // (what gfx942 / gfx950 make of relaxed agent-scope atomics: 3.4 us per launch less).  Tune knob 5 = 3;
+                       // (what gfx942 / gfx950 make of relaxed agent-scope atomics: 3.4 us per launch less).  Knobs::fenced_reduce;
                        // tests/test_ortho_chain_gpu.py runs both and requires identical bits, tests/test_abi.py checks the
                        // sc1 bits in the code object.
 };
@@ -3615,12 +3255,8 @@ struct HipEngine : dla::Engine {
   long long syn_row0 = 0; int syn_n = 0, syn_rw = 0; double syn_sigma = 0.0;
   // rccl
   ncclComm_t comm = nullptr;
-  // experiment knobs (DLA_OPT_TUNE0 + i) for tools/tune_ab.py: 0 = ritz pipeline depth for wide blocks (1 = none, 4),
-  // 1 = ritz grid factor, 2 = gemm pipeline depth for wide blocks (1 = none, 4), 3 = gemm grid factor,
-  // 4 = gram blocks-per-pass override (0 = built-in choice everywhere)
-  int tune[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  void set_tune(int i, int v) override { if (i >= 0 && i < 8) tune[i] = v; }
-  int get_tune(int i) override { return (i >= 0 && i < 8) ? tune[i] : 0; }
+  void set_tune(int i, int v) override { knobs.set(i, v); }
+  int get_tune(int i) override { return knobs.get(i); }
   void begin_solve() override { x3_cooldown = X3_COOLDOWN_START; }
   // per-kernel statistics (names as rocprofv3 prints them, without namespace / argument list)
   struct KStat { long long launches = 0; double alg_bytes = 0.0, ms = 0.0, flops = 0.0; };
@@ -3653,6 +3289,89 @@ struct HipEngine : dla::Engine {
 
   const char* name() const override { return nm.c_str(); }
   void* stream() override { return (void*)st; }
+
+  // The experiment knobs (options DLA_OPT_TUNE0 + i, i = 0 .. 7): what the tests, the benchmark ($DIAGLIB_BENCH_TUNE) and the A/B and fuzz
+  // tools switch by number.  All 0 is the product; a value that is not named here selects nothing.  The numbers stand in this struct
+  // and nowhere else: the engine asks one predicate per decision.  (The same table for the tools' side: tools/README.md.)
+  struct Knobs {
+    int tune[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    void set(int i, int v) { if (i >= 0 && i < 8) tune[i] = v; }
+    int get(int i) const { return (i >= 0 && i < 8) ? tune[i] : 0; }
+    // ---- knob 0: the Ritz sweep (ritz_residual_once, ritz_residual_p, ritz_residual2)
+    // 1 / 4: column-step pipeline of depth 0 / 4 for plain blocks of two and three tiles, no quarter tiles; -1: the kernel's own (tools/tune_ab.py)
+    int ritz_pipe_depth() const { return tune[0] == 1 ? 0 : tune[0] == 4 ? 4 : -1; }
+    // 5: Ritz step and P products never in one pass (A/B switch, no record kept)
+    bool ritz_p_separate() const { return tune[0] == 5; }
+    // 6: the two-coefficient sweep ritz2_kernel off, three sweeps instead (A/B switch, no record kept)
+    bool no_ritz2() const { return tune[0] == 6; }
+    // ---- knob 1: blocks of a Ritz sweep, as a multiple of the built-in count (tools/tune_ab.py)
+    int ritz_grid_factor() const { return tune[1] > 0 ? tune[1] : 1; }
+    // ---- knob 2: the plain panel product (gemm_chunk)
+    // 1 / 4: as knob 0 = 1 / 4, for the plain product and update of two and three tiles (tools/tune_ab.py)
+    int gemm_pipe_depth() const { return tune[2] == 1 ? 0 : tune[2] == 4 ? 4 : -1; }
+    // ---- knob 3: > 0: cap on resident blocks per CU of the panel-product kernels (tools/tune_fused.py)
+    int gemm_blocks_per_cu() const { return tune[3] > 0 ? tune[3] : 0; }
+    // ---- knob 4: blocks of the Gram sweeps
+    // > 0: blocks per pass of gram_plan and wp_plan (tools/tune_ab.py, tools/ab/combox_ab.py)
+    int gram_blocks_override() const { return tune[4] > 0 ? tune[4] : 0; }
+    // -1: the measuring sweeps of up to five X tiles with one block per CU (measured r05, see wp_plan)
+    bool wp_one_block_per_cu() const { return tune[4] == -1; }
+    // ---- knob 5: the Gram kernels and their reduction
+    // 2: the direct-load gram_kernel everywhere (tools/tune_gram.py)
+    bool direct_gram() const { return tune[5] == 2; }
+    // 3: GramReduceArgs::fenced (tests/test_ortho_chain_gpu.py requires identical bits)
+    bool fenced_reduce() const { return tune[5] == 3; }
+    // ---- knob 6: the orthogonalisation chain
+    // 2: the host polls the stream, no event packet (wait_stream)
+    bool poll_stream() const { return tune[6] == 2; }
+    // 3: no chain, the host-driven loop (parity knob of tests/test_ortho_chain_gpu.py, tools/fuzz_parity.py)
+    bool host_loop() const { return tune[6] == 3; }
+    // 4: the cross-rank exchange as a launch of its own, not in the reduction kernel (A/B switch, no record kept; bench.py's own example)
+    bool exchange_own_launch() const { return tune[6] == 4; }
+    // 5: one-tile blocks keep the LDS-loop k x k step of ortho_tail_kernel (A/B switch, no record kept)
+    bool no_mfma_kxk() const { return tune[6] == 5; }
+    // 6: one-tile blocks on the sweep-per-update schedule (A/B switch, no record kept)
+    bool no_pending_factor() const { return tune[6] == 6; }
+    // 7 / 8: wide blocks without the one-sweep [X | U] Gram (tools/wide_solve_ab.py, tools/iters_probe.py)
+    bool no_wide_gramx() const { return tune[6] == 7 || tune[6] == 8; }
+    // 7 also: the leading ortho_cd runs to convergence (OrthoTailArgs::lead_once = 0)
+    bool lead_full() const { return tune[6] == 7; }
+    // 9: wide blocks without the storing sweep OP_XW (tools/ab/wide_xw_ab.py)
+    bool no_wide_xw() const { return tune[6] == 9; }
+    // 10: the storing sweep for three-tile blocks too (measured r04, see ortho_chain_begin)
+    bool wide_xw_three_tiles() const { return tune[6] == 10; }
+    // 11: b_ortho_ahead declines: the metric Cholesky-QR waits for the chain (A/B switch, no record kept)
+    bool no_b_ortho_ahead() const { return tune[6] == 11; }
+    // 12: never the three-pass schedule (tests, tools/fuzz_ortho.py, tools/profile_all.sh)
+    bool five_sweep() const { return tune[6] == 12; }
+    // 13: the three-pass schedule from the first chain, no cooldown (same)
+    bool three_pass_always() const { return tune[6] == 13; }
+    // 14: basis_exact_ok() answers no (tools/ab/exact_ab.sh, tests/test_pending_basis_gpu.py)
+    bool mode5_as_mode4() const { return tune[6] == 14; }
+    // what basis_exact_ok() needs of the three above
+    bool no_exact_basis() const { return host_loop() || no_mfma_kxk() || mode5_as_mode4(); }
+    // OrthoTailArgs::gp; 15: from U^T U as the reference's, 16: level shifts on the projected block's Gram matrix (tools/ab/exact_ab.sh, see launch_op)
+    int first_factor_source() const { return tune[6] == 15 ? 0 : tune[6] == 16 ? 2 : 1; }
+    // 17: plans keep OP_CLOSE / OP_FINAL where the caller takes the closing block (r05 trace, see ortho_chain_begin)
+    bool keep_closing_launches() const { return tune[6] == 17; }
+    // ---- knob 7: kernel variants of the wide blocks (tools/quarter_tile_ab.py unless another record is named)
+    // 1: full 16x16x4 tiles only (tests/test_quarter_tiles_gpu.py compares both)
+    bool no_quarter_tiles() const { return tune[7] == 1; }
+    // 2: GramArgs::noskip, the loads of fully padded column groups are issued too
+    bool gram_load_pads() const { return tune[7] == 2; }
+    // 3: Gram passes of at most 12 accumulator tiles
+    bool narrow_gram_passes() const { return tune[7] == 3; }
+    // 4: the row products do not load the next row tile ahead (GemmArgs::xpf = 0)
+    bool no_next_tile_prefetch() const { return tune[7] == 4; }
+    // 5: 64-row wave tiles (RTP = 2) in the fused three-tile sweep
+    bool fused3_two_row_groups() const { return tune[7] == 5; }
+    // 8: the lower triangle of two panels in several passes, not gram_lds_kernel LOW
+    bool no_low_single() const { return tune[7] == 8; }
+    // 9: small_copy_kernel instead of the runtime's copy (see stage_slot)
+    bool own_copy_kernel() const { return tune[7] == 9; }
+    // 22 / 23: one first-level group per 16 / 64 block partials (measured r06, DESIGN "Measured and rejected")
+    int reduce_group_size() const { return tune[7] == 22 ? 16 : tune[7] == 23 ? 64 : 32; }
+  } knobs;
 
   // What the launches of the current step are enqueued under.  Nothing a launch depends on is a bare engine member: a caller
   // installs a modified copy with CtxScope, which puts back what was there before on every way out.  Outside any scope the
@@ -4051,7 +3770,7 @@ struct HipEngine : dla::Engine {
   {
     const double t0 = now();
     hipError_t q;
-    if (tune[6] == 2) {                      // A/B: poll the stream itself, no event packet
+    if (knobs.poll_stream()) {               // A/B: poll the stream itself, no event packet
       while ((q = hipStreamQuery(st)) == hipErrorNotReady) {
 #if defined(__x86_64__)
         __builtin_ia32_pause();
@@ -4090,7 +3809,7 @@ struct HipEngine : dla::Engine {
   // straight into the slot (stage_slot), stage_commit enqueues the copy.
   // (The runtime's copy shows up as __amd_rocclr_copyBuffer, 16 us of stream time per 30 KB in a solve's trace, and in isolation
   // a copy kernel of the engine's own is faster -- tools/upload_probe.hip: 26 us host-to-consumer against 20 us -- but inside a
-  // solve it buys nothing: interleaved A/B, knob 7 = 9, 16.88 / 16.90 ms against 16.90 / 16.88 at n = 2e6 and 3.90 / 3.90 against
+  // solve it buys nothing: interleaved A/B, Knobs::own_copy_kernel, 16.88 / 16.90 ms against 16.90 / 16.88 at n = 2e6 and 3.90 / 3.90 against
   // 3.86 / 3.87 at 250 k rows.  The runtime's copy stays.)
   int stage_slot(size_t bytes, double** host, int* slot_out)
   {
@@ -4115,7 +3834,7 @@ struct HipEngine : dla::Engine {
   }
   int stage_commit(int slot, size_t bytes, double* dev)
   {
-    if (tune[7] != 9) {
+    if (!knobs.own_copy_kernel()) {
       HIPCHK(hipMemcpyAsync(dev, h_ring[slot], bytes, hipMemcpyHostToDevice, st));
     } else {                                 // A/B: a copy kernel of the engine's own reading the mapped slot
       const int cnt = (int)(bytes / sizeof(double));
@@ -4407,10 +4126,9 @@ struct HipEngine : dla::Engine {
   }
 
   // groups of the reduction's first level: one per 32 block partials, at most 32 (the second level adds them in one pass of 32 loads).
-  // (tune knob 7 = 22 / 23: A/B, one group per 16 / 64 partials -- measured r06, see DESIGN "Measured and rejected")
   int reduce_groups(int nblk) const
   {
-    const int per = tune[7] == 22 ? 16 : tune[7] == 23 ? 64 : 32;
+    const int per = knobs.reduce_group_size();
     return std::max(1, std::min(32, (nblk + per - 1) / per));
   }
   struct Rode { bool tail = false, exchange = false; };   // what went along in a reduction kernel: the chain's tail, the cross-rank sum
@@ -4418,7 +4136,7 @@ struct HipEngine : dla::Engine {
   {
     Rode rode;
     if (ra.ldc == 0) ra.ldc = ra.l;
-    ra.fenced = tune[5] == 3 ? 1 : 0;
+    ra.fenced = knobs.fenced_reduce() ? 1 : 0;
     rode.tail = lc.fuse_tail && !(p2p.on && ra.ldc * ra.k > P2P_MAX_DOUBLES);   // beyond a mailbox slot: separate launches
     if (rode.tail) {
       ra.do_tail = 1; ra.tail = lc.tail;
@@ -4462,14 +4180,14 @@ struct HipEngine : dla::Engine {
   int launch_op(int op, int n, int m, int k, const double* x, const double* bx, double* u, bool publish, int fold)
   {
     OrthoTailArgs tail{d_ost, h_ost.dev(), d_small, d_wpk, d_wfull, d_cpk2, op, m, k, m > 0 ? 1 : 0, ortho_maxit, publish ? 1 : 0,
-                       fold, tune[6] == 7 ? 0 : 1, d_xug, d_wst, d_dbg, lc.xw ? 1 : 0};
+                       fold, knobs.lead_full() ? 0 : 1, d_xug, d_wst, d_dbg, lc.xw ? 1 : 0};
     if ((fold == 1 && op == OP_GRAMX) || op == OP_XW || op == OP_COMBOX) tail.gsrc = d_xug;
     tail.x3 = lc.x3 ? 1 : 0;
-    // (knob 6 = 15: A/B, the first factor from U^T U as the reference's; 16: A/B, level shifts on the projected block's Gram matrix
+    // (A/B, Knobs::first_factor_source: 0 = the first factor from U^T U as the reference's; 2 = level shifts on the projected block's Gram matrix
     //  instead of the reference's order for a numerically rank-deficient block -- 14.2-14.36 against 14.37-14.46 ms on the benchmark,
     //  but such a block's weakest columns then depend on the schedule, and the reference's dense test matrix with unit guesses takes
     //  another history (tests/test_trace_text.py::dav_n1000_unit fails with it, also when only the drivers' chains use it): not shipped)
-    tail.gp = tune[6] == 15 ? 0 : tune[6] == 16 ? 2 : 1;
+    tail.gp = knobs.first_factor_source();
     tail.dmat = (policy.basis_exact && fold && m > 0 && dmat_nontrivial && dmat_cols == m && m <= DMAT_LD) ? d_dmat : nullptr;
     tail.dmat_ld = DMAT_LD;
     tail.drop_final = (policy.drop_final && m > 0) ? 1 : 0;
@@ -4481,7 +4199,7 @@ struct HipEngine : dla::Engine {
     int stc = DLA_OK;
     {
       LaunchCtx step = lc;
-      step.fuse_tail = p2p.on ? tune[6] != 4 : (nranks <= 1 && !comm);     // (knob 6 = 4: the exchange as a launch of its own)
+      step.fuse_tail = p2p.on ? !knobs.exchange_own_launch() : (nranks <= 1 && !comm);
       step.tail = tail;
       step.phase = &d_ost->phase;
       step.want = (op == OP_GRAMX) ? (int)OP_GRAM_UU : (lc.x3 && op == OP_COMBO) ? (int)OP_COMBOX : op;   // the first sweep answers the start phase
@@ -4580,8 +4298,8 @@ struct HipEngine : dla::Engine {
     // (one U tile beside up to five X tiles: at most 212 / 252 registers and 55 KB of LDS per block -- two blocks per CU, two waves
     //  per SIMD: measured r05 at n = 2e6, interleaved: +5 ... 11 % for the projection sweep, +3 ... 9 % for the storing one; beyond
     //  five tiles the kernels need more than 256 registers and a second block per CU only runs behind the first)
-    p.blocks = (int)std::max(1LL, std::min((long long)ncu * ((p.self || (p.kt == 1 && p.tlw <= 5 && tune[4] != -1)) ? 2 : 1), want));   // (knob 4 = -1: A/B)
-    if (tune[4] > 0) p.blocks = (int)std::max(1LL, std::min((long long)tune[4], want));
+    p.blocks = (int)std::max(1LL, std::min((long long)ncu * ((p.self || (p.kt == 1 && p.tlw <= 5 && !knobs.wp_one_block_per_cu())) ? 2 : 1), want));
+    if (knobs.gram_blocks_override()) p.blocks = (int)std::max(1LL, std::min((long long)knobs.gram_blocks_override(), want));
     p.extra = p.self ? 0 : p.kt * (p.kt + 1) / 2;          // tiles (qi >= qj) of the Gram matrix of the U block
     p.slots = p.self ? 1 : p.tlw * p.kt + p.extra;
     return p;
@@ -4657,7 +4375,7 @@ struct HipEngine : dla::Engine {
                                      // because a threshold would make the projections inexact by that threshold)
   int basis_state(int m) const override { return m <= 0 ? 0 : dmat_cols != m ? -1 : dmat_nontrivial ? 1 : 0; }
   int basis_capacity() const override { return DMAT_LD; }
-  bool basis_exact_ok() const override { return !hook && !local_only && tune[6] != 3 && tune[6] != 5 && tune[6] != 14 && lds_limit > (size_t)128 * 1024; }   // (knob 6 = 14: A/B, mode 5 behaves like mode 4)
+  bool basis_exact_ok() const override { return !hook && !local_only && !knobs.no_exact_basis() && lds_limit > (size_t)128 * 1024; }
   int basis_dd(int m, int k, double* xu, int ld) override
   {
     if (!policy.basis_exact || m <= 0) return DLA_OK;
@@ -4749,7 +4467,7 @@ struct HipEngine : dla::Engine {
       err = "ortho_chain: dla_expand_project mode 5 needs the caller's pending blocks (dla_basis_sync after every block of the basis)";
       return (int)DLA_ERR_ARG;
     };
-    if (tune[6] == 3 || policy.chain_off) return not_handled();                  // A/B / the caller's request: host-driven loop
+    if (knobs.host_loop() || policy.chain_off) return not_handled();                // A/B / the caller's request: host-driven loop
     if (hook || local_only || k <= 0 || k > 48) return not_handled();     // hook reductions need the host between sweeps
     const bool vsx = m > 0;
     if (vsx && !(u == x + (size_t)n * m && can_combo(m, k))) return not_handled();
@@ -4757,10 +4475,10 @@ struct HipEngine : dla::Engine {
     // k x k steps on the matrix cores (ortho_tail16) for one-tile blocks; with them, on the 16-byte path and while X^T U fits one
     // pass of the storing sweep (12 tiles), the pending-factor schedule (fold = 1); otherwise the sweep-per-update one (fold = 2)
     const bool vec2 = even_rows(n) && (((uintptr_t)u | (uintptr_t)x | (uintptr_t)bx) % 16 == 0);
-    int fold = (k <= 16 && tune[6] != 5) ? 2 : 0;
-    if (fold && vsx && vec2 && m <= 192 && tune[6] != 6 && lds_limit > (size_t)128 * 1024) fold = 1;
+    int fold = (k <= 16 && !knobs.no_mfma_kxk()) ? 2 : 0;
+    if (fold && vsx && vec2 && m <= 192 && !knobs.no_pending_factor() && lds_limit > (size_t)128 * 1024) fold = 1;
     // ... and with the standard inner product (bx == x: the panel the projection subtracts is the panel it measures against) the
-    // three-pass schedule: projections that measure X^T U and U^T U of what they store (tune knob 6 = 12: the five-sweep one)
+    // three-pass schedule: projections that measure X^T U and U^T U of what they store (Knobs::five_sweep keeps the five-sweep one)
     // For callers that finish their blocks in memory (plain ortho_vs_x, dla_expand_project modes 0 / 1 / 4) not while expansion blocks
     // come out of their first projection numerically rank deficient (level shifts: the benchmark operator's rank-4 coupling leaves 4
     // new directions per 13-column block): there the written update and the storing sweep follow whatever the projection measured
@@ -4774,11 +4492,11 @@ struct HipEngine : dla::Engine {
     // (policy.basis_exact: the caller keeps its pending blocks on the device (dla_basis_sync) and every projection of this chain is exact
     //  against the FINISHED basis -- a loose stored basis costs later chains nothing, so the schedule that ends soonest always)
     if (policy.basis_exact && vsx && (fold == 0 || dmat_cols != m || (dmat_nontrivial && m > DMAT_LD))) return not_handled();
-    const bool x3 = fold == 1 && bx == x && tune[6] != 12 && (x3_cooldown <= 0 || tune[6] == 13 || rebuilt || policy.basis_exact);
+    const bool x3 = fold == 1 && bx == x && !knobs.five_sweep() && (x3_cooldown <= 0 || knobs.three_pass_always() || rebuilt || policy.basis_exact);
     // wider blocks (LDS-loop tail): X^T U and U^T U in ONE sweep when [X | U] fits one pass of the Gram kernel (the plain
     // product with the contiguous panel [X | U] on the left: U follows X, bx == x) and the leading ortho_cd takes one step
     const int ktw = (k + 15) / 16;
-    const bool wide_gramx = fold == 0 && vsx && vec2 && bx == x && tune[6] != 7 && tune[6] != 8 && ktw >= 2 && ktw <= 3 &&
+    const bool wide_gramx = fold == 0 && vsx && vec2 && bx == x && !knobs.no_wide_gramx() && ktw >= 2 && ktw <= 3 &&
                             (m + k + 15) / 16 <= (ktw == 2 ? 8 : 7) && lds_limit > (size_t)128 * 1024;
     // ([X | U] in TWO passes of that sweep -- the 18-column block behind 125 basis columns of the cfg 4 shape would then take
     //  `6 4 2 8 4 5` instead of `1 3 4 2 2 3 4 5` -- measured r06: 32.23-32.27 against 32.24-32.38 ms per solve, no gain; not built in)
@@ -4786,8 +4504,8 @@ struct HipEngine : dla::Engine {
     // one-tile schedule closes with) while X^T U fits one pass beside the block's tiles: 5 sweeps per call instead of 6
     // (two-tile blocks: measured r04 at n = 1e7, m = 64, k = 32: 1777 us against 937 + 1010 for the two sweeps it replaces; the
     //  three-tile sweep does 108 MFMAs per 16 rows with one wave per SIMD and runs at 3.9 TB/s -- 2960 us against 1212 + 1682: it
-    //  stays off unless tune knob 6 = 10 asks for it)
-    const bool wide_xw = wide_gramx && (ktw == 2 || tune[6] == 10) && (m + 15) / 16 <= wp_max_tlw(ktw) && (m + k) * k <= XUG_DOUBLES && tune[6] != 9;
+    //  stays off unless Knobs::wide_xw_three_tiles asks for it)
+    const bool wide_xw = wide_gramx && (ktw == 2 || knobs.wide_xw_three_tiles()) && (m + 15) / 16 <= wp_max_tlw(ktw) && (m + k) * k <= XUG_DOUBLES && !knobs.no_wide_xw();
     int stc = ensure_chain_buffers();
     if (stc) return stc;
     // First chain of a shape: walk every launch path it may take WITHOUT launching (workspaces grow now, not half way; a
@@ -4860,8 +4578,8 @@ struct HipEngine : dla::Engine {
     // machine ends with the block pending and never asks for OP_CLOSE / OP_FINAL) get plans without them: the fused step of the
     // last planned sweep reports where the machine stands whether or not it was that sweep's turn (gram_reduce_kernel<true>).  Two
     // predicated-off sweeps and two k x k launches less per chain: 19 us (r05 trace: 0.15 ms per benchmark solve, 0.23 per LOBPCG solve).
-    const bool fused_steps = p2p.on ? (tune[6] != 4 && (m + k) * k <= P2P_MAX_DOUBLES) : (nranks <= 1 && !comm);
-    const bool lean = vsx && rebuilt && m + k <= PEND_ROWS && fused_steps && tune[6] != 17;
+    const bool fused_steps = p2p.on ? (!knobs.exchange_own_launch() && (m + k) * k <= P2P_MAX_DOUBLES) : (nranks <= 1 && !comm);
+    const bool lean = vsx && rebuilt && m + k <= PEND_ROWS && fused_steps && !knobs.keep_closing_launches();
     if (lean) {
       while (plan.size() > 1 && (plan.back() == OP_FINAL || plan.back() == OP_CLOSE)) plan.pop_back();
     } else
@@ -5052,7 +4770,7 @@ struct HipEngine : dla::Engine {
   int b_ortho_ahead(int n, int k, double* u, double* bu, bool behind_chain, int* handled) override
   {
     *handled = 0;
-    if (k <= 0 || k > 48 || hook || local_only || tune[6] == 11) return DLA_OK;
+    if (k <= 0 || k > 48 || hook || local_only || knobs.no_b_ortho_ahead()) return DLA_OK;
     bind();
     { const int stz = reserve_zeroed(d_bgo, 1); if (stz) return stz; }
     HIPCHK(h_bstat.reserve(1));
@@ -5146,7 +4864,7 @@ struct HipEngine : dla::Engine {
   }
   // (a pass narrower than one tile, e.g. the 4-column W^T x of the benchmark operator, would stage mostly
   // duplicates of its last column: it keeps the direct-load kernel)
-  bool use_lds_gram(bool vec2, int l, int kt) const { return vec2 && kt <= 3 && l > 8 && tune[5] != 2; }
+  bool use_lds_gram(bool vec2, int l, int kt) const { return vec2 && kt <= 3 && l > 8 && !knobs.direct_gram(); }
   template <int TLW, int KT>
   int launch_gram(const GramArgs& a, dim3 grid, const GramPlan& p)
   {
@@ -5182,7 +4900,7 @@ struct HipEngine : dla::Engine {
     const bool vec2 = even_rows(n) && aligned;
     // (even n: at most 3 U tiles per pass, so that the LDS-staged kernel serves every pass -- the direct-load kernel a
     // fourth tile would need measured 2.6 TB/s on the 111-column S^T A S of LOBPCG at n_max = 37)
-    int kt = std::min(tu, (vec2 && l > 8 && tune[5] != 2) ? 3 : 4);
+    int kt = std::min(tu, (vec2 && l > 8 && !knobs.direct_gram()) ? 3 : 4);
     const int passes_u = (tu + kt - 1) / kt;
     kt = (tu + passes_u - 1) / passes_u;
     const bool ldsk = use_lds_gram(vec2, l, kt);
@@ -5193,7 +4911,7 @@ struct HipEngine : dla::Engine {
     // AGPRs, up to 21 tiles: fewer passes = fewer re-reads of U, and `lower` passes skip the tiles above the diagonal)
     static const int maxtl_lds[4] = {0, 12, 8, 7};
     int mt = ldsk ? maxtl_lds[kt] : maxtl[kt];
-    if (tune[7] == 3) mt = (ldsk && kt == 1) ? 12 : maxtl[kt];       // A/B: the narrower passes
+    if (knobs.narrow_gram_passes()) mt = (ldsk && kt == 1) ? 12 : maxtl[kt];       // A/B: the narrower passes
     // the LDS-staged kernel stages 16 (tlw + kt) columns of 18 doubles per wave: keep the pass inside lds_limit
     if (ldsk) mt = std::max(1, std::min(mt, (int)(lds_limit / (sizeof(double) * 4 * 16 * 18)) - kt));
     const int passes_x = (tx + mt - 1) / mt;
@@ -5217,7 +4935,7 @@ struct HipEngine : dla::Engine {
     int qt = (ldsk && passes_u == 1 && kt >= 2) ? quarter_tiles(k, vec2) : 0;
     // the lower triangle of X^T U for two different panels of 49..112 columns (S^T A S of LOBPCG at n_max = 21 / 37):
     // one pass over both panels with the 10..28 tile pairs on or below the diagonal (gram_lds_kernel LOW)
-    const bool low_single = lower && ldsk && !self && l == k && tx >= 4 && tx <= 7 && passes > 1 && tune[7] != 8 &&
+    const bool low_single = lower && ldsk && !self && l == k && tx >= 4 && tx <= 7 && passes > 1 && !knobs.no_low_single() &&
                             sizeof(double) * 4 * 16 * (size_t)(2 * tx) * 18 <= lds_limit;
     if (low_single) { kt = tlw = tx; px = 1; passes = 1; qt = 0; }
     const int ch = vec2 ? 32 : 16;
@@ -5228,7 +4946,7 @@ struct HipEngine : dla::Engine {
     // the narrowest sweeps (a block against itself, or fewer than 8 columns against a block) have too few loads in
     // flight with one block per CU: two per CU measured +11 % / +19 % there and -1..-3 % everywhere else
     if (tlw * kt == 1 && ((same && l == k) || l <= 8)) blocks_per_pass = (int)std::max(1LL, std::min(2LL * ncu, want));
-    if (tune[4] > 0) blocks_per_pass = (int)std::max(1LL, std::min((long long)tune[4], want));
+    if (knobs.gram_blocks_override()) blocks_per_pass = (int)std::max(1LL, std::min((long long)knobs.gram_blocks_override(), want));
     const int rows = (ldsk && !low_single && gram_can32(tlw, kt) && lds_rows(tlw, kt) == 32) ? 32 : 16;
     return GramPlan{tlw, kt, px, passes, rows, ldsk, self, qt, low_single, lower, blocks_per_pass, vec2};
   }
@@ -5243,7 +4961,7 @@ struct HipEngine : dla::Engine {
     if (stc) return stc;
     stc = ensure_small(sizeof(double) * (size_t)l * k);
     if (stc) return stc;
-    GramArgs a{x, u, d_partial, (long long)n, l, k, p.px, p.lower ? 1 : 0, lc.phase, lc.want, tune[7] == 2 ? 1 : 0};
+    GramArgs a{x, u, d_partial, (long long)n, l, k, p.px, p.lower ? 1 : 0, lc.phase, lc.want, knobs.gram_load_pads() ? 1 : 0};
     dim3 grid(blocks_per_pass, passes);
     {
       const bool same = (x == u) && (l == k);
@@ -5463,7 +5181,7 @@ struct HipEngine : dla::Engine {
   int quarter_tiles(int k, bool vec2) const
   {
     const int kt = (k + 15) / 16, rem = k - 16 * (kt - 1);
-    return (vec2 && kt >= 2 && kt <= 3 && rem <= 8 && tune[7] != 1) ? (rem + 3) / 4 : 0;
+    return (vec2 && kt >= 2 && kt <= 3 && rem <= 8 && !knobs.no_quarter_tiles()) ? (rem + 3) / 4 : 0;
   }
 
   template <int KT, typename ARGS>
@@ -5492,15 +5210,15 @@ struct HipEngine : dla::Engine {
   }
 
   template <int KT, typename ARGS>
-  void launch_gemm(const ARGS& a, int blocks, size_t lds, bool vec2, int mode, int qt)
+  void launch_gemm(const ARGS& a, int blocks, size_t lds, bool vec2, int mode, int qt, int pipe)
   {
 #define GM(V, M) DLA_LAUNCH((gemm_kernel<KT, V, M, ARGS>), dim3(blocks), dim3(256), lds, st, a)
 #define GMQP(M, Q, P) DLA_LAUNCH((gemm_kernel<KT, 2, M, ARGS, false, (M == 2 ? 0 : 1), P, 9, Q>), dim3(blocks), dim3(256), lds, st, a)
 #define GMQ(M, Q) GMQP(M, Q, 2)      /* (a third step per stage costs these kernels their second wave per SIMD: update -22 %) */
 #define GMP(M, P) DLA_LAUNCH((gemm_kernel<KT, 2, M, ARGS, false, 1, P>), dim3(blocks), dim3(256), lds, st, a)
-    if (vec2 && KT >= 2 && (mode == 0 || mode == 1) && (tune[2] == 1 || tune[2] == 4)) {
-      if (tune[2] == 1) { if (mode == 0) GMP(0, 0); else GMP(1, 0); }
-      else              { if (mode == 0) GMP(0, 4); else GMP(1, 4); }
+    if (vec2 && KT >= 2 && pipe != 2) {   // (a depth other than these kernels' own: Knobs::gemm_pipe_depth -- mode 0 / 1, no quarter tiles)
+      if (pipe == 0) { if (mode == 0) GMP(0, 0); else GMP(1, 0); }
+      else           { if (mode == 0) GMP(0, 4); else GMP(1, 4); }
       return;
     }
     if constexpr (KT >= 2) {
@@ -5530,7 +5248,9 @@ struct HipEngine : dla::Engine {
       if (stc) return stc;
     }
     const bool vec2 = even_rows(n) && (((uintptr_t)x | (uintptr_t)z) % 16 == 0);
-    int qt = (tune[2] == 1 || tune[2] == 4) && !fuse ? 0 : quarter_tiles(k, vec2);
+    // the variant, decided once: quarter tiles, pipeline depth and (below) row groups go into the booked name AND pick the instance
+    const int ab_depth = fuse ? -1 : knobs.gemm_pipe_depth();
+    int qt = ab_depth >= 0 ? 0 : quarter_tiles(k, vec2);
     // (the plain two-tile update is the one sweep that measured slower with quarter tiles, -9 % at L = 63, k = 21:
     // tools/quarter_tile_ab.py)
     if (!fuse && mode == 1 && kt == 2) qt = 0;
@@ -5539,11 +5259,12 @@ struct HipEngine : dla::Engine {
     const size_t lds_c = sizeof(double) * (size_t)l4 * (qt > 0 ? 16 * (kt - 1) + 8 : 16 * kt);
     const size_t lds = fuse ? std::max(lds_c + sizeof(double) * 4 * 16 * (16 * kt + 9), (size_t)8192) : lds_c;
     int per_cu = lds > 80 * 1024 ? 1 : lds > 40 * 1024 ? 2 : 4;
-    if (tune[3] > 0) per_cu = (int)std::max((size_t)1, std::min((size_t)tune[3], (size_t)(156 * 1024) / std::max(lds, (size_t)4096)));
+    if (knobs.gemm_blocks_per_cu()) per_cu = (int)std::max((size_t)1, std::min((size_t)knobs.gemm_blocks_per_cu(), (size_t)(156 * 1024) / std::max(lds, (size_t)4096)));
     // row groups per wave tile (gemm_kernel RTP): the fused three-tile sweeps need > 256 registers with two groups, one
     // wave per SIMD; with one group two fit -- when the LDS leaves room for a second block per CU (measured +9..20 %,
     // and -26 % when it does not)
-    const int rtp = (fuse && kt == 3 && vec2 && per_cu >= 2 && tune[7] != 5) ? 1 : 2;
+    const int rtp = (fuse && kt == 3 && vec2 && per_cu >= 2 && !knobs.fused3_two_row_groups()) ? 1 : 2;
+    const int pipe = (ab_depth >= 0 && vec2 && kt >= 2 && (mode == 0 || mode == 1)) ? ab_depth : (fuse && kt >= 3) ? 3 : kt >= 2 ? 2 : 0;
     const int wt = (vec2 ? 32 : 16) * rtp;
     const long long ntiles = ((long long)n + wt - 1) / wt;
     const int blocks = (int)std::max(1LL, std::min((long long)ncu * per_cu, (ntiles + 3) / 4));
@@ -5554,12 +5275,11 @@ struct HipEngine : dla::Engine {
     }
     GemmArgs a{};
     a.x = x + (size_t)l0 * n; a.cpk = cpk_dev ? cpk_dev : d_cpk; a.z = z; a.n = n; a.l = l; a.l4 = l4; a.k = k; a.gpart = d_partial;
-    a.phase = lc.phase; a.want = lc.want; a.xpf = tune[7] == 4 ? 0 : 1;
+    a.phase = lc.phase; a.want = lc.want; a.xpf = knobs.no_next_tile_prefetch() ? 0 : 1;
     const double rd = (mode == 0) ? 8.0 * n * (double)l : (mode == 2 ? 8.0 * n * (double)k : 8.0 * n * (double)(l + k));
     char kn[96];
     std::snprintf(kn, sizeof kn, "gemm_kernel<%d, %d, %d, %s, %s, %d, %d, 9, %d, %d>", kt, vec2 ? 2 : 1, mode, inl ? "GemmArgsInl" : "GemmArgs",
-                  fuse ? "true" : "false", mode == 2 ? 0 : 1,
-                  (fuse && kt >= 3) ? 3 : kt >= 2 ? 2 : 0, qt, rtp);
+                  fuse ? "true" : "false", mode == 2 ? 0 : 1, pipe, qt, rtp);
     Scope s(this, cls, rd + 8.0 * n * (double)k, (cls == DLA_OP_TRMM ? 1.0 : 2.0) * (double)n * l * k, kn);
     if (inl) {
       GemmArgsInl ai{};
@@ -5568,7 +5288,7 @@ struct HipEngine : dla::Engine {
         for (int p = 0; p < l; ++p) ai.cin[p * 16 + j] = c_host[(size_t)(l0 + p) + (size_t)j * ldc];
       int stl = DLA_OK;
       if (fuse) stl = launch_gemm_gram<1>(ai, blocks, lds, vec2, mode, 0, 2);
-      else launch_gemm<1>(ai, blocks, lds, vec2, mode, 0);
+      else launch_gemm<1>(ai, blocks, lds, vec2, mode, 0, pipe);
       if (stl) return stl;
       HIPCHK(hipGetLastError());
       return DLA_OK;
@@ -5583,9 +5303,9 @@ struct HipEngine : dla::Engine {
       return DLA_OK;
     }
     switch (kt) {
-      case 1: launch_gemm<1>(a, blocks, lds, vec2, mode, 0); break;
-      case 2: launch_gemm<2>(a, blocks, lds, vec2, mode, qt); break;
-      case 3: launch_gemm<3>(a, blocks, lds, vec2, mode, qt); break;
+      case 1: launch_gemm<1>(a, blocks, lds, vec2, mode, 0, pipe); break;
+      case 2: launch_gemm<2>(a, blocks, lds, vec2, mode, qt, pipe); break;
+      case 3: launch_gemm<3>(a, blocks, lds, vec2, mode, qt, pipe); break;
       default: err = "gemm: k > 48 not supported in one call"; return DLA_ERR_ARG;
     }
     HIPCHK(hipGetLastError());
@@ -5674,7 +5394,7 @@ struct HipEngine : dla::Engine {
     if (k2 <= 0) return ritz_residual(n, l, m, v, av, y_host, ldy, eig, n_res, skip, evec, r, avy, out);
     const uintptr_t al = (uintptr_t)v | (uintptr_t)av | (uintptr_t)evec | (uintptr_t)r | (uintptr_t)avy | (uintptr_t)p2 | (uintptr_t)ap2;
     const int ktot = (m + k2 + 15) / 16, l4 = ((l + 3) / 4) * 4;
-    const bool one_pass = even_rows(n) && (al % 16 == 0) && m <= 48 && ktot <= 5 && tune[0] != 5 &&
+    const bool one_pass = even_rows(n) && (al % 16 == 0) && m <= 48 && ktot <= 5 && !knobs.ritz_p_separate() &&
                           sizeof(double) * (size_t)l4 * 16 * ktot <= ritz_dyn_limit(ktot);
     if (!one_pass) return Engine::ritz_residual_p(n, l, m, v, av, y_host, ldy, eig, n_res, skip, evec, r, avy, out, k2, c2_host, ldc2, p2, ap2);
     // [Y | C2] as one coefficient block
@@ -5708,7 +5428,11 @@ struct HipEngine : dla::Engine {
     const int l4 = ((l + 3) / 4) * 4;
     uintptr_t al = (uintptr_t)v | (uintptr_t)av | (uintptr_t)evec | (uintptr_t)r | (uintptr_t)avy | (uintptr_t)p2 | (uintptr_t)ap2;   // (null pointers are aligned)
     const bool vec2 = even_rows(n) && (al % 16 == 0);
-    const int qt = (tune[0] == 1 || tune[0] == 4) ? 0 : quarter_tiles(m + k2, vec2);
+    // the variant, decided once: quarter tiles, pipeline depth and extra products go into the booked name AND pick the instance
+    const int ab_depth = knobs.ritz_pipe_depth();
+    const int qt = ab_depth >= 0 ? 0 : quarter_tiles(m + k2, vec2);
+    const bool xp = k2 > 0;
+    const int pipe = (ab_depth >= 0 && !xp && vec2 && kt >= 2) ? ab_depth : kt >= 3 ? 3 : kt >= 2 ? 2 : 0;
     // LDS copy of Y (a quarter-tile kernel keeps 8 columns of the last tile)
     const size_t lds_c = sizeof(double) * (size_t)l4 * (qt > 0 ? 16 * (kt - 1) + 8 : 16 * kt);
     if (lds_c > ritz_dyn_limit(kt)) {
@@ -5750,7 +5474,7 @@ struct HipEngine : dla::Engine {
     const long long ntiles = ((long long)n + rg - 1) / rg;
     const size_t lds = std::max(lds_c, sizeof(double) * 4 * 16 * kt * 2);
     const int per_cu = lds > 80 * 1024 ? 1 : lds > 40 * 1024 ? 2 : 4;
-    const int blocks = (int)std::max(1LL, std::min((long long)ncu * per_cu * (tune[1] > 0 ? tune[1] : 1), (ntiles + 7) / 8));
+    const int blocks = (int)std::max(1LL, std::min((long long)ncu * per_cu * knobs.ritz_grid_factor(), (ntiles + 7) / 8));
     stc = ensure_partial(sizeof(double) * (size_t)blocks * 16 * kt * 2);
     if (stc) return stc;
     const int nslots = (local_only || nranks < 1) ? 1 : nranks;
@@ -5761,67 +5485,25 @@ struct HipEngine : dla::Engine {
     const int ncol = 16 * kt;
     {
       char kn[64];
-      // (the name rocprofv3 prints: the last argument is the scheduling variant of the wide sweeps, tune knob 0 = 7 ... 11)
-      const int t0 = tune[0];
-#ifdef DLA_AB_VARIANTS
-      const int sched = (k2 > 0 && qt == 0 && kt >= 4) ? (t0 == 7 ? 1 : t0 == 8 ? 2 : t0 == 11 ? 5 : (kt == 5 && t0 == 9) ? 3 : (kt == 5 && t0 == 10) ? 4 : 0) : 0;
-#else
-      const int sched = 0; (void)t0;
-#endif
-      // (tune knob 0 = 12: A/B, the wide Ritz + P sweeps with two wave groups per block -- ritz_pair_kernel, see there)
-#ifdef DLA_AB_VARIANTS
-      const bool pair = k2 > 0 && qt == 0 && kt >= 4 && vec2 && tune[0] >= 12 && tune[0] <= 15;
-#else
-      const bool pair = false;
-#endif
-      const int pdepth = tune[0] == 12 ? -1 : 15 - tune[0];      // pipeline depth of both groups: the sweep's own default, 2, 1, 0
-      if (pair) std::snprintf(kn, sizeof kn, "ritz_pair_kernel<%d, %d, 2, true, %d, %d>", kt == 5 ? 3 : 2, 2, pdepth < 0 ? (kt == 5 ? 3 : 2) : pdepth, pdepth < 0 ? 2 : pdepth);
-      else
-      std::snprintf(kn, sizeof kn, "ritz_kernel<%d, %d, 3, %d, %d, %s, %d>", kt, vec2 ? 2 : 1, kt >= 3 ? 3 : kt >= 2 ? 2 : 0, qt, k2 > 0 ? "true" : "false", sched);
+      // (the name rocprofv3 prints; the last argument is ritz_kernel's reserved one)
+      std::snprintf(kn, sizeof kn, "ritz_kernel<%d, %d, 3, %d, %d, %s, 0>", kt, vec2 ? 2 : 1, pipe, qt, xp ? "true" : "false");
       // (flops: the two Ritz products and, with extra columns, the two panel products they replace)
       Scope s(this, DLA_OP_RITZ, 8.0 * n * (2.0 * l + ((avy ? 2.0 : 1.0) + (evec ? 1.0 : 0.0)) * m + 2.0 * k2),
               4.0 * (double)n * l * (m + k2) + 5.0 * (double)n * nact, kn);
 #define RZ(K) do { auto kfn = K; if (!raise_lds((const void*)kfn, lds, ritz_static_lds(kt))) return DLA_ERR_RUNTIME; DLA_LAUNCH(kfn, dim3(blocks), dim3(256), lds, st, a); } while (0)
-#define RZP(K) do { auto kfn = K; if (!raise_lds((const void*)kfn, lds, ritz_static_lds(4))) return DLA_ERR_RUNTIME; DLA_LAUNCH(kfn, dim3(blocks), dim3(512), lds, st, a); } while (0)
-#ifdef DLA_AB_VARIANTS
-      if (pair) {
-        if (kt == 5) {
-          if (pdepth < 0) RZP((ritz_pair_kernel<3, 2, 2, true>));
-          else if (pdepth == 2) RZP((ritz_pair_kernel<3, 2, 2, true, 2, 2>));
-          else if (pdepth == 1) RZP((ritz_pair_kernel<3, 2, 2, true, 1, 1>));
-          else RZP((ritz_pair_kernel<3, 2, 2, true, 0, 0>));
-        } else {
-          if (pdepth < 0 || pdepth == 2) RZP((ritz_pair_kernel<2, 2, 2, true>));
-          else if (pdepth == 1) RZP((ritz_pair_kernel<2, 2, 2, true, 1, 1>));
-          else RZP((ritz_pair_kernel<2, 2, 2, true, 0, 0>));
-        }
-      } else
-#endif
-      if (k2 > 0) {
+      if (xp) {
         // [Y | C2]: vec2 guaranteed by the caller (ritz_residual_p)
         if (qt == 1) { if (kt == 2) RZ((ritz_kernel<2, 2, 3, 2, 1, true>)); else RZ((ritz_kernel<3, 2, 3, 3, 1, true>)); }
         else if (qt == 2) { if (kt == 2) RZ((ritz_kernel<2, 2, 3, 2, 2, true>)); else RZ((ritz_kernel<3, 2, 3, 3, 2, true>)); }
         else if (kt == 1) RZ((ritz_kernel<1, 2, 3, 0, 0, true>));
         else if (kt == 2) RZ((ritz_kernel<2, 2, 3, 2, 0, true>));
         else if (kt == 3) RZ((ritz_kernel<3, 2, 3, 3, 0, true>));
-#ifdef DLA_AB_VARIANTS
-        // (the hand-scheduled variants of round 4 -- iglp_opt, two sched_group_barrier pipelines, role-swapping stages: none faster
-        //  than the compiler's order, profiles/r04/ritz_sched_ab.txt -- are built only with -DDLA_AB_VARIANTS, for tools/ritz_sched_ab.py)
-        else if (kt == 4 && tune[0] == 7) RZ((ritz_kernel<4, 2, 3, 3, 0, true, 1>));
-        else if (kt == 4 && tune[0] == 8) RZ((ritz_kernel<4, 2, 3, 3, 0, true, 2>));
-        else if (kt == 5 && tune[0] == 7) RZ((ritz_kernel<5, 2, 3, 3, 0, true, 1>));
-        else if (kt == 5 && tune[0] == 8) RZ((ritz_kernel<5, 2, 3, 3, 0, true, 2>));
-        else if (kt == 4 && tune[0] == 11) RZ((ritz_kernel<4, 2, 3, 3, 0, true, 5>));
-        else if (kt == 5 && tune[0] == 11) RZ((ritz_kernel<5, 2, 3, 3, 0, true, 5>));
-        else if (kt == 5 && tune[0] == 9) RZ((ritz_kernel<5, 2, 3, 3, 0, true, 3>));
-        else if (kt == 5 && tune[0] == 10) RZ((ritz_kernel<5, 2, 3, 3, 0, true, 4>));
-#endif
         else if (kt == 4) RZ((ritz_kernel<4, 2, 3, 3, 0, true>));
         else RZ((ritz_kernel<5, 2, 3, 3, 0, true>));        // (pipeline depth 2 / 4 measured: 8.9 / 7.9 ms against 7.5 at 37 + 37 columns)
-      } else if (vec2 && kt >= 2 && tune[0] == 1) {
+      } else if (kt >= 2 && pipe == 0) {             // (Knobs::ritz_pipe_depth: vec2, no quarter tiles)
         if (kt == 2) RZ((ritz_kernel<2, 2, 3, 0>));
         else RZ((ritz_kernel<3, 2, 3, 0>));
-      } else if (vec2 && kt >= 2 && tune[0] == 4) {
+      } else if (pipe == 4) {
         if (kt == 2) RZ((ritz_kernel<2, 2, 3, 4>));
         else RZ((ritz_kernel<3, 2, 3, 4>));
       } else if (vec2 && qt == 1) {
@@ -5840,7 +5522,6 @@ struct HipEngine : dla::Engine {
         else RZ((ritz_kernel<3, 1>));
       }
 #undef RZ
-#undef RZP
     }
     {
       Scope s2(this, DLA_OP_RITZ, 0.0, 0.0, "ritz_reduce_kernel");
@@ -5866,7 +5547,7 @@ struct HipEngine : dla::Engine {
   {
     const int kt = (m + 15) / 16, l4 = ((l + 3) / 4) * 4;
     const size_t lds_c = sizeof(double) * (size_t)l4 * 16 * 2 * kt;
-    if (m > 48 || m <= 0 || l <= 0 || lds_c > std::min((size_t)150 * 1024, lds_limit > 2048 ? lds_limit - 2048 : 0) || tune[0] == 6)
+    if (m > 48 || m <= 0 || l <= 0 || lds_c > std::min((size_t)150 * 1024, lds_limit > 2048 ? lds_limit - 2048 : 0) || knobs.no_ritz2())
       return Engine::ritz_residual2(n, l, m, v, av, y1_host, ldy1, y2_host, ldy2, eig, n_res, skip, e, r, t_work, junk, out);
     // [Y1 | Y2] packed as 2 kt tiles: Y2 starts at tile kt
     std::vector<double> yy((size_t)l * (16 * kt + m), 0.0);

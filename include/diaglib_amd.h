@@ -100,8 +100,9 @@ enum {
                                       (dla_pending_block); 0: every block is finished in memory (modes 3 / 4 behave like 1 / 0) --
                                       same eigenpairs either way, for A/B runs and tests in one process.  New contexts start
                                       with 0 when $DIAGLIB_AMD_NO_PENDING is set                                              */
-  DLA_OPT_TUNE0 = 100              /* 100..107: kernel-shape experiment knobs for the interleaved A/B tools
-                                      (tools/tune_*.py, tools/kernel_bench.py); 0 = the shipped default          */
+  DLA_OPT_TUNE0 = 100              /* 100..107: experiment knobs of the engine for the A/B tools, the fuzz tools and the tests;
+                                      0 = the shipped default.  What each value selects: tools/README.md,
+                                      "Interleaved A/B tools"                                                    */
 };
 
 /* op classes for statistics */

@@ -38,8 +38,7 @@ for L in (26, 65, 117):
             ctx.ortho_vs_x(panel.col(0, L), panel.col(L, k))
             outs[v] = panel.col(L, k).download()
             for name, st in ctx.kernel_stats().items():
-                if name.startswith(("gemm_kernel<1, 2, 0, GemmArgs, true", "gemm_kernel<1, 2, 1, GemmArgs, true",
-                                    "gemm_lds_kernel<1, 0, true", "gemm_lds_kernel<1, 1, true")):
+                if name.startswith(("gemm_kernel<1, 2, 0, GemmArgs, true", "gemm_kernel<1, 2, 1, GemmArgs, true")):
                     res.setdefault(("proj", v), []).append(st["alg_bytes"] / st["ms"] / 1e6)
                 if name.startswith("gemm_kernel<1, 2, 2, GemmArgsInl, true"):
                     res.setdefault(("trmm", v), []).append(st["alg_bytes"] / st["ms"] / 1e6)

@@ -42,7 +42,7 @@ EXPORTS = [
     "dla_call_matvec", "dla_call_precnd", "dla_expand_project", "dla_expand_project_metric",
     "dla_syev", "dla_syev_lowest", "dla_potrf_lower", "dla_trtri_lower", "dla_norm_est",
     "dla_synth_setup", "dla_synth_matvec", "dla_synth_precnd", "dla_synth_apbmul", "dla_synth_ambmul", "dla_synth_spdmul", "dla_synth_smdmul",
-    "dla_synth_metric", "dla_synth_lrprec1", "dla_synth_lrprec2", "dla_pending_factor", "dla_pending_block", "dla_basis_admit", "dla_basis_fold", "dla_basis_sync", "dla_spmm_setup_csr", "dla_spmm_setup_csr_sharded", "dla_spmm_matvec", "dla_spmm_precnd",
+    "dla_synth_metric", "dla_synth_lrprec1", "dla_synth_lrprec2", "dla_pending_factor", "dla_pending_block", "dla_basis_admit", "dla_basis_fold", "dla_basis_sync", "dla_spmm_setup_csr", "dla_spmm_setup_csr_fmt", "dla_spmm_info", "dla_spmm_setup_csr_sharded", "dla_spmm_matvec", "dla_spmm_precnd",
     "dla_davidson_driver", "dla_gen_david_driver", "dla_lobpcg_driver", "dla_caslr_eff_driver", "dla_caslr_driver", "dla_call_lrprec",
     "dla_last_solve_info", "dla_set_solve_info",
 ]
@@ -63,6 +63,16 @@ class Stats(C.Structure):
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("launches", C.c_longlong), ("alg_bytes", C.c_double), ("ms", C.c_double),
                 ("flops", C.c_double)]
+
+
+SPMM_ELL, SPMM_SELL, SPMM_AUTO = 0, 1, 2
+SPMM_FORMATS = {"ell": SPMM_ELL, "sell": SPMM_SELL, "auto": SPMM_AUTO}
+
+
+class SpmmInfo(C.Structure):
+    _fields_ = [("format", C.c_int), ("n", C.c_int), ("slice_rows", C.c_int), ("sort_window", C.c_int), ("long_row_threshold", C.c_int),
+                ("nnz", C.c_longlong), ("stored", C.c_longlong), ("slices", C.c_int), ("long_rows", C.c_int),
+                ("long_entries", C.c_longlong), ("device_bytes", C.c_longlong)]
 
 
 class DlaError(RuntimeError):
@@ -135,6 +145,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dla_basis_fold": (i, [i, i, vp, i, vp, i]),
         "dla_basis_sync": (i, [vp, i, i, vp, i]),
         "dla_spmm_setup_csr": (i, [vp, i, vp, vp, vp]),
+        "dla_spmm_setup_csr_fmt": (i, [vp, i, vp, vp, vp, i]), "dla_spmm_info": (i, [vp, C.POINTER(SpmmInfo)]),
         "dla_spmm_setup_csr_sharded": (i, [vp, i, C.c_longlong, C.c_longlong, vp, vp, vp]),
         "dla_davidson_driver": (None, [i, i, i, i, i, d, i, d, vp, vp, vp, vp, c_ip]),
         "dla_lobpcg_driver": (None, [i, i, i, i, i, i, d, d, vp, vp, vp, vp, vp, c_ip]),
@@ -505,13 +516,28 @@ class Context:
     def synth_setup(self, n_global: int, row0: int, n_local: int, rank_w: int = 4, sigma: float = 0.5) -> None:
         self._chk(self.lib.dla_synth_setup(self.h, n_global, row0, n_local, rank_w, sigma))
 
-    def spmm_setup(self, a) -> None:
-        """hand a scipy.sparse matrix (symmetric, square) to the sample ELLPACK operator of this thread's context"""
+    def spmm_setup(self, a, fmt: str = "ell") -> None:
+        """hand a scipy.sparse matrix (symmetric, square) to the sample sparse operator of this thread's context; fmt = "ell"
+        (ELLPACK, padded to the widest row), "sell" (sliced ELLPACK with a CSR tail: storage follows the non-zeros) or "auto" (ELLPACK while its padding is small)"""
+        if fmt not in SPMM_FORMATS:
+            raise ValueError(f"spmm_setup: fmt must be one of {sorted(SPMM_FORMATS)}, not {fmt!r}")
         a = a.tocsr()
         rp = np.ascontiguousarray(a.indptr, dtype=np.int64)
         ci = np.ascontiguousarray(a.indices, dtype=np.int32)
         va = np.ascontiguousarray(a.data, dtype=np.float64)
-        self._chk(self.lib.dla_spmm_setup_csr(self.h, a.shape[0], rp.ctypes.data, ci.ctypes.data, va.ctypes.data))
+        if fmt == "ell":
+            self._chk(self.lib.dla_spmm_setup_csr(self.h, a.shape[0], rp.ctypes.data, ci.ctypes.data, va.ctypes.data))
+        else:
+            self._chk(self.lib.dla_spmm_setup_csr_fmt(self.h, a.shape[0], rp.ctypes.data, ci.ctypes.data, va.ctypes.data, SPMM_FORMATS[fmt]))
+
+    def spmm_info(self) -> dict:
+        """what the operator set up last occupies: format ("ell" / "sell"), n, nnz, stored, slices, long_rows, long_entries,
+        device_bytes and the layout constants (include/diaglib_amd.h, dla_spmm_info)"""
+        o = SpmmInfo()
+        self._chk(self.lib.dla_spmm_info(self.h, C.byref(o)))
+        d = {name: int(getattr(o, name)) for name, _ in SpmmInfo._fields_}
+        d["format"] = {v: k for k, v in SPMM_FORMATS.items()}[d["format"]]
+        return d
 
     def spmm_setup_sharded(self, a_rows, row0: int, n_global: int) -> None:
         """hand THIS rank's rows (a scipy.sparse matrix of shape n_local x n_global, global column indices) of a banded

@@ -3,6 +3,7 @@
 // engine (hip_engine.hip: HIP kernels, streams, RCCL).  The product library links exactly
 // one engine, the HIP one; there is no CPU engine in the product.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <string>
 #include <vector>
@@ -264,7 +265,7 @@ struct Engine : BlockOps {
   virtual int callback_begin(int /*mode*/) { return 0; }
   virtual int callback_end(int /*mode*/) { return 0; }
 
-  // sample sparse operator (ELLPACK SpMM + its diagonal preconditioner)
+  // sample sparse operator (ELLPACK or sliced-ELLPACK SpMM + its diagonal preconditioner)
   virtual int spmm_setup_csr(int /*n*/, const long long* /*rowptr*/, const int* /*colind*/, const double* /*values*/) { return DLA_ERR_ARG; }
   // the same operator on a row shard: rows row0 .. row0 + n_local - 1 of A with GLOBAL column indices.  Columns outside the
   // shard must lie within `halo` rows of it (a banded matrix); every rank publishes its first and last `halo` rows of x through
@@ -272,6 +273,9 @@ struct Engine : BlockOps {
   // every rank calls it (the halo width is agreed by a max-reduction).
   virtual int spmm_setup_csr_sharded(int /*n_local*/, long long /*row0*/, long long /*n_global*/, const long long* /*rowptr*/,
                                      const long long* /*colind*/, const double* /*values*/) { return DLA_ERR_ARG; }
+  // the single-rank operator in a chosen storage format (DLA_SPMM_ELL / _SELL / _AUTO: sell_build below) and what was stored
+  virtual int spmm_setup_csr_fmt(int /*n*/, const long long* /*rowptr*/, const int* /*colind*/, const double* /*values*/, int /*format*/) { return DLA_ERR_ARG; }
+  virtual int spmm_info(struct dla_spmm_info* /*out*/) { return DLA_ERR_ARG; }
   virtual int spmm_matvec(int /*n*/, int /*m*/, const double* /*x*/, double* /*ax*/) { return DLA_ERR_ARG; }
   virtual int spmm_precnd(int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return DLA_ERR_ARG; }
 
@@ -398,6 +402,100 @@ inline void sharded_ell_build(int n, long long row0, const long long* rowptr, co
       e.col[(size_t)q * n + i] = (int)(c - row0 + halo);
       e.val[(size_t)q * n + i] = in ? values[p0 + q] : 0.0;
       if (in && c == row0 + i) e.diag[i] += values[p0 + q];
+    }
+  }
+}
+
+// ---- the single-rank operator as sliced ELLPACK (SELL-C-sigma) with a CSR tail for long rows (spmm_setup_csr_fmt)
+// Storage follows the non-zeros, not widest row x n: rows are sorted by descending length (stable) inside windows of SELL_SIGMA
+// rows, cut into slices of SELL_C consecutive slots, and every slice is padded to ITS longest row only.  One wavefront owns a
+// slice, so entry (q, lane) of slice s lives at slice_ptr[s] + q * SELL_C + lane and both matrix streams stay coalesced as in
+// the plain ELLPACK kernel.  A row with more than SELL_LONG_ROW entries would widen its whole slice: it counts as an empty row
+// in the slices (sorted and padded as one) and is kept whole, in the caller's order, in the CSR tail.
+// The three constants are unmeasured starting values: SELL_C is the wavefront width, the other two are guesses.
+constexpr int SELL_C = 64;
+constexpr int SELL_SIGMA = 4096;
+constexpr int SELL_LONG_ROW = 256;
+// AUTO keeps plain ELLPACK while its padding w n / nnz stays at or below this (a guess as well)
+constexpr double SPMM_AUTO_ELL_PADDING = 1.25;
+
+struct SellLayout {
+  int n = 0, slices = 0;
+  long long nnz = 0, stored = 0, long_entries = 0;   // stored: padded entries of the slices
+  std::vector<long long> slice_ptr;   // [slices + 1], in entries; the width of slice s is (slice_ptr[s + 1] - slice_ptr[s]) / SELL_C
+  std::vector<int> perm;              // [n]: slot -> row; ~row (negative) for a row that lives in the tail: its slot stores nothing
+  std::vector<int> col;               // [stored], the caller's column numbering; padding points at the row itself with a zero
+  std::vector<double> val, diag;      // [stored], [n]: diag[i] = sum of all (i, i) entries, tail rows included
+  std::vector<int> long_row;          // the tail: rows, [long_rows + 1] offsets, columns and values in the caller's order
+  std::vector<long long> long_ptr;
+  std::vector<int> long_col;
+  std::vector<double> long_val;
+};
+// what every single-rank setup checks, in the words of spmm_setup_csr; w = widest row, nnz = entries
+inline int spmm_csr_check(int n, const long long* rowptr, const int* colind, const double* values, int format, int* w, long long* nnz,
+                          std::string& err)
+{
+  *w = 0; *nnz = 0;
+  if (format != DLA_SPMM_ELL && format != DLA_SPMM_SELL && format != DLA_SPMM_AUTO) { err = "spmm_setup_csr_fmt: unknown format"; return DLA_ERR_ARG; }
+  if (n <= 0 || !rowptr || !colind || !values) { err = "spmm_setup_csr_fmt: bad arguments"; return DLA_ERR_ARG; }
+  for (int i = 0; i < n; ++i) {
+    if (rowptr[i + 1] < rowptr[i]) { err = "spmm_setup_csr_fmt: row pointers not ascending"; return DLA_ERR_ARG; }
+    if (rowptr[i + 1] - rowptr[i] > *w) *w = (int)std::min<long long>(rowptr[i + 1] - rowptr[i], 2147483647LL);
+  }
+  if (*w <= 0) { err = "spmm_setup_csr_fmt: empty matrix"; return DLA_ERR_ARG; }
+  for (long long p = rowptr[0]; p < rowptr[n]; ++p)
+    if (colind[p] < 0 || colind[p] >= n) { err = "spmm_setup_csr_fmt: column index out of range"; return DLA_ERR_ARG; }
+  *nnz = rowptr[n] - rowptr[0];
+  return DLA_OK;
+}
+// the format a checked matrix is stored in
+inline int spmm_pick_format(int format, int w, int n, long long nnz)
+{
+  if (format != DLA_SPMM_AUTO) return format;
+  return (double)w * (double)n <= SPMM_AUTO_ELL_PADDING * (double)nnz ? DLA_SPMM_ELL : DLA_SPMM_SELL;
+}
+// (the arrays have passed spmm_csr_check)
+inline void sell_build(int n, const long long* rowptr, const int* colind, const double* values, SellLayout& s)
+{
+  s.n = n; s.slices = (n + SELL_C - 1) / SELL_C; s.nnz = rowptr[n] - rowptr[0];
+  auto tail = [&](int i) { return rowptr[i + 1] - rowptr[i] > SELL_LONG_ROW; };
+  auto len = [&](int i) { return tail(i) ? 0 : (int)(rowptr[i + 1] - rowptr[i]); };   // what row i asks of its slice
+  std::vector<int> order((size_t)n);
+  for (int i = 0; i < n; ++i) order[i] = i;
+  for (int w0 = 0; w0 < n; w0 += SELL_SIGMA)
+    std::stable_sort(order.begin() + w0, order.begin() + std::min(n, w0 + SELL_SIGMA), [&](int a, int b) { return len(a) > len(b); });
+  s.slice_ptr.assign((size_t)s.slices + 1, 0);
+  for (int sl = 0; sl < s.slices; ++sl) {
+    int width = 0;
+    for (int slot = sl * SELL_C; slot < std::min(n, (sl + 1) * SELL_C); ++slot) width = std::max(width, len(order[slot]));
+    s.slice_ptr[sl + 1] = s.slice_ptr[sl] + (long long)width * SELL_C;
+  }
+  s.stored = s.slice_ptr[s.slices];
+  s.perm.assign((size_t)n, 0);
+  s.col.assign((size_t)s.stored, 0); s.val.assign((size_t)s.stored, 0.0); s.diag.assign((size_t)n, 0.0);
+  s.long_row.clear(); s.long_ptr.assign(1, 0); s.long_col.clear(); s.long_val.clear();
+  for (int i = 0; i < n; ++i) {
+    for (long long p = rowptr[i]; p < rowptr[i + 1]; ++p) if (colind[p] == i) s.diag[i] += values[p];
+    if (!tail(i)) continue;
+    s.long_row.push_back(i);
+    s.long_col.insert(s.long_col.end(), colind + rowptr[i], colind + rowptr[i + 1]);
+    s.long_val.insert(s.long_val.end(), values + rowptr[i], values + rowptr[i + 1]);
+    s.long_ptr.push_back((long long)s.long_col.size());
+  }
+  s.long_entries = (long long)s.long_col.size();
+  for (int sl = 0; sl < s.slices; ++sl) {
+    const long long base = s.slice_ptr[sl];
+    const int width = (int)((s.slice_ptr[sl + 1] - base) / SELL_C);
+    for (int lane = 0; lane < SELL_C; ++lane) {
+      const int slot = sl * SELL_C + lane;
+      const int i = slot < n ? order[slot] : 0;          // (slots past n pad with zeros that point at row 0)
+      const int li = slot < n ? len(i) : 0;
+      if (slot < n) s.perm[slot] = tail(i) ? ~i : i;
+      for (int q = 0; q < width; ++q) {
+        const bool in = q < li;
+        s.col[(size_t)(base + (long long)q * SELL_C + lane)] = in ? colind[rowptr[i] + q] : i;
+        s.val[(size_t)(base + (long long)q * SELL_C + lane)] = in ? values[rowptr[i] + q] : 0.0;
+      }
     }
   }
 }

@@ -1550,6 +1550,8 @@ __global__ void synth_precnd_kernel(int n, int m, double fac, const double* __re
 // thread keeps its w (column, value) pairs in registers while it walks the m right-hand sides.  The gathers
 // x[col][c] are the irregular part; for the banded / stencil matrices of the test suite neighbouring rows gather
 // neighbouring entries.  HBM-bound: 12 w n bytes of matrix + 16 n m bytes of vectors per call (+ gather overfetch).
+// Padding to the WIDEST row is what makes this format unusable for a matrix with a few long rows: dla_spmm_setup_csr_fmt stores
+// those as sliced ELLPACK with a CSR tail (sell_spmm_kernel / csr_long_rows_kernel below) behind the same two callbacks.
 template <int W>
 __global__ __launch_bounds__(256) void ell_spmm_kernel(int n, int m, int w, const int* __restrict__ col,
                                                        const double* __restrict__ val, const double* __restrict__ x,
@@ -1577,6 +1579,94 @@ __global__ __launch_bounds__(256) void ell_spmm_kernel(int n, int m, int w, cons
         double s = 0.0;
         for (int q = 0; q < w; ++q) s += val[(size_t)q * n + i] * xc[col[(size_t)q * n + i]];
         __builtin_nontemporal_store(s, ax + (size_t)c * n + i);
+      }
+    }
+  }
+}
+
+// The same product from sliced ELLPACK (dla::SellLayout, dla_spmm_setup_csr_fmt): one wavefront owns a slice of 64 slots, entry
+// (q, lane) of slice s at slice_ptr[s] + 64 q + lane, so both matrix streams are read in full 256- / 512-byte rows as above
+// while the width is the slice's own.  A slice can be hundreds of entries wide, so the (column, value) pairs cannot wait in
+// registers for all m right-hand sides as they do above: each pair is loaded once per chunk of MC columns and feeds MC
+// accumulators -- MC independent gathers in flight per entry -- and the chunk loop sits INSIDE the slice loop, where the
+// slice's second read comes from cache (64 x width x 12 bytes: 196 KiB at the widest, usually a few KiB).  Per (row, column)
+// the entries are accumulated in stored order, one fused multiply-add each, from 0.0: the bits of ell_spmm_kernel.
+// perm[slot] is the row a slot computes; negative: the row lives in the CSR tail (csr_long_rows_kernel writes it); slots past n
+// in the last slice and tail slots store nothing, so every element of ax has exactly one writer.
+template <int MC>
+__global__ __launch_bounds__(256) void sell_spmm_kernel(int n, int m, int slices, const long long* __restrict__ slice_ptr,
+                                                        const int* __restrict__ perm, const int* __restrict__ col,
+                                                        const double* __restrict__ val, const double* __restrict__ x,
+                                                        double* __restrict__ ax)
+{
+  const int lane = threadIdx.x & 63;
+  for (int s = blockIdx.x * 4 + (threadIdx.x >> 6); s < slices; s += gridDim.x * 4) {
+    const long long p0 = slice_ptr[s];
+    const int width = (int)((slice_ptr[s + 1] - p0) >> 6);
+    const int slot = s * 64 + lane;
+    const int row = slot < n ? perm[slot] : -1;
+    const int* cs = col + p0 + lane;
+    const double* vs = val + p0 + lane;
+    for (int c0 = 0; c0 < m; c0 += MC) {
+      const double* xc = x + (size_t)c0 * n;
+      double acc[MC];
+#pragma unroll
+      for (int k = 0; k < MC; ++k) acc[k] = 0.0;
+      if (c0 + MC <= m) {
+        for (int q = 0; q < width; ++q) {
+          const int cj = cs[(size_t)q * 64];
+          const double vj = vs[(size_t)q * 64];
+#pragma unroll
+          for (int k = 0; k < MC; ++k) acc[k] = fma(vj, xc[(size_t)k * n + cj], acc[k]);
+        }
+      } else {
+        const int mc = m - c0;
+        for (int q = 0; q < width; ++q) {
+          const int cj = cs[(size_t)q * 64];
+          const double vj = vs[(size_t)q * 64];
+#pragma unroll
+          for (int k = 0; k < MC; ++k) if (k < mc) acc[k] = fma(vj, xc[(size_t)k * n + cj], acc[k]);
+        }
+      }
+      if (row >= 0) {
+#pragma unroll
+        for (int k = 0; k < MC; ++k) if (c0 + k < m) __builtin_nontemporal_store(acc[k], ax + (size_t)(c0 + k) * n + row);
+      }
+    }
+  }
+}
+
+// The CSR tail of the sliced format: one wavefront per long row, lanes striding over the row's entries (coalesced), per-lane
+// partial sums for MC columns, then a butterfly over the 64 lanes -- a fixed shape, so the result does not depend on timing --
+// and lane 0 stores.  No atomics: a row has one writer.
+template <int MC>
+__global__ __launch_bounds__(256) void csr_long_rows_kernel(int n, int m, int nlong, const int* __restrict__ long_row,
+                                                            const long long* __restrict__ long_ptr, const int* __restrict__ col,
+                                                            const double* __restrict__ val, const double* __restrict__ x,
+                                                            double* __restrict__ ax)
+{
+  const int lane = threadIdx.x & 63;
+  for (int r = blockIdx.x * 4 + (threadIdx.x >> 6); r < nlong; r += gridDim.x * 4) {
+    const int row = long_row[r];
+    const long long p0 = long_ptr[r], p1 = long_ptr[r + 1];
+    for (int c0 = 0; c0 < m; c0 += MC) {
+      const double* xc = x + (size_t)c0 * n;
+      const int mc = min(MC, m - c0);
+      double acc[MC];
+#pragma unroll
+      for (int k = 0; k < MC; ++k) acc[k] = 0.0;
+      for (long long p = p0 + lane; p < p1; p += 64) {
+        const int cj = col[p];
+        const double vj = val[p];
+#pragma unroll
+        for (int k = 0; k < MC; ++k) if (k < mc) acc[k] = fma(vj, xc[(size_t)k * n + cj], acc[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < MC; ++k)
+        for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
+      if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < MC; ++k) if (k < mc) ax[(size_t)(c0 + k) * n + row] = acc[k];
       }
     }
   }
@@ -5674,7 +5764,7 @@ struct HipEngine : dla::Engine {
     return DLA_OK;
   }
 
-  // ---- sample sparse operator (ELLPACK)
+  // ---- sample sparse operator (ELLPACK; sliced ELLPACK below)
   DeviceBuffer<int> d_ell_col; DeviceBuffer<double> d_ell_val, d_ell_diag;
   int ell_n = 0, ell_w = 0;
   // replace the operator on the device (both set-up routines end here); the caller has bound the device.  The arrays only grow:
@@ -5716,6 +5806,76 @@ struct HipEngine : dla::Engine {
     HIPCHK(hipSetDevice(device));
     { const int stc = upload_ell(col, val, diag); if (stc) return stc; }
     ell_n = n; ell_w = w; ell_sharded = false; ell_halo = 0;
+    spmm_fmt = DLA_SPMM_ELL; spmm_nnz = rowptr[n] - rowptr[0];
+    return DLA_OK;
+  }
+  // ---- ... as sliced ELLPACK with a CSR tail (dla::sell_build).  The slices and the tail share the ELLPACK blocks -- columns and
+  // values of the tail follow the `stored` padded entries of the slices -- so either format replaces the other in place.
+  int spmm_fmt = -1;                 // DLA_SPMM_ELL / DLA_SPMM_SELL: what the blocks hold; -1 before any setup
+  long long spmm_nnz = 0, sell_stored = 0, sell_long_entries = 0;
+  int sell_slices = 0, sell_long_rows = 0;
+  DeviceBuffer<long long> d_sell_ptr, d_long_ptr;
+  DeviceBuffer<int> d_sell_perm, d_long_row;
+  static constexpr int SELL_MC = 8, LONG_MC = 4;   // right-hand sides per load of a matrix entry (sell_spmm_kernel / csr_long_rows_kernel)
+  int spmm_setup_csr_fmt(int n, const long long* rowptr, const int* colind, const double* values, int format) override
+  {
+    int w = 0; long long nnz = 0;
+    { const int stc = dla::spmm_csr_check(n, rowptr, colind, values, format, &w, &nnz, err); if (stc) return stc; }
+    if (dla::spmm_pick_format(format, w, n, nnz) == DLA_SPMM_ELL) return spmm_setup_csr(n, rowptr, colind, values);
+    dla::SellLayout L;
+    dla::sell_build(n, rowptr, colind, values, L);
+    const size_t tot = (size_t)(L.stored + L.long_entries), nl = L.long_row.size();
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(d_ell_col.reserve(tot));
+    HIPCHK(d_ell_val.reserve(tot));
+    HIPCHK(d_ell_diag.reserve((size_t)n));
+    HIPCHK(d_sell_ptr.reserve(L.slice_ptr.size()));
+    HIPCHK(d_sell_perm.reserve((size_t)n));
+    HIPCHK(d_long_row.reserve(std::max<size_t>(1, nl)));
+    HIPCHK(d_long_ptr.reserve(nl + 1));
+    auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
+    HIPCHK(up(d_ell_col, L.col.data(), sizeof(int) * L.col.size()));
+    HIPCHK(up(d_ell_val, L.val.data(), sizeof(double) * L.val.size()));
+    HIPCHK(up(d_ell_col + L.stored, L.long_col.data(), sizeof(int) * L.long_col.size()));
+    HIPCHK(up(d_ell_val + L.stored, L.long_val.data(), sizeof(double) * L.long_val.size()));
+    HIPCHK(up(d_ell_diag, L.diag.data(), sizeof(double) * (size_t)n));
+    HIPCHK(up(d_sell_ptr, L.slice_ptr.data(), sizeof(long long) * L.slice_ptr.size()));
+    HIPCHK(up(d_sell_perm, L.perm.data(), sizeof(int) * (size_t)n));
+    HIPCHK(up(d_long_row, L.long_row.data(), sizeof(int) * nl));
+    HIPCHK(up(d_long_ptr, L.long_ptr.data(), sizeof(long long) * (nl + 1)));
+    ell_n = n; ell_w = 0; ell_sharded = false; ell_halo = 0;
+    spmm_fmt = DLA_SPMM_SELL; spmm_nnz = nnz; sell_stored = L.stored; sell_long_entries = L.long_entries;
+    sell_slices = L.slices; sell_long_rows = (int)nl;
+    return DLA_OK;
+  }
+  int spmm_info(struct dla_spmm_info* out) override
+  {
+    if (spmm_fmt < 0 || !out) { err = "spmm_info: no operator has been set up"; return DLA_ERR_ARG; }
+    const bool sell = spmm_fmt == DLA_SPMM_SELL;
+    struct dla_spmm_info zero{};    // (elaborated: the function of the same name hides the struct)
+    *out = zero;
+    out->format = spmm_fmt; out->n = ell_n; out->nnz = spmm_nnz;
+    out->stored = sell ? sell_stored : (long long)ell_w * ell_n;
+    out->device_bytes = 12 * out->stored + 8 * (long long)ell_n;
+    if (sell) {
+      out->slice_rows = dla::SELL_C; out->sort_window = dla::SELL_SIGMA; out->long_row_threshold = dla::SELL_LONG_ROW;
+      out->slices = sell_slices; out->long_rows = sell_long_rows; out->long_entries = sell_long_entries;
+      out->device_bytes += 12 * sell_long_entries + 4 * (long long)ell_n + 8 * ((long long)sell_slices + 1) + 12 * (long long)sell_long_rows + 8;
+    }
+    return DLA_OK;
+  }
+  int spmm_matvec_sell(int n, int m, const double* x, double* ax)
+  {
+    const int cap = ncu * 8;
+    DLA_LAUNCH((sell_spmm_kernel<SELL_MC>), dim3(std::max(1, std::min(cap, (sell_slices + 3) / 4))), dim3(256), 0, st, n, m, sell_slices,
+               (const long long*)d_sell_ptr, (const int*)d_sell_perm, (const int*)d_ell_col, (const double*)d_ell_val, x, ax);
+    HIPCHK(hipGetLastError());
+    if (sell_long_rows > 0) {
+      DLA_LAUNCH((csr_long_rows_kernel<LONG_MC>), dim3(std::max(1, std::min(cap, (sell_long_rows + 3) / 4))), dim3(256), 0, st, n, m, sell_long_rows,
+                 (const int*)d_long_row, (const long long*)d_long_ptr, (const int*)d_ell_col + sell_stored, (const double*)d_ell_val + sell_stored, x, ax);
+      HIPCHK(hipGetLastError());
+    }
     return DLA_OK;
   }
   // ---- ... on a row shard (banded matrices: the columns of a shard reach at most `halo` rows into its neighbours)
@@ -5784,6 +5944,7 @@ struct HipEngine : dla::Engine {
     stc = upload_ell(e.col, e.val, e.diag);
     if (stc) return stc;
     ell_n = n; ell_w = e.w; ell_halo = (int)halo; ell_sharded = true;
+    spmm_fmt = DLA_SPMM_ELL; spmm_nnz = rowptr[n] - rowptr[0];
     return DLA_OK;
   }
   int spmm_matvec_sharded(int n, int m, const double* x, double* ax)
@@ -5826,6 +5987,10 @@ struct HipEngine : dla::Engine {
   int spmm_matvec(int n, int m, const double* x, double* ax) override
   {
     if (n != ell_n || !d_ell_col) { err = "spmm_matvec: n differs from setup"; return DLA_ERR_ARG; }
+    if (spmm_fmt == DLA_SPMM_SELL) {
+      Scope s(this, DLA_OP_MATVEC, 12.0 * (double)(sell_stored + sell_long_entries) + 4.0 * n + 16.0 * (double)n * m, 2.0 * (double)spmm_nnz * m);
+      return spmm_matvec_sell(n, m, x, ax);
+    }
     Scope s(this, DLA_OP_MATVEC, 12.0 * (double)ell_w * n + 16.0 * (double)n * m, 2.0 * (double)ell_w * n * m);
     if (ell_sharded) return spmm_matvec_sharded(n, m, x, ax);
     const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));

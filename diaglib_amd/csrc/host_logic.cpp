@@ -1856,6 +1856,19 @@ int dla_spmm_setup_csr(dla_ctx* c, int n, const long long* rowptr, const int* co
   return engfail(c, c->eng->spmm_setup_csr(n, rowptr, colind, values));
 }
 
+int dla_spmm_setup_csr_fmt(dla_ctx* c, int n, const long long* rowptr, const int* colind, const double* values, int format)
+{
+  if (!c) return DLA_ERR_ARG;
+  g_spmm_ctx = c;
+  return engfail(c, c->eng->spmm_setup_csr_fmt(n, rowptr, colind, values, format));
+}
+
+int dla_spmm_info(dla_ctx* c, struct dla_spmm_info* out)
+{
+  if (!c || !out) return DLA_ERR_ARG;
+  return engfail(c, c->eng->spmm_info(out));
+}
+
 int dla_spmm_setup_csr_sharded(dla_ctx* c, int n_local, long long row0, long long n_global, const long long* rowptr,
                                const long long* colind, const double* values)
 {

@@ -436,7 +436,8 @@ void dla_set_solve_info(int iters, int matvec_cols, int restarts);   /* used by 
 
 /* ---------------------------------------------------------------- sample sparse operator
  * A device-resident operator for callers whose matrix is sparse and symmetric: hand A over once in CSR form (host arrays,
- * 0-based, 64-bit row pointers); it is kept on the device as column-major ELLPACK.  dla_spmm_matvec / dla_spmm_precnd have the
+ * 0-based, 64-bit row pointers); it is kept on the device as column-major ELLPACK or, on request, as sliced ELLPACK with a CSR
+ * tail (below).  dla_spmm_matvec / dla_spmm_precnd have the
  * reference's callback shapes matvec(n,m,x,ax) / precnd(n,m,fac,x,px) (README.md:34-35, main.f90:72-90, 146-171) and expect
  * DEVICE addresses (DLA_OPT_CALLBACKS_ON_DEVICE = 1); the preconditioner is the harness' x / (a_ii + fac).  They act on the
  * operator the calling thread set up last and enqueue on that context's stream.
@@ -446,8 +447,35 @@ void dla_set_solve_info(int iters, int matvec_cols, int restarts);   /* used by 
  * and last `halo` rows of every rank's x block through the SAME transport as the small products -- every rank fills its own two
  * slots of a zeroed nranks x 2 x halo x m buffer and the all-reduce sum gathers them (all-reduce only; 2 halo m
  * doubles per rank and call) -- and a matrix with longer-range couplings is refused.  Collective: every rank calls the setup,
- * with shards contiguous in rank order; with one rank it equals dla_spmm_setup_csr. */
+ * with shards contiguous in rank order; with one rank it equals dla_spmm_setup_csr.
+ * Storage formats (dla_spmm_setup_csr_fmt, single rank): ELLPACK pads every row to the WIDEST one -- ideal for stencils and
+ * bands, unusable when a few rows are long (one dense row at n = 20 000 costs 4.8 GB).  DLA_SPMM_SELL stores sliced ELLPACK
+ * instead: rows sorted by descending length inside windows of sort_window rows, slices of slice_rows consecutive slots padded to
+ * their own longest row, and rows above long_row_threshold entries kept whole in a CSR tail -- storage and traffic follow the
+ * non-zeros.  Rows that are not in the tail come out with the same bits as from ELLPACK (same order of accumulation); repeated
+ * products are bit-identical in both formats.  DLA_SPMM_AUTO takes ELLPACK while its padding (widest row x n / nnz) is at most
+ * 1.25 and SELL otherwise.  The two callbacks serve whichever format was set up last; a refused setup replaces nothing.
+ * dla_spmm_setup_csr is always ELLPACK, and dla_spmm_setup_csr_sharded stays ELLPACK plus halo: sharding the sliced format is
+ * out of scope here. */
+enum { DLA_SPMM_ELL = 0, DLA_SPMM_SELL = 1, DLA_SPMM_AUTO = 2 };
+/* what the calling context's operator occupies (a struct tag only: C keeps tags apart from the function of the same name) */
+struct dla_spmm_info {
+  int format;                 /* DLA_SPMM_ELL or DLA_SPMM_SELL: what is stored (never AUTO) */
+  int n;
+  int slice_rows;             /* SELL: rows per slice (64), sorting window (4096) and the row length above which a row goes */
+  int sort_window;            /*       to the CSR tail (256); 0 for ELLPACK                                                 */
+  int long_row_threshold;
+  long long nnz;              /* entries handed over */
+  long long stored;           /* padded entries of the ELLPACK or sliced part */
+  int slices;                 /* SELL: slices, rows in the tail and their entries; 0 for ELLPACK */
+  int long_rows;
+  long long long_entries;
+  long long device_bytes;     /* bytes of the arrays a product and the preconditioner read (allocations only grow: a smaller
+                                 operator after a larger one keeps the larger blocks) */
+};
 int  dla_spmm_setup_csr(dla_ctx* ctx, int n, const long long* rowptr, const int* colind, const double* values);
+int  dla_spmm_setup_csr_fmt(dla_ctx* ctx, int n, const long long* rowptr, const int* colind, const double* values, int format);
+int  dla_spmm_info(dla_ctx* ctx, struct dla_spmm_info* out);   /* DLA_ERR_ARG before any setup */
 int  dla_spmm_setup_csr_sharded(dla_ctx* ctx, int n_local, long long row0, long long n_global, const long long* rowptr,
                                 const long long* colind_global, const double* values);
 void dla_spmm_matvec(const int* n, const int* m, const double* x_dev, double* ax_dev);

@@ -43,6 +43,7 @@ EXPORTS = [
     "dla_syev", "dla_syev_lowest", "dla_potrf_lower", "dla_trtri_lower", "dla_norm_est",
     "dla_synth_setup", "dla_synth_matvec", "dla_synth_precnd", "dla_synth_apbmul", "dla_synth_ambmul", "dla_synth_spdmul", "dla_synth_smdmul",
     "dla_synth_metric", "dla_synth_lrprec1", "dla_synth_lrprec2", "dla_pending_factor", "dla_pending_block", "dla_basis_admit", "dla_basis_fold", "dla_basis_sync", "dla_spmm_setup_csr", "dla_spmm_setup_csr_fmt", "dla_spmm_info", "dla_spmm_setup_csr_sharded", "dla_spmm_matvec", "dla_spmm_precnd",
+    "dla_spmm_setup_metric_csr", "dla_spmm_metric_info", "dla_spmm_drop_metric", "dla_spmm_bvec", "dla_spmm_precnd_pencil",
     "dla_davidson_driver", "dla_gen_david_driver", "dla_lobpcg_driver", "dla_caslr_eff_driver", "dla_caslr_driver", "dla_call_lrprec",
     "dla_last_solve_info", "dla_set_solve_info",
 ]
@@ -147,6 +148,9 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dla_spmm_setup_csr": (i, [vp, i, vp, vp, vp]),
         "dla_spmm_setup_csr_fmt": (i, [vp, i, vp, vp, vp, i]), "dla_spmm_info": (i, [vp, C.POINTER(SpmmInfo)]),
         "dla_spmm_setup_csr_sharded": (i, [vp, i, C.c_longlong, C.c_longlong, vp, vp, vp]),
+        "dla_spmm_setup_metric_csr": (i, [vp, i, vp, vp, vp, i]), "dla_spmm_metric_info": (i, [vp, C.POINTER(SpmmInfo)]),
+        "dla_spmm_drop_metric": (i, [vp]),
+        "dla_spmm_bvec": (None, [c_ip, c_ip, vp, vp]), "dla_spmm_precnd_pencil": (None, [c_ip, c_ip, c_dp, vp, vp]),
         "dla_davidson_driver": (None, [i, i, i, i, i, d, i, d, vp, vp, vp, vp, c_ip]),
         "dla_lobpcg_driver": (None, [i, i, i, i, i, i, d, d, vp, vp, vp, vp, vp, c_ip]),
         "dla_caslr_eff_driver": (None, [i, i, i, i, i, d, i, vp, vp, vp, vp, vp, vp, vp, c_ip]),
@@ -538,6 +542,29 @@ class Context:
         d = {name: int(getattr(o, name)) for name, _ in SpmmInfo._fields_}
         d["format"] = {v: k for k, v in SPMM_FORMATS.items()}[d["format"]]
         return d
+
+    def spmm_setup_metric(self, b, fmt: str = "ell") -> None:
+        """hand a scipy.sparse matrix (symmetric positive definite, square) to this context as the metric B of A x = lambda B x,
+        beside the operator of spmm_setup and independent of it; fmt as in spmm_setup.  dla_spmm_bvec then applies it"""
+        if fmt not in SPMM_FORMATS:
+            raise ValueError(f"spmm_setup_metric: fmt must be one of {sorted(SPMM_FORMATS)}, not {fmt!r}")
+        b = b.tocsr()
+        rp = np.ascontiguousarray(b.indptr, dtype=np.int64)
+        ci = np.ascontiguousarray(b.indices, dtype=np.int32)
+        va = np.ascontiguousarray(b.data, dtype=np.float64)
+        self._chk(self.lib.dla_spmm_setup_metric_csr(self.h, b.shape[0], rp.ctypes.data, ci.ctypes.data, va.ctypes.data, SPMM_FORMATS[fmt]))
+
+    def spmm_metric_info(self) -> dict:
+        """spmm_info of the metric; raises while none is set"""
+        o = SpmmInfo()
+        self._chk(self.lib.dla_spmm_metric_info(self.h, C.byref(o)))
+        d = {name: int(getattr(o, name)) for name, _ in SpmmInfo._fields_}
+        d["format"] = {v: k for k, v in SPMM_FORMATS.items()}[d["format"]]
+        return d
+
+    def spmm_drop_metric(self) -> None:
+        """free the metric's device blocks (nothing happens without one); the operator stays as it is"""
+        self._chk(self.lib.dla_spmm_drop_metric(self.h))
 
     def spmm_setup_sharded(self, a_rows, row0: int, n_global: int) -> None:
         """hand THIS rank's rows (a scipy.sparse matrix of shape n_local x n_global, global column indices) of a banded

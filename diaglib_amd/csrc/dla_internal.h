@@ -278,6 +278,13 @@ struct Engine : BlockOps {
   virtual int spmm_info(struct dla_spmm_info* /*out*/) { return DLA_ERR_ARG; }
   virtual int spmm_matvec(int /*n*/, int /*m*/, const double* /*x*/, double* /*ax*/) { return DLA_ERR_ARG; }
   virtual int spmm_precnd(int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return DLA_ERR_ARG; }
+  // a second sparse matrix beside the operator: the metric B of A x = lambda B x (single rank, any storage format), its product
+  // bx = B x and the diagonal preconditioner of the pencil, px = x / (a_ii + fac b_ii).  Setting or dropping it leaves A alone.
+  virtual int spmm_setup_metric(int /*n*/, const long long* /*rowptr*/, const int* /*colind*/, const double* /*values*/, int /*format*/) { return DLA_ERR_ARG; }
+  virtual int spmm_metric_info(struct dla_spmm_info* /*out*/) { return DLA_ERR_ARG; }
+  virtual int spmm_drop_metric() { return DLA_ERR_ARG; }
+  virtual int spmm_bvec(int /*n*/, int /*m*/, const double* /*x*/, double* /*bx*/) { return DLA_ERR_ARG; }
+  virtual int spmm_precnd_pencil(int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return DLA_ERR_ARG; }
 
   // Staging pipeline of host-mode callbacks: column chunks of a block travel device -> host on one copy stream, the
   // user's routine works on the chunk that has arrived, finished chunks travel host -> device on a second copy stream

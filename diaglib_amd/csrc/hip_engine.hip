@@ -1687,6 +1687,24 @@ __global__ void diag_precnd_kernel(int n, int m, double fac, const double* __res
   }
 }
 
+// px = x / (a_ii + fac b_ii) where |a_ii + fac b_ii| > 1e-5, else x: the same preconditioner on the diagonal of the pencil
+// A - lambda B (fac = -lambda), for a context that holds a sparse metric beside its operator.  The product fac b_ii is rounded
+// before the sum (no contraction into a fused multiply-add): den is what a host caller gets from the same expression, also where
+// the two terms cancel.  16 n m bytes of vectors + 16 n bytes of the two diagonals.
+__global__ void pencil_precnd_kernel(int n, int m, double fac, const double* __restrict__ a_diag, const double* __restrict__ b_diag,
+                                     const double* __restrict__ x, double* __restrict__ px)
+{
+#pragma clang fp contract(off)
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const double den = a_diag[i] + fac * b_diag[i];
+    const bool use = fabs(den) > 1.0e-5;
+    for (int c = 0; c < m; ++c) {
+      const double v = x[(size_t)c * n + i];
+      px[(size_t)c * n + i] = use ? v / den : v;
+    }
+  }
+}
+
 // The same product on a ROW SHARD of A (dla_spmm_setup_csr_sharded): col[] indexes the extended local vector
 // [last `halo` rows of the previous rank | the shard's n rows | first `halo` rows of the next rank]; the two halo pieces have
 // arrived through the small-product all-reduce (halo_pack_kernel: every rank fills its own two slots of a zeroed buffer, the sum
@@ -5765,22 +5783,39 @@ struct HipEngine : dla::Engine {
   }
 
   // ---- sample sparse operator (ELLPACK; sliced ELLPACK below)
-  DeviceBuffer<int> d_ell_col; DeviceBuffer<double> d_ell_val, d_ell_diag;
-  int ell_n = 0, ell_w = 0;
-  // replace the operator on the device (both set-up routines end here); the caller has bound the device.  The arrays only grow:
-  // a smaller operator after a larger one keeps the larger blocks (the kernels go by ell_n / ell_w); the same holds for synth_setup
-  int upload_ell(const std::vector<int>& col, const std::vector<double>& val, const std::vector<double>& diag)
+  // Everything ONE stored sparse matrix consists of.  The context holds two: the operator A (dla_spmm_matvec / dla_spmm_precnd) and
+  // the metric B of a generalised problem (dla_spmm_bvec); the set-up, info and launch functions below take the one they act on,
+  // so the two have independent storage and independent formats and B's products come from the code that forms A's.
+  struct SparseOp {
+    DeviceBuffer<int> col; DeviceBuffer<double> val, diag;   // ELLPACK blocks, or the slices followed by the CSR tail; diag[n]
+    int n = 0, w = 0;                  // w: ELLPACK width (0 for the sliced format)
+    int fmt = -1;                      // DLA_SPMM_ELL / DLA_SPMM_SELL: what the blocks hold; -1 while nothing is stored
+    long long nnz = 0, sell_stored = 0, sell_long_entries = 0;
+    int sell_slices = 0, sell_long_rows = 0;
+    DeviceBuffer<long long> sell_ptr, long_ptr;
+    DeviceBuffer<int> sell_perm, long_row;
+    // give the device blocks back (the caller has waited for the stream)
+    void drop()
+    {
+      col.reset(); val.reset(); diag.reset(); sell_ptr.reset(); long_ptr.reset(); sell_perm.reset(); long_row.reset();
+      n = w = 0; fmt = -1; nnz = sell_stored = sell_long_entries = 0; sell_slices = sell_long_rows = 0;
+    }
+  };
+  SparseOp op_a, op_b;
+  // replace a matrix on the device (both ELLPACK set-up routines end here); the caller has bound the device.  The arrays only grow:
+  // a smaller matrix after a larger one keeps the larger blocks (the kernels go by n / w); the same holds for synth_setup
+  int upload_ell(SparseOp& op, const std::vector<int>& col, const std::vector<double>& val, const std::vector<double>& diag)
   {
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(d_ell_col.reserve(col.size()));
-    HIPCHK(d_ell_val.reserve(val.size()));
-    HIPCHK(d_ell_diag.reserve(diag.size()));
-    HIPCHK(hipMemcpy(d_ell_col, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_ell_val, val.data(), sizeof(double) * val.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_ell_diag, diag.data(), sizeof(double) * diag.size(), hipMemcpyHostToDevice));
+    HIPCHK(op.col.reserve(col.size()));
+    HIPCHK(op.val.reserve(val.size()));
+    HIPCHK(op.diag.reserve(diag.size()));
+    HIPCHK(hipMemcpy(op.col, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(op.val, val.data(), sizeof(double) * val.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(op.diag, diag.data(), sizeof(double) * diag.size(), hipMemcpyHostToDevice));
     return DLA_OK;
   }
-  int spmm_setup_csr(int n, const long long* rowptr, const int* colind, const double* values) override
+  int setup_ell(SparseOp& op, int n, const long long* rowptr, const int* colind, const double* values)
   {
     if (n <= 0 || !rowptr || !colind || !values) { err = "spmm_setup_csr: bad arguments"; return DLA_ERR_ARG; }
     int w = 0;
@@ -5804,81 +5839,107 @@ struct HipEngine : dla::Engine {
       }
     }
     HIPCHK(hipSetDevice(device));
-    { const int stc = upload_ell(col, val, diag); if (stc) return stc; }
-    ell_n = n; ell_w = w; ell_sharded = false; ell_halo = 0;
-    spmm_fmt = DLA_SPMM_ELL; spmm_nnz = rowptr[n] - rowptr[0];
+    { const int stc = upload_ell(op, col, val, diag); if (stc) return stc; }
+    op.n = n; op.w = w;
+    op.fmt = DLA_SPMM_ELL; op.nnz = rowptr[n] - rowptr[0];
+    return DLA_OK;
+  }
+  int spmm_setup_csr(int n, const long long* rowptr, const int* colind, const double* values) override
+  {
+    { const int stc = setup_ell(op_a, n, rowptr, colind, values); if (stc) return stc; }
+    ell_sharded = false; ell_halo = 0;
     return DLA_OK;
   }
   // ---- ... as sliced ELLPACK with a CSR tail (dla::sell_build).  The slices and the tail share the ELLPACK blocks -- columns and
   // values of the tail follow the `stored` padded entries of the slices -- so either format replaces the other in place.
-  int spmm_fmt = -1;                 // DLA_SPMM_ELL / DLA_SPMM_SELL: what the blocks hold; -1 before any setup
-  long long spmm_nnz = 0, sell_stored = 0, sell_long_entries = 0;
-  int sell_slices = 0, sell_long_rows = 0;
-  DeviceBuffer<long long> d_sell_ptr, d_long_ptr;
-  DeviceBuffer<int> d_sell_perm, d_long_row;
   static constexpr int SELL_MC = 8, LONG_MC = 4;   // right-hand sides per load of a matrix entry (sell_spmm_kernel / csr_long_rows_kernel)
-  int spmm_setup_csr_fmt(int n, const long long* rowptr, const int* colind, const double* values, int format) override
+  int setup_fmt(SparseOp& op, int n, const long long* rowptr, const int* colind, const double* values, int format)
   {
     int w = 0; long long nnz = 0;
     { const int stc = dla::spmm_csr_check(n, rowptr, colind, values, format, &w, &nnz, err); if (stc) return stc; }
-    if (dla::spmm_pick_format(format, w, n, nnz) == DLA_SPMM_ELL) return spmm_setup_csr(n, rowptr, colind, values);
+    if (dla::spmm_pick_format(format, w, n, nnz) == DLA_SPMM_ELL) return setup_ell(op, n, rowptr, colind, values);
     dla::SellLayout L;
     dla::sell_build(n, rowptr, colind, values, L);
     const size_t tot = (size_t)(L.stored + L.long_entries), nl = L.long_row.size();
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(d_ell_col.reserve(tot));
-    HIPCHK(d_ell_val.reserve(tot));
-    HIPCHK(d_ell_diag.reserve((size_t)n));
-    HIPCHK(d_sell_ptr.reserve(L.slice_ptr.size()));
-    HIPCHK(d_sell_perm.reserve((size_t)n));
-    HIPCHK(d_long_row.reserve(std::max<size_t>(1, nl)));
-    HIPCHK(d_long_ptr.reserve(nl + 1));
+    HIPCHK(op.col.reserve(tot));
+    HIPCHK(op.val.reserve(tot));
+    HIPCHK(op.diag.reserve((size_t)n));
+    HIPCHK(op.sell_ptr.reserve(L.slice_ptr.size()));
+    HIPCHK(op.sell_perm.reserve((size_t)n));
+    HIPCHK(op.long_row.reserve(std::max<size_t>(1, nl)));
+    HIPCHK(op.long_ptr.reserve(nl + 1));
     auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
-    HIPCHK(up(d_ell_col, L.col.data(), sizeof(int) * L.col.size()));
-    HIPCHK(up(d_ell_val, L.val.data(), sizeof(double) * L.val.size()));
-    HIPCHK(up(d_ell_col + L.stored, L.long_col.data(), sizeof(int) * L.long_col.size()));
-    HIPCHK(up(d_ell_val + L.stored, L.long_val.data(), sizeof(double) * L.long_val.size()));
-    HIPCHK(up(d_ell_diag, L.diag.data(), sizeof(double) * (size_t)n));
-    HIPCHK(up(d_sell_ptr, L.slice_ptr.data(), sizeof(long long) * L.slice_ptr.size()));
-    HIPCHK(up(d_sell_perm, L.perm.data(), sizeof(int) * (size_t)n));
-    HIPCHK(up(d_long_row, L.long_row.data(), sizeof(int) * nl));
-    HIPCHK(up(d_long_ptr, L.long_ptr.data(), sizeof(long long) * (nl + 1)));
-    ell_n = n; ell_w = 0; ell_sharded = false; ell_halo = 0;
-    spmm_fmt = DLA_SPMM_SELL; spmm_nnz = nnz; sell_stored = L.stored; sell_long_entries = L.long_entries;
-    sell_slices = L.slices; sell_long_rows = (int)nl;
+    HIPCHK(up(op.col, L.col.data(), sizeof(int) * L.col.size()));
+    HIPCHK(up(op.val, L.val.data(), sizeof(double) * L.val.size()));
+    HIPCHK(up(op.col + L.stored, L.long_col.data(), sizeof(int) * L.long_col.size()));
+    HIPCHK(up(op.val + L.stored, L.long_val.data(), sizeof(double) * L.long_val.size()));
+    HIPCHK(up(op.diag, L.diag.data(), sizeof(double) * (size_t)n));
+    HIPCHK(up(op.sell_ptr, L.slice_ptr.data(), sizeof(long long) * L.slice_ptr.size()));
+    HIPCHK(up(op.sell_perm, L.perm.data(), sizeof(int) * (size_t)n));
+    HIPCHK(up(op.long_row, L.long_row.data(), sizeof(int) * nl));
+    HIPCHK(up(op.long_ptr, L.long_ptr.data(), sizeof(long long) * (nl + 1)));
+    op.n = n; op.w = 0;
+    op.fmt = DLA_SPMM_SELL; op.nnz = nnz; op.sell_stored = L.stored; op.sell_long_entries = L.long_entries;
+    op.sell_slices = L.slices; op.sell_long_rows = (int)nl;
+    return DLA_OK;
+  }
+  int spmm_setup_csr_fmt(int n, const long long* rowptr, const int* colind, const double* values, int format) override
+  {
+    { const int stc = setup_fmt(op_a, n, rowptr, colind, values, format); if (stc) return stc; }
+    ell_sharded = false; ell_halo = 0;
+    return DLA_OK;
+  }
+  int op_info(const SparseOp& op, struct dla_spmm_info* out) const
+  {
+    const bool sell = op.fmt == DLA_SPMM_SELL;
+    struct dla_spmm_info zero{};    // (elaborated: the function of the same name hides the struct)
+    *out = zero;
+    out->format = op.fmt; out->n = op.n; out->nnz = op.nnz;
+    out->stored = sell ? op.sell_stored : (long long)op.w * op.n;
+    out->device_bytes = 12 * out->stored + 8 * (long long)op.n;
+    if (sell) {
+      out->slice_rows = dla::SELL_C; out->sort_window = dla::SELL_SIGMA; out->long_row_threshold = dla::SELL_LONG_ROW;
+      out->slices = op.sell_slices; out->long_rows = op.sell_long_rows; out->long_entries = op.sell_long_entries;
+      out->device_bytes += 12 * op.sell_long_entries + 4 * (long long)op.n + 8 * ((long long)op.sell_slices + 1) + 12 * (long long)op.sell_long_rows + 8;
+    }
     return DLA_OK;
   }
   int spmm_info(struct dla_spmm_info* out) override
   {
-    if (spmm_fmt < 0 || !out) { err = "spmm_info: no operator has been set up"; return DLA_ERR_ARG; }
-    const bool sell = spmm_fmt == DLA_SPMM_SELL;
-    struct dla_spmm_info zero{};    // (elaborated: the function of the same name hides the struct)
-    *out = zero;
-    out->format = spmm_fmt; out->n = ell_n; out->nnz = spmm_nnz;
-    out->stored = sell ? sell_stored : (long long)ell_w * ell_n;
-    out->device_bytes = 12 * out->stored + 8 * (long long)ell_n;
-    if (sell) {
-      out->slice_rows = dla::SELL_C; out->sort_window = dla::SELL_SIGMA; out->long_row_threshold = dla::SELL_LONG_ROW;
-      out->slices = sell_slices; out->long_rows = sell_long_rows; out->long_entries = sell_long_entries;
-      out->device_bytes += 12 * sell_long_entries + 4 * (long long)ell_n + 8 * ((long long)sell_slices + 1) + 12 * (long long)sell_long_rows + 8;
-    }
-    return DLA_OK;
+    if (op_a.fmt < 0 || !out) { err = "spmm_info: no operator has been set up"; return DLA_ERR_ARG; }
+    return op_info(op_a, out);
   }
-  int spmm_matvec_sell(int n, int m, const double* x, double* ax)
+  int op_matvec_sell(const SparseOp& op, int n, int m, const double* x, double* ax)
   {
     const int cap = ncu * 8;
-    DLA_LAUNCH((sell_spmm_kernel<SELL_MC>), dim3(std::max(1, std::min(cap, (sell_slices + 3) / 4))), dim3(256), 0, st, n, m, sell_slices,
-               (const long long*)d_sell_ptr, (const int*)d_sell_perm, (const int*)d_ell_col, (const double*)d_ell_val, x, ax);
+    DLA_LAUNCH((sell_spmm_kernel<SELL_MC>), dim3(std::max(1, std::min(cap, (op.sell_slices + 3) / 4))), dim3(256), 0, st, n, m, op.sell_slices,
+               (const long long*)op.sell_ptr, (const int*)op.sell_perm, (const int*)op.col, (const double*)op.val, x, ax);
     HIPCHK(hipGetLastError());
-    if (sell_long_rows > 0) {
-      DLA_LAUNCH((csr_long_rows_kernel<LONG_MC>), dim3(std::max(1, std::min(cap, (sell_long_rows + 3) / 4))), dim3(256), 0, st, n, m, sell_long_rows,
-                 (const int*)d_long_row, (const long long*)d_long_ptr, (const int*)d_ell_col + sell_stored, (const double*)d_ell_val + sell_stored, x, ax);
+    if (op.sell_long_rows > 0) {
+      DLA_LAUNCH((csr_long_rows_kernel<LONG_MC>), dim3(std::max(1, std::min(cap, (op.sell_long_rows + 3) / 4))), dim3(256), 0, st, n, m, op.sell_long_rows,
+                 (const int*)op.long_row, (const long long*)op.long_ptr, (const int*)op.col + op.sell_stored, (const double*)op.val + op.sell_stored, x, ax);
       HIPCHK(hipGetLastError());
     }
     return DLA_OK;
   }
-  // ---- ... on a row shard (banded matrices: the columns of a shard reach at most `halo` rows into its neighbours)
+  // ax = (the matrix of op) x on one rank, in the format op holds (n == op.n has been checked)
+  int op_matvec(const SparseOp& op, int n, int m, const double* x, double* ax)
+  {
+    if (op.fmt == DLA_SPMM_SELL) {
+      Scope s(this, DLA_OP_MATVEC, 12.0 * (double)(op.sell_stored + op.sell_long_entries) + 4.0 * n + 16.0 * (double)n * m, 2.0 * (double)op.nnz * m);
+      return op_matvec_sell(op, n, m, x, ax);
+    }
+    Scope s(this, DLA_OP_MATVEC, 12.0 * (double)op.w * n + 16.0 * (double)n * m, 2.0 * (double)op.w * n * m);
+    const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
+#define ELL(W) DLA_LAUNCH((ell_spmm_kernel<W>), dim3(blocks), dim3(256), 0, st, n, m, op.w, (const int*)op.col, (const double*)op.val, x, ax)
+    if (op.w <= 4) ELL(4); else if (op.w <= 8) ELL(8); else if (op.w <= 16) ELL(16); else if (op.w <= 32) ELL(32); else ELL(0);
+#undef ELL
+    HIPCHK(hipGetLastError());
+    return DLA_OK;
+  }
+  // ---- ... on a row shard (banded matrices: the columns of a shard reach at most `halo` rows into its neighbours); A only
   int ell_halo = 0;                  // rows exchanged with each neighbour; 0 = the operator is not sharded
   bool ell_sharded = false;
   DeviceBuffer<double> d_halo;
@@ -5910,7 +5971,9 @@ struct HipEngine : dla::Engine {
   {
     int w = 0; long long need = 0;
     std::string lerr;
-    const int bad = (values == nullptr) ? DLA_ERR_ARG : dla::sharded_ell_need(n, row0, n_global, rowptr, colind, &w, &need, lerr);
+    // (a metric beside a sharded operator would have to be sharded as well: refused like a bad shard, so that every rank agrees)
+    if (op_b.fmt >= 0) lerr = "spmm_setup_csr_sharded: this context holds a metric (dla_spmm_setup_metric_csr), and a row-sharded metric is not supported; drop it first";
+    const int bad = (op_b.fmt >= 0 || values == nullptr) ? DLA_ERR_ARG : dla::sharded_ell_need(n, row0, n_global, rowptr, colind, &w, &need, lerr);
     const int nr = std::max(1, nranks);
     // agree on the halo width and check the layout, collectively: [max need | any failure | row0 and n of every rank (slots)]
     std::vector<double> mx{(double)need, bad ? 1.0 : 0.0};
@@ -5941,10 +6004,10 @@ struct HipEngine : dla::Engine {
     dla::ShardedEll e;
     dla::sharded_ell_build(n, row0, rowptr, colind, values, (int)halo, e);
     bind();
-    stc = upload_ell(e.col, e.val, e.diag);
+    stc = upload_ell(op_a, e.col, e.val, e.diag);
     if (stc) return stc;
-    ell_n = n; ell_w = e.w; ell_halo = (int)halo; ell_sharded = true;
-    spmm_fmt = DLA_SPMM_ELL; spmm_nnz = rowptr[n] - rowptr[0];
+    op_a.n = n; op_a.w = e.w; ell_halo = (int)halo; ell_sharded = true;
+    op_a.fmt = DLA_SPMM_ELL; op_a.nnz = rowptr[n] - rowptr[0];
     return DLA_OK;
   }
   int spmm_matvec_sharded(int n, int m, const double* x, double* ax)
@@ -5977,8 +6040,8 @@ struct HipEngine : dla::Engine {
       // (the first / last rank never index their missing neighbour: any valid address serves)
       const double* prev = d_halo + (size_t)((rank > 0 ? (rank - 1) * 2 + 1 : 0) * mcur) * H;
       const double* next = d_halo + (size_t)((rank + 1 < nr ? (rank + 1) * 2 : 0) * mcur) * H;
-#define ELLH(W) DLA_LAUNCH((ell_spmm_halo_kernel<W>), dim3(blocks), dim3(256), 0, st, n, mcur, ell_w, H, (const int*)d_ell_col, (const double*)d_ell_val, xc, prev, next, ax + (size_t)c0 * n)
-      if (ell_w <= 4) ELLH(4); else if (ell_w <= 8) ELLH(8); else if (ell_w <= 16) ELLH(16); else if (ell_w <= 32) ELLH(32); else ELLH(0);
+#define ELLH(W) DLA_LAUNCH((ell_spmm_halo_kernel<W>), dim3(blocks), dim3(256), 0, st, n, mcur, op_a.w, H, (const int*)op_a.col, (const double*)op_a.val, xc, prev, next, ax + (size_t)c0 * n)
+      if (op_a.w <= 4) ELLH(4); else if (op_a.w <= 8) ELLH(8); else if (op_a.w <= 16) ELLH(16); else if (op_a.w <= 32) ELLH(32); else ELLH(0);
 #undef ELLH
       HIPCHK(hipGetLastError());
     }
@@ -5986,26 +6049,58 @@ struct HipEngine : dla::Engine {
   }
   int spmm_matvec(int n, int m, const double* x, double* ax) override
   {
-    if (n != ell_n || !d_ell_col) { err = "spmm_matvec: n differs from setup"; return DLA_ERR_ARG; }
-    if (spmm_fmt == DLA_SPMM_SELL) {
-      Scope s(this, DLA_OP_MATVEC, 12.0 * (double)(sell_stored + sell_long_entries) + 4.0 * n + 16.0 * (double)n * m, 2.0 * (double)spmm_nnz * m);
-      return spmm_matvec_sell(n, m, x, ax);
+    if (n != op_a.n || !op_a.col) { err = "spmm_matvec: n differs from setup"; return DLA_ERR_ARG; }
+    if (ell_sharded) {
+      Scope s(this, DLA_OP_MATVEC, 12.0 * (double)op_a.w * n + 16.0 * (double)n * m, 2.0 * (double)op_a.w * n * m);
+      return spmm_matvec_sharded(n, m, x, ax);
     }
-    Scope s(this, DLA_OP_MATVEC, 12.0 * (double)ell_w * n + 16.0 * (double)n * m, 2.0 * (double)ell_w * n * m);
-    if (ell_sharded) return spmm_matvec_sharded(n, m, x, ax);
-    const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
-#define ELL(W) DLA_LAUNCH((ell_spmm_kernel<W>), dim3(blocks), dim3(256), 0, st, n, m, ell_w, (const int*)d_ell_col, (const double*)d_ell_val, x, ax)
-    if (ell_w <= 4) ELL(4); else if (ell_w <= 8) ELL(8); else if (ell_w <= 16) ELL(16); else if (ell_w <= 32) ELL(32); else ELL(0);
-#undef ELL
-    HIPCHK(hipGetLastError());
-    return DLA_OK;
+    return op_matvec(op_a, n, m, x, ax);
   }
   int spmm_precnd(int n, int m, double fac, const double* x, double* px) override
   {
-    if (n != ell_n || !d_ell_diag) { err = "spmm_precnd: n differs from setup"; return DLA_ERR_ARG; }
+    if (n != op_a.n || !op_a.diag) { err = "spmm_precnd: n differs from setup"; return DLA_ERR_ARG; }
     Scope s(this, DLA_OP_PRECND, 8.0 * n * (2.0 * m + 1.0), (double)n * m);
     const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
-    DLA_LAUNCH(diag_precnd_kernel, dim3(blocks), dim3(256), 0, st, n, m, fac, (const double*)d_ell_diag, x, px);
+    DLA_LAUNCH(diag_precnd_kernel, dim3(blocks), dim3(256), 0, st, n, m, fac, (const double*)op_a.diag, x, px);
+    HIPCHK(hipGetLastError());
+    return DLA_OK;
+  }
+  // ---- ... and a second matrix beside it: the metric B of A x = lambda B x (bvec of reference diaglib.f90:1855), single rank
+  int spmm_setup_metric(int n, const long long* rowptr, const int* colind, const double* values, int format) override
+  {
+    if (ell_sharded) { err = "spmm_setup_metric_csr: the operator of this context is row-sharded, and a row-sharded metric is not supported"; return DLA_ERR_ARG; }
+    const int stc = setup_fmt(op_b, n, rowptr, colind, values, format);
+    if (stc == DLA_ERR_ARG) err = "spmm_setup_metric_csr: " + err;
+    return stc;
+  }
+  int spmm_metric_info(struct dla_spmm_info* out) override
+  {
+    if (op_b.fmt < 0 || !out) { err = "spmm_metric_info: no metric has been set up"; return DLA_ERR_ARG; }
+    return op_info(op_b, out);
+  }
+  int spmm_drop_metric() override
+  {
+    if (op_b.fmt < 0 && !op_b.col) return DLA_OK;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipStreamSynchronize(st));     // (products of B may still be queued)
+    op_b.drop();
+    return DLA_OK;
+  }
+  int spmm_bvec(int n, int m, const double* x, double* bx) override
+  {
+    if (op_b.fmt < 0) { err = "spmm_bvec: no metric has been set up (dla_spmm_setup_metric_csr)"; return DLA_ERR_ARG; }
+    if (n != op_b.n) { err = "spmm_bvec: n differs from the metric's"; return DLA_ERR_ARG; }
+    return op_matvec(op_b, n, m, x, bx);
+  }
+  int spmm_precnd_pencil(int n, int m, double fac, const double* x, double* px) override
+  {
+    if (op_a.fmt < 0 || !op_a.diag) { err = "spmm_precnd_pencil: no operator has been set up"; return DLA_ERR_ARG; }
+    if (op_b.fmt < 0) { err = "spmm_precnd_pencil: no metric has been set up (dla_spmm_setup_metric_csr)"; return DLA_ERR_ARG; }
+    if (op_a.n != op_b.n) { err = "spmm_precnd_pencil: the operator has " + std::to_string(op_a.n) + " rows and the metric " + std::to_string(op_b.n); return DLA_ERR_ARG; }
+    if (n != op_a.n) { err = "spmm_precnd_pencil: n differs from setup"; return DLA_ERR_ARG; }
+    Scope s(this, DLA_OP_PRECND, 16.0 * (double)n * m + 16.0 * (double)n, 2.0 * (double)n * m);
+    const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
+    DLA_LAUNCH(pencil_precnd_kernel, dim3(blocks), dim3(256), 0, st, n, m, fac, (const double*)op_a.diag, (const double*)op_b.diag, x, px);
     HIPCHK(hipGetLastError());
     return DLA_OK;
   }

@@ -1228,7 +1228,7 @@ static bool builtin_operator(dla_matvec_fn fn)
 {
   return (void*)fn == (void*)&dla_synth_matvec || (void*)fn == (void*)&dla_spmm_matvec || (void*)fn == (void*)&dla_synth_apbmul ||
          (void*)fn == (void*)&dla_synth_ambmul || (void*)fn == (void*)&dla_synth_spdmul || (void*)fn == (void*)&dla_synth_smdmul ||
-         (void*)fn == (void*)&dla_synth_metric;
+         (void*)fn == (void*)&dla_synth_metric || (void*)fn == (void*)&dla_spmm_bvec;
 }
 
 int dla_call_matvec(dla_ctx* c, dla_matvec_fn fn, int n, int m, const double* x, double* ax)
@@ -1753,7 +1753,8 @@ int dla_call_precnd(dla_ctx* c, dla_precnd_fn fn, int n, int m, double fac, cons
   DLA_T("dla_call_precnd");
   if (m <= 0) return DLA_OK;
   if (c->callbacks_on_device) {
-    const int order = ((void*)fn == (void*)&dla_synth_precnd || (void*)fn == (void*)&dla_spmm_precnd) ? 2 : c->callback_order;
+    const int order = ((void*)fn == (void*)&dla_synth_precnd || (void*)fn == (void*)&dla_spmm_precnd ||
+                       (void*)fn == (void*)&dla_spmm_precnd_pencil) ? 2 : c->callback_order;
     int st = c->eng->callback_begin(order);
     if (st) return engfail(c, st);
     fn(&n, &m, &fac, x, px);
@@ -1890,6 +1891,41 @@ void dla_spmm_precnd(const int* n, const int* m, const double* fac, const double
   dla_ctx* c = g_spmm_ctx;
   if (!c) { callback_failed(DLA_ERR_ARG, "dla_spmm_precnd before dla_spmm_setup_csr"); return; }
   if (int st = c->eng->spmm_precnd(*n, *m, *fac, x, px)) callback_failed(st, "spmm_precnd failed: " + c->eng->err);
+}
+
+// ---- ... and the metric of a generalised problem beside it (bvec of reference diaglib.f90:1855; the harness' smult, main.f90:115-144)
+int dla_spmm_setup_metric_csr(dla_ctx* c, int n, const long long* rowptr, const int* colind, const double* values, int format)
+{
+  if (!c) return DLA_ERR_ARG;
+  const int st = engfail(c, c->eng->spmm_setup_metric(n, rowptr, colind, values, format));
+  if (st == DLA_OK) g_spmm_ctx = c;
+  return st;
+}
+
+int dla_spmm_metric_info(dla_ctx* c, struct dla_spmm_info* out)
+{
+  if (!c || !out) return DLA_ERR_ARG;
+  return engfail(c, c->eng->spmm_metric_info(out));
+}
+
+int dla_spmm_drop_metric(dla_ctx* c)
+{
+  if (!c) return DLA_ERR_ARG;
+  return engfail(c, c->eng->spmm_drop_metric());
+}
+
+void dla_spmm_bvec(const int* n, const int* m, const double* x, double* bx)
+{
+  dla_ctx* c = g_spmm_ctx;
+  if (!c) { callback_failed(DLA_ERR_ARG, "dla_spmm_bvec before dla_spmm_setup_metric_csr"); return; }
+  if (int st = c->eng->spmm_bvec(*n, *m, x, bx)) callback_failed(st, "dla_spmm_bvec failed: " + c->eng->err);
+}
+
+void dla_spmm_precnd_pencil(const int* n, const int* m, const double* fac, const double* x, double* px)
+{
+  dla_ctx* c = g_spmm_ctx;
+  if (!c) { callback_failed(DLA_ERR_ARG, "dla_spmm_precnd_pencil before dla_spmm_setup_csr and dla_spmm_setup_metric_csr"); return; }
+  if (int st = c->eng->spmm_precnd_pencil(*n, *m, *fac, x, px)) callback_failed(st, "dla_spmm_precnd_pencil failed: " + c->eng->err);
 }
 
 }  // extern "C"

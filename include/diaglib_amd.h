@@ -90,7 +90,7 @@ enum {
                                       takes another route than planned the operator is called a SECOND time on the finished
                                       block and its first output is dropped -- the reference calls matvec exactly once per
                                       block (diaglib.f90:1685, 394-397), so:
-                                      1 (default): only for the library's own device operators (dla_synth_*, dla_spmm_matvec),
+                                      1 (default): only for the library's own device operators (dla_synth_*, dla_spmm_matvec, dla_spmm_bvec),
                                          which are pure functions of their input; a caller's callback is called once, in order;
                                       2: also for the caller's device-mode callbacks (ordering contract 0 or 2) -- the caller
                                          states that the operator keeps no state between calls;
@@ -456,7 +456,19 @@ void dla_set_solve_info(int iters, int matvec_cols, int restarts);   /* used by 
  * products are bit-identical in both formats.  DLA_SPMM_AUTO takes ELLPACK while its padding (widest row x n / nnz) is at most
  * 1.25 and SELL otherwise.  The two callbacks serve whichever format was set up last; a refused setup replaces nothing.
  * dla_spmm_setup_csr is always ELLPACK, and dla_spmm_setup_csr_sharded stays ELLPACK plus halo: sharding the sliced format is
- * out of scope here. */
+ * out of scope here.
+ * The metric of a generalised problem A x = lambda B x (dla_spmm_setup_metric_csr, single rank): a context keeps a second sparse
+ * matrix B beside its operator, handed over the same way and stored in any of the formats above.  dla_spmm_bvec has the shape of
+ * the reference's bvec(n,m,x,bx) (diaglib.f90:1855, gen_david_driver; the harness' smult, main.f90:115-144) and goes where a host
+ * bvec would go in gen_david_driver and lobpcg_driver(gen_eig = .true.), so that a whole generalised solve stays in HBM.  It runs
+ * the kernels dla_spmm_matvec runs: B x comes out with the bits the operator slot gives for the same matrix in the same format.
+ * A and B are independent storage with independent formats: setting, replacing or dropping one never touches the other's blocks
+ * or results, a refused setup replaces nothing, and dla_spmm_info keeps describing A only (dla_spmm_metric_info describes B).
+ * dla_spmm_precnd stays the harness' x / (a_ii + fac), which the reference harness passes for the generalised problem too
+ * (main.f90:491-492, 511-512); dla_spmm_precnd_pencil divides by the diagonal of the pencil, a_ii + fac b_ii, instead and needs
+ * both matrices with the same n.  A callback that finds its matrix missing, or another n, fails through the status of
+ * dla_call_matvec / dla_call_precnd with a message that names it.  A row-sharded metric is out of scope: the metric is refused
+ * on a context whose operator came from dla_spmm_setup_csr_sharded, and that setup is refused while a metric is present. */
 enum { DLA_SPMM_ELL = 0, DLA_SPMM_SELL = 1, DLA_SPMM_AUTO = 2 };
 /* what the calling context's operator occupies (a struct tag only: C keeps tags apart from the function of the same name) */
 struct dla_spmm_info {
@@ -480,6 +492,14 @@ int  dla_spmm_setup_csr_sharded(dla_ctx* ctx, int n_local, long long row0, long 
                                 const long long* colind_global, const double* values);
 void dla_spmm_matvec(const int* n, const int* m, const double* x_dev, double* ax_dev);
 void dla_spmm_precnd(const int* n, const int* m, const double* fac, const double* x_dev, double* px_dev);
+/* a second sparse symmetric matrix B (positive definite: not checked, b_ortho reports a failed Cholesky as it does for any
+   metric) beside the operator A of this context; format as in dla_spmm_setup_csr_fmt (ELL / SELL / AUTO), single rank */
+int  dla_spmm_setup_metric_csr(dla_ctx* ctx, int n, const long long* rowptr, const int* colind, const double* values, int format);
+int  dla_spmm_metric_info(dla_ctx* ctx, struct dla_spmm_info* out);   /* DLA_ERR_ARG while no metric is set */
+int  dla_spmm_drop_metric(dla_ctx* ctx);                              /* frees B's device blocks; no-op without one */
+void dla_spmm_bvec(const int* n, const int* m, const double* x_dev, double* bx_dev);          /* bx = B x */
+void dla_spmm_precnd_pencil(const int* n, const int* m, const double* fac, const double* x_dev, double* px_dev);
+                                          /* px = x / (a_ii + fac b_ii) where |a_ii + fac b_ii| > 1e-5, else x */
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,9 @@
 #include <vector>
 #include "dla_internal.h"
 #include "hip_owned.h"
+#include "hip_plans.h"
+
+using namespace dla_plans;   // the decisions (hip_plans.h); this file launches what they say
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 typedef double v2d __attribute__((ext_vector_type(2)));
@@ -1766,18 +1769,10 @@ __global__ void halo_pack_kernel(int n, int m, int halo, int nranks, int rank, c
 // (OrthoDev::phase).  The host enqueues the sequence of sweeps it expects (the one the previous call took); every
 // sweep and every tail kernel checks the phase and leaves at once when it is not its turn (DLA_PREDICATED), so a
 // wrong guess costs empty launches, never a wrong result.  One host wait at the end reads the state back.
-// OP_GRAMX / OP_GRAMW / OP_XW belong to the pending-factor schedule (k <= 16, even n; see ortho_tail16): X^T U and U^T U in one
-// sweep over [X | U]; the Gram matrix of U W formed on the fly; both at once
-// OP_COMBOX / OP_CLOSE belong to the three-pass schedule (OrthoTailArgs::x3, see ortho_tail16): the projection sweep that also
-// measures X^T U and U^T U of what it stores, and the closing projection that measures nothing.  OP_TRMMC is OP_TRMMG (the written
-// update U <- U W with the Gram matrix of what it stores) behind a measuring sweep whose X^T U is carried through it, S W: the
-// macro-iteration of ortho_cd that a caller with pending blocks gets instead of one more projection (see ortho_tail16)
-enum { OP_NONE = 0, OP_GRAM_UU = 1, OP_TRMMG = 2, OP_XU = 3, OP_COMBO = 4, OP_FINAL = 5, OP_GRAMX = 6, OP_GRAMW = 7, OP_XW = 8,
-       OP_COMBOX = 9, OP_CLOSE = 10, OP_TRMMC = 11 };
+// (The sweeps' names, OP_*, are shared with the host's planning: hip_plans.h.)
 // the block a chain leaves pending, in pinned host memory: [row][PEND_LD] with the rows of E (the part that multiplies X: only the
 // three-pass schedule has one) followed by the k rows of the triangular factor T, then the header {sequence number, rows of E}
 #define PEND_LD 48
-#define PEND_ROWS 640
 #define PEND_HDR ((size_t)PEND_ROWS * PEND_LD)
 // dla_expand_project mode 4: the caller's stored basis is orthonormal to 1e-8 per block only (pending factors and projections), and a
 // projection against it leaves (X_c^T X_c - I) S of what it removes -- up to m 1e-8 |S| over a basis of m columns.  A chain of that
@@ -2394,7 +2389,7 @@ __device__ __forceinline__ double wave_sum(double v)
 // LDS use of ortho_tail16 (doubles): [0,256) G hand-over / transpose scratch (16 x 17), [272,528) Wd for the assembly,
 // [528,784) Wp for the assembly
 #define T16_LDS_DOUBLES 784
-#define T16_ZS_ROWS 320                    // rows of the coefficient block the exact projection (OrthoTailArgs::dmat) keeps in LDS behind them
+#define T16_ZS_ROWS DMAT_LD                // rows of the coefficient block the exact projection (OrthoTailArgs::dmat) keeps in LDS behind them
 
 // One step of the state machine for k <= 16, called by ALL 256 threads of a block (wave 0 does the serial part, all four
 // waves assemble the coefficient block of a projection sweep).  g_in_lds: lds[64 r + lane] already holds the Gram matrix
@@ -3079,7 +3074,6 @@ __global__ __launch_bounds__(256) void ortho_tail16_kernel(OrthoTailArgs a)
 //   * a launch belongs to the device-driven chains like any other: when it is not its turn (DLA_PREDICATED) it returns
 //     before touching a mailbox, on every rank alike (all ranks hold the same phase).
 #define P2P_MAX_RANKS 8
-#define P2P_MAX_DOUBLES 16384              // 128 KB per slot (the widest projection block of BASELINE cfg 4/5 fits)
 #define P2P_FLAG_STRIDE 16                 // one flag per 128-byte line
 #define P2P_ERR_WORD(nr) ((size_t)2 * (nr) * P2P_FLAG_STRIDE)   // index of the error word behind a mailbox's flags
 struct P2PArgs {
@@ -3398,88 +3392,8 @@ struct HipEngine : dla::Engine {
   const char* name() const override { return nm.c_str(); }
   void* stream() override { return (void*)st; }
 
-  // The experiment knobs (options DLA_OPT_TUNE0 + i, i = 0 .. 7): what the tests, the benchmark ($DIAGLIB_BENCH_TUNE) and the A/B and fuzz
-  // tools switch by number.  All 0 is the product; a value that is not named here selects nothing.  The numbers stand in this struct
-  // and nowhere else: the engine asks one predicate per decision.  (The same table for the tools' side: tools/README.md.)
-  struct Knobs {
-    int tune[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    void set(int i, int v) { if (i >= 0 && i < 8) tune[i] = v; }
-    int get(int i) const { return (i >= 0 && i < 8) ? tune[i] : 0; }
-    // ---- knob 0: the Ritz sweep (ritz_residual_once, ritz_residual_p, ritz_residual2)
-    // 1 / 4: column-step pipeline of depth 0 / 4 for plain blocks of two and three tiles, no quarter tiles; -1: the kernel's own (tools/tune_ab.py)
-    int ritz_pipe_depth() const { return tune[0] == 1 ? 0 : tune[0] == 4 ? 4 : -1; }
-    // 5: Ritz step and P products never in one pass (A/B switch, no record kept)
-    bool ritz_p_separate() const { return tune[0] == 5; }
-    // 6: the two-coefficient sweep ritz2_kernel off, three sweeps instead (A/B switch, no record kept)
-    bool no_ritz2() const { return tune[0] == 6; }
-    // ---- knob 1: blocks of a Ritz sweep, as a multiple of the built-in count (tools/tune_ab.py)
-    int ritz_grid_factor() const { return tune[1] > 0 ? tune[1] : 1; }
-    // ---- knob 2: the plain panel product (gemm_chunk)
-    // 1 / 4: as knob 0 = 1 / 4, for the plain product and update of two and three tiles (tools/tune_ab.py)
-    int gemm_pipe_depth() const { return tune[2] == 1 ? 0 : tune[2] == 4 ? 4 : -1; }
-    // ---- knob 3: > 0: cap on resident blocks per CU of the panel-product kernels (tools/tune_fused.py)
-    int gemm_blocks_per_cu() const { return tune[3] > 0 ? tune[3] : 0; }
-    // ---- knob 4: blocks of the Gram sweeps
-    // > 0: blocks per pass of gram_plan and wp_plan (tools/tune_ab.py, tools/ab/combox_ab.py)
-    int gram_blocks_override() const { return tune[4] > 0 ? tune[4] : 0; }
-    // -1: the measuring sweeps of up to five X tiles with one block per CU (measured r05, see wp_plan)
-    bool wp_one_block_per_cu() const { return tune[4] == -1; }
-    // ---- knob 5: the Gram kernels and their reduction
-    // 2: the direct-load gram_kernel everywhere (tools/tune_gram.py)
-    bool direct_gram() const { return tune[5] == 2; }
-    // 3: GramReduceArgs::fenced (tests/test_ortho_chain_gpu.py requires identical bits)
-    bool fenced_reduce() const { return tune[5] == 3; }
-    // ---- knob 6: the orthogonalisation chain
-    // 2: the host polls the stream, no event packet (wait_stream)
-    bool poll_stream() const { return tune[6] == 2; }
-    // 3: no chain, the host-driven loop (parity knob of tests/test_ortho_chain_gpu.py, tools/fuzz_parity.py)
-    bool host_loop() const { return tune[6] == 3; }
-    // 4: the cross-rank exchange as a launch of its own, not in the reduction kernel (A/B switch, no record kept; bench.py's own example)
-    bool exchange_own_launch() const { return tune[6] == 4; }
-    // 5: one-tile blocks keep the LDS-loop k x k step of ortho_tail_kernel (A/B switch, no record kept)
-    bool no_mfma_kxk() const { return tune[6] == 5; }
-    // 6: one-tile blocks on the sweep-per-update schedule (A/B switch, no record kept)
-    bool no_pending_factor() const { return tune[6] == 6; }
-    // 7 / 8: wide blocks without the one-sweep [X | U] Gram (tools/wide_solve_ab.py, tools/iters_probe.py)
-    bool no_wide_gramx() const { return tune[6] == 7 || tune[6] == 8; }
-    // 7 also: the leading ortho_cd runs to convergence (OrthoTailArgs::lead_once = 0)
-    bool lead_full() const { return tune[6] == 7; }
-    // 9: wide blocks without the storing sweep OP_XW (tools/ab/wide_xw_ab.py)
-    bool no_wide_xw() const { return tune[6] == 9; }
-    // 10: the storing sweep for three-tile blocks too (measured r04, see ortho_chain_begin)
-    bool wide_xw_three_tiles() const { return tune[6] == 10; }
-    // 11: b_ortho_ahead declines: the metric Cholesky-QR waits for the chain (A/B switch, no record kept)
-    bool no_b_ortho_ahead() const { return tune[6] == 11; }
-    // 12: never the three-pass schedule (tests, tools/fuzz_ortho.py, tools/profile_all.sh)
-    bool five_sweep() const { return tune[6] == 12; }
-    // 13: the three-pass schedule from the first chain, no cooldown (same)
-    bool three_pass_always() const { return tune[6] == 13; }
-    // 14: basis_exact_ok() answers no (tools/ab/exact_ab.sh, tests/test_pending_basis_gpu.py)
-    bool mode5_as_mode4() const { return tune[6] == 14; }
-    // what basis_exact_ok() needs of the three above
-    bool no_exact_basis() const { return host_loop() || no_mfma_kxk() || mode5_as_mode4(); }
-    // OrthoTailArgs::gp; 15: from U^T U as the reference's, 16: level shifts on the projected block's Gram matrix (tools/ab/exact_ab.sh, see launch_op)
-    int first_factor_source() const { return tune[6] == 15 ? 0 : tune[6] == 16 ? 2 : 1; }
-    // 17: plans keep OP_CLOSE / OP_FINAL where the caller takes the closing block (r05 trace, see ortho_chain_begin)
-    bool keep_closing_launches() const { return tune[6] == 17; }
-    // ---- knob 7: kernel variants of the wide blocks (tools/quarter_tile_ab.py unless another record is named)
-    // 1: full 16x16x4 tiles only (tests/test_quarter_tiles_gpu.py compares both)
-    bool no_quarter_tiles() const { return tune[7] == 1; }
-    // 2: GramArgs::noskip, the loads of fully padded column groups are issued too
-    bool gram_load_pads() const { return tune[7] == 2; }
-    // 3: Gram passes of at most 12 accumulator tiles
-    bool narrow_gram_passes() const { return tune[7] == 3; }
-    // 4: the row products do not load the next row tile ahead (GemmArgs::xpf = 0)
-    bool no_next_tile_prefetch() const { return tune[7] == 4; }
-    // 5: 64-row wave tiles (RTP = 2) in the fused three-tile sweep
-    bool fused3_two_row_groups() const { return tune[7] == 5; }
-    // 8: the lower triangle of two panels in several passes, not gram_lds_kernel LOW
-    bool no_low_single() const { return tune[7] == 8; }
-    // 9: small_copy_kernel instead of the runtime's copy (see stage_slot)
-    bool own_copy_kernel() const { return tune[7] == 9; }
-    // 22 / 23: one first-level group per 16 / 64 block partials (measured r06, DESIGN "Measured and rejected")
-    int reduce_group_size() const { return tune[7] == 22 ? 16 : tune[7] == 23 ? 64 : 32; }
-  } knobs;
+  Knobs knobs;                       // the experiment knobs (hip_plans.h)
+  PlanEnv env() const { return PlanEnv{ncu, lds_limit, knobs}; }     // what the planners read of this engine
 
   // What the launches of the current step are enqueued under.  Nothing a launch depends on is a bare engine member: a caller
   // installs a modified copy with CtxScope, which puts back what was there before on every way out.  Outside any scope the
@@ -3560,7 +3474,7 @@ struct HipEngine : dla::Engine {
     HIPCHK(d_small.reserve(512 * 512));
     HIPCHK(h_small.reserve(512 * 512));
     HIPCHK(d_ticket.reserve(4100));                                         // [4096] per output tile + 1 global
-    HIPCHK(hipMemsetAsync(d_ticket, 0, sizeof(unsigned) * 4100, st));       // (on the engine's stream: see d_halo)
+    HIPCHK(hipMemsetAsync(d_ticket, 0, sizeof(unsigned) * 4100, st));       // (on the engine's stream: see RowShard::d_halo)
     return DLA_OK;
   }
 
@@ -4182,7 +4096,6 @@ struct HipEngine : dla::Engine {
   DeviceBuffer<unsigned long long> d_dbg;   // $DIAGLIB_AMD_CHAIN_DEBUG: time stamps of the chain's steps (empty otherwise)
   DeviceBuffer<double> d_wst;               // pending factors of ortho_tail16 (3 x 256 doubles)
   DeviceBuffer<double> d_xug;               // X^T U | U^T U of the last OP_GRAMX / OP_XW sweep: (m + k) x k
-  static const int XUG_DOUBLES = 640 * 16;
   // RCCL inside a device-driven chain: the collective itself cannot be predicated (it is enqueued by the host), so a launch
   // whose turn it is not still all-reduces whatever its source buffer holds.  Out of place, into these buffers, that is harmless:
   // the source is never scaled, and the tail that would read the result is predicated off like its sweep.
@@ -4191,17 +4104,6 @@ struct HipEngine : dla::Engine {
   MappedHostBuffer<double> h_tpend;  // the factor a drop_final chain left pending (OrthoTailArgs::t_host)
   int t_seq = 0;                     // sequence number of the chain being enqueued
   int t_pending_k = 0;               // > 0: the last chain ended with a k x k factor pending and nobody has fetched it yet
-  // What tells two chains apart.  Plans are remembered per shape with wide_gramx and dropf (vsx follows from m there); the walked
-  // launch paths depend on neither, so chain_verified keeps those two fields false; kind() forgets the basis width.
-  struct ChainShape {
-    int k = 0, m = 0, fold = 0;
-    bool vsx = false, wide_gramx = false, wide_xw = false, dropf = false, x3 = false;
-    bool operator<(const ChainShape& o) const
-    {
-      return std::tie(k, m, fold, vsx, wide_gramx, wide_xw, dropf, x3) < std::tie(o.k, o.m, o.fold, o.vsx, o.wide_gramx, o.wide_xw, o.dropf, o.x3);
-    }
-    ChainShape kind() const { ChainShape s = *this; s.m = 0; return s; }
-  };
   std::map<ChainShape, std::vector<int>> plan_of_shape;   // the sweeps the last chain of that shape executed
   std::map<ChainShape, std::vector<int>> plan_of_kind;    // ... the most recent chain of that kind() and width, whatever its m
   std::set<ChainShape> chain_verified;                    // shapes whose launch paths have been walked (see ortho_chain)
@@ -4381,37 +4283,6 @@ struct HipEngine : dla::Engine {
     DLA_LAUNCH(kfn, grid, dim3(256), lds, st, a);
     return DLA_OK;
   }
-  // widest X pass of the pending-factor sweeps: 12 X tiles beside one U tile, 8 beside two (16 + 3 accumulator tiles), 5 beside
-  // three (15 + 6)
-  static int wp_max_tlw(int kt) { return kt <= 1 ? 12 : kt == 2 ? 8 : 5; }
-  // pass shape of a pending-factor sweep: what the kernel's name, its instance and the reduction behind it are all read from
-  struct WpPlan { int tlw, kt, R, passes, blocks, extra, slots; bool self; };
-  WpPlan wp_plan(int n, int m, int k) const
-  {
-    WpPlan p{};
-    p.self = (m == 0);
-    p.kt = (k + 15) / 16;
-    const int tx = p.self ? 1 : (m + 15) / 16;
-    p.passes = p.self ? 1 : (tx + wp_max_tlw(p.kt) - 1) / wp_max_tlw(p.kt);
-    p.tlw = (tx + p.passes - 1) / p.passes;
-    if (p.kt == 1) {
-      static const int avail[] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12};
-      for (int v : avail) if (v >= p.tlw) { p.tlw = v; break; }
-    }
-    // the staged image of the widest pass: 13 tiles of 16 rows (4 waves x 13 x 16 x 18 doubles = 117 KiB); under a refused
-    // LDS raise the chain is not taken at all (ortho_chain).  (A block against itself is one tile beside one: 32 rows.)
-    p.R = (p.kt == 1 && p.tlw <= 2) ? 32 : 16;
-    const long long nchunks = ((long long)n + 31) / 32;
-    const long long want = (nchunks + 15) / 16;
-    // (one U tile beside up to five X tiles: at most 212 / 252 registers and 55 KB of LDS per block -- two blocks per CU, two waves
-    //  per SIMD: measured r05 at n = 2e6, interleaved: +5 ... 11 % for the projection sweep, +3 ... 9 % for the storing one; beyond
-    //  five tiles the kernels need more than 256 registers and a second block per CU only runs behind the first)
-    p.blocks = (int)std::max(1LL, std::min((long long)ncu * ((p.self || (p.kt == 1 && p.tlw <= 5 && !knobs.wp_one_block_per_cu())) ? 2 : 1), want));
-    if (knobs.gram_blocks_override()) p.blocks = (int)std::max(1LL, std::min((long long)knobs.gram_blocks_override(), want));
-    p.extra = p.self ? 0 : p.kt * (p.kt + 1) / 2;          // tiles (qi >= qj) of the Gram matrix of the U block
-    p.slots = p.self ? 1 : p.tlw * p.kt + p.extra;
-    return p;
-  }
   //   cx != nullptr (m > 0, uw = u, one pass): U <- [X | U] C' stored, X^T U and U^T U of the stored result (OP_COMBOX)
   int gram_wp_once(int n, int m, const double* x, int k, const double* u, const double* wp, double* uw, StepOut& out, const double* cx = nullptr)
   {
@@ -4419,7 +4290,7 @@ struct HipEngine : dla::Engine {
     const bool self = (m == 0);
     if (cx != nullptr && (self || uw == nullptr || wp != nullptr || k > 16)) { err = "gram_wp: bad projection sweep"; return DLA_ERR_ARG; }
     if (k > 48 || (self && k > 16)) { err = "gram_wp: block too wide"; return DLA_ERR_ARG; }
-    const WpPlan p = wp_plan(n, m, k);
+    const WpPlan p = wp_plan(env(), n, m, k, cx != nullptr);
     const int tlw = p.tlw, kt = p.kt, passes = p.passes, blocks = p.blocks, extra = p.extra, slots = p.slots;
     int stc = ensure_partial(sizeof(double) * (size_t)passes * blocks * slots * 256);
     if (stc) return stc;
@@ -4431,12 +4302,10 @@ struct HipEngine : dla::Engine {
     GramArgs a{self ? u : x, u, d_partial, (long long)n, self ? k : m, k, passes, 0, lc.phase, lc.want, 0, wp, uw, cx};
     dim3 grid(blocks, passes);
     {
-      char kn[64];
-      std::snprintf(kn, sizeof kn, "gram_lds_kernel<%d, %d, 1, %d, %d, 0, 0, %d>", tlw, kt, p.R, self ? 1 : 0, cx ? 2 : 1);
       // reference-schedule flops: the Gram matrix (2 n k^2), X^T U (2 n m k), and the triangular update the sweep applies on the fly
       // (n k^2) -- or, for the projection sweep, the update U -= X (X^T U) (2 n m k) with the pending factor (n k^2)
       Scope s(this, cx ? DLA_OP_GEMM : DLA_OP_GRAM, 8.0 * (double)n * (double)(m + k + (uw ? k : 0)),
-              2.0 * (double)n * (m + k) * k + ((wp || cx) ? 1.0 * (double)n * k * k : 0.0) + (cx ? 2.0 * (double)n * m * k : 0.0), kn);
+              2.0 * (double)n * (m + k) * k + ((wp || cx) ? 1.0 * (double)n * k * k : 0.0) + (cx ? 2.0 * (double)n * m * k : 0.0), p.name());
       int r_ = DLA_ERR_RUNTIME;
 #define GWP(T, K, RR) if (tlw == T && kt == K && p.R == RR) r_ = launch_gram_wp<T, K, RR>(a, grid, self); else
       GWP(1, 1, 32) GWP(2, 1, 32) GWP(3, 1, 16) GWP(4, 1, 16) GWP(5, 1, 16) GWP(6, 1, 16) GWP(7, 1, 16) GWP(8, 1, 16) GWP(10, 1, 16) GWP(12, 1, 16)
@@ -4471,7 +4340,6 @@ struct HipEngine : dla::Engine {
 
   // ---- the caller's pending blocks on the device (dla_basis_sync): D, upper triangular, column-major with leading dimension
   // DMAT_LD -- what the exact projection of ortho_tail16 multiplies with.  Columns arrive in order, block by block.
-  static const int DMAT_LD = T16_ZS_ROWS;
   DeviceBuffer<double> d_dmat;
   // the same on the host, column by column (column j: rows 0 .. j) -- what the host-driven loop multiplies with (basis_dd).  The host
   // copy has no width limit: a basis that outgrows the device copy (DMAT_LD columns) goes on with blocks finished in memory by the
@@ -4575,45 +4443,21 @@ struct HipEngine : dla::Engine {
       err = "ortho_chain: dla_expand_project mode 5 needs the caller's pending blocks (dla_basis_sync after every block of the basis)";
       return (int)DLA_ERR_ARG;
     };
-    if (knobs.host_loop() || policy.chain_off) return not_handled();                // A/B / the caller's request: host-driven loop
-    if (hook || local_only || k <= 0 || k > 48) return not_handled();     // hook reductions need the host between sweeps
+    // which schedule, if any: chain_choice (hip_plans.h) reads these facts and the policy, and nothing else
     const bool vsx = m > 0;
-    if (vsx && !(u == x + (size_t)n * m && can_combo(m, k))) return not_handled();
-    if (!vsx && fused_lds(k, k) > lds_limit) return DLA_OK;
-    // k x k steps on the matrix cores (ortho_tail16) for one-tile blocks; with them, on the 16-byte path and while X^T U fits one
-    // pass of the storing sweep (12 tiles), the pending-factor schedule (fold = 1); otherwise the sweep-per-update one (fold = 2)
-    const bool vec2 = even_rows(n) && (((uintptr_t)u | (uintptr_t)x | (uintptr_t)bx) % 16 == 0);
-    int fold = (k <= 16 && !knobs.no_mfma_kxk()) ? 2 : 0;
-    if (fold && vsx && vec2 && m <= 192 && !knobs.no_pending_factor() && lds_limit > (size_t)128 * 1024) fold = 1;
-    // ... and with the standard inner product (bx == x: the panel the projection subtracts is the panel it measures against) the
-    // three-pass schedule: projections that measure X^T U and U^T U of what they store (Knobs::five_sweep keeps the five-sweep one)
-    // For callers that finish their blocks in memory (plain ortho_vs_x, dla_expand_project modes 0 / 1 / 4) not while expansion blocks
-    // come out of their first projection numerically rank deficient (level shifts: the benchmark operator's rank-4 coupling leaves 4
-    // new directions per 13-column block): there the written update and the storing sweep follow whatever the projection measured
-    // and the closing projection only needs its Gram matrix (measured r05, interleaved: 17.0 against 16.35 ms per benchmark solve;
-    // 138.5 against 144.3 ms on the random-guess leg, which never shifts).  A chain that reports a level shift switches the schedule
-    // off for the next 16 chains, and every solve starts with two chains of the five-sweep schedule (on the benchmark the first one
-    // shifts).  Callers that take the closing block on their small matrices (modes 3 and 5) always run it: `rebuilt`, `policy.basis_exact`.
-    // (A block that is used once and rebuilt -- LOBPCG's W, dla_expand_project mode 3: pending blocks without a bound on the Gram
-    //  matrix -- leaves nothing in a basis: the three-pass schedule always; measured r05, n = 2e6, 8 roots: 15.99 against 17.07 ms.)
-    const bool rebuilt = policy.rebuilt();
-    // (policy.basis_exact: the caller keeps its pending blocks on the device (dla_basis_sync) and every projection of this chain is exact
-    //  against the FINISHED basis -- a loose stored basis costs later chains nothing, so the schedule that ends soonest always)
-    if (policy.basis_exact && vsx && (fold == 0 || dmat_cols != m || (dmat_nontrivial && m > DMAT_LD))) return not_handled();
-    const bool x3 = fold == 1 && bx == x && !knobs.five_sweep() && (x3_cooldown <= 0 || knobs.three_pass_always() || rebuilt || policy.basis_exact);
-    // wider blocks (LDS-loop tail): X^T U and U^T U in ONE sweep when [X | U] fits one pass of the Gram kernel (the plain
-    // product with the contiguous panel [X | U] on the left: U follows X, bx == x) and the leading ortho_cd takes one step
-    const int ktw = (k + 15) / 16;
-    const bool wide_gramx = fold == 0 && vsx && vec2 && bx == x && !knobs.no_wide_gramx() && ktw >= 2 && ktw <= 3 &&
-                            (m + k + 15) / 16 <= (ktw == 2 ? 8 : 7) && lds_limit > (size_t)128 * 1024;
-    // ([X | U] in TWO passes of that sweep -- the 18-column block behind 125 basis columns of the cfg 4 shape would then take
-    //  `6 4 2 8 4 5` instead of `1 3 4 2 2 3 4 5` -- measured r06: 32.23-32.27 against 32.24-32.38 ms per solve, no gain; not built in)
-    // ... and inside the loop the triangular update is stored together with X^T U and U^T U of what it stores (OP_XW, the sweep the
-    // one-tile schedule closes with) while X^T U fits one pass beside the block's tiles: 5 sweeps per call instead of 6
-    // (two-tile blocks: measured r04 at n = 1e7, m = 64, k = 32: 1777 us against 937 + 1010 for the two sweeps it replaces; the
-    //  three-tile sweep does 108 MFMAs per 16 rows with one wave per SIMD and runs at 3.9 TB/s -- 2960 us against 1212 + 1682: it
-    //  stays off unless Knobs::wide_xw_three_tiles asks for it)
-    const bool wide_xw = wide_gramx && (ktw == 2 || knobs.wide_xw_three_tiles()) && (m + 15) / 16 <= wp_max_tlw(ktw) && (m + k) * k <= XUG_DOUBLES && !knobs.no_wide_xw();
+    ChainIn in{};
+    in.m = m; in.k = k;
+    in.vec2 = even_rows(n) && (((uintptr_t)u | (uintptr_t)x | (uintptr_t)bx) % 16 == 0);
+    in.bx_is_x = bx == x;
+    in.combo_ok = vsx && u == x + (size_t)n * m && can_combo(m, k);
+    in.host_between = hook || local_only;
+    in.x3_cooldown = x3_cooldown; in.dmat_cols = dmat_cols; in.dmat_nontrivial = dmat_nontrivial;
+    in.fused_lds_kk = k > 0 ? fused_lds(k, k) : 0;
+    const ChainChoice choice = chain_choice(env(), policy, in);
+    if (choice.take == ChainChoice::host_loop) return not_handled();
+    if (choice.take == ChainChoice::nothing) return DLA_OK;
+    const int fold = choice.fold;
+    const bool x3 = choice.x3, wide_gramx = choice.wide_gramx, wide_xw = choice.wide_xw;
     int stc = ensure_chain_buffers();
     if (stc) return stc;
     // First chain of a shape: walk every launch path it may take WITHOUT launching (workspaces grow now, not half way; a
@@ -4670,32 +4514,9 @@ struct HipEngine : dla::Engine {
     shape.k = k; shape.m = m; shape.fold = fold; shape.vsx = vsx; shape.wide_gramx = wide_gramx; shape.wide_xw = wide_xw; shape.dropf = dropf; shape.x3 = x3;
     std::vector<int> plan = plan_of_shape[shape];
     if (plan.empty()) plan = plan_of_kind[shape.kind()];   // most recent call of this kind and width
-    if (plan.empty()) {
-      // the schedule measured on the reference: cd x2, [projection, cd x2], [projection, cd x1]
-      if (x3) plan = {OP_GRAMX, OP_COMBOX, OP_COMBOX, OP_CLOSE, OP_FINAL};
-      else if (fold == 1) plan = {OP_GRAMX, OP_COMBO, OP_TRMMG, OP_XW, OP_COMBO, OP_FINAL};
-      else if (wide_xw) plan = {OP_GRAMX, OP_COMBO, OP_XW, OP_COMBO, OP_FINAL};
-      else if (wide_gramx) plan = {OP_GRAMX, OP_COMBO, OP_TRMMG, OP_XU, OP_COMBO, OP_FINAL};
-      else if (vsx) plan = {OP_GRAM_UU, OP_TRMMG, OP_XU, OP_COMBO, OP_TRMMG, OP_XU, OP_COMBO, OP_FINAL};
-      else plan = {OP_GRAM_UU, OP_TRMMG, OP_FINAL};
-    }
-    // every plan ends with OP_FINAL: its tail is a launch of its own that always runs and reports where the machine stands (a
-    // fused tail is skipped together with a sweep whose turn it is not).  With drop_final the machine never asks for the sweep
-    // itself, and the executed list a plan is remembered from does not contain it
-    // Callers that take the closing block on their small matrices without a bound on the factor (dla_expand_project modes 3 and 5: the
-    // machine ends with the block pending and never asks for OP_CLOSE / OP_FINAL) get plans without them: the fused step of the
-    // last planned sweep reports where the machine stands whether or not it was that sweep's turn (gram_reduce_kernel<true>).  Two
-    // predicated-off sweeps and two k x k launches less per chain: 19 us (r05 trace: 0.15 ms per benchmark solve, 0.23 per LOBPCG solve).
-    const bool fused_steps = p2p.on ? (!knobs.exchange_own_launch() && (m + k) * k <= P2P_MAX_DOUBLES) : (nranks <= 1 && !comm);
-    const bool lean = vsx && rebuilt && m + k <= PEND_ROWS && fused_steps && !knobs.keep_closing_launches();
-    if (lean) {
-      while (plan.size() > 1 && (plan.back() == OP_FINAL || plan.back() == OP_CLOSE)) plan.pop_back();
-    } else
-    if (plan.empty() || plan.back() != OP_FINAL) plan.push_back(OP_FINAL);
-    // (three-pass schedule: whether a chain ends with its closing block pending or with the closing sweep depends on the last bits
-    //  of a Gram matrix -- a plan remembered from a chain that ended pending keeps the sweep in place: an empty launch when it
-    //  is not needed, against a host round trip and a repeated operator call when it is)
-    if (x3 && !lean && std::find(plan.begin(), plan.end(), (int)OP_CLOSE) == plan.end()) plan.insert(plan.end() - 1, (int)OP_CLOSE);
+    if (plan.empty()) plan = default_plan(shape);
+    const bool lean = chain_lean(env(), policy, m, k, Transport{p2p.on, nranks, comm != nullptr});
+    plan = close_plan(plan, lean, x3);
     // (The plain projection sweep never stands in for the measuring one, although it is faster -- 4 m / 16 fewer MFMAs per 16 rows,
     //  5.7 against 5.0-5.4 TB/s -- and its measurement is thrown away whenever the block it stored needs a level shift: which
     //  sweep ran would decide what the step behind it knows, the chain's path would depend on the plan, the plan on the chains
@@ -4824,8 +4645,7 @@ struct HipEngine : dla::Engine {
           default: err = "ortho_chain: device state machine in an unexpected phase"; return DLA_ERR_RUNTIME;
         }
       }
-      if (run.lean && sres.phase != OP_CLOSE && sres.phase != OP_FINAL)
-        while (plan.size() > 1 && (plan.back() == OP_FINAL || plan.back() == OP_CLOSE)) plan.pop_back();
+      if (run.lean && sres.phase != OP_CLOSE && sres.phase != OP_FINAL) trim_closing(plan);
       h_ost->status = -1;
     }
     if (sres.status == OST_RUNNING) { err = "ortho_chain: no progress"; return DLA_ERR_RUNTIME; }
@@ -4915,30 +4735,13 @@ struct HipEngine : dla::Engine {
   }
 
   // ---- Gram
-  // Pass shape of one Gram launch (gram_plan): the kernel's name for the statistics and the instance that is launched are both
-  // read from it.
-  struct GramPlan {
-    int tlw, kt;           // tile shape of one pass: KT U-tiles x TLW X-tiles
-    int px, passes;        // passes over X, passes in all
-    int rows;              // rows of a staged tile (LDS-staged kernel): 16 or 32
-    bool lds;              // the LDS-staged kernel (gram_lds_kernel), else the direct-load one (gram_kernel)
-    bool self;             // ... a block against itself in one pass: staged once (gram_lds_kernel SELF)
-    int qt;                // ... quarter tiles of its last U tile (gram_lds_kernel QT)
-    bool low_single;       // ... the lower triangle of two different panels in a single pass (gram_lds_kernel LOW)
-    bool lower;            // only the tile pairs on or below the block diagonal are formed
-    int blocks_per_pass;
-    bool vec2;             // the 16-byte path
-  };
-  // whether a pass of tlw + kt tiles can be staged 32 rows at a time at all, and the rows per step of the direct-load kernel
-  static constexpr bool gram_can32(int tlw, int kt) { return sizeof(double) * 4 * 16 * (tlw + kt) * 34 <= 150 * 1024 && tlw + kt <= 7; }
-  static constexpr int gram_rs(int tlw, int kt) { return (tlw * kt >= 6) ? 2 : 4; }
   template <int TLW, int KT, int R>
   int launch_gram_lds(const GramArgs& a, dim3 grid, const GramPlan& p)
   {
 #define GLK(SELF_, Q)                                                                                          \
     do {                                                                                                      \
       auto kfn = gram_lds_kernel<TLW, KT, 1, R, SELF_, Q>;                                                    \
-      const size_t lds = sizeof(double) * 4 * 16 * (SELF_ ? TLW : TLW + KT) * (R + 2);                        \
+      const size_t lds = gram_lds_bytes(TLW, KT, R, SELF_, false);                                            \
       if (!raise_lds((const void*)kfn, lds)) return DLA_ERR_RUNTIME;                                          \
       DLA_LAUNCH(kfn, grid, dim3(256), lds, st, a);                                                   \
       return DLA_OK;                                                                                          \
@@ -4955,24 +4758,14 @@ struct HipEngine : dla::Engine {
   }
   // single-pass lower triangle (gram_lds_kernel LOW): T x T tiles, 16-row wave tiles
   template <int T>
-  int launch_gram_low(const GramArgs& a, dim3 grid)
+  int launch_gram_low(const GramArgs& a, dim3 grid, const GramPlan& p)
   {
     auto kfn = gram_lds_kernel<T, T, 1, 16, 0, 0, 1>;
-    const size_t lds = sizeof(double) * 4 * 16 * (2 * T) * 18;
+    const size_t lds = gram_lds_bytes(T, T, 16, false, true);
     if (!raise_lds((const void*)kfn, lds)) return DLA_ERR_RUNTIME;
     DLA_LAUNCH(kfn, grid, dim3(256), lds, st, a);
     return DLA_OK;
   }
-  // tile rows of the LDS-staged kernel: 32 for narrow passes (few loads per tile otherwise) and for 3-tile U blocks,
-  // 16 elsewhere (A/B at n = 2e6, tools/tune_gram.py)
-  int lds_rows(int tlw, int kt) const
-  {
-    const int r = ((tlw <= 2 || kt == 3) && tlw + kt <= 7) ? 32 : 16;   // (more than 7 tiles of 32 rows: too many staging registers)
-    return (r == 32 && sizeof(double) * 4 * 16 * (size_t)(tlw + kt) * 34 > lds_limit) ? 16 : r;
-  }
-  // (a pass narrower than one tile, e.g. the 4-column W^T x of the benchmark operator, would stage mostly
-  // duplicates of its last column: it keeps the direct-load kernel)
-  bool use_lds_gram(bool vec2, int l, int kt) const { return vec2 && kt <= 3 && l > 8 && !knobs.direct_gram(); }
   template <int TLW, int KT>
   int launch_gram(const GramArgs& a, dim3 grid, const GramPlan& p)
   {
@@ -5000,68 +4793,10 @@ struct HipEngine : dla::Engine {
   {
     return with_lds_retry([&]() { return gram_dev_once(n, l, x, k, u, cls, lower, out); });
   }
-  // same: x == u; aligned: both panels start on 16 bytes
-  GramPlan gram_plan(int n, int l, int k, bool same, bool aligned, bool lower) const
-  {
-    const int tx = (l + 15) / 16, tu = (k + 15) / 16;
-    // tile shape of one pass: KT U-tiles x TLW X-tiles, at most 12 accumulators
-    const bool vec2 = even_rows(n) && aligned;
-    // (even n: at most 3 U tiles per pass, so that the LDS-staged kernel serves every pass -- the direct-load kernel a
-    // fourth tile would need measured 2.6 TB/s on the 111-column S^T A S of LOBPCG at n_max = 37)
-    int kt = std::min(tu, (vec2 && l > 8 && !knobs.direct_gram()) ? 3 : 4);
-    const int passes_u = (tu + kt - 1) / kt;
-    kt = (tu + passes_u - 1) / passes_u;
-    const bool ldsk = use_lds_gram(vec2, l, kt);
-    // widest pass: the direct-load kernel loses its register prefetch stage beyond 8 tiles (measured); the LDS-staged
-    // one keeps all of X's columns of up to 12 tiles in one pass, so U is read once for L <= 192
-    static const int maxtl[5] = {0, 8, 6, 4, 3};
-    // (the LDS-staged kernel runs at one wave per SIMD for wide passes anyway; its accumulators spill over into the
-    // AGPRs, up to 21 tiles: fewer passes = fewer re-reads of U, and `lower` passes skip the tiles above the diagonal)
-    static const int maxtl_lds[4] = {0, 12, 8, 7};
-    int mt = ldsk ? maxtl_lds[kt] : maxtl[kt];
-    if (knobs.narrow_gram_passes()) mt = (ldsk && kt == 1) ? 12 : maxtl[kt];       // A/B: the narrower passes
-    // the LDS-staged kernel stages 16 (tlw + kt) columns of 18 doubles per wave: keep the pass inside lds_limit
-    if (ldsk) mt = std::max(1, std::min(mt, (int)(lds_limit / (sizeof(double) * 4 * 16 * 18)) - kt));
-    const int passes_x = (tx + mt - 1) / mt;
-    int tlw = (tx + passes_x - 1) / passes_x;
-    // round up to an instantiated width
-    static const int avail1[] = {1, 2, 3, 4, 6, 8, 12};
-    static const int avail1l[] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12};
-    if (kt == 1 && ldsk) { for (int v : avail1l) if (v >= tlw) { tlw = v; break; } }
-    else if (kt == 1) { for (int v : avail1) if (v >= tlw) { tlw = v; break; } }
-    else if (kt == 2 && ldsk) { tlw = std::min(tlw, 8); }                       // 1..8 all instantiated
-    else if (kt == 3 && ldsk) { tlw = std::min(tlw, 7); }                       // 1..7
-    else if (kt == 2) { tlw = tlw <= 1 ? 1 : tlw <= 2 ? 2 : tlw <= 4 ? 4 : 6; }
-    else if (kt == 3) { tlw = tlw <= 1 ? 1 : tlw <= 2 ? 2 : 4; }
-    else { tlw = tlw <= 1 ? 1 : tlw <= 2 ? 2 : 3; }
-    int px = (tx + tlw - 1) / tlw;
-    int passes = px * passes_u;
-    // a block against itself in a single pass: one staged image serves both operands, and only the tile pairs on or
-    // below the diagonal are formed (the host side mirrors, see gram())
-    const bool self = ldsk && same && l == k && passes == 1 && tlw == kt;
-    if (self) lower = true;
-    int qt = (ldsk && passes_u == 1 && kt >= 2) ? quarter_tiles(k, vec2) : 0;
-    // the lower triangle of X^T U for two different panels of 49..112 columns (S^T A S of LOBPCG at n_max = 21 / 37):
-    // one pass over both panels with the 10..28 tile pairs on or below the diagonal (gram_lds_kernel LOW)
-    const bool low_single = lower && ldsk && !self && l == k && tx >= 4 && tx <= 7 && passes > 1 && !knobs.no_low_single() &&
-                            sizeof(double) * 4 * 16 * (size_t)(2 * tx) * 18 <= lds_limit;
-    if (low_single) { kt = tlw = tx; px = 1; passes = 1; qt = 0; }
-    const int ch = vec2 ? 32 : 16;
-    long long nchunks = ((long long)n + ch - 1) / ch;
-    long long want = (nchunks + 4 * 4 - 1) / (4 * 4);   // >= 4 chunks per wave
-    // one 4-wave block per CU and pass (256 on MI355X) measured best: 512 is -1.5 %, 384 / 128 are -15 / -30 %
-    int blocks_per_pass = (int)std::max(1LL, std::min((long long)ncu, want));
-    // the narrowest sweeps (a block against itself, or fewer than 8 columns against a block) have too few loads in
-    // flight with one block per CU: two per CU measured +11 % / +19 % there and -1..-3 % everywhere else
-    if (tlw * kt == 1 && ((same && l == k) || l <= 8)) blocks_per_pass = (int)std::max(1LL, std::min(2LL * ncu, want));
-    if (knobs.gram_blocks_override()) blocks_per_pass = (int)std::max(1LL, std::min((long long)knobs.gram_blocks_override(), want));
-    const int rows = (ldsk && !low_single && gram_can32(tlw, kt) && lds_rows(tlw, kt) == 32) ? 32 : 16;
-    return GramPlan{tlw, kt, px, passes, rows, ldsk, self, qt, low_single, lower, blocks_per_pass, vec2};
-  }
   int gram_dev_once(int n, int l, const double* x, int k, const double* u, int cls, bool lower, StepOut& out)
   {
     out = StepOut{};
-    const GramPlan p = gram_plan(n, l, k, x == u, ((uintptr_t)x | (uintptr_t)u) % 16 == 0, lower);
+    const GramPlan p = gram_plan(env(), n, l, k, x == u, peers_even && ((uintptr_t)x | (uintptr_t)u) % 16 == 0, lower);
     const int tlw = p.tlw, kt = p.kt, passes = p.passes, blocks_per_pass = p.blocks_per_pass;
     out.lower_only = p.self;
     const int slots = tlw * kt;
@@ -5073,14 +4808,10 @@ struct HipEngine : dla::Engine {
     dim3 grid(blocks_per_pass, passes);
     {
       const bool same = (x == u) && (l == k);
-      char kn[64];
-      if (p.lds)
-        std::snprintf(kn, sizeof kn, "gram_lds_kernel<%d, %d, 1, %d, %d, %d, %d, 0>", tlw, kt, p.rows, p.self ? 1 : 0, p.qt, p.low_single ? 1 : 0);
-      else std::snprintf(kn, sizeof kn, "gram_kernel<%d, %d, %d, %d, 0, -1>", tlw, kt, p.vec2 ? 2 : 1, gram_rs(tlw, kt));
-      Scope s(this, cls, 8.0 * (double)n * (same ? (double)k : (double)(l + k)), 2.0 * (double)n * l * k, kn);
+      Scope s(this, cls, 8.0 * (double)n * (same ? (double)k : (double)(l + k)), 2.0 * (double)n * l * k, p.name());
       if (p.low_single) {
-        int r_ = tlw == 4 ? launch_gram_low<4>(a, grid) : tlw == 5 ? launch_gram_low<5>(a, grid) : tlw == 6 ? launch_gram_low<6>(a, grid)
-                                                                                                          : launch_gram_low<7>(a, grid);
+        int r_ = tlw == 4 ? launch_gram_low<4>(a, grid, p) : tlw == 5 ? launch_gram_low<5>(a, grid, p) : tlw == 6 ? launch_gram_low<6>(a, grid, p)
+                                                                                                                   : launch_gram_low<7>(a, grid, p);
         if (r_) return r_;
       } else
 #define GL(T, K) if (tlw == T && kt == K) { int r_ = launch_gram<T, K>(a, grid, p); if (r_) return r_; } else
@@ -5285,13 +5016,6 @@ struct HipEngine : dla::Engine {
     return stage_commit(slot, sizeof(double) * cnt, d_cpk);
   }
 
-  // quarter tiles of the last 16-column tile (0: none): blocks of 17..24 and 33..40 columns on the 16-byte path
-  int quarter_tiles(int k, bool vec2) const
-  {
-    const int kt = (k + 15) / 16, rem = k - 16 * (kt - 1);
-    return (vec2 && kt >= 2 && kt <= 3 && rem <= 8 && !knobs.no_quarter_tiles()) ? (rem + 3) / 4 : 0;
-  }
-
   template <int KT, typename ARGS>
   int launch_gemm_gram(const ARGS& a, int blocks, size_t lds, bool vec2, int mode, int qt, int rtp)
   {
@@ -5348,34 +5072,15 @@ struct HipEngine : dla::Engine {
                  int* fused_blocks = nullptr, const double* cpk_dev = nullptr)
   {
     const bool fuse = fused_blocks != nullptr;
-    const int kt = (k + 15) / 16;
-    const int l4 = ((l + 3) / 4) * 4;
-    const bool inl = (cpk_dev == nullptr && kt == 1 && l4 <= 16);
+    const bool vec2 = even_rows(n) && (((uintptr_t)x | (uintptr_t)z) % 16 == 0);
+    const GemmPlan p = gemm_plan(env(), n, l, k, mode, fuse, cpk_dev != nullptr, vec2);
+    const int kt = p.kt, l4 = p.l4, qt = p.qt, rtp = p.rtp, pipe = p.pipe, blocks = p.blocks;
+    const bool inl = p.inl;
+    const size_t lds = p.lds;
     if (!inl && cpk_dev == nullptr) {
       int stc = upload_packed(c_host, ldc, l0, l, k, kt, l4);
       if (stc) return stc;
     }
-    const bool vec2 = even_rows(n) && (((uintptr_t)x | (uintptr_t)z) % 16 == 0);
-    // the variant, decided once: quarter tiles, pipeline depth and (below) row groups go into the booked name AND pick the instance
-    const int ab_depth = fuse ? -1 : knobs.gemm_pipe_depth();
-    int qt = ab_depth >= 0 ? 0 : quarter_tiles(k, vec2);
-    // (the plain two-tile update is the one sweep that measured slower with quarter tiles, -9 % at L = 63, k = 21:
-    // tools/quarter_tile_ab.py)
-    if (!fuse && mode == 1 && kt == 2) qt = 0;
-    // LDS copy of C (a quarter-tile kernel keeps 8 columns of the last tile); the fused variant adds 4 wave tiles of
-    // 16 rows x (16 kt + 9) doubles, and needs >= 8 KiB for the final reduction
-    const size_t lds_c = sizeof(double) * (size_t)l4 * (qt > 0 ? 16 * (kt - 1) + 8 : 16 * kt);
-    const size_t lds = fuse ? std::max(lds_c + sizeof(double) * 4 * 16 * (16 * kt + 9), (size_t)8192) : lds_c;
-    int per_cu = lds > 80 * 1024 ? 1 : lds > 40 * 1024 ? 2 : 4;
-    if (knobs.gemm_blocks_per_cu()) per_cu = (int)std::max((size_t)1, std::min((size_t)knobs.gemm_blocks_per_cu(), (size_t)(156 * 1024) / std::max(lds, (size_t)4096)));
-    // row groups per wave tile (gemm_kernel RTP): the fused three-tile sweeps need > 256 registers with two groups, one
-    // wave per SIMD; with one group two fit -- when the LDS leaves room for a second block per CU (measured +9..20 %,
-    // and -26 % when it does not)
-    const int rtp = (fuse && kt == 3 && vec2 && per_cu >= 2 && !knobs.fused3_two_row_groups()) ? 1 : 2;
-    const int pipe = (ab_depth >= 0 && vec2 && kt >= 2 && (mode == 0 || mode == 1)) ? ab_depth : (fuse && kt >= 3) ? 3 : kt >= 2 ? 2 : 0;
-    const int wt = (vec2 ? 32 : 16) * rtp;
-    const long long ntiles = ((long long)n + wt - 1) / wt;
-    const int blocks = (int)std::max(1LL, std::min((long long)ncu * per_cu, (ntiles + 3) / 4));
     if (fuse) {
       int stp = ensure_partial(sizeof(double) * (size_t)blocks * kt * kt * 256);
       if (stp) return stp;
@@ -5385,10 +5090,7 @@ struct HipEngine : dla::Engine {
     a.x = x + (size_t)l0 * n; a.cpk = cpk_dev ? cpk_dev : d_cpk; a.z = z; a.n = n; a.l = l; a.l4 = l4; a.k = k; a.gpart = d_partial;
     a.phase = lc.phase; a.want = lc.want; a.xpf = knobs.no_next_tile_prefetch() ? 0 : 1;
     const double rd = (mode == 0) ? 8.0 * n * (double)l : (mode == 2 ? 8.0 * n * (double)k : 8.0 * n * (double)(l + k));
-    char kn[96];
-    std::snprintf(kn, sizeof kn, "gemm_kernel<%d, %d, %d, %s, %s, %d, %d, 9, %d, %d>", kt, vec2 ? 2 : 1, mode, inl ? "GemmArgsInl" : "GemmArgs",
-                  fuse ? "true" : "false", mode == 2 ? 0 : 1, pipe, qt, rtp);
-    Scope s(this, cls, rd + 8.0 * n * (double)k, (cls == DLA_OP_TRMM ? 1.0 : 2.0) * (double)n * l * k, kn);
+    Scope s(this, cls, rd + 8.0 * n * (double)k, (cls == DLA_OP_TRMM ? 1.0 : 2.0) * (double)n * l * k, p.name());
     if (inl) {
       GemmArgsInl ai{};
       ai.x = a.x; ai.z = z; ai.n = n; ai.l = l; ai.l4 = l4; ai.k = k; ai.gpart = d_partial;
@@ -5487,12 +5189,6 @@ struct HipEngine : dla::Engine {
     return with_lds_retry([&]() { return ritz_residual_once(n, l, m, v, av, y_host, ldy, eig, n_res, skip, evec, r, avy, out); });
   }
   bool ritz_p_declined = false;
-  // dynamic LDS a Ritz sweep may ask for: the four- and five-tile kernels keep their norm accumulators in 48.6 KiB of static LDS
-  static size_t ritz_lds_cap(int kt) { return (size_t)(kt >= 4 ? 100 : 150) * 1024; }
-  // static LDS of ritz_kernel: theta / active, and for four and five tiles the per-lane norm accumulators (s_nrm, 48 KiB)
-  static size_t ritz_static_lds(int kt) { return (size_t)1024 + (kt >= 4 ? sizeof(double) * 4 * 48 * 16 * 2 : 0); }
-  // dynamic LDS a Ritz sweep of kt column tiles may ask for: its own cap, and the engine's limit minus what the kernel holds statically
-  size_t ritz_dyn_limit(int kt) const { const size_t st_ = ritz_static_lds(kt); return std::min(ritz_lds_cap(kt), lds_limit > st_ ? lds_limit - st_ : (size_t)0); }
   // the sweep with k2 extra products (Engine::ritz_residual_p): one pass when [Y | C2] fits five column tiles and the LDS copy,
   // otherwise the Ritz step and two panel products
   int ritz_residual_p(int n, int l, int m, const double* v, const double* av, const double* y_host, int ldy,
@@ -5503,7 +5199,7 @@ struct HipEngine : dla::Engine {
     const uintptr_t al = (uintptr_t)v | (uintptr_t)av | (uintptr_t)evec | (uintptr_t)r | (uintptr_t)avy | (uintptr_t)p2 | (uintptr_t)ap2;
     const int ktot = (m + k2 + 15) / 16, l4 = ((l + 3) / 4) * 4;
     const bool one_pass = even_rows(n) && (al % 16 == 0) && m <= 48 && ktot <= 5 && !knobs.ritz_p_separate() &&
-                          sizeof(double) * (size_t)l4 * 16 * ktot <= ritz_dyn_limit(ktot);
+                          sizeof(double) * (size_t)l4 * 16 * ktot <= ritz_dyn_limit(env(), ktot);
     if (!one_pass) return Engine::ritz_residual_p(n, l, m, v, av, y_host, ldy, eig, n_res, skip, evec, r, avy, out, k2, c2_host, ldc2, p2, ap2);
     // [Y | C2] as one coefficient block
     std::vector<double> yc((size_t)l * (m + k2));
@@ -5532,18 +5228,13 @@ struct HipEngine : dla::Engine {
       }
       return DLA_OK;
     }
-    const int kt = (m + k2 + 15) / 16;      // column tiles of [Y | C2]
-    const int l4 = ((l + 3) / 4) * 4;
-    uintptr_t al = (uintptr_t)v | (uintptr_t)av | (uintptr_t)evec | (uintptr_t)r | (uintptr_t)avy | (uintptr_t)p2 | (uintptr_t)ap2;   // (null pointers are aligned)
-    const bool vec2 = even_rows(n) && (al % 16 == 0);
-    // the variant, decided once: quarter tiles, pipeline depth and extra products go into the booked name AND pick the instance
-    const int ab_depth = knobs.ritz_pipe_depth();
-    const int qt = ab_depth >= 0 ? 0 : quarter_tiles(m + k2, vec2);
-    const bool xp = k2 > 0;
-    const int pipe = (ab_depth >= 0 && !xp && vec2 && kt >= 2) ? ab_depth : kt >= 3 ? 3 : kt >= 2 ? 2 : 0;
-    // LDS copy of Y (a quarter-tile kernel keeps 8 columns of the last tile)
-    const size_t lds_c = sizeof(double) * (size_t)l4 * (qt > 0 ? 16 * (kt - 1) + 8 : 16 * kt);
-    if (lds_c > ritz_dyn_limit(kt)) {
+    const uintptr_t al = (uintptr_t)v | (uintptr_t)av | (uintptr_t)evec | (uintptr_t)r | (uintptr_t)avy | (uintptr_t)p2 | (uintptr_t)ap2;   // (null pointers are aligned)
+    const int nslots = (local_only || nranks < 1) ? 1 : nranks;
+    const RitzPlan p = ritz_plan(env(), n, l, m, k2, even_rows(n) && (al % 16 == 0), nslots);
+    const int kt = p.kt, l4 = p.l4, qt = p.qt, pipe = p.pipe, blocks = p.blocks, ncol = p.ncol;
+    const bool vec2 = p.vec2, xp = p.xp;
+    const size_t lds = p.lds;
+    if (!p.fits) {
       if (k2 > 0) { ritz_p_declined = true; err = "ritz sweep with extra products: coefficient block beyond the LDS limit"; return DLA_ERR_RUNTIME; }
       // Y does not fit the LDS copy in one piece (wide block times deep subspace, e.g. 37 columns x 20 blocks): form the
       // two products with the chunked panel GEMM, then run the fused sweep on the n x m results with Y = identity
@@ -5578,26 +5269,16 @@ struct HipEngine : dla::Engine {
       if (skip && skip[j]) continue;
       a.theta[j] = eig[j]; a.active[j] = 1; ++nact;
     }
-    const int rg = vec2 ? 32 : 16;
-    const long long ntiles = ((long long)n + rg - 1) / rg;
-    const size_t lds = std::max(lds_c, sizeof(double) * 4 * 16 * kt * 2);
-    const int per_cu = lds > 80 * 1024 ? 1 : lds > 40 * 1024 ? 2 : 4;
-    const int blocks = (int)std::max(1LL, std::min((long long)ncu * per_cu * knobs.ritz_grid_factor(), (ntiles + 7) / 8));
     stc = ensure_partial(sizeof(double) * (size_t)blocks * 16 * kt * 2);
     if (stc) return stc;
-    const int nslots = (local_only || nranks < 1) ? 1 : nranks;
-    stc = ensure_small(sizeof(double) * (size_t)16 * kt * (1 + nslots));
+    stc = ensure_small(sizeof(double) * p.small_doubles());
     if (stc) return stc;
     a.v = v; a.av = av; a.cpk = d_cpk; a.evec = evec; a.r = r; a.avy = avy; a.red = d_partial;
     a.n = n; a.l = l; a.l4 = l4; a.k = m;
-    const int ncol = 16 * kt;
     {
-      char kn[64];
-      // (the name rocprofv3 prints; the last argument is ritz_kernel's reserved one)
-      std::snprintf(kn, sizeof kn, "ritz_kernel<%d, %d, 3, %d, %d, %s, 0>", kt, vec2 ? 2 : 1, pipe, qt, xp ? "true" : "false");
       // (flops: the two Ritz products and, with extra columns, the two panel products they replace)
       Scope s(this, DLA_OP_RITZ, 8.0 * n * (2.0 * l + ((avy ? 2.0 : 1.0) + (evec ? 1.0 : 0.0)) * m + 2.0 * k2),
-              4.0 * (double)n * l * (m + k2) + 5.0 * (double)n * nact, kn);
+              4.0 * (double)n * l * (m + k2) + 5.0 * (double)n * nact, p.name());
 #define RZ(K) do { auto kfn = K; if (!raise_lds((const void*)kfn, lds, ritz_static_lds(kt))) return DLA_ERR_RUNTIME; DLA_LAUNCH(kfn, dim3(blocks), dim3(256), lds, st, a); } while (0)
       if (xp) {
         // [Y | C2]: vec2 guaranteed by the caller (ritz_residual_p)
@@ -5638,7 +5319,7 @@ struct HipEngine : dla::Engine {
     }
     HIPCHK(hipGetLastError());
     // sums and all ranks' maxima in one collective (reference :1730-1731 are two reductions)
-    stc = sum_to_host(ncol * (1 + nslots), 0);
+    stc = sum_to_host((int)p.small_doubles(), 0);
     if (stc) return stc;
     for (int j = 0; j < n_res; ++j) {
       double mx = 0.0;
@@ -5653,9 +5334,13 @@ struct HipEngine : dla::Engine {
                      const double* y2_host, int ldy2, const double* eig, int n_res, const int* skip,
                      double* e, double* r, double* t_work, double* junk, double* out) override
   {
-    const int kt = (m + 15) / 16, l4 = ((l + 3) / 4) * 4;
-    const size_t lds_c = sizeof(double) * (size_t)l4 * 16 * 2 * kt;
-    if (m > 48 || m <= 0 || l <= 0 || lds_c > std::min((size_t)150 * 1024, lds_limit > 2048 ? lds_limit - 2048 : 0) || knobs.no_ritz2())
+    const uintptr_t al = (uintptr_t)v | (uintptr_t)av | (uintptr_t)e | (uintptr_t)r;
+    const int nslots = (local_only || nranks < 1) ? 1 : nranks;
+    const Ritz2Plan p = ritz2_plan(env(), n, l, m, even_rows(n) && (al % 16 == 0), nslots);
+    const int kt = p.kt, l4 = p.l4, blocks = p.blocks, ncol = p.ncol;
+    const bool vec2 = p.vec2;
+    const size_t lds = p.lds;
+    if (!p.fits)
       return Engine::ritz_residual2(n, l, m, v, av, y1_host, ldy1, y2_host, ldy2, eig, n_res, skip, e, r, t_work, junk, out);
     // [Y1 | Y2] packed as 2 kt tiles: Y2 starts at tile kt
     std::vector<double> yy((size_t)l * (16 * kt + m), 0.0);
@@ -5671,26 +5356,15 @@ struct HipEngine : dla::Engine {
       if (skip && skip[j]) continue;
       a.theta[j] = eig[j]; a.active[j] = 1; ++nact;
     }
-    const uintptr_t al = (uintptr_t)v | (uintptr_t)av | (uintptr_t)e | (uintptr_t)r;
-    const bool vec2 = even_rows(n) && (al % 16 == 0);
-    const int rg = vec2 ? 32 : 16;
-    const long long ntiles = ((long long)n + rg - 1) / rg;
-    const size_t lds = std::max(lds_c, sizeof(double) * 4 * 16 * kt * 2);
-    const int per_cu = lds > 80 * 1024 ? 1 : lds > 40 * 1024 ? 2 : 4;
-    const int blocks = (int)std::max(1LL, std::min((long long)ncu * per_cu, (ntiles + 7) / 8));
     stc = ensure_partial(sizeof(double) * (size_t)blocks * 16 * kt * 2);
     if (stc) return stc;
-    const int nslots = (local_only || nranks < 1) ? 1 : nranks;
-    stc = ensure_small(sizeof(double) * (size_t)16 * kt * (1 + nslots));
+    stc = ensure_small(sizeof(double) * p.small_doubles());
     if (stc) return stc;
     a.v = v; a.av = av; a.cpk = d_cpk; a.evec = e; a.r = r; a.avy = nullptr; a.red = d_partial;
     a.n = n; a.l = l; a.l4 = l4; a.k = m;
-    const int ncol = 16 * kt;
     {
-      char kn[64];
-      std::snprintf(kn, sizeof kn, "ritz2_kernel<%d, %d>", kt, vec2 ? 2 : 1);
       // (flops: the two products and the residual correction, as the reference's dgemm pair + daxpy / dnrm2 loop)
-      Scope s(this, DLA_OP_RITZ, 8.0 * n * (2.0 * l + 2.0 * m), 4.0 * (double)n * l * m + 5.0 * (double)n * nact, kn);
+      Scope s(this, DLA_OP_RITZ, 8.0 * n * (2.0 * l + 2.0 * m), 4.0 * (double)n * l * m + 5.0 * (double)n * nact, p.name());
 #define RZ2(K) do { auto kfn = K; if (!raise_lds((const void*)kfn, lds, 1024)) return DLA_ERR_RUNTIME; DLA_LAUNCH(kfn, dim3(blocks), dim3(256), lds, st, a); } while (0)
       if (vec2) { if (kt == 1) RZ2((ritz2_kernel<1, 2>)); else if (kt == 2) RZ2((ritz2_kernel<2, 2>)); else RZ2((ritz2_kernel<3, 2>)); }
       else { if (kt == 1) RZ2((ritz2_kernel<1, 1>)); else if (kt == 2) RZ2((ritz2_kernel<2, 1>)); else RZ2((ritz2_kernel<3, 1>)); }
@@ -5702,7 +5376,7 @@ struct HipEngine : dla::Engine {
                          h_small.dev(), nslots, local_only ? 0 : rank);
     }
     HIPCHK(hipGetLastError());
-    stc = sum_to_host(ncol * (1 + nslots), 0);
+    stc = sum_to_host((int)p.small_doubles(), 0);
     if (stc) return stc;
     for (int j = 0; j < n_res; ++j) {
       double mx = 0.0;
@@ -5802,6 +5476,16 @@ struct HipEngine : dla::Engine {
     }
   };
   SparseOp op_a, op_b;
+  // A on a row shard (spmm_setup_sharded; A only): whether it is, and the exchange with the neighbouring ranks.  The one place that
+  // answers "is A sharded" -- the sharded set-up and the metric's refuse each other by it.
+  struct RowShard {
+    bool on = false;
+    int halo = 0;                      // rows exchanged with each neighbour
+    DeviceBuffer<double> d_halo;
+    std::vector<double> h_halo;        // host mirror for the hook transport
+    // A is whole again; the exchange buffers only grow, like the operator's blocks (upload_ell)
+    void drop() { on = false; halo = 0; }
+  } shard;
   // replace a matrix on the device (both ELLPACK set-up routines end here); the caller has bound the device.  The arrays only grow:
   // a smaller matrix after a larger one keeps the larger blocks (the kernels go by n / w); the same holds for synth_setup
   int upload_ell(SparseOp& op, const std::vector<int>& col, const std::vector<double>& val, const std::vector<double>& diag)
@@ -5847,7 +5531,7 @@ struct HipEngine : dla::Engine {
   int spmm_setup_csr(int n, const long long* rowptr, const int* colind, const double* values) override
   {
     { const int stc = setup_ell(op_a, n, rowptr, colind, values); if (stc) return stc; }
-    ell_sharded = false; ell_halo = 0;
+    shard.drop();
     return DLA_OK;
   }
   // ---- ... as sliced ELLPACK with a CSR tail (dla::sell_build).  The slices and the tail share the ELLPACK blocks -- columns and
@@ -5888,7 +5572,7 @@ struct HipEngine : dla::Engine {
   int spmm_setup_csr_fmt(int n, const long long* rowptr, const int* colind, const double* values, int format) override
   {
     { const int stc = setup_fmt(op_a, n, rowptr, colind, values, format); if (stc) return stc; }
-    ell_sharded = false; ell_halo = 0;
+    shard.drop();
     return DLA_OK;
   }
   int op_info(const SparseOp& op, struct dla_spmm_info* out) const
@@ -5940,10 +5624,6 @@ struct HipEngine : dla::Engine {
     return DLA_OK;
   }
   // ---- ... on a row shard (banded matrices: the columns of a shard reach at most `halo` rows into its neighbours); A only
-  int ell_halo = 0;                  // rows exchanged with each neighbour; 0 = the operator is not sharded
-  bool ell_sharded = false;
-  DeviceBuffer<double> d_halo;
-  std::vector<double> h_halo;        // host mirror for the hook transport
   // all-reduce of a few host values through the engine's small-product transport (setup-time agreement between the ranks)
   bool has_transport() const override { return hook != nullptr || comm != nullptr || p2p.on; }
   int allreduce_host(double* v, int count, int op) override
@@ -6006,40 +5686,40 @@ struct HipEngine : dla::Engine {
     bind();
     stc = upload_ell(op_a, e.col, e.val, e.diag);
     if (stc) return stc;
-    op_a.n = n; op_a.w = e.w; ell_halo = (int)halo; ell_sharded = true;
+    op_a.n = n; op_a.w = e.w; shard.halo = (int)halo; shard.on = true;
     op_a.fmt = DLA_SPMM_ELL; op_a.nnz = rowptr[n] - rowptr[0];
     return DLA_OK;
   }
   int spmm_matvec_sharded(int n, int m, const double* x, double* ax)
   {
-    const int nr = std::max(1, nranks), H = ell_halo;
+    const int nr = std::max(1, nranks), H = shard.halo;
     const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
     // columns per exchange: a mailbox slot of the peer-to-peer transport holds P2P_MAX_DOUBLES
     int mc = m;
     if (H > 0 && nr > 1) mc = std::max(1, std::min(m, P2P_MAX_DOUBLES / (nr * 2 * H)));
     const size_t need = (size_t)std::max(1, nr * 2 * mc * std::max(1, H));
-    if (need > d_halo.capacity()) {
+    if (need > shard.d_halo.capacity()) {
       HIPCHK(hipStreamSynchronize(st));
-      HIPCHK(d_halo.reserve(need));
+      HIPCHK(shard.d_halo.reserve(need));
       // (on the engine's stream: hipMemset runs on the null stream, which this non-blocking stream does not wait for -- the
       //  zeros would land in the middle of the first exchange)
-      HIPCHK(hipMemsetAsync(d_halo, 0, sizeof(double) * need, st));
-      h_halo.assign(need, 0.0);
+      HIPCHK(hipMemsetAsync(shard.d_halo, 0, sizeof(double) * need, st));
+      shard.h_halo.assign(need, 0.0);
     }
     for (int c0 = 0; c0 < m; c0 += mc) {
       const int mcur = std::min(mc, m - c0);
       const double* xc = x + (size_t)c0 * n;
       if (H > 0 && nr > 1) {
         const int total = nr * 2 * mcur * H;
-        DLA_LAUNCH(halo_pack_kernel, dim3(std::max(1, std::min(64, (total + 255) / 256))), dim3(256), 0, st, n, mcur, H, nr, rank, xc, d_halo);
+        DLA_LAUNCH(halo_pack_kernel, dim3(std::max(1, std::min(64, (total + 255) / 256))), dim3(256), 0, st, n, mcur, H, nr, rank, xc, shard.d_halo);
         HIPCHK(hipGetLastError());
         StepOut halo_out;
-        const int stc = allreduce_dev(d_halo, total, 0, h_halo.data(), halo_out);
+        const int stc = allreduce_dev(shard.d_halo, total, 0, shard.h_halo.data(), halo_out);
         if (stc) return stc;
       }
       // (the first / last rank never index their missing neighbour: any valid address serves)
-      const double* prev = d_halo + (size_t)((rank > 0 ? (rank - 1) * 2 + 1 : 0) * mcur) * H;
-      const double* next = d_halo + (size_t)((rank + 1 < nr ? (rank + 1) * 2 : 0) * mcur) * H;
+      const double* prev = shard.d_halo + (size_t)((rank > 0 ? (rank - 1) * 2 + 1 : 0) * mcur) * H;
+      const double* next = shard.d_halo + (size_t)((rank + 1 < nr ? (rank + 1) * 2 : 0) * mcur) * H;
 #define ELLH(W) DLA_LAUNCH((ell_spmm_halo_kernel<W>), dim3(blocks), dim3(256), 0, st, n, mcur, op_a.w, H, (const int*)op_a.col, (const double*)op_a.val, xc, prev, next, ax + (size_t)c0 * n)
       if (op_a.w <= 4) ELLH(4); else if (op_a.w <= 8) ELLH(8); else if (op_a.w <= 16) ELLH(16); else if (op_a.w <= 32) ELLH(32); else ELLH(0);
 #undef ELLH
@@ -6050,7 +5730,7 @@ struct HipEngine : dla::Engine {
   int spmm_matvec(int n, int m, const double* x, double* ax) override
   {
     if (n != op_a.n || !op_a.col) { err = "spmm_matvec: n differs from setup"; return DLA_ERR_ARG; }
-    if (ell_sharded) {
+    if (shard.on) {
       Scope s(this, DLA_OP_MATVEC, 12.0 * (double)op_a.w * n + 16.0 * (double)n * m, 2.0 * (double)op_a.w * n * m);
       return spmm_matvec_sharded(n, m, x, ax);
     }
@@ -6068,7 +5748,7 @@ struct HipEngine : dla::Engine {
   // ---- ... and a second matrix beside it: the metric B of A x = lambda B x (bvec of reference diaglib.f90:1855), single rank
   int spmm_setup_metric(int n, const long long* rowptr, const int* colind, const double* values, int format) override
   {
-    if (ell_sharded) { err = "spmm_setup_metric_csr: the operator of this context is row-sharded, and a row-sharded metric is not supported"; return DLA_ERR_ARG; }
+    if (shard.on) { err = "spmm_setup_metric_csr: the operator of this context is row-sharded, and a row-sharded metric is not supported"; return DLA_ERR_ARG; }
     const int stc = setup_fmt(op_b, n, rowptr, colind, values, format);
     if (stc == DLA_ERR_ARG) err = "spmm_setup_metric_csr: " + err;
     return stc;

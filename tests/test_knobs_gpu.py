@@ -1,4 +1,4 @@
-"""The engine's experiment knobs (DLA_OPT_TUNE0 + i, HipEngine::Knobs) still reach the decisions that the tests, bench.py and the
+"""The engine's experiment knobs (DLA_OPT_TUNE0 + i, Knobs in hip_plans.h) still reach the decisions that the tests, bench.py and the
 A/B tools take from them -- read off the kernels that ran (launch counts of ctx.kernel_stats()), not off the results, which the
 suites of the kernels themselves check.
 
@@ -208,3 +208,110 @@ def test_default_names_are_the_benchmarks_keys(blocks):
     assert "ritz_kernel<1, 2, 3, 0, 0, false, 0>" in names, names                    # the benchmark's dominant kernel
     assert any(re.match(r"gemm_kernel<\d+, \d+, 2,", nm) for nm in names), names      # bench.py's pattern for the triangular update
     assert any(nm.startswith("gram") for nm in names) and any(nm.startswith("ritz") for nm in names)
+
+
+FAMILIES = r"(gram_lds_kernel|gram_kernel|gemm_kernel|ritz_kernel|ritz2_kernel)<"
+
+
+def test_solver_names_are_the_planners_names(blocks):
+    """every knob 0.  The statistics carry names and no shapes, so names are tied to shapes in two steps.
+
+    1. One Davidson and one LOBPCG solve (8 roots, n_max = 13): every name of the Gram, product, Ritz and tail families that they book
+       is one of bench.py's keys (the two-coefficient Ritz sweep, which bench.py does not key, by its own pattern), and every Gram,
+       product and Ritz sweep carries a name the CPU planners (tests/plans_driver.cpp) print at n = 4096 for a shape such a solve can
+       issue -- blocks shrink as roots converge, so every basis width up to 20 blocks counts.  This step alone would pass
+       a wrong argument that spells another name of the family.
+    2. The sweeps those solves are made of, called one at a time at known shapes in the same context, with the statistics reset
+       before each: the names booked must EQUAL what the driver prints for the request line of exactly that (n, l, k, ...) -- mode,
+       fuse, packed_on_device, same and lower as the call site passes them.  For the chain, whose sweeps depend on the schedule that
+       is taken, the names must lie within the driver's for that chain's m and k, and its measuring sweep and fused projection must
+       be among them."""
+    from test_plans import env_line, run_plans
+    n_targ, n_max, max_dav = 8, 13, 20
+    x, u = blocks
+    wide = np.asfortranarray(np.hstack([x, x, x])[:, :117])
+    ones = lambda l, k: np.asfortranarray(np.ones((l, k)))
+    tri = np.asfortranarray(np.triu(np.ones((13, 13))) + np.eye(13))
+
+    def ritz(c, l, m):
+        v, av = c.panel(np.asfortranarray(wide[:, :l])), c.panel(np.asfortranarray(wide[:, 3:l + 3]))
+        c.ritz_residual(v, av, np.asfortranarray(np.eye(l)[:, :m]), np.arange(float(m)), m, np.zeros(m, np.int32), c.panel(N, m), c.panel(N, m))
+
+    def combo(c):
+        p = c.panel(np.asfortranarray(np.hstack([x[:, :26], u[:, :13]])))
+        c.combo_gram(p.col(0, 26), np.asfortranarray(np.eye(39)[:, 26:]), p.col(26, 13))
+
+    def same13(c):
+        p = c.panel(np.asfortranarray(u[:, :13]))
+        c.gram(p, p)
+
+    # (request line of the plans driver, the call of exactly that shape)
+    known = [
+        (f"gram {N} 13 13 1 1 0", same13),
+        (f"gram {N} 26 13 0 1 0", lambda c: c.gram(c.panel(np.asfortranarray(x[:, :26])), c.panel(np.asfortranarray(u[:, :13])))),
+        (f"gram {N} 117 13 0 1 0", lambda c: c.gram(c.panel(wide), c.panel(np.asfortranarray(u[:, :13])))),
+        (f"gram {N} 42 21 0 1 0", lambda c: c.gram(c.panel(np.asfortranarray(x)), c.panel(np.asfortranarray(u)))),
+        (f"gram {N} 4 13 0 1 0", lambda c: c.gram(c.panel(np.asfortranarray(x[:, :4])), c.panel(np.asfortranarray(u[:, :13])))),
+        (f"gram {N} 39 39 0 1 1", lambda c: c.gram_lower(c.panel(np.asfortranarray(x[:, :39])), c.panel(np.asfortranarray(wide[:, 50:89])))),
+        (f"gemm {N} 13 13 0 0 0 1", lambda c: c.panel_gemm(c.panel(np.asfortranarray(x[:, :13])), ones(13, 13), c.panel(N, 13))),
+        (f"gemm {N} 26 13 0 0 0 1", lambda c: c.panel_gemm(c.panel(np.asfortranarray(x[:, :26])), ones(26, 13), c.panel(N, 13))),
+        (f"gemm {N} 42 21 0 0 0 1", lambda c: c.panel_gemm(c.panel(np.asfortranarray(x)), ones(42, 21), c.panel(N, 21))),
+        (f"gemm {N} 42 21 1 1 0 1", lambda c: c.update_gram(c.panel(np.asfortranarray(x)), np.asfortranarray(x.T @ u), c.panel(np.asfortranarray(u)))),
+        (f"gemm {N} 39 13 0 1 0 1", combo),
+        (f"gemm {N} 13 13 2 0 0 1", lambda c: c.trmm_linvt(c.panel(np.asfortranarray(u[:, :13])), np.asfortranarray(tri.T))),
+        (f"gemm {N} 13 13 2 1 0 1", lambda c: c.trmm_gram(c.panel(np.asfortranarray(u[:, :13])), tri)),
+        (f"ritz {N} 26 8 0 1 1", lambda c: ritz(c, 26, 8)),
+        (f"ritz {N} 104 13 0 1 1", lambda c: ritz(c, 104, 13)),
+        (f"ritz {N} 42 21 0 1 1", lambda c: ritz(c, 42, 21)),
+    ]
+
+    def swept(names):
+        return sorted(nm for nm in names if re.match(FAMILIES, nm))
+
+    def work(c):
+        c.set_option(capi.OPT_CALLBACKS_ON_DEVICE, 1)
+        c.synth_setup(N, 0, N)
+        mv, pc = capi.fn_address("dla_synth_matvec"), capi.fn_address("dla_synth_precnd")
+        guess = np.zeros((N, n_max), order="F")
+        guess[np.arange(n_max), np.arange(n_max)] = 1.0
+        c.reset_stats()
+        c.davidson_driver(N, n_targ, n_max, 100, 1e-9, max_dav, 0.0, mv, pc, c.panel(guess))      # (whether they converge is the solver suites' matter)
+        c.lobpcg_driver(N, n_targ, n_max, 60, 1e-9, 0.0, mv, pc, c.panel(guess))
+        solves = launched(c)
+        one_by_one = []
+        for _, call in known:
+            c.reset_stats()
+            call(c)
+            one_by_one.append(swept(launched(c)))
+        return solves, one_by_one, swept(first_chain(c, blocks, 26, 13)[0])
+    names, one_by_one, chain = fresh_context(work)
+    print(sorted(names))
+    # ---- 1. the solves
+    keys = BENCH_KEYS + [r"ritz2_kernel<[123], [12]>"]
+    for nm in names:            # (a solve also books the operator's and the element-wise kernels, which belong to no family)
+        if re.match(r"(gram|gemm|ritz|ortho)", nm):
+            assert any(re.fullmatch(pat, nm) for pat in keys), nm
+    basis = range(0, max_dav * n_max + 1)
+    lines = [env_line()]              # (no name depends on the CU count: it only sets block counts)
+    lines += [f"gram {N} {l} {k} {same} 1 {low}" for l in basis[1:] for k in range(1, 49) for same in (0, 1) for low in (0, 1) if l == k or not (same or low)]
+    lines += [f"gram {N} {l} {l} {same} 1 {low}" for l in basis[49:] for same in (0, 1) for low in (0, 1)]
+    lines += [f"wp {N} {m} {k} {pr}" for m in basis for k in range(1, n_max + 1) for pr in (0, 1) if m or not pr]
+    lines += [f"gemm {N} {l} {k} {mode} {fuse} {pk} 1" for l in basis[1:] for k in range(1, 49) for mode in range(4) for fuse in (0, 1) for pk in (0, 1)
+              if not (fuse and mode == 3)]
+    lines += [f"ritz {N} {l} {m} {k2} 1 1" for l in basis[1:] for m in range(1, n_max + 1) for k2 in range(0, 2 * n_max + 1)]
+    lines += [f"ritz2 {N} {l} {m} 1 1" for l in basis[1:] for m in range(1, n_max + 1)]
+    table = {name for _, name in run_plans(lines)[0]}
+    ran = swept(names)
+    assert any(nm.startswith("gram") for nm in ran) and any(nm.startswith("gemm") for nm in ran) and any(nm.startswith("ritz") for nm in ran)
+    assert not [nm for nm in ran if nm not in table], [nm for nm in ran if nm not in table]
+    # ---- 2. one sweep at a time, one to one
+    expect = [name for _, name in run_plans([env_line()] + [req for req, _ in known])[0]]
+    for (req, _), want, got in zip(known, expect, one_by_one):
+        print(req, "->", want, got)
+        assert got == [want], (req, want, got)
+    m, k = 26, 13
+    lines = [env_line(), f"wp {N} {m} {k} 0", f"gemm {N} {m + k} {k} 0 1 1 1", f"wp {N} {m} {k} 1"]
+    lines += [f"gemm {N} {l} {k} {mode} {fuse} 1 1" for l in (k, m + k) for mode in (0, 2) for fuse in (0, 1)]
+    of_chain = [name for _, name in run_plans(lines)[0]]
+    print("chain", chain)
+    assert set(chain) <= set(of_chain) and of_chain[0] in chain and of_chain[1] in chain, (chain, of_chain)

@@ -73,7 +73,8 @@ SPMM_FORMATS = {"ell": SPMM_ELL, "sell": SPMM_SELL, "auto": SPMM_AUTO}
 class SpmmInfo(C.Structure):
     _fields_ = [("format", C.c_int), ("n", C.c_int), ("slice_rows", C.c_int), ("sort_window", C.c_int), ("long_row_threshold", C.c_int),
                 ("nnz", C.c_longlong), ("stored", C.c_longlong), ("slices", C.c_int), ("long_rows", C.c_int),
-                ("long_entries", C.c_longlong), ("device_bytes", C.c_longlong)]
+                ("long_entries", C.c_longlong), ("device_bytes", C.c_longlong), ("long_segment_entries", C.c_int), ("long_segments", C.c_int),
+                ("multi_segments", C.c_int)]
 
 
 class DlaError(RuntimeError):
@@ -536,7 +537,7 @@ class Context:
 
     def spmm_info(self) -> dict:
         """what the operator set up last occupies: format ("ell" / "sell"), n, nnz, stored, slices, long_rows, long_entries,
-        device_bytes and the layout constants (include/diaglib_amd.h, dla_spmm_info)"""
+        long_segments, multi_segments, device_bytes and the layout constants (include/diaglib_amd.h, dla_spmm_info)"""
         o = SpmmInfo()
         self._chk(self.lib.dla_spmm_info(self.h, C.byref(o)))
         d = {name: int(getattr(o, name)) for name, _ in SpmmInfo._fields_}

@@ -419,10 +419,16 @@ inline void sharded_ell_build(int n, long long row0, const long long* rowptr, co
 // slice, so entry (q, lane) of slice s lives at slice_ptr[s] + q * SELL_C + lane and both matrix streams stay coalesced as in
 // the plain ELLPACK kernel.  A row with more than SELL_LONG_ROW entries would widen its whole slice: it counts as an empty row
 // in the slices (sorted and padded as one) and is kept whole, in the caller's order, in the CSR tail.
+// A tail row is multiplied in segments of SELL_LONG_SEG entries, one wavefront each (the contract: include/diaglib_amd.h): segment s
+// of a row with entries [p0, p1) covers [p0 + s SEG, min(p1, p0 + (s + 1) SEG)).  A row of one segment is stored by the wavefront
+// that sums it; a longer row owns one slot per segment in a workspace of partial sums, added in segment order by one thread.
 // The three constants are unmeasured starting values: SELL_C is the wavefront width, the other two are guesses.
 constexpr int SELL_C = 64;
 constexpr int SELL_SIGMA = 4096;
 constexpr int SELL_LONG_ROW = 256;
+// (a starting value as well; a multiple of the wavefront width, so that every lane of a full segment takes the same number of entries)
+constexpr int SELL_LONG_SEG = 4096;
+static_assert(SELL_LONG_SEG > 0 && SELL_LONG_SEG % 64 == 0, "a segment of a tail row is a positive multiple of 64 entries");
 // AUTO keeps plain ELLPACK while its padding w n / nnz stays at or below this (a guess as well)
 constexpr double SPMM_AUTO_ELL_PADDING = 1.25;
 
@@ -437,6 +443,13 @@ struct SellLayout {
   std::vector<long long> long_ptr;
   std::vector<int> long_col;
   std::vector<double> long_val;
+  // the segments of the tail rows, in row order: [long_segments + 1] first entries in long_col / long_val, the tail row (an index
+  // into long_row) each belongs to, and its slot in the workspace of partial sums (-1: the only segment of its row, stored straight)
+  int long_segments = 0, multi_segments = 0;   // all segments; segments of rows with more than one = slots of the workspace
+  std::vector<long long> seg_ptr;
+  std::vector<int> seg_row, seg_part;
+  // the rows of more than one segment: the row, and [multi rows + 1] offsets of its slots (part_ptr[j + 1] - part_ptr[j] segments)
+  std::vector<int> multi_row, part_ptr;
 };
 // what every single-rank setup checks, in the words of spmm_setup_csr; w = widest row, nnz = entries
 inline int spmm_csr_check(int n, const long long* rowptr, const int* colind, const double* values, int format, int* w, long long* nnz,
@@ -490,6 +503,18 @@ inline void sell_build(int n, const long long* rowptr, const int* colind, const 
     s.long_ptr.push_back((long long)s.long_col.size());
   }
   s.long_entries = (long long)s.long_col.size();
+  s.seg_ptr.assign(1, 0); s.seg_row.clear(); s.seg_part.clear(); s.multi_row.clear(); s.part_ptr.assign(1, 0);
+  for (size_t r = 0; r < s.long_row.size(); ++r) {
+    const long long p0 = s.long_ptr[r], p1 = s.long_ptr[r + 1];
+    const int segs = (int)((p1 - p0 + SELL_LONG_SEG - 1) / SELL_LONG_SEG);
+    for (int g = 0; g < segs; ++g) {
+      s.seg_row.push_back((int)r);
+      s.seg_part.push_back(segs > 1 ? s.part_ptr.back() + g : -1);
+      s.seg_ptr.push_back(std::min(p1, p0 + (long long)(g + 1) * SELL_LONG_SEG));
+    }
+    if (segs > 1) { s.multi_row.push_back(s.long_row[r]); s.part_ptr.push_back(s.part_ptr.back() + segs); }
+  }
+  s.long_segments = (int)s.seg_row.size(); s.multi_segments = s.part_ptr.back();
   for (int sl = 0; sl < s.slices; ++sl) {
     const long long base = s.slice_ptr[sl];
     const int width = (int)((s.slice_ptr[sl + 1] - base) / SELL_C);

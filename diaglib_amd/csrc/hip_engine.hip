@@ -1554,7 +1554,7 @@ __global__ void synth_precnd_kernel(int n, int m, double fac, const double* __re
 // x[col][c] are the irregular part; for the banded / stencil matrices of the test suite neighbouring rows gather
 // neighbouring entries.  HBM-bound: 12 w n bytes of matrix + 16 n m bytes of vectors per call (+ gather overfetch).
 // Padding to the WIDEST row is what makes this format unusable for a matrix with a few long rows: dla_spmm_setup_csr_fmt stores
-// those as sliced ELLPACK with a CSR tail (sell_spmm_kernel / csr_long_rows_kernel below) behind the same two callbacks.
+// those as sliced ELLPACK with a CSR tail (sell_spmm_kernel / csr_long_segments_kernel below) behind the same two callbacks.
 template <int W>
 __global__ __launch_bounds__(256) void ell_spmm_kernel(int n, int m, int w, const int* __restrict__ col,
                                                        const double* __restrict__ val, const double* __restrict__ x,
@@ -1594,7 +1594,7 @@ __global__ __launch_bounds__(256) void ell_spmm_kernel(int n, int m, int w, cons
 // accumulators -- MC independent gathers in flight per entry -- and the chunk loop sits INSIDE the slice loop, where the
 // slice's second read comes from cache (64 x width x 12 bytes: 196 KiB at the widest, usually a few KiB).  Per (row, column)
 // the entries are accumulated in stored order, one fused multiply-add each, from 0.0: the bits of ell_spmm_kernel.
-// perm[slot] is the row a slot computes; negative: the row lives in the CSR tail (csr_long_rows_kernel writes it); slots past n
+// perm[slot] is the row a slot computes; negative: the row lives in the CSR tail (csr_long_segments_kernel / long_rows_combine_kernel write it); slots past n
 // in the last slice and tail slots store nothing, so every element of ax has exactly one writer.
 template <int MC>
 __global__ __launch_bounds__(256) void sell_spmm_kernel(int n, int m, int slices, const long long* __restrict__ slice_ptr,
@@ -1639,19 +1639,23 @@ __global__ __launch_bounds__(256) void sell_spmm_kernel(int n, int m, int slices
   }
 }
 
-// The CSR tail of the sliced format: one wavefront per long row, lanes striding over the row's entries (coalesced), per-lane
-// partial sums for MC columns, then a butterfly over the 64 lanes -- a fixed shape, so the result does not depend on timing --
-// and lane 0 stores.  No atomics: a row has one writer.
+// The CSR tail of the sliced format (the contract: include/diaglib_amd.h): one wavefront per SEGMENT of a long row (at most
+// dla::SELL_LONG_SEG entries, dla::sell_build), lanes striding over the segment's entries (coalesced), per-lane partial sums for MC
+// columns, then a butterfly over the 64 lanes -- a fixed shape, so the result does not depend on timing -- and lane 0 stores: to
+// ax where the segment is its row's only one (seg_part < 0), else to the segment's slot of the workspace, part[slot * m + column],
+// which long_rows_combine_kernel adds up.  No atomics: every element of ax and of the workspace has one writer.
 template <int MC>
-__global__ __launch_bounds__(256) void csr_long_rows_kernel(int n, int m, int nlong, const int* __restrict__ long_row,
-                                                            const long long* __restrict__ long_ptr, const int* __restrict__ col,
-                                                            const double* __restrict__ val, const double* __restrict__ x,
-                                                            double* __restrict__ ax)
+__global__ __launch_bounds__(256) void csr_long_segments_kernel(int n, int m, int nseg, const long long* __restrict__ seg_ptr,
+                                                                const int* __restrict__ seg_row, const int* __restrict__ seg_part,
+                                                                const int* __restrict__ long_row, const int* __restrict__ col,
+                                                                const double* __restrict__ val, const double* __restrict__ x,
+                                                                double* __restrict__ ax, double* __restrict__ part)
 {
   const int lane = threadIdx.x & 63;
-  for (int r = blockIdx.x * 4 + (threadIdx.x >> 6); r < nlong; r += gridDim.x * 4) {
-    const int row = long_row[r];
-    const long long p0 = long_ptr[r], p1 = long_ptr[r + 1];
+  for (int g = blockIdx.x * 4 + (threadIdx.x >> 6); g < nseg; g += gridDim.x * 4) {
+    const int row = long_row[seg_row[g]];
+    const int slot = seg_part[g];
+    const long long p0 = seg_ptr[g], p1 = seg_ptr[g + 1];
     for (int c0 = 0; c0 < m; c0 += MC) {
       const double* xc = x + (size_t)c0 * n;
       const int mc = min(MC, m - c0);
@@ -1669,9 +1673,29 @@ __global__ __launch_bounds__(256) void csr_long_rows_kernel(int n, int m, int nl
         for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
       if (lane == 0) {
 #pragma unroll
-        for (int k = 0; k < MC; ++k) if (k < mc) ax[(size_t)(c0 + k) * n + row] = acc[k];
+        for (int k = 0; k < MC; ++k)
+          if (k < mc) {
+            if (slot < 0) ax[(size_t)(c0 + k) * n + row] = acc[k];
+            else part[(size_t)slot * m + (c0 + k)] = acc[k];
+          }
       }
     }
+  }
+}
+
+// ... and the rows of more than one segment: one thread per (row, column) adds the row's partial sums in segment order,
+// ((part_0 + part_1) + part_2) + ..., plain double additions, and stores to ax.  Runs behind csr_long_segments_kernel on the stream.
+__global__ __launch_bounds__(256) void long_rows_combine_kernel(int n, int m, int nmulti, const int* __restrict__ multi_row,
+                                                                const int* __restrict__ part_ptr, const double* __restrict__ part,
+                                                                double* __restrict__ ax)
+{
+  const long long total = (long long)nmulti * m;
+  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
+    const int j = (int)(t / m), c = (int)(t - (long long)j * m);
+    const int s0 = part_ptr[j], s1 = part_ptr[j + 1];
+    double sum = part[(size_t)s0 * m + c];
+    for (int sg = s0 + 1; sg < s1; ++sg) sum += part[(size_t)sg * m + c];
+    ax[(size_t)c * n + multi_row[j]] = sum;
   }
 }
 
@@ -5466,13 +5490,17 @@ struct HipEngine : dla::Engine {
     int fmt = -1;                      // DLA_SPMM_ELL / DLA_SPMM_SELL: what the blocks hold; -1 while nothing is stored
     long long nnz = 0, sell_stored = 0, sell_long_entries = 0;
     int sell_slices = 0, sell_long_rows = 0;
-    DeviceBuffer<long long> sell_ptr, long_ptr;
-    DeviceBuffer<int> sell_perm, long_row;
+    int sell_long_segments = 0, sell_multi_rows = 0, sell_multi_segments = 0;   // the tail's segments (dla::SellLayout)
+    DeviceBuffer<long long> sell_ptr, seg_ptr;
+    DeviceBuffer<int> sell_perm, long_row, seg_row, seg_part, multi_row, part_ptr;
+    DeviceBuffer<double> long_part;    // partial sums of the rows of more than one segment: multi_segments x m, grown by the product
     // give the device blocks back (the caller has waited for the stream)
     void drop()
     {
-      col.reset(); val.reset(); diag.reset(); sell_ptr.reset(); long_ptr.reset(); sell_perm.reset(); long_row.reset();
+      col.reset(); val.reset(); diag.reset(); sell_ptr.reset(); seg_ptr.reset(); sell_perm.reset(); long_row.reset();
+      seg_row.reset(); seg_part.reset(); multi_row.reset(); part_ptr.reset(); long_part.reset();
       n = w = 0; fmt = -1; nnz = sell_stored = sell_long_entries = 0; sell_slices = sell_long_rows = 0;
+      sell_long_segments = sell_multi_rows = sell_multi_segments = 0;
     }
   };
   SparseOp op_a, op_b;
@@ -5536,7 +5564,7 @@ struct HipEngine : dla::Engine {
   }
   // ---- ... as sliced ELLPACK with a CSR tail (dla::sell_build).  The slices and the tail share the ELLPACK blocks -- columns and
   // values of the tail follow the `stored` padded entries of the slices -- so either format replaces the other in place.
-  static constexpr int SELL_MC = 8, LONG_MC = 4;   // right-hand sides per load of a matrix entry (sell_spmm_kernel / csr_long_rows_kernel)
+  static constexpr int SELL_MC = 8, LONG_MC = 4;   // right-hand sides per load of a matrix entry (sell_spmm_kernel / csr_long_segments_kernel)
   int setup_fmt(SparseOp& op, int n, const long long* rowptr, const int* colind, const double* values, int format)
   {
     int w = 0; long long nnz = 0;
@@ -5544,7 +5572,7 @@ struct HipEngine : dla::Engine {
     if (dla::spmm_pick_format(format, w, n, nnz) == DLA_SPMM_ELL) return setup_ell(op, n, rowptr, colind, values);
     dla::SellLayout L;
     dla::sell_build(n, rowptr, colind, values, L);
-    const size_t tot = (size_t)(L.stored + L.long_entries), nl = L.long_row.size();
+    const size_t tot = (size_t)(L.stored + L.long_entries), nl = L.long_row.size(), ns = L.seg_row.size(), nm = L.multi_row.size();
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(op.col.reserve(tot));
@@ -5553,7 +5581,11 @@ struct HipEngine : dla::Engine {
     HIPCHK(op.sell_ptr.reserve(L.slice_ptr.size()));
     HIPCHK(op.sell_perm.reserve((size_t)n));
     HIPCHK(op.long_row.reserve(std::max<size_t>(1, nl)));
-    HIPCHK(op.long_ptr.reserve(nl + 1));
+    HIPCHK(op.seg_ptr.reserve(ns + 1));
+    HIPCHK(op.seg_row.reserve(std::max<size_t>(1, ns)));
+    HIPCHK(op.seg_part.reserve(std::max<size_t>(1, ns)));
+    HIPCHK(op.multi_row.reserve(std::max<size_t>(1, nm)));
+    HIPCHK(op.part_ptr.reserve(nm + 1));
     auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
     HIPCHK(up(op.col, L.col.data(), sizeof(int) * L.col.size()));
     HIPCHK(up(op.val, L.val.data(), sizeof(double) * L.val.size()));
@@ -5563,10 +5595,15 @@ struct HipEngine : dla::Engine {
     HIPCHK(up(op.sell_ptr, L.slice_ptr.data(), sizeof(long long) * L.slice_ptr.size()));
     HIPCHK(up(op.sell_perm, L.perm.data(), sizeof(int) * (size_t)n));
     HIPCHK(up(op.long_row, L.long_row.data(), sizeof(int) * nl));
-    HIPCHK(up(op.long_ptr, L.long_ptr.data(), sizeof(long long) * (nl + 1)));
+    HIPCHK(up(op.seg_ptr, L.seg_ptr.data(), sizeof(long long) * (ns + 1)));
+    HIPCHK(up(op.seg_row, L.seg_row.data(), sizeof(int) * ns));
+    HIPCHK(up(op.seg_part, L.seg_part.data(), sizeof(int) * ns));
+    HIPCHK(up(op.multi_row, L.multi_row.data(), sizeof(int) * nm));
+    HIPCHK(up(op.part_ptr, L.part_ptr.data(), sizeof(int) * (nm + 1)));
     op.n = n; op.w = 0;
     op.fmt = DLA_SPMM_SELL; op.nnz = nnz; op.sell_stored = L.stored; op.sell_long_entries = L.long_entries;
     op.sell_slices = L.slices; op.sell_long_rows = (int)nl;
+    op.sell_long_segments = L.long_segments; op.sell_multi_rows = (int)nm; op.sell_multi_segments = L.multi_segments;
     return DLA_OK;
   }
   int spmm_setup_csr_fmt(int n, const long long* rowptr, const int* colind, const double* values, int format) override
@@ -5586,7 +5623,10 @@ struct HipEngine : dla::Engine {
     if (sell) {
       out->slice_rows = dla::SELL_C; out->sort_window = dla::SELL_SIGMA; out->long_row_threshold = dla::SELL_LONG_ROW;
       out->slices = op.sell_slices; out->long_rows = op.sell_long_rows; out->long_entries = op.sell_long_entries;
-      out->device_bytes += 12 * op.sell_long_entries + 4 * (long long)op.n + 8 * ((long long)op.sell_slices + 1) + 12 * (long long)op.sell_long_rows + 8;
+      out->long_segment_entries = dla::SELL_LONG_SEG; out->long_segments = op.sell_long_segments; out->multi_segments = op.sell_multi_segments;
+      // (the tail's tables: long_row; seg_ptr, seg_row, seg_part; multi_row, part_ptr)
+      out->device_bytes += 12 * op.sell_long_entries + 4 * (long long)op.n + 8 * ((long long)op.sell_slices + 1) + 4 * (long long)op.sell_long_rows +
+                           16 * (long long)op.sell_long_segments + 8 + 8 * (long long)op.sell_multi_rows + 4;
     }
     return DLA_OK;
   }
@@ -5595,25 +5635,39 @@ struct HipEngine : dla::Engine {
     if (op_a.fmt < 0 || !out) { err = "spmm_info: no operator has been set up"; return DLA_ERR_ARG; }
     return op_info(op_a, out);
   }
-  int op_matvec_sell(const SparseOp& op, int n, int m, const double* x, double* ax)
+  // slices kernel, segments kernel, combine kernel; p: the tail's launch shapes and workspace (long_rows_plan)
+  int op_matvec_sell(SparseOp& op, const LongRowsPlan& p, int n, int m, const double* x, double* ax)
   {
     const int cap = ncu * 8;
+    if (p.part_doubles > op.long_part.capacity()) {
+      HIPCHK(hipStreamSynchronize(st));       // (queued products may still use the old block)
+      HIPCHK(op.long_part.reserve(p.part_doubles));
+    }
     DLA_LAUNCH((sell_spmm_kernel<SELL_MC>), dim3(std::max(1, std::min(cap, (op.sell_slices + 3) / 4))), dim3(256), 0, st, n, m, op.sell_slices,
                (const long long*)op.sell_ptr, (const int*)op.sell_perm, (const int*)op.col, (const double*)op.val, x, ax);
     HIPCHK(hipGetLastError());
-    if (op.sell_long_rows > 0) {
-      DLA_LAUNCH((csr_long_rows_kernel<LONG_MC>), dim3(std::max(1, std::min(cap, (op.sell_long_rows + 3) / 4))), dim3(256), 0, st, n, m, op.sell_long_rows,
-                 (const int*)op.long_row, (const long long*)op.long_ptr, (const int*)op.col + op.sell_stored, (const double*)op.val + op.sell_stored, x, ax);
+    if (op.sell_long_segments > 0) {
+      DLA_LAUNCH((csr_long_segments_kernel<LONG_MC>), dim3(p.seg_blocks), dim3(256), 0, st, n, m, op.sell_long_segments, (const long long*)op.seg_ptr,
+                 (const int*)op.seg_row, (const int*)op.seg_part, (const int*)op.long_row, (const int*)op.col + op.sell_stored,
+                 (const double*)op.val + op.sell_stored, x, ax, (double*)op.long_part);
+      HIPCHK(hipGetLastError());
+    }
+    if (p.combine_blocks > 0) {
+      DLA_LAUNCH(long_rows_combine_kernel, dim3(p.combine_blocks), dim3(256), 0, st, n, m, op.sell_multi_rows, (const int*)op.multi_row,
+                 (const int*)op.part_ptr, (const double*)op.long_part, ax);
       HIPCHK(hipGetLastError());
     }
     return DLA_OK;
   }
   // ax = (the matrix of op) x on one rank, in the format op holds (n == op.n has been checked)
-  int op_matvec(const SparseOp& op, int n, int m, const double* x, double* ax)
+  int op_matvec(SparseOp& op, int n, int m, const double* x, double* ax)
   {
     if (op.fmt == DLA_SPMM_SELL) {
-      Scope s(this, DLA_OP_MATVEC, 12.0 * (double)(op.sell_stored + op.sell_long_entries) + 4.0 * n + 16.0 * (double)n * m, 2.0 * (double)op.nnz * m);
-      return op_matvec_sell(op, n, m, x, ax);
+      const LongRowsPlan p = long_rows_plan(env(), op.sell_long_segments, op.sell_multi_rows, op.sell_multi_segments, m, LONG_MC);
+      // (the partial sums are written once and read once)
+      Scope s(this, DLA_OP_MATVEC, 12.0 * (double)(op.sell_stored + op.sell_long_entries) + 4.0 * n + 16.0 * (double)n * m + 16.0 * (double)p.part_doubles,
+              2.0 * (double)op.nnz * m, op.sell_long_segments > 0 ? p.name() : std::string());
+      return op_matvec_sell(op, p, n, m, x, ax);
     }
     Scope s(this, DLA_OP_MATVEC, 12.0 * (double)op.w * n + 16.0 * (double)n * m, 2.0 * (double)op.w * n * m);
     const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));

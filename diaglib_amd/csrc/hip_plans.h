@@ -390,6 +390,29 @@ inline Ritz2Plan ritz2_plan(const PlanEnv& env, int n, int l, int m, bool vec2, 
   return p;
 }
 
+// ---- the CSR tail of the sliced sparse operator (csr_long_segments_kernel, long_rows_combine_kernel)
+// One wavefront per segment of a tail row, four per block, grid-stride beyond 8 blocks per CU (the cap of the other operator
+// kernels); rows of more than one segment leave one partial sum per segment and right-hand side in a workspace, which one thread per
+// (row, right-hand side) adds in segment order.  A function of the layout's counts (dla::SellLayout) and the block width only.
+struct LongRowsPlan {
+  int mc;                // right-hand sides per load of a matrix entry
+  int seg_blocks;        // blocks of 256 threads of the segments kernel (>= 1)
+  int combine_blocks;    // ... of the combine kernel; 0: no row has more than one segment, nothing is launched
+  size_t part_doubles;   // the workspace: multi_segments x m
+  // (the product of an operator with a tail is booked under the name of the kernel that walks it)
+  std::string name() const { return plan_name("csr_long_segments_kernel<%d>", mc); }
+};
+inline LongRowsPlan long_rows_plan(const PlanEnv& env, int long_segments, int multi_rows, int multi_segments, int m, int mc)
+{
+  const long long cap = (long long)env.ncu * 8;
+  LongRowsPlan p{};
+  p.mc = mc;
+  p.seg_blocks = (int)std::max(1LL, std::min(cap, ((long long)long_segments + 3) / 4));
+  p.combine_blocks = multi_segments > 0 ? (int)std::max(1LL, std::min(cap, ((long long)multi_rows * m + 255) / 256)) : 0;
+  p.part_doubles = (size_t)std::max(0, multi_segments) * (size_t)std::max(0, m);
+  return p;
+}
+
 // ---- the orthogonalisation chain
 // The sweeps of a chain, as the host plans them and as the tail kernels name the next one in device memory (OrthoDev::phase).
 // OP_GRAMX / OP_GRAMW / OP_XW belong to the pending-factor schedule (k <= 16, even n; see ortho_tail16): X^T U and U^T U in one

@@ -457,6 +457,16 @@ void dla_set_solve_info(int iters, int matvec_cols, int restarts);   /* used by 
  * 1.25 and SELL otherwise.  The two callbacks serve whichever format was set up last; a refused setup replaces nothing.
  * dla_spmm_setup_csr is always ELLPACK, and dla_spmm_setup_csr_sharded stays ELLPACK plus halo: sharding the sliced format is
  * out of scope here.
+ * How a tail row is summed (the contract; SEG = long_segment_entries, a positive multiple of 64).  A tail row with entries
+ * [p0, p1) in the caller's order has S = ceil((p1 - p0) / SEG) segments, segment s covering [p0 + s SEG, min(p1, p0 + (s + 1) SEG)),
+ * and one wavefront of 64 lanes forms the partial of one segment, per right-hand side: lane l starts from 0.0 and takes the
+ * segment's entries l, l + 64, l + 128, ... in that order, one fma(value, x[col], acc) each; then for off = 32, 16, 8, 4, 2, 1 every
+ * lane does acc += acc of lane (l xor off); lane 0's value is the partial.  With S = 1 the partial is the row's result (every
+ * tail row of up to SEG entries).  With S > 1 the result is ((part_0 + part_1) + part_2) + ..., plain double additions in ascending
+ * segment order by one thread per (row, right-hand side), from a workspace of multi_segments x m doubles that belongs to the
+ * stored matrix (the operator and the metric each have their own; it grows with m and is not counted in device_bytes).  No
+ * atomics and no arrival order anywhere: every element of the result and of the workspace has exactly one writer, so repeated
+ * products are bit-identical, and every row stays within (len + 2) eps |A||x| of the exact product.
  * The metric of a generalised problem A x = lambda B x (dla_spmm_setup_metric_csr, single rank): a context keeps a second sparse
  * matrix B beside its operator, handed over the same way and stored in any of the formats above.  dla_spmm_bvec has the shape of
  * the reference's bvec(n,m,x,bx) (diaglib.f90:1855, gen_david_driver; the harness' smult, main.f90:115-144) and goes where a host
@@ -484,6 +494,9 @@ struct dla_spmm_info {
   long long long_entries;
   long long device_bytes;     /* bytes of the arrays a product and the preconditioner read (allocations only grow: a smaller
                                  operator after a larger one keeps the larger blocks) */
+  int long_segment_entries;   /* SELL: entries per segment of a tail row (SEG above), all segments of the tail, and the segments */
+  int long_segments;          /*       of rows with more than one (= rows of the workspace of partial sums); 0 for ELLPACK      */
+  int multi_segments;
 };
 int  dla_spmm_setup_csr(dla_ctx* ctx, int n, const long long* rowptr, const int* colind, const double* values);
 int  dla_spmm_setup_csr_fmt(dla_ctx* ctx, int n, const long long* rowptr, const int* colind, const double* values, int format);

@@ -6,10 +6,12 @@ comparison of the two results.
   (a) the matrices ELLPACK was built for: a 5-point Laplacian and a band of half-width 6
   (b) ragged matrices whose ELLPACK padding w n / nnz is 1.1, 1.25, 1.5, 2 and 4 (w = 16, rows capped so that ELLPACK fits):
       where the two curves cross is where DLA_SPMM_AUTO should change its mind
-  (c) the skewed matrices of tests/spmm_cases.py (power-law rows, one dense row), sliced format only, as
-      (12 (stored + long_entries) + 4 n + 16 n m) / time beside the STREAM triad of the same run
+  (c) the skewed matrices of tests/spmm_cases.py (power-law rows, one dense row), sliced format only: the tail as the layout
+      cut it (long_rows, long_segments of long_segment_entries entries, multi_segments = partial sums per right-hand side) and
+      one product as (12 (stored + long_entries) + 4 n + 16 n m) / time beside the STREAM triad of the same run.  This is the
+      leg to repeat when dla::SELL_LONG_SEG is tuned: build with each candidate and compare the lines (legs = c)
 
-python tools/tune_spmm_format.py [n] [m] [rounds] > profiles/spmm_formats.txt"""
+python tools/tune_spmm_format.py [n] [m] [rounds] [legs = abc] >> profiles/spmm_formats.txt"""
 import os
 import sys
 
@@ -24,6 +26,7 @@ from spmm_cases import skewed_csr  # noqa: E402
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 2_000_000
 m = int(sys.argv[2]) if len(sys.argv) > 2 else 13
 rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+legs = sys.argv[4] if len(sys.argv) > 4 else "abc"
 REPS = 20
 ctx = capi.Context()
 ctx.set_option(capi.OPT_PROFILE, 1)
@@ -96,24 +99,28 @@ print(f"# tools/tune_spmm_format.py n={n} m={m} rounds={rounds} reps={REPS} back
 triad = ctx.stream_triad(32 * 1024 * 1024, 5)
 print(f"# STREAM triad of this run: {triad:.0f} GB/s")
 rng = np.random.default_rng(3)
-print("# (a) stencil and band")
-nx = 2000
-t = lambda k: sp.diags([-np.ones(k - 1), 2 * np.ones(k), -np.ones(k - 1)], [-1, 0, 1])  # noqa: E731
-ab("5-point laplacian", raw(sp.kron(sp.identity(n // nx), t(nx)) + sp.kron(t(n // nx), sp.identity(nx))) if n % nx == 0 else raw(t(n)))
-half = 6
-band = sp.diags([rng.standard_normal(n - k) for k in range(1, half + 1)], list(range(1, half + 1)), shape=(n, n))
-ab("band, half-width 6", raw(band + band.T + sp.diags(np.arange(1.0, n + 1.0))))
-print("# (b) ragged: rows of 16 or 2 entries in random order")
-for padding in (1.1, 1.25, 1.5, 2.0, 4.0):
-    ab(f"ragged, ell padding {padding:4.2f}", two_lengths(rng, 16, 2, padding))
-print("# (c) skewed (power-law rows, one dense row): sliced format only")
-for seed in (7, 8, 9):
-    info = setup(skewed_csr(np.random.default_rng(seed), n), "sell")
-    ms = [product_ms() for _ in range(rounds)]
-    med = float(np.median(ms))
-    gbs = sell_bytes(info) / med / 1e6
-    print(f"skewed seed {seed}: nnz {info['nnz']}  stored + long {(info['stored'] + info['long_entries']) / info['nnz']:.3f} x nnz  long rows {info['long_rows']}  "
-          f"device {info['device_bytes'] / 2 ** 20:.0f} MiB | {med:7.3f} ms (band {100 * (max(ms) - min(ms)) / med:4.1f} %)  "
-          f"{gbs:6.0f} GB/s algorithmic = {gbs / triad:.2f} x triad", flush=True)
+if "a" in legs:
+    print("# (a) stencil and band")
+    nx = 2000
+    t = lambda k: sp.diags([-np.ones(k - 1), 2 * np.ones(k), -np.ones(k - 1)], [-1, 0, 1])  # noqa: E731
+    ab("5-point laplacian", raw(sp.kron(sp.identity(n // nx), t(nx)) + sp.kron(t(n // nx), sp.identity(nx))) if n % nx == 0 else raw(t(n)))
+    half = 6
+    band = sp.diags([rng.standard_normal(n - k) for k in range(1, half + 1)], list(range(1, half + 1)), shape=(n, n))
+    ab("band, half-width 6", raw(band + band.T + sp.diags(np.arange(1.0, n + 1.0))))
+if "b" in legs:
+    print("# (b) ragged: rows of 16 or 2 entries in random order")
+    for padding in (1.1, 1.25, 1.5, 2.0, 4.0):
+        ab(f"ragged, ell padding {padding:4.2f}", two_lengths(rng, 16, 2, padding))
+if "c" in legs:
+    print("# (c) skewed (power-law rows, one dense row): sliced format only")
+    for seed in (7, 8, 9):
+        info = setup(skewed_csr(np.random.default_rng(seed), n), "sell")
+        ms = [product_ms() for _ in range(rounds)]
+        med = float(np.median(ms))
+        gbs = sell_bytes(info) / med / 1e6
+        print(f"skewed seed {seed}: nnz {info['nnz']}  stored + long {(info['stored'] + info['long_entries']) / info['nnz']:.3f} x nnz  long rows {info['long_rows']}  "
+              f"long segments {info['long_segments']} of {info['long_segment_entries']}  multi segments {info['multi_segments']}  "
+              f"device {info['device_bytes'] / 2 ** 20:.0f} MiB | m = {m}: {med:7.3f} ms (min {min(ms):7.3f} max {max(ms):7.3f}, band {100 * (max(ms) - min(ms)) / med:4.1f} %)  "
+              f"{gbs:6.0f} GB/s algorithmic = {gbs / triad:.3f} x triad", flush=True)
 ctx.set_option(capi.OPT_CALLBACKS_ON_DEVICE, 0)
 ctx.set_option(capi.OPT_PROFILE, 0)

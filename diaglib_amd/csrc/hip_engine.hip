@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 #include <cstring>
 #include <ctime>
 #include <map>
@@ -3361,6 +3362,13 @@ struct TimedLaunch { hipEvent_t a, b; int cls; std::string kname; };
 // every launch of the engine goes through here: a dry run (HipEngine::LaunchCtx::dry) walks the launch paths -- shape decisions,
 // workspace growth, requests for more than 64 KiB of LDS -- without launching anything
 #define DLA_LAUNCH(...) do { if (!lc.dry) hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+// A dispatch ladder over an instance list of hip_plans.h: f(std::integral_constant<size_t, I>) for I = 0 .. N - 1 until one call
+// returns true (false: no row took the plan).  Inside f, `constexpr auto s = LIST[decltype(i)::value]` has the row's fields as
+// compile-time values, so every listed row is instantiated and nothing else is.
+template <typename F, size_t... I>
+bool first_instance(std::index_sequence<I...>, F&& f) { return (f(std::integral_constant<size_t, I>{}) || ...); }
+template <size_t N, typename F>
+bool first_instance(F&& f) { return first_instance(std::make_index_sequence<N>{}, f); }
 
 struct HipEngine : dla::Engine {
   int device = 0;
@@ -4286,7 +4294,7 @@ struct HipEngine : dla::Engine {
       // the projection sweep (WP == 2): one U tile
       if constexpr (KT == 1) {
         auto kfn = gram_lds_kernel<TLW, 1, 1, R, 0, 0, 0, 2>;
-        const size_t lds = sizeof(double) * 4 * 16 * (TLW + 1) * (R + 2);
+        const size_t lds = gram_lds_bytes(TLW, 1, R, false, false);
         if (!raise_lds((const void*)kfn, lds)) return DLA_ERR_RUNTIME;
         DLA_LAUNCH(kfn, grid, dim3(256), lds, st, a);
         return DLA_OK;
@@ -4296,13 +4304,13 @@ struct HipEngine : dla::Engine {
     if (self) {
       if constexpr (TLW == 1 && KT == 1) {
         auto kfn = gram_lds_kernel<1, 1, 1, 32, 1, 0, 0, 1>;
-        const size_t lds = sizeof(double) * 4 * 16 * 34;
+        const size_t lds = gram_lds_bytes(1, 1, 32, true, false);
         DLA_LAUNCH(kfn, grid, dim3(256), lds, st, a);
       }
       return DLA_OK;
     }
     auto kfn = gram_lds_kernel<TLW, KT, 1, R, 0, 0, 0, 1>;
-    const size_t lds = sizeof(double) * 4 * 16 * (TLW + KT) * (R + 2);
+    const size_t lds = gram_lds_bytes(TLW, KT, R, false, false);
     if (!raise_lds((const void*)kfn, lds)) return DLA_ERR_RUNTIME;
     DLA_LAUNCH(kfn, grid, dim3(256), lds, st, a);
     return DLA_OK;
@@ -4331,12 +4339,13 @@ struct HipEngine : dla::Engine {
       Scope s(this, cx ? DLA_OP_GEMM : DLA_OP_GRAM, 8.0 * (double)n * (double)(m + k + (uw ? k : 0)),
               2.0 * (double)n * (m + k) * k + ((wp || cx) ? 1.0 * (double)n * k * k : 0.0) + (cx ? 2.0 * (double)n * m * k : 0.0), p.name());
       int r_ = DLA_ERR_RUNTIME;
-#define GWP(T, K, RR) if (tlw == T && kt == K && p.R == RR) r_ = launch_gram_wp<T, K, RR>(a, grid, self); else
-      GWP(1, 1, 32) GWP(2, 1, 32) GWP(3, 1, 16) GWP(4, 1, 16) GWP(5, 1, 16) GWP(6, 1, 16) GWP(7, 1, 16) GWP(8, 1, 16) GWP(10, 1, 16) GWP(12, 1, 16)
-      GWP(1, 2, 16) GWP(2, 2, 16) GWP(3, 2, 16) GWP(4, 2, 16) GWP(5, 2, 16) GWP(6, 2, 16) GWP(7, 2, 16) GWP(8, 2, 16)
-      GWP(1, 3, 16) GWP(2, 3, 16) GWP(3, 3, 16) GWP(4, 3, 16) GWP(5, 3, 16)
-      { err = "gram_wp: no kernel instance"; }
-#undef GWP
+      if (!first_instance<std::size(WP_TILES)>([&](auto i) {
+            constexpr WpTile s = WP_TILES[decltype(i)::value];
+            if (tlw != s.tlw || kt != s.kt || p.R != s.R) return false;
+            r_ = launch_gram_wp<s.tlw, s.kt, s.R>(a, grid, self);
+            return true;
+          }))
+        err = "gram_wp: no kernel instance";
       if (r_) return r_;
     }
     const int n_out = self ? 1 : passes * tlw * kt + extra;
@@ -4799,8 +4808,7 @@ struct HipEngine : dla::Engine {
         return launch_gram_lds<TLW, KT, 16>(a, grid, p);
       }
     }
-    if constexpr (TLW == 5 || TLW == 7 || TLW == 10 || (TLW == 12 && KT > 1) || (TLW == 3 && KT >= 2 && KT <= 3) || (TLW >= 5 && KT == 3) ||
-                  (TLW >= 7 && KT == 2)) {
+    if constexpr (!gram_direct_instance(TLW, KT)) {
       err = "gram: width without a direct-load instance";
       return DLA_ERR_RUNTIME;
     } else {
@@ -4833,18 +4841,21 @@ struct HipEngine : dla::Engine {
     {
       const bool same = (x == u) && (l == k);
       Scope s(this, cls, 8.0 * (double)n * (same ? (double)k : (double)(l + k)), 2.0 * (double)n * l * k, p.name());
-      if (p.low_single) {
-        int r_ = tlw == 4 ? launch_gram_low<4>(a, grid, p) : tlw == 5 ? launch_gram_low<5>(a, grid, p) : tlw == 6 ? launch_gram_low<6>(a, grid, p)
-                                                                                                                   : launch_gram_low<7>(a, grid, p);
-        if (r_) return r_;
-      } else
-#define GL(T, K) if (tlw == T && kt == K) { int r_ = launch_gram<T, K>(a, grid, p); if (r_) return r_; } else
-      GL(1, 1) GL(2, 1) GL(3, 1) GL(4, 1) GL(5, 1) GL(6, 1) GL(7, 1) GL(8, 1) GL(10, 1) GL(12, 1)
-      GL(1, 2) GL(2, 2) GL(3, 2) GL(4, 2) GL(5, 2) GL(6, 2) GL(7, 2) GL(8, 2)
-      GL(1, 3) GL(2, 3) GL(3, 3) GL(4, 3) GL(5, 3) GL(6, 3) GL(7, 3)
-      GL(1, 4) GL(2, 4) GL(3, 4)
-      { err = "gram: no kernel instance"; return DLA_ERR_RUNTIME; }
-#undef GL
+      int r_ = DLA_ERR_RUNTIME;
+      const bool hit = p.low_single ? first_instance<std::size(GRAM_LOW_TILES)>([&](auto i) {
+                                        constexpr int T = GRAM_LOW_TILES[decltype(i)::value];
+                                        if (tlw != T) return false;
+                                        r_ = launch_gram_low<T>(a, grid, p);
+                                        return true;
+                                      })
+                                    : first_instance<std::size(GRAM_TILES)>([&](auto i) {
+                                        constexpr GramTile s = GRAM_TILES[decltype(i)::value];
+                                        if (tlw != s.tlw || kt != s.kt) return false;
+                                        r_ = launch_gram<s.tlw, s.kt>(a, grid, p);
+                                        return true;
+                                      });
+      if (!hit) err = "gram: no kernel instance";
+      if (r_) return r_;
     }
     return reduce_and_sum(cls, d_small + lc.small_off, lc.phase ? nullptr : h_small.dev() + lc.small_off, blocks_per_pass, l, k, tlw, kt, p.px,
                           passes * slots, 0, 0, out);
@@ -4936,13 +4947,6 @@ struct HipEngine : dla::Engine {
         g_host[(size_t)i2 + (size_t)j * ldg] = low ? h_small[(size_t)i2 + (size_t)j * k] : h_small[(size_t)j + (size_t)i2 * k];
       }
     return DLA_OK;
-  }
-
-  // dynamic LDS of a fused sweep: packed C (l rows) + 4 wave-private transpose tiles
-  static size_t fused_lds(int l, int k)
-  {
-    const int kt = (k + 15) / 16, l4 = ((l + 3) / 4) * 4;
-    return std::max(sizeof(double) * ((size_t)kt * l4 * 16 + (size_t)4 * 16 * (16 * kt + 9)), (size_t)8192);
   }
 
   // U <- U W and G = U^T U of the result, one sweep (k <= 48); otherwise two sweeps
@@ -5040,6 +5044,8 @@ struct HipEngine : dla::Engine {
     return stage_commit(slot, sizeof(double) * cnt, d_cpk);
   }
 
+  // (The gemm_kernel ladders keep their macros and have no instance list in hip_plans.h: their instances are a product of independent
+  //  flags -- argument type x KT x VEC x MODE x fuse x depth x quarter tiles x row groups -- and a list of rows would be longer.)
   template <int KT, typename ARGS>
   int launch_gemm_gram(const ARGS& a, int blocks, size_t lds, bool vec2, int mode, int qt, int rtp)
   {
@@ -5303,38 +5309,20 @@ struct HipEngine : dla::Engine {
       // (flops: the two Ritz products and, with extra columns, the two panel products they replace)
       Scope s(this, DLA_OP_RITZ, 8.0 * n * (2.0 * l + ((avy ? 2.0 : 1.0) + (evec ? 1.0 : 0.0)) * m + 2.0 * k2),
               4.0 * (double)n * l * (m + k2) + 5.0 * (double)n * nact, p.name());
-#define RZ(K) do { auto kfn = K; if (!raise_lds((const void*)kfn, lds, ritz_static_lds(kt))) return DLA_ERR_RUNTIME; DLA_LAUNCH(kfn, dim3(blocks), dim3(256), lds, st, a); } while (0)
-      if (xp) {
-        // [Y | C2]: vec2 guaranteed by the caller (ritz_residual_p)
-        if (qt == 1) { if (kt == 2) RZ((ritz_kernel<2, 2, 3, 2, 1, true>)); else RZ((ritz_kernel<3, 2, 3, 3, 1, true>)); }
-        else if (qt == 2) { if (kt == 2) RZ((ritz_kernel<2, 2, 3, 2, 2, true>)); else RZ((ritz_kernel<3, 2, 3, 3, 2, true>)); }
-        else if (kt == 1) RZ((ritz_kernel<1, 2, 3, 0, 0, true>));
-        else if (kt == 2) RZ((ritz_kernel<2, 2, 3, 2, 0, true>));
-        else if (kt == 3) RZ((ritz_kernel<3, 2, 3, 3, 0, true>));
-        else if (kt == 4) RZ((ritz_kernel<4, 2, 3, 3, 0, true>));
-        else RZ((ritz_kernel<5, 2, 3, 3, 0, true>));        // (pipeline depth 2 / 4 measured: 8.9 / 7.9 ms against 7.5 at 37 + 37 columns)
-      } else if (kt >= 2 && pipe == 0) {             // (Knobs::ritz_pipe_depth: vec2, no quarter tiles)
-        if (kt == 2) RZ((ritz_kernel<2, 2, 3, 0>));
-        else RZ((ritz_kernel<3, 2, 3, 0>));
-      } else if (pipe == 4) {
-        if (kt == 2) RZ((ritz_kernel<2, 2, 3, 4>));
-        else RZ((ritz_kernel<3, 2, 3, 4>));
-      } else if (vec2 && qt == 1) {
-        if (kt == 2) RZ((ritz_kernel<2, 2, 3, 2, 1>));
-        else RZ((ritz_kernel<3, 2, 3, 3, 1>));
-      } else if (vec2 && qt == 2) {
-        if (kt == 2) RZ((ritz_kernel<2, 2, 3, 2, 2>));
-        else RZ((ritz_kernel<3, 2, 3, 3, 2>));
-      } else if (vec2) {
-        if (kt == 1) RZ((ritz_kernel<1, 2>));
-        else if (kt == 2) RZ((ritz_kernel<2, 2>));
-        else RZ((ritz_kernel<3, 2>));
-      } else {
-        if (kt == 1) RZ((ritz_kernel<1, 1>));
-        else if (kt == 2) RZ((ritz_kernel<2, 1>));
-        else RZ((ritz_kernel<3, 1>));
+      // (with extra products the 16-byte path is guaranteed by the caller, ritz_residual_p)
+      int r_ = DLA_OK;
+      if (!first_instance<std::size(RITZ_INSTANCES)>([&](auto i) {
+            constexpr RitzInstance s = RITZ_INSTANCES[decltype(i)::value];
+            if (kt != s.kt || (vec2 ? 2 : 1) != s.vec || pipe != s.pipe || qt != s.qt || xp != s.xp) return false;
+            auto kfn = ritz_kernel<s.kt, s.vec, 3, s.pipe, s.qt, s.xp>;
+            if (!raise_lds((const void*)kfn, lds, ritz_static_lds(kt))) r_ = DLA_ERR_RUNTIME;
+            else DLA_LAUNCH(kfn, dim3(blocks), dim3(256), lds, st, a);
+            return true;
+          })) {
+        err = "ritz: no kernel instance";
+        return DLA_ERR_RUNTIME;
       }
-#undef RZ
+      if (r_) return r_;
     }
     {
       Scope s2(this, DLA_OP_RITZ, 0.0, 0.0, "ritz_reduce_kernel");

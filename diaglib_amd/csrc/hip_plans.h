@@ -4,10 +4,14 @@
 // knobs and the chain policy.  The planners have no members and touch no global; the engine owns every piece of state
 // (remembered plans, the cooldown, the LDS limit, pointers) and passes what a decision reads.  hip_engine.hip takes a plan,
 // books plan.name() and dispatches on the plan's fields; tests/plans_driver.cpp calls the same functions on the CPU.
+// Which template instances of the Gram, pending-factor and Ritz kernels exist is spelled once, in the lists below (GRAM_TILES,
+// gram_direct_instance, GRAM_LOW_TILES, WP_TILES, RITZ_INSTANCES): the planners round to a listed width, the engine's ladders
+// instantiate and launch exactly the listed rows, and tests/test_plans.py holds its own transcription against what the driver prints.
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdio>
+#include <iterator>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -125,6 +129,52 @@ inline int quarter_tiles(const PlanEnv& env, int k, bool vec2)
 // resident blocks per CU that the dynamic LDS of a panel-product or Ritz sweep leaves room for
 inline int blocks_per_cu(size_t lds) { return lds > 80 * 1024 ? 1 : lds > 40 * 1024 ? 2 : 4; }
 
+// ---- the instance lists: one row per template instance the engine's ladders can launch (plain integers, compile-time)
+// gram_kernel / gram_lds_kernel passes of kt U-tiles x tlw X-tiles
+struct GramTile { int tlw, kt; };
+constexpr GramTile GRAM_TILES[] = {
+  {1, 1}, {2, 1}, {3, 1}, {4, 1}, {5, 1}, {6, 1}, {7, 1}, {8, 1}, {10, 1}, {12, 1},
+  {1, 2}, {2, 2}, {3, 2}, {4, 2}, {5, 2}, {6, 2}, {7, 2}, {8, 2},
+  {1, 3}, {2, 3}, {3, 3}, {4, 3}, {5, 3}, {6, 3}, {7, 3},
+  {1, 4}, {2, 4}, {3, 4}};
+// ... of which the direct-load gram_kernel has these (the LDS-staged kernel has every listed pair of up to three U tiles)
+constexpr bool gram_direct_instance(int tlw, int kt)
+{
+  return !(tlw == 5 || tlw == 7 || tlw == 10 || (tlw == 12 && kt > 1) || (tlw == 3 && kt >= 2 && kt <= 3) || (tlw >= 5 && kt == 3) ||
+           (tlw >= 7 && kt == 2));
+}
+// tiles per side of the single-pass lower triangle (gram_lds_kernel LOW)
+constexpr int GRAM_LOW_TILES[] = {4, 5, 6, 7};
+// sweeps of the pending-factor schedule (gram_lds_kernel WP), with the rows R of a staged tile
+struct WpTile { int tlw, kt, R; };
+constexpr WpTile WP_TILES[] = {
+  {1, 1, 32}, {2, 1, 32}, {3, 1, 16}, {4, 1, 16}, {5, 1, 16}, {6, 1, 16}, {7, 1, 16}, {8, 1, 16}, {10, 1, 16}, {12, 1, 16},
+  {1, 2, 16}, {2, 2, 16}, {3, 2, 16}, {4, 2, 16}, {5, 2, 16}, {6, 2, 16}, {7, 2, 16}, {8, 2, 16},
+  {1, 3, 16}, {2, 3, 16}, {3, 3, 16}, {4, 3, 16}, {5, 3, 16}};
+// ritz_kernel<kt, vec, 3, pipe, qt, xp>
+struct RitzInstance { int kt, vec, pipe, qt; bool xp; };
+constexpr RitzInstance RITZ_INSTANCES[] = {
+  // [Y | C2] with extra products (16-byte path only); (pipeline depth 2 / 4 of the five-tile one measured: 8.9 / 7.9 ms against 7.5
+  // at 37 + 37 columns)
+  {2, 2, 2, 1, true}, {3, 2, 3, 1, true}, {2, 2, 2, 2, true}, {3, 2, 3, 2, true},
+  {1, 2, 0, 0, true}, {2, 2, 2, 0, true}, {3, 2, 3, 0, true}, {4, 2, 3, 0, true}, {5, 2, 3, 0, true},
+  // plain, 16-byte path: the depths of Knobs::ritz_pipe_depth, quarter tiles, the kernels' own depth
+  {2, 2, 0, 0, false}, {3, 2, 0, 0, false}, {2, 2, 4, 0, false}, {3, 2, 4, 0, false},
+  {2, 2, 2, 1, false}, {3, 2, 3, 1, false}, {2, 2, 2, 2, false}, {3, 2, 3, 2, false},
+  {1, 2, 0, 0, false}, {2, 2, 2, 0, false}, {3, 2, 3, 0, false},
+  // plain, 8-byte path
+  {1, 1, 0, 0, false}, {2, 1, 2, 0, false}, {3, 1, 3, 0, false}};
+// "round up to an instantiated width": the narrowest listed pass of kt U-tiles that holds `want` X-tiles and that `ok` admits; null
+// when the list has none (the planner keeps its width, and the ladder reports that there is no kernel instance)
+template <typename Tile, size_t N, typename Ok>
+constexpr const Tile* listed_pass(const Tile (&list)[N], int kt, int want, Ok ok)
+{
+  const Tile* best = nullptr;
+  for (const Tile& t : list)
+    if (t.kt == kt && t.tlw >= want && ok(t) && (!best || t.tlw < best->tlw)) best = &t;
+  return best;
+}
+
 // ---- Gram
 // whether a pass of tlw + kt tiles can be staged 32 rows at a time at all, and the rows per step of the direct-load kernel
 constexpr bool gram_can32(int tlw, int kt) { return sizeof(double) * 4 * 16 * (tlw + kt) * 34 <= 150 * 1024 && tlw + kt <= 7; }
@@ -159,7 +209,7 @@ struct GramPlan {
   bool lower;            // only the tile pairs on or below the block diagonal are formed
   int blocks_per_pass;
   bool vec2;             // the 16-byte path
-  // the name rocprofv3 prints for the instance the GL ladder picks
+  // the name rocprofv3 prints for the instance gram_dev_once picks from GRAM_TILES / GRAM_LOW_TILES
   std::string name() const
   {
     if (lds) return plan_name("gram_lds_kernel<%d, %d, 1, %d, %d, %d, %d, 0>", tlw, kt, rows, self ? 1 : 0, qt, low_single ? 1 : 0);
@@ -194,15 +244,7 @@ inline GramPlan gram_plan(const PlanEnv& env, int n, int l, int k, bool same, bo
   const int passes_x = (tx + mt - 1) / mt;
   int tlw = (tx + passes_x - 1) / passes_x;
   // round up to an instantiated width
-  static const int avail1[] = {1, 2, 3, 4, 6, 8, 12};
-  static const int avail1l[] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12};
-  if (kt == 1 && ldsk) { for (int v : avail1l) if (v >= tlw) { tlw = v; break; } }
-  else if (kt == 1) { for (int v : avail1) if (v >= tlw) { tlw = v; break; } }
-  else if (kt == 2 && ldsk) { tlw = std::min(tlw, 8); }                       // 1..8 all instantiated
-  else if (kt == 3 && ldsk) { tlw = std::min(tlw, 7); }                       // 1..7
-  else if (kt == 2) { tlw = tlw <= 1 ? 1 : tlw <= 2 ? 2 : tlw <= 4 ? 4 : 6; }
-  else if (kt == 3) { tlw = tlw <= 1 ? 1 : tlw <= 2 ? 2 : 4; }
-  else { tlw = tlw <= 1 ? 1 : tlw <= 2 ? 2 : 3; }
+  if (const GramTile* t = listed_pass(GRAM_TILES, kt, tlw, [&](const GramTile& g) { return ldsk || gram_direct_instance(g.tlw, g.kt); })) tlw = t->tlw;
   int px = (tx + tlw - 1) / tlw;
   int passes = px * passes_u;
   // a block against itself in a single pass: one staged image serves both operands, and only the tile pairs on or
@@ -237,7 +279,7 @@ struct WpPlan {
   int tlw, kt, R, passes, blocks, extra, slots;
   bool self;             // m == 0: the block against itself
   bool project;          // the projection sweep that measures what it stores (WP == 2), else the measuring / storing one (WP == 1)
-  std::string name() const { return plan_name("gram_lds_kernel<%d, %d, 1, %d, %d, 0, 0, %d>", tlw, kt, R, self ? 1 : 0, project ? 2 : 1); }
+  std::string name() const { return plan_name("gram_lds_kernel<%d, %d, 1, %d, %d, 0, 0, %d>", tlw, kt, R, self ? 1 : 0, project ? 2 : 1); }  size_t lds_bytes() const { return gram_lds_bytes(tlw, kt, R, self, false); }
 };
 inline WpPlan wp_plan(const PlanEnv& env, int n, int m, int k, bool project)
 {
@@ -249,13 +291,10 @@ inline WpPlan wp_plan(const PlanEnv& env, int n, int m, int k, bool project)
   const int tx = p.self ? 1 : (m + 15) / 16;
   p.passes = p.self ? 1 : (tx + wp_max_tlw(p.kt) - 1) / wp_max_tlw(p.kt);
   p.tlw = (tx + p.passes - 1) / p.passes;
-  if (p.kt == 1) {
-    static const int avail[] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12};
-    for (int v : avail) if (v >= p.tlw) { p.tlw = v; break; }
-  }
   // the staged image of the widest pass: 13 tiles of 16 rows (4 waves x 13 x 16 x 18 doubles = 117 KiB); under a refused
   // LDS raise the chain is not taken at all (ortho_chain).  (A block against itself is one tile beside one: 32 rows.)
-  p.R = (p.kt == 1 && p.tlw <= 2) ? 32 : 16;
+  p.R = 16;
+  if (const WpTile* t = listed_pass(WP_TILES, p.kt, p.tlw, [](const WpTile&) { return true; })) { p.tlw = t->tlw; p.R = t->R; }
   const long long nchunks = ((long long)n + 31) / 32;
   const long long want = (nchunks + 15) / 16;
   // (one U tile beside up to five X tiles: at most 212 / 252 registers and 55 KB of LDS per block -- two blocks per CU, two waves
@@ -312,6 +351,14 @@ inline GemmPlan gemm_plan(const PlanEnv& env, int n, int l, int k, int mode, boo
   const long long ntiles = ((long long)n + wt - 1) / wt;
   const int blocks = (int)std::max(1LL, std::min((long long)env.ncu * per_cu, (ntiles + 3) / 4));
   return GemmPlan{kt, l4, inl, qt, lds, per_cu, rtp, pipe, blocks, vec2, fuse, mode};
+}
+
+// dynamic LDS of a fused sweep as the engine's decisions read it (can_combo, the fused update and triangular update, ChainIn::fused_lds_kk):
+// packed C (l rows) + 4 wave-private transpose tiles.  Not GemmPlan::lds, which knows the quarter tiles of the launch itself.
+inline size_t fused_lds(int l, int k)
+{
+  const int kt = (k + 15) / 16, l4 = ((l + 3) / 4) * 4;
+  return std::max(sizeof(double) * ((size_t)kt * l4 * 16 + (size_t)4 * 16 * (16 * kt + 9)), (size_t)8192);
 }
 
 // ---- Ritz sweep (ritz_kernel, ritz2_kernel)

@@ -5,13 +5,15 @@
 //   env NCU LDS_LIMIT T0 .. T7                      the device and the knobs of the requests that follow
 //   policy DROP_FINAL PUBLISH_PENDING BASIS_EXACT CHAIN_OFF DROP_TOL
 //   gram N L K SAME ALIGNED LOWER
-//   wp N M K PROJECT
+//   wp N M K PROJECT                   wp_lds N M K PROJECT: WpPlan::lds_bytes alone
 //   gemm N L K MODE FUSE PACKED_ON_DEVICE VEC2
 //   ritz N L M K2 VEC2 NSLOTS          ritz2 N L M VEC2 NSLOTS
 //   chain M K VEC2 BX_IS_X COMBO_OK HOST_BETWEEN X3_COOLDOWN DMAT_COLS DMAT_NONTRIVIAL FUSED_LDS_KK
 //   default K M FOLD VSX WIDE_GRAMX WIDE_XW DROPF X3          (a ChainShape)
 //   lean M K P2P_ON NRANKS COMM
 //   close LEAN X3 OP ...
+//   fused L K                          fused_lds
+//   instances                          the instance lists, one line per list, and gram_direct_instance over tlw 1..12 x kt 1..4
 #include <cstdio>
 #include <iostream>
 #include <sstream>
@@ -57,6 +59,10 @@ int main()
       const WpPlan p = wp_plan(env, n, m, k, project);
       std::printf("tlw=%d kt=%d R=%d passes=%d blocks=%d extra=%d slots=%d self=%d max_tlw=%d | %s\n", p.tlw, p.kt, p.R, p.passes, p.blocks, p.extra,
                   p.slots, p.self, wp_max_tlw(p.kt), p.name().c_str());
+    } else if (what == "wp_lds") {
+      int n, m, k; bool project;
+      ss >> n >> m >> k >> project;
+      std::printf("lds_bytes=%zu\n", wp_plan(env, n, m, k, project).lds_bytes());
     } else if (what == "gemm") {
       int n, l, k, mode; bool fuse, packed, vec2;
       ss >> n >> l >> k >> mode >> fuse >> packed >> vec2;
@@ -95,6 +101,23 @@ int main()
       ss >> lean >> x3;
       while (ss >> op) plan.push_back(op);
       print_ops(close_plan(plan, lean, x3));
+    } else if (what == "fused") {
+      int l, k;
+      ss >> l >> k;
+      std::printf("fused_lds=%zu\n", fused_lds(l, k));
+    } else if (what == "instances") {
+      std::printf("gram_tiles=");
+      for (const GramTile& t : GRAM_TILES) std::printf("%d,%d;", t.tlw, t.kt);
+      std::printf(" gram_direct=");
+      for (int t = 1; t <= 12; ++t)
+        for (int k = 1; k <= 4; ++k) if (gram_direct_instance(t, k)) std::printf("%d,%d;", t, k);
+      std::printf(" gram_low_tiles=");
+      for (int t : GRAM_LOW_TILES) std::printf("%d;", t);
+      std::printf(" wp_tiles=");
+      for (const WpTile& t : WP_TILES) std::printf("%d,%d,%d;", t.tlw, t.kt, t.R);
+      std::printf(" ritz_instances=");
+      for (const RitzInstance& r : RITZ_INSTANCES) std::printf("%d,%d,%d,%d,%d;", r.kt, r.vec, r.pipe, r.qt, r.xp ? 1 : 0);
+      std::printf("\n");
     } else {
       std::fprintf(stderr, "unknown request: %s\n", line.c_str());
       return 2;

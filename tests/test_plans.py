@@ -4,7 +4,10 @@ quarter tiles, pipeline depth, the booked kernel names and the schedule of an or
 tests/plans_driver.cpp is compiled with g++ and no ROCm include (tests/_build/, $DIAGLIB_HOSTSIM_SANITIZE honoured, as
 tests/test_sell_layout.py does); it reads shape lines and prints plan fields and names from the product's own planners.  Expected
 values come from outside the planners: the committed rocprofv3 record of the benchmark, the literal names tests/test_knobs_gpu.py
-asserts, the instance lists of the dispatch ladders in hip_engine.hip (transcribed below), and the rules the planners' comments state."""
+asserts, the rules the planners' comments state, and the kernels' instance lists.  Those lists live in hip_plans.h (GRAM_TILES,
+gram_direct_instance, GRAM_LOW_TILES, WP_TILES, RITZ_INSTANCES), where the planners and the dispatch ladders of hip_engine.hip both
+read them; they are transcribed below as literal sets, and test_transcribed_instance_lists_are_the_engines holds each transcription
+against what the driver prints from the header."""
 import csv
 import itertools
 import os
@@ -43,7 +46,7 @@ def run_plans(lines):
         d = {}
         for kv in fields.split():
             key, val = kv.split("=")
-            d[key] = val if key in ("take", "ops") else int(val)
+            d[key] = val if key in ("take", "ops") or ";" in val else int(val)
         if "ops" in d:
             d["ops"] = [int(v) for v in d["ops"].split(",")] if d["ops"] else []
         res.append((d, name))
@@ -105,13 +108,39 @@ def test_names_the_knob_tests_assert():
 
 
 # ---------------------------------------------------------------- b. invariants the kernels impose
-# the (TLW, KT) pairs of the GL ladder in gram_dev_once
+# the (TLW, KT) pairs gram_dev_once can launch (GRAM_TILES)
 GL = {(t, 1) for t in (1, 2, 3, 4, 5, 6, 7, 8, 10, 12)} | {(t, 2) for t in range(1, 9)} | {(t, 3) for t in range(1, 8)} | {(t, 4) for t in (1, 2, 3)}
 
 
 def direct_load_instance(t, k):
     """the widths launch_gram has a gram_kernel instance for"""
     return not (t in (5, 7, 10) or (t == 12 and k > 1) or (t == 3 and 2 <= k <= 3) or (t >= 5 and k == 3) or (t >= 7 and k == 2))
+
+
+# the (TLW, KT, R) triples gram_wp_once can launch (WP_TILES)
+GWP = {(t, 1, 32) for t in (1, 2)} | {(t, 1, 16) for t in (3, 4, 5, 6, 7, 8, 10, 12)} | {(t, 2, 16) for t in range(1, 9)} | {(t, 3, 16) for t in range(1, 6)}
+
+
+def listed_instances():
+    """what the driver prints of hip_plans.h: each list as a list of integer tuples, in the header's order"""
+    res, _ = run_plans(["instances"])
+    return {key: [tuple(int(v) for v in row.split(",")) for row in val.split(";") if row] for key, val in res[0][0].items()}
+
+
+def test_transcribed_instance_lists_are_the_engines():
+    inst = listed_instances()
+    for rows in inst.values():
+        assert len(set(rows)) == len(rows), rows                     # no row twice: a ladder launches the first hit
+    assert set(inst["gram_tiles"]) == GL and len(inst["gram_tiles"]) == 28
+    assert set(inst["gram_direct"]) == {(t, k) for t in range(1, 13) for k in range(1, 5) if direct_load_instance(t, k)}
+    assert inst["gram_low_tiles"] == [(4,), (5,), (6,), (7,)]
+    assert set(inst["wp_tiles"]) == GWP and len(inst["wp_tiles"]) == 23
+    # ritz_kernel<kt, vec, 3, pipe, qt, xp>: (kt, vec, pipe, qt, xp), the kernel's own pipeline depth 0 / 2 / 3 / 3 / 3 by kt
+    own = {1: 0, 2: 2, 3: 3, 4: 3, 5: 3}
+    ritz = {(kt, 2, own[kt], 0, 1) for kt in range(1, 6)} | {(kt, 2, own[kt], qt, 1) for kt in (2, 3) for qt in (1, 2)}
+    ritz |= {(kt, 2, pipe, 0, 0) for kt in (2, 3) for pipe in (0, 4)} | {(kt, 2, own[kt], qt, 0) for kt in (2, 3) for qt in (1, 2)}
+    ritz |= {(kt, vec, own[kt], 0, 0) for kt in (1, 2, 3) for vec in (1, 2)}
+    assert set(inst["ritz_instances"]) == ritz and len(inst["ritz_instances"]) == 23
 
 
 @pytest.mark.parametrize("lds_limit", [64 * KIB, 160 * KIB])
@@ -171,8 +200,11 @@ def test_gemm_plans_fit_the_kernels(knob):
 
 @pytest.mark.parametrize("knob", [0, 1, 4])
 def test_ritz_plans_fit_the_kernels(knob):
-    cases = [(l, m, k2, v) for l in (8, 13, 26, 104, 260, 520, 740) for m in range(1, 49) for k2 in (0, 5, 13, 37) for v in (0, 1)
+    # (with extra products up to five column tiles, plain blocks up to three: m + k2 = 49 .. 80 are the four- and five-tile kernels)
+    cases = [(l, m, k2, v) for l in (8, 13, 26, 104, 260, 520, 740) for m in range(1, 49) for k2 in (0, 5, 13, 24, 32, 37) for v in (0, 1)
              if m + k2 <= 80 and (k2 == 0 or v)]
+    rows = listed_instances()["ritz_instances"]
+    tiles_that_fit = set()
     res, _ = run_plans([env_line(t0=knob)] + [f"ritz {N_BENCH} {l} {m} {k2} {v} 1" for l, m, k2, v in cases])
     for (l, m, k2, v), (p, name) in zip(cases, res):
         what = (l, m, k2, v, p, name)
@@ -187,20 +219,38 @@ def test_ritz_plans_fit_the_kernels(knob):
             assert p["pipe"] == own, what
         assert p["qt"] in (0, 1, 2) and (not p["qt"] or (1 <= (m + k2) % 16 <= 8 and kt in (2, 3) and v)), what
         assert 1 <= p["blocks"] <= NCU * p["per_cu"], what
+        if p["fits"]:
+            # the one instance ritz_residual_once launches for it: no plan that fits may reach "ritz: no kernel instance"
+            assert rows.count((p["kt"], 2 if v else 1, p["pipe"], p["qt"], p["xp"])) == 1, what
+            tiles_that_fit.add((p["kt"], p["xp"]))
+    assert tiles_that_fit == {(kt, 0) for kt in (1, 2, 3)} | {(kt, 1) for kt in (1, 2, 3, 4, 5)}
 
 
 def test_pending_factor_sweeps_fit_the_kernels():
-    """the GWP ladder of gram_wp_once"""
-    gwp = {(t, 1, 32) for t in (1, 2)} | {(t, 1, 16) for t in (3, 4, 5, 6, 7, 8, 10, 12)} | {(t, 2, 16) for t in range(1, 9)} | {(t, 3, 16) for t in range(1, 6)}
+    """the WP_TILES ladder of gram_wp_once"""
     cases = [(m, k, pr) for m in range(0, 209) for k in range(1, 49) for pr in (0, 1) if not (pr and (k > 16 or m == 0)) and not (m == 0 and k > 16)]
     res, _ = run_plans([env_line()] + [f"wp {N_BENCH} {m} {k} {pr}" for m, k, pr in cases])
-    for (m, k, pr), (p, name) in zip(cases, res):
-        what = (m, k, pr, p, name)
-        assert (p["tlw"], p["kt"], p["R"]) in gwp and p["tlw"] <= p["max_tlw"], what
+    lds, _ = run_plans([env_line()] + [f"wp_lds {N_BENCH} {m} {k} {pr}" for m, k, pr in cases])
+    for (m, k, pr), (p, name), (b, _) in zip(cases, res, lds):
+        what = (m, k, pr, p, name, b)
+        assert (p["tlw"], p["kt"], p["R"]) in GWP and p["tlw"] <= p["max_tlw"], what
         assert p["passes"] * p["tlw"] >= -(-m // 16) and p["kt"] == -(-k // 16), what
         assert p["self"] == int(m == 0) and 1 <= p["blocks"] <= 2 * NCU, what
         assert 8 * 4 * 16 * (p["tlw"] + p["kt"]) * (p["R"] + 2) <= LDS, what
         assert name.endswith(", %d>" % (2 if pr else 1)), what
+        # WpPlan::lds_bytes, the dynamic LDS of the launch, is the arithmetic launch_gram_wp used to write by hand
+        assert b["lds_bytes"] == (8 * 4 * 16 * 34 if m == 0 else 8 * 4 * 16 * (p["tlw"] + p["kt"]) * (p["R"] + 2)), what
+
+
+def test_fused_lds_is_the_formula_the_engine_had():
+    """fused_lds, which can_combo, the fused updates and ChainIn::fused_lds_kk read, at (k, k), (m + k, k) and (l, k): packed C of l
+    rows rounded to 4 and kt column tiles, 4 wave tiles of 16 x (16 kt + 9) doubles, at least 8 KiB"""
+    shapes = sorted({(k, k) for k in range(1, 49)} | {(m + k, k) for m in (13, 16, 125, 192, 208, 500) for k in (8, 13, 16, 17, 32, 48)} |
+                    {(l, k) for l in (1, 4, 13, 16, 17, 42, 63, 104, 208, 320, 512) for k in (1, 13, 16, 21, 33, 48)})
+    res, _ = run_plans([f"fused {l} {k}" for l, k in shapes])
+    for (l, k), (d, _) in zip(shapes, res):
+        kt, l4 = -(-k // 16), -(-l // 4) * 4
+        assert d["fused_lds"] == max(8 * (kt * l4 * 16 + 4 * 16 * (16 * kt + 9)), 8192), (l, k, d)
 
 
 # ---------------------------------------------------------------- c. the chain schedule

@@ -44,6 +44,7 @@ EXPORTS = [
     "dla_synth_setup", "dla_synth_matvec", "dla_synth_precnd", "dla_synth_apbmul", "dla_synth_ambmul", "dla_synth_spdmul", "dla_synth_smdmul",
     "dla_synth_metric", "dla_synth_lrprec1", "dla_synth_lrprec2", "dla_pending_factor", "dla_pending_block", "dla_basis_admit", "dla_basis_fold", "dla_basis_sync", "dla_spmm_setup_csr", "dla_spmm_setup_csr_fmt", "dla_spmm_info", "dla_spmm_setup_csr_sharded", "dla_spmm_matvec", "dla_spmm_precnd",
     "dla_spmm_setup_metric_csr", "dla_spmm_metric_info", "dla_spmm_drop_metric", "dla_spmm_bvec", "dla_spmm_precnd_pencil",
+    "dla_spmm_setup_csr_dev", "dla_spmm_refresh_values_dev",
     "dla_davidson_driver", "dla_gen_david_driver", "dla_lobpcg_driver", "dla_caslr_eff_driver", "dla_caslr_driver", "dla_call_lrprec",
     "dla_last_solve_info", "dla_set_solve_info",
 ]
@@ -152,6 +153,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dla_spmm_setup_metric_csr": (i, [vp, i, vp, vp, vp, i]), "dla_spmm_metric_info": (i, [vp, C.POINTER(SpmmInfo)]),
         "dla_spmm_drop_metric": (i, [vp]),
         "dla_spmm_bvec": (None, [c_ip, c_ip, vp, vp]), "dla_spmm_precnd_pencil": (None, [c_ip, c_ip, c_dp, vp, vp]),
+        "dla_spmm_setup_csr_dev": (i, [vp, i, i, vp, vp, vp, i]), "dla_spmm_refresh_values_dev": (i, [vp, i, i, vp, vp, vp]),
         "dla_davidson_driver": (None, [i, i, i, i, i, d, i, d, vp, vp, vp, vp, c_ip]),
         "dla_lobpcg_driver": (None, [i, i, i, i, i, i, d, d, vp, vp, vp, vp, vp, c_ip]),
         "dla_caslr_eff_driver": (None, [i, i, i, i, i, d, i, vp, vp, vp, vp, vp, vp, vp, c_ip]),
@@ -575,6 +577,46 @@ class Context:
         ci = np.ascontiguousarray(a.indices, dtype=np.int64)
         va = np.ascontiguousarray(a.data, dtype=np.float64)
         self._chk(self.lib.dla_spmm_setup_csr_sharded(self.h, a.shape[0], row0, n_global, rp.ctypes.data, ci.ctypes.data, va.ctypes.data))
+
+    @staticmethod
+    def _device_csr(who: str, crow, col, val):
+        """the three CSR tensors as the C-ABI wants them (int64 / int32 / float64, contiguous, on the GPU), converted where that loses
+        nothing and refused with a ValueError otherwise; torch's current stream is waited for, so that the arrays are complete"""
+        import torch
+        for name, t in (("crow", crow), ("col", col), ("val", val)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 1:
+                raise ValueError(f"{who}: {name} must be a one-dimensional torch tensor")
+        if crow.dtype not in (torch.int32, torch.int64) or col.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{who}: crow and col must be int32 or int64 tensors, not {crow.dtype} and {col.dtype}")
+        if not val.dtype.is_floating_point:
+            raise ValueError(f"{who}: val must be a floating-point tensor, not {val.dtype}")
+        if crow.numel() < 2:
+            raise ValueError(f"{who}: crow must hold n + 1 >= 2 row pointers")
+        dev = next((t.device for t in (val, col, crow) if t.is_cuda), torch.device("cuda"))
+        crow = crow.to(device=dev, dtype=torch.int64).contiguous()
+        if col.dtype == torch.int64 and col.numel() and (int(col.min()) < -2 ** 31 or int(col.max()) >= 2 ** 31):
+            raise ValueError(f"{who}: a column index does not fit 32 bits")
+        col = col.to(device=dev, dtype=torch.int32).contiguous()
+        val = val.to(device=dev, dtype=torch.float64).contiguous()
+        if col.numel() != val.numel() or int(crow[-1]) > col.numel() or int(crow[0]) < 0:
+            raise ValueError(f"{who}: crow describes entries that col ({col.numel()}) and val ({val.numel()}) do not hold")
+        torch.cuda.current_stream(dev).synchronize()
+        return crow, col, val
+
+    def spmm_setup_device(self, crow, col, val, fmt: str = "ell", metric: bool = False) -> None:
+        """spmm_setup (metric: spmm_setup_metric) from CSR arrays that are torch tensors on the GPU -- e.g. crow_indices(),
+        col_indices() and values() of a torch.sparse_csr_tensor: only the row pointers travel to the host.  The tensors may be
+        freed or overwritten when the call returns"""
+        if fmt not in SPMM_FORMATS:
+            raise ValueError(f"spmm_setup_device: fmt must be one of {sorted(SPMM_FORMATS)}, not {fmt!r}")
+        crow, col, val = self._device_csr("spmm_setup_device", crow, col, val)
+        self._chk(self.lib.dla_spmm_setup_csr_dev(self.h, int(bool(metric)), crow.numel() - 1, crow.data_ptr(), col.data_ptr(), val.data_ptr(),
+                                                  SPMM_FORMATS[fmt]))
+
+    def spmm_refresh_values_device(self, crow, col, val, metric: bool = False) -> None:
+        """new values for the pattern the operator (metric: the metric) was set up with; raises while the pattern differs"""
+        crow, col, val = self._device_csr("spmm_refresh_values_device", crow, col, val)
+        self._chk(self.lib.dla_spmm_refresh_values_dev(self.h, int(bool(metric)), crow.numel() - 1, crow.data_ptr(), col.data_ptr(), val.data_ptr()))
 
     def synth_matvec(self, x: DevPanel, ax: DevPanel) -> None:
         self._chk(self.lib.dla_call_matvec(self.h, fn_address("dla_synth_matvec"), x.n, x.m, x.ptr, ax.ptr))

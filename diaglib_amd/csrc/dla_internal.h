@@ -285,6 +285,11 @@ struct Engine : BlockOps {
   virtual int spmm_drop_metric() { return DLA_ERR_ARG; }
   virtual int spmm_bvec(int /*n*/, int /*m*/, const double* /*x*/, double* /*bx*/) { return DLA_ERR_ARG; }
   virtual int spmm_precnd_pencil(int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return DLA_ERR_ARG; }
+  // either matrix (which: 0 = the operator A, 1 = the metric B) from CSR arrays in DEVICE memory, and new values for a stored pattern
+  virtual int spmm_setup_csr_dev(int /*which*/, int /*n*/, const long long* /*rowptr_dev*/, const int* /*colind_dev*/, const double* /*values_dev*/,
+                                 int /*format*/) { return DLA_ERR_ARG; }
+  virtual int spmm_refresh_values_dev(int /*which*/, int /*n*/, const long long* /*rowptr_dev*/, const int* /*colind_dev*/,
+                                      const double* /*values_dev*/) { return DLA_ERR_ARG; }
 
   // Staging pipeline of host-mode callbacks: column chunks of a block travel device -> host on one copy stream, the
   // user's routine works on the chunk that has arrived, finished chunks travel host -> device on a second copy stream
@@ -474,8 +479,11 @@ inline int spmm_pick_format(int format, int w, int n, long long nnz)
   if (format != DLA_SPMM_AUTO) return format;
   return (double)w * (double)n <= SPMM_AUTO_ELL_PADDING * (double)nnz ? DLA_SPMM_ELL : DLA_SPMM_SELL;
 }
-// (the arrays have passed spmm_csr_check)
-inline void sell_build(int n, const long long* rowptr, const int* colind, const double* values, SellLayout& s)
+// The layout in two steps, so that a caller whose entries live in device memory runs the first on the row pointers alone and fills
+// the blocks there (hip_engine.hip, setup_dev): sell_layout computes everything that depends on the row LENGTHS -- perm, slice_ptr,
+// stored, the tail's rows, offsets and segment tables -- and never reads a column or a value; sell_fill scatters the entries of
+// host arrays into col / val / long_col / long_val and sums the diagonal.  (the row pointers have passed spmm_csr_check)
+inline void sell_layout(int n, const long long* rowptr, SellLayout& s)
 {
   s.n = n; s.slices = (n + SELL_C - 1) / SELL_C; s.nnz = rowptr[n] - rowptr[0];
   auto tail = [&](int i) { return rowptr[i + 1] - rowptr[i] > SELL_LONG_ROW; };
@@ -492,17 +500,15 @@ inline void sell_build(int n, const long long* rowptr, const int* colind, const 
   }
   s.stored = s.slice_ptr[s.slices];
   s.perm.assign((size_t)n, 0);
-  s.col.assign((size_t)s.stored, 0); s.val.assign((size_t)s.stored, 0.0); s.diag.assign((size_t)n, 0.0);
-  s.long_row.clear(); s.long_ptr.assign(1, 0); s.long_col.clear(); s.long_val.clear();
+  for (int slot = 0; slot < n; ++slot) s.perm[slot] = tail(order[slot]) ? ~order[slot] : order[slot];
+  s.col.clear(); s.val.clear(); s.diag.clear(); s.long_col.clear(); s.long_val.clear();
+  s.long_row.clear(); s.long_ptr.assign(1, 0);
   for (int i = 0; i < n; ++i) {
-    for (long long p = rowptr[i]; p < rowptr[i + 1]; ++p) if (colind[p] == i) s.diag[i] += values[p];
     if (!tail(i)) continue;
     s.long_row.push_back(i);
-    s.long_col.insert(s.long_col.end(), colind + rowptr[i], colind + rowptr[i + 1]);
-    s.long_val.insert(s.long_val.end(), values + rowptr[i], values + rowptr[i + 1]);
-    s.long_ptr.push_back((long long)s.long_col.size());
+    s.long_ptr.push_back(s.long_ptr.back() + (rowptr[i + 1] - rowptr[i]));
   }
-  s.long_entries = (long long)s.long_col.size();
+  s.long_entries = s.long_ptr.back();
   s.seg_ptr.assign(1, 0); s.seg_row.clear(); s.seg_part.clear(); s.multi_row.clear(); s.part_ptr.assign(1, 0);
   for (size_t r = 0; r < s.long_row.size(); ++r) {
     const long long p0 = s.long_ptr[r], p1 = s.long_ptr[r + 1];
@@ -515,14 +521,26 @@ inline void sell_build(int n, const long long* rowptr, const int* colind, const 
     if (segs > 1) { s.multi_row.push_back(s.long_row[r]); s.part_ptr.push_back(s.part_ptr.back() + segs); }
   }
   s.long_segments = (int)s.seg_row.size(); s.multi_segments = s.part_ptr.back();
+}
+// (s comes from sell_layout of the same row pointers; the columns have passed spmm_csr_check)
+inline void sell_fill(int n, const long long* rowptr, const int* colind, const double* values, SellLayout& s)
+{
+  s.col.assign((size_t)s.stored, 0); s.val.assign((size_t)s.stored, 0.0); s.diag.assign((size_t)n, 0.0);
+  s.long_col.clear(); s.long_val.clear();
+  for (int i = 0; i < n; ++i)
+    for (long long p = rowptr[i]; p < rowptr[i + 1]; ++p) if (colind[p] == i) s.diag[i] += values[p];
+  for (const int i : s.long_row) {
+    s.long_col.insert(s.long_col.end(), colind + rowptr[i], colind + rowptr[i + 1]);
+    s.long_val.insert(s.long_val.end(), values + rowptr[i], values + rowptr[i + 1]);
+  }
   for (int sl = 0; sl < s.slices; ++sl) {
     const long long base = s.slice_ptr[sl];
     const int width = (int)((s.slice_ptr[sl + 1] - base) / SELL_C);
     for (int lane = 0; lane < SELL_C; ++lane) {
       const int slot = sl * SELL_C + lane;
-      const int i = slot < n ? order[slot] : 0;          // (slots past n pad with zeros that point at row 0)
-      const int li = slot < n ? len(i) : 0;
-      if (slot < n) s.perm[slot] = tail(i) ? ~i : i;
+      const bool tail = slot < n && s.perm[slot] < 0;
+      const int i = slot < n ? (tail ? ~s.perm[slot] : s.perm[slot]) : 0;          // (slots past n pad with zeros that point at row 0)
+      const int li = (slot < n && !tail) ? (int)(rowptr[i + 1] - rowptr[i]) : 0;   // (a tail row asks nothing of its slice)
       for (int q = 0; q < width; ++q) {
         const bool in = q < li;
         s.col[(size_t)(base + (long long)q * SELL_C + lane)] = in ? colind[rowptr[i] + q] : i;
@@ -530,6 +548,11 @@ inline void sell_build(int n, const long long* rowptr, const int* colind, const 
       }
     }
   }
+}
+inline void sell_build(int n, const long long* rowptr, const int* colind, const double* values, SellLayout& s)
+{
+  sell_layout(n, rowptr, s);
+  sell_fill(n, rowptr, colind, values, s);
 }
 
 Engine* make_engine(int device, std::string& err);

@@ -1700,6 +1700,165 @@ __global__ __launch_bounds__(256) void long_rows_combine_kernel(int n, int m, in
   }
 }
 
+// ---- the same two formats filled from CSR arrays that are already in DEVICE memory (dla_spmm_setup_csr_dev), and new values for a
+// stored pattern (dla_spmm_refresh_values_dev).  The host keeps what depends on the row lengths alone (dla::sell_layout on the
+// downloaded row pointers); everything proportional to the number of entries happens here.  Every output element has one writer; the
+// only atomic is the OR into one flag word ("a column is out of range" / "the pattern differs").  Where each entry goes is spelled
+// once, in the three walkers below: f(d, p, i) is called for every stored element d of the blocks with the position p of its entry
+// in the caller's arrays, or p = -1 for padding, which is a zero that points at row i.  The fill kernels, their value-only
+// variants and the comparison of a refresh all go through them.  Positions are rowptr[i] + shift + q: shift is 0 at set-up and, at a
+// refresh, the distance between the caller's first row pointer and the stored one (the stored row pointers then index the
+// caller's arrays, whose entry count has been checked, so no read leaves them whatever the caller's row pointers hold).
+// ELLPACK, col[q n + i]: a wavefront on 64 consecutive rows, so the stores of one q are full rows of 256 / 512 bytes and the CSR
+// reads are the strided side (each lane walks its own row; neighbouring lanes of a stencil's rows sit w entries apart).
+template <class F>
+__device__ __forceinline__ void ell_walk(int n, int w, const long long* __restrict__ rowptr, long long shift, F f)
+{
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const long long p0 = rowptr[i] + shift, len = rowptr[i + 1] - rowptr[i];
+    for (int q = 0; q < w; ++q) f((size_t)q * n + i, q < len ? p0 + q : -1LL, i);
+  }
+}
+// sliced ELLPACK: one wavefront per slice, entry (q, lane) at slice_ptr[s] + 64 q + lane; a tail row asks nothing of its slice and
+// slots past n point at row 0, exactly as dla::sell_fill pads
+template <class F>
+__device__ __forceinline__ void sell_walk(int n, int slices, const long long* __restrict__ slice_ptr, const int* __restrict__ perm,
+                                          const long long* __restrict__ rowptr, long long shift, F f)
+{
+  const int lane = threadIdx.x & 63;
+  for (int s = blockIdx.x * 4 + (threadIdx.x >> 6); s < slices; s += gridDim.x * 4) {
+    const long long base = slice_ptr[s];
+    const int width = (int)((slice_ptr[s + 1] - base) >> 6);
+    const int slot = s * 64 + lane;
+    const int pr = slot < n ? perm[slot] : 0;
+    const int i = pr < 0 ? ~pr : pr;
+    const int li = (slot < n && pr >= 0) ? (int)(rowptr[i + 1] - rowptr[i]) : 0;
+    const long long p0 = rowptr[i] + shift;
+    for (int q = 0; q < width; ++q) f((size_t)(base + (long long)q * 64 + lane), q < li ? p0 + q : -1LL, i);
+  }
+}
+// the CSR tail behind the slices: one wavefront per segment, lanes striding over its entries (both sides coalesced); entry t of the
+// tail is entry t - long_ptr[r] of its row
+template <class F>
+__device__ __forceinline__ void tail_walk(int nseg, long long stored, const long long* __restrict__ seg_ptr, const int* __restrict__ seg_row,
+                                          const int* __restrict__ long_row, const long long* __restrict__ long_ptr,
+                                          const long long* __restrict__ rowptr, long long shift, F f)
+{
+  const int lane = threadIdx.x & 63;
+  for (int g = blockIdx.x * 4 + (threadIdx.x >> 6); g < nseg; g += gridDim.x * 4) {
+    const int r = seg_row[g];
+    const long long src0 = rowptr[long_row[r]] + shift - long_ptr[r];
+    for (long long t = seg_ptr[g] + lane; t < seg_ptr[g + 1]; t += 64) f((size_t)(stored + t), src0 + t, 0);
+  }
+}
+
+// every column of the caller's entries lies in [0, n): all entries, coalesced; runs (and is waited for) before any kernel indexes with them
+__global__ __launch_bounds__(256) void csr_check_cols_kernel(long long nnz, const int* __restrict__ colind, int n, unsigned* __restrict__ flag)
+{
+  bool bad = false;
+  for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < nnz; p += (long long)gridDim.x * 256) {
+    const int c = colind[p];
+    bad |= c < 0 || c >= n;
+  }
+  if (bad) atomicOr(flag, 1u);
+}
+// VALS_ONLY: the columns stay as they are (refresh)
+template <bool VALS_ONLY>
+__global__ __launch_bounds__(256) void ell_fill_kernel(int n, int w, const long long* __restrict__ rowptr, long long shift,
+                                                       const int* __restrict__ colind, const double* __restrict__ values,
+                                                       int* __restrict__ col, double* __restrict__ val)
+{
+  ell_walk(n, w, rowptr, shift, [&](size_t d, long long p, int i) {
+    if constexpr (!VALS_ONLY) col[d] = p >= 0 ? colind[p] : i;
+    val[d] = p >= 0 ? values[p] : 0.0;
+  });
+}
+template <bool VALS_ONLY>
+__global__ __launch_bounds__(256) void sell_fill_kernel(int n, int slices, const long long* __restrict__ slice_ptr, const int* __restrict__ perm,
+                                                        const long long* __restrict__ rowptr, long long shift, const int* __restrict__ colind,
+                                                        const double* __restrict__ values, int* __restrict__ col, double* __restrict__ val)
+{
+  sell_walk(n, slices, slice_ptr, perm, rowptr, shift, [&](size_t d, long long p, int i) {
+    if constexpr (!VALS_ONLY) col[d] = p >= 0 ? colind[p] : i;
+    val[d] = p >= 0 ? values[p] : 0.0;
+  });
+}
+template <bool VALS_ONLY>
+__global__ __launch_bounds__(256) void tail_copy_kernel(int nseg, long long stored, const long long* __restrict__ seg_ptr,
+                                                        const int* __restrict__ seg_row, const int* __restrict__ long_row,
+                                                        const long long* __restrict__ long_ptr, const long long* __restrict__ rowptr, long long shift,
+                                                        const int* __restrict__ colind, const double* __restrict__ values,
+                                                        int* __restrict__ col, double* __restrict__ val)
+{
+  tail_walk(nseg, stored, seg_ptr, seg_row, long_row, long_ptr, rowptr, shift, [&](size_t d, long long p, int) {
+    if constexpr (!VALS_ONLY) col[d] = colind[p];
+    val[d] = values[p];
+  });
+}
+// diag[i] = the sum of the (i, i) entries in the caller's order, from 0.0, plain additions: the bits of the host set-up.  A
+// wavefront takes 64 consecutive rows.  Each lane walks its own row while that row has at most long_len entries; a longer one is
+// never walked by one thread (a dense row of 2e6 entries took 180 ms that way in the product): the whole
+// wavefront scans it 64 entries at a time, in order, and adds the matches of each scan in ascending entry order.
+__global__ __launch_bounds__(256) void csr_diag_kernel(int n, int long_len, const long long* __restrict__ rowptr, long long shift,
+                                                       const int* __restrict__ colind, const double* __restrict__ values,
+                                                       double* __restrict__ diag)
+{
+  const int lane = threadIdx.x & 63;
+  for (long long base = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; base < n; base += (long long)gridDim.x * 256) {
+    const int i = (int)base + lane;
+    const bool live = i < n;
+    const long long p0 = live ? rowptr[i] + shift : 0, len = live ? rowptr[i + 1] - rowptr[i] : 0;
+    const bool whole_wave = len > long_len;
+    double d = 0.0;
+    if (!whole_wave)
+      for (long long p = p0; p < p0 + len; ++p) if (colind[p] == i) d += values[p];
+    unsigned long long todo = __ballot(whole_wave);
+    while (todo) {
+      const int b = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      const long long q0 = __shfl(p0, b, 64), q1 = q0 + __shfl(len, b, 64);
+      const int row = (int)base + b;
+      double sum = 0.0;
+      for (long long p = q0; p < q1; p += 64) {
+        const bool hit = p + lane < q1 && colind[p + lane] == row;
+        const double v = hit ? values[p + lane] : 0.0;
+        unsigned long long hits = __ballot(hit);
+        while (hits) {
+          const int h = __ffsll((long long)hits) - 1;
+          hits &= hits - 1;
+          sum += __shfl(v, h, 64);
+        }
+      }
+      if (lane == b) d = sum;
+    }
+    if (live) diag[i] = d;
+  }
+}
+// refresh: is the caller's pattern the stored one?  Read-only.  Bit 1 of the flag: a row of the caller's row pointers has another
+// length than the stored row; bit 2: a stored column differs from the caller's, looked up through the walkers that filled it
+// (stored row pointers, see above).  SELL: the slices and the tail; else ELLPACK.
+template <bool SELL>
+__global__ __launch_bounds__(256) void pattern_compare_kernel(int n, int w, int slices, int nseg, long long stored,
+                                                              const long long* __restrict__ slice_ptr, const int* __restrict__ perm,
+                                                              const long long* __restrict__ seg_ptr, const int* __restrict__ seg_row,
+                                                              const int* __restrict__ long_row, const long long* __restrict__ long_ptr,
+                                                              const long long* __restrict__ rowptr, long long shift,
+                                                              const long long* __restrict__ rowptr_new, const int* __restrict__ colind,
+                                                              const int* __restrict__ col, unsigned* __restrict__ flag)
+{
+  unsigned bad = 0;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
+    if (rowptr_new[i + 1] - rowptr_new[i] != rowptr[i + 1] - rowptr[i]) bad |= 1u;
+  auto same = [&](size_t d, long long p, int) { if (p >= 0 && col[d] != colind[p]) bad |= 2u; };
+  if constexpr (SELL) {
+    sell_walk(n, slices, slice_ptr, perm, rowptr, shift, same);
+    tail_walk(nseg, stored, seg_ptr, seg_row, long_row, long_ptr, rowptr, shift, same);
+  } else {
+    ell_walk(n, w, rowptr, shift, same);
+  }
+  if (bad) atomicOr(flag, bad);
+}
+
 // px = x / (d + fac) where |d + fac| > 1e-5, else x: the harness' diagonal preconditioner (main.f90:161-169) on the
 // diagonal of the sparse operator
 __global__ void diag_precnd_kernel(int n, int m, double fac, const double* __restrict__ diag, const double* __restrict__ x,
@@ -5482,11 +5641,13 @@ struct HipEngine : dla::Engine {
     DeviceBuffer<long long> sell_ptr, seg_ptr;
     DeviceBuffer<int> sell_perm, long_row, seg_row, seg_part, multi_row, part_ptr;
     DeviceBuffer<double> long_part;    // partial sums of the rows of more than one segment: multi_segments x m, grown by the product
+    // what only a refresh of the values reads (refresh_dev): the caller's row pointers [n + 1] and the tail rows' offsets [long_rows + 1]
+    DeviceBuffer<long long> rowptr, long_ptr;
     // give the device blocks back (the caller has waited for the stream)
     void drop()
     {
       col.reset(); val.reset(); diag.reset(); sell_ptr.reset(); seg_ptr.reset(); sell_perm.reset(); long_row.reset();
-      seg_row.reset(); seg_part.reset(); multi_row.reset(); part_ptr.reset(); long_part.reset();
+      seg_row.reset(); seg_part.reset(); multi_row.reset(); part_ptr.reset(); long_part.reset(); rowptr.reset(); long_ptr.reset();
       n = w = 0; fmt = -1; nnz = sell_stored = sell_long_entries = 0; sell_slices = sell_long_rows = 0;
       sell_long_segments = sell_multi_rows = sell_multi_segments = 0;
     }
@@ -5540,6 +5701,8 @@ struct HipEngine : dla::Engine {
     }
     HIPCHK(hipSetDevice(device));
     { const int stc = upload_ell(op, col, val, diag); if (stc) return stc; }
+    HIPCHK(op.rowptr.reserve((size_t)n + 1));
+    HIPCHK(hipMemcpy(op.rowptr, rowptr, sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice));
     op.n = n; op.w = w;
     op.fmt = DLA_SPMM_ELL; op.nnz = rowptr[n] - rowptr[0];
     return DLA_OK;
@@ -5553,16 +5716,11 @@ struct HipEngine : dla::Engine {
   // ---- ... as sliced ELLPACK with a CSR tail (dla::sell_build).  The slices and the tail share the ELLPACK blocks -- columns and
   // values of the tail follow the `stored` padded entries of the slices -- so either format replaces the other in place.
   static constexpr int SELL_MC = 8, LONG_MC = 4;   // right-hand sides per load of a matrix entry (sell_spmm_kernel / csr_long_segments_kernel)
-  int setup_fmt(SparseOp& op, int n, const long long* rowptr, const int* colind, const double* values, int format)
+  // room for a sliced layout in op's blocks and the layout's small tables (everything but the entries and the diagonal); rowptr: host.
+  // The caller has bound the device and waited for the stream.
+  int place_sell(SparseOp& op, int n, const dla::SellLayout& L, const long long* rowptr)
   {
-    int w = 0; long long nnz = 0;
-    { const int stc = dla::spmm_csr_check(n, rowptr, colind, values, format, &w, &nnz, err); if (stc) return stc; }
-    if (dla::spmm_pick_format(format, w, n, nnz) == DLA_SPMM_ELL) return setup_ell(op, n, rowptr, colind, values);
-    dla::SellLayout L;
-    dla::sell_build(n, rowptr, colind, values, L);
     const size_t tot = (size_t)(L.stored + L.long_entries), nl = L.long_row.size(), ns = L.seg_row.size(), nm = L.multi_row.size();
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipStreamSynchronize(st));
     HIPCHK(op.col.reserve(tot));
     HIPCHK(op.val.reserve(tot));
     HIPCHK(op.diag.reserve((size_t)n));
@@ -5574,12 +5732,9 @@ struct HipEngine : dla::Engine {
     HIPCHK(op.seg_part.reserve(std::max<size_t>(1, ns)));
     HIPCHK(op.multi_row.reserve(std::max<size_t>(1, nm)));
     HIPCHK(op.part_ptr.reserve(nm + 1));
+    HIPCHK(op.rowptr.reserve((size_t)n + 1));
+    HIPCHK(op.long_ptr.reserve(nl + 1));
     auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
-    HIPCHK(up(op.col, L.col.data(), sizeof(int) * L.col.size()));
-    HIPCHK(up(op.val, L.val.data(), sizeof(double) * L.val.size()));
-    HIPCHK(up(op.col + L.stored, L.long_col.data(), sizeof(int) * L.long_col.size()));
-    HIPCHK(up(op.val + L.stored, L.long_val.data(), sizeof(double) * L.long_val.size()));
-    HIPCHK(up(op.diag, L.diag.data(), sizeof(double) * (size_t)n));
     HIPCHK(up(op.sell_ptr, L.slice_ptr.data(), sizeof(long long) * L.slice_ptr.size()));
     HIPCHK(up(op.sell_perm, L.perm.data(), sizeof(int) * (size_t)n));
     HIPCHK(up(op.long_row, L.long_row.data(), sizeof(int) * nl));
@@ -5588,10 +5743,181 @@ struct HipEngine : dla::Engine {
     HIPCHK(up(op.seg_part, L.seg_part.data(), sizeof(int) * ns));
     HIPCHK(up(op.multi_row, L.multi_row.data(), sizeof(int) * nm));
     HIPCHK(up(op.part_ptr, L.part_ptr.data(), sizeof(int) * (nm + 1)));
+    HIPCHK(up(op.rowptr, rowptr, sizeof(long long) * ((size_t)n + 1)));
+    HIPCHK(up(op.long_ptr, L.long_ptr.data(), sizeof(long long) * (nl + 1)));
+    return DLA_OK;
+  }
+  // op holds the sliced layout L from now on
+  static void hold_sell(SparseOp& op, int n, const dla::SellLayout& L)
+  {
     op.n = n; op.w = 0;
-    op.fmt = DLA_SPMM_SELL; op.nnz = nnz; op.sell_stored = L.stored; op.sell_long_entries = L.long_entries;
-    op.sell_slices = L.slices; op.sell_long_rows = (int)nl;
-    op.sell_long_segments = L.long_segments; op.sell_multi_rows = (int)nm; op.sell_multi_segments = L.multi_segments;
+    op.fmt = DLA_SPMM_SELL; op.nnz = L.nnz; op.sell_stored = L.stored; op.sell_long_entries = L.long_entries;
+    op.sell_slices = L.slices; op.sell_long_rows = (int)L.long_row.size();
+    op.sell_long_segments = L.long_segments; op.sell_multi_rows = (int)L.multi_row.size(); op.sell_multi_segments = L.multi_segments;
+  }
+  int setup_fmt(SparseOp& op, int n, const long long* rowptr, const int* colind, const double* values, int format)
+  {
+    int w = 0; long long nnz = 0;
+    { const int stc = dla::spmm_csr_check(n, rowptr, colind, values, format, &w, &nnz, err); if (stc) return stc; }
+    if (dla::spmm_pick_format(format, w, n, nnz) == DLA_SPMM_ELL) return setup_ell(op, n, rowptr, colind, values);
+    dla::SellLayout L;
+    dla::sell_build(n, rowptr, colind, values, L);
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipStreamSynchronize(st));
+    { const int stc = place_sell(op, n, L, rowptr); if (stc) return stc; }
+    auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
+    HIPCHK(up(op.col, L.col.data(), sizeof(int) * L.col.size()));
+    HIPCHK(up(op.val, L.val.data(), sizeof(double) * L.val.size()));
+    HIPCHK(up(op.col + L.stored, L.long_col.data(), sizeof(int) * L.long_col.size()));
+    HIPCHK(up(op.val + L.stored, L.long_val.data(), sizeof(double) * L.long_val.size()));
+    HIPCHK(up(op.diag, L.diag.data(), sizeof(double) * (size_t)n));
+    hold_sell(op, n, L);
+    return DLA_OK;
+  }
+  // ---- ... and from CSR arrays in DEVICE memory (dla_spmm_setup_csr_dev), with the result of setup_fmt for the same arrays: the row
+  // pointers come to the host (8 (n + 1) bytes, the only transfer that grows with n), where the checks on them, the choice of the
+  // format and dla::sell_layout run as they do above; the entries never leave the device (the kernels beside ell_spmm_kernel).
+  // Order of the launches: csr_check_cols_kernel runs alone and is waited for; while a column is out of range nothing else is
+  // launched, so no kernel ever indexes with an unchecked column (the fill kernels only copy columns, the product gathers with
+  // them) and nothing of the slot has been touched -- not even grown, which would discard its blocks.  Synchronous: the call
+  // returns after the stream has been waited for.  The set-up kernels are not booked into the statistics (the host set-up is not).
+  DeviceBuffer<unsigned> d_setup_flag;
+  // flag word <- 0 / flag word -> host, behind what is queued on the stream
+  int flag_clear()
+  {
+    HIPCHK(d_setup_flag.reserve(1));
+    HIPCHK(hipMemsetAsync(d_setup_flag, 0, sizeof(unsigned), st));
+    return DLA_OK;
+  }
+  int flag_read(unsigned* out)
+  {
+    HIPCHK(hipMemcpyAsync(out, d_setup_flag, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return DLA_OK;
+  }
+  // the entries of the caller's arrays into op's blocks (VALS_ONLY: the values alone) and the diagonal, in the format op holds;
+  // rowptr (device) and shift as the walkers take them
+  template <bool VALS_ONLY>
+  int fill_from_device(SparseOp& op, const long long* rowptr, long long shift, const int* colind, const double* values)
+  {
+    const bool sell = op.fmt == DLA_SPMM_SELL;
+    const SpmmSetupPlan p = spmm_setup_plan(env(), op.n, op.nnz, sell ? op.sell_slices : 0, sell ? op.sell_long_segments : 0);
+    if (sell) {
+      DLA_LAUNCH((sell_fill_kernel<VALS_ONLY>), dim3(p.slice_blocks), dim3(256), 0, st, op.n, op.sell_slices, (const long long*)op.sell_ptr,
+                 (const int*)op.sell_perm, rowptr, shift, colind, values, (int*)op.col, (double*)op.val);
+      HIPCHK(hipGetLastError());
+      if (p.seg_blocks > 0) {
+        DLA_LAUNCH((tail_copy_kernel<VALS_ONLY>), dim3(p.seg_blocks), dim3(256), 0, st, op.sell_long_segments, op.sell_stored,
+                   (const long long*)op.seg_ptr, (const int*)op.seg_row, (const int*)op.long_row, (const long long*)op.long_ptr, rowptr, shift,
+                   colind, values, (int*)op.col, (double*)op.val);
+        HIPCHK(hipGetLastError());
+      }
+    } else {
+      DLA_LAUNCH((ell_fill_kernel<VALS_ONLY>), dim3(p.row_blocks), dim3(256), 0, st, op.n, op.w, rowptr, shift, colind, values, (int*)op.col,
+                 (double*)op.val);
+      HIPCHK(hipGetLastError());
+    }
+    DLA_LAUNCH(csr_diag_kernel, dim3(p.row_blocks), dim3(256), 0, st, op.n, dla::SELL_LONG_ROW, rowptr, shift, colind, values, (double*)op.diag);
+    HIPCHK(hipGetLastError());
+    return DLA_OK;
+  }
+  int setup_dev(SparseOp& op, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev, int format)
+  {
+    if (format != DLA_SPMM_ELL && format != DLA_SPMM_SELL && format != DLA_SPMM_AUTO) { err = "spmm_setup_csr_dev: unknown format"; return DLA_ERR_ARG; }
+    if (n <= 0 || !rowptr_dev || !colind_dev || !values_dev) { err = "spmm_setup_csr_dev: bad arguments"; return DLA_ERR_ARG; }
+    bind();
+    const double t_host = dla::ApiTimer::on() ? dla::ApiTimer::now() : 0.0;
+    std::vector<long long> rp((size_t)n + 1);
+    HIPCHK(hipMemcpyAsync(rp.data(), rowptr_dev, sizeof(long long) * rp.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));       // (queued products of the slot's previous matrix are done as well)
+    int w = 0;
+    for (int i = 0; i < n; ++i) {
+      if (rp[i + 1] < rp[i]) { err = "spmm_setup_csr_dev: row pointers not ascending"; return DLA_ERR_ARG; }
+      if (rp[i + 1] - rp[i] > w) w = (int)std::min<long long>(rp[i + 1] - rp[i], 2147483647LL);
+    }
+    if (w <= 0) { err = "spmm_setup_csr_dev: empty matrix"; return DLA_ERR_ARG; }
+    if (rp[0] < 0) { err = "spmm_setup_csr_dev: bad arguments"; return DLA_ERR_ARG; }      // (the host entry would read in front of its arrays)
+    const long long nnz = rp[n] - rp[0];
+    const bool sell = dla::spmm_pick_format(format, w, n, nnz) == DLA_SPMM_SELL;
+    dla::SellLayout L;
+    if (sell) dla::sell_layout(n, rp.data(), L);
+    // ($DIAGLIB_AMD_HOSTTIME: what of this call is still host work, for tools/time_spmm_setup.py)
+    if (dla::ApiTimer::on()) dla::ApiTimer::add(sell ? "  spmm_setup_csr_dev host part, sell" : "  spmm_setup_csr_dev host part, ell", dla::ApiTimer::now() - t_host);
+    // every check that reads the entries, before the first write into the slot (see above)
+    {
+      const SpmmSetupPlan p = spmm_setup_plan(env(), n, nnz, 0, 0);
+      unsigned bad = 0;
+      { const int stc = flag_clear(); if (stc) return stc; }
+      DLA_LAUNCH(csr_check_cols_kernel, dim3(p.entry_blocks), dim3(256), 0, st, nnz, colind_dev + rp[0], n, (unsigned*)d_setup_flag);
+      HIPCHK(hipGetLastError());
+      { const int stc = flag_read(&bad); if (stc) return stc; }
+      if (bad) { err = "spmm_setup_csr_dev: column index out of range"; return DLA_ERR_ARG; }
+    }
+    if (sell) {
+      { const int stc = place_sell(op, n, L, rp.data()); if (stc) return stc; }
+      hold_sell(op, n, L);
+    } else {
+      HIPCHK(op.col.reserve((size_t)w * n));
+      HIPCHK(op.val.reserve((size_t)w * n));
+      HIPCHK(op.diag.reserve((size_t)n));
+      HIPCHK(op.rowptr.reserve((size_t)n + 1));
+      HIPCHK(hipMemcpy(op.rowptr, rp.data(), sizeof(long long) * rp.size(), hipMemcpyHostToDevice));
+      op.n = n; op.w = w;
+      op.fmt = DLA_SPMM_ELL; op.nnz = nnz;
+    }
+    { const int stc = fill_from_device<false>(op, rowptr_dev, 0, colind_dev, values_dev); if (stc) return stc; }
+    HIPCHK(hipStreamSynchronize(st));       // (the caller may free or overwrite its arrays from here on)
+    return DLA_OK;
+  }
+  int spmm_setup_csr_dev(int which, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev, int format) override
+  {
+    if (which != 0 && which != 1) { err = "spmm_setup_csr_dev: which must be 0 (the operator) or 1 (the metric)"; return DLA_ERR_ARG; }
+    if (which == 1 && shard.on) { err = "spmm_setup_csr_dev: the operator of this context is row-sharded, and a row-sharded metric is not supported"; return DLA_ERR_ARG; }
+    { const int stc = setup_dev(which ? op_b : op_a, n, rowptr_dev, colind_dev, values_dev, format); if (stc) return stc; }
+    if (which == 0) shard.drop();
+    return DLA_OK;
+  }
+  // new values for the pattern a slot holds: everything is compared in a read-only pass (pattern_compare_kernel) that is waited
+  // for before the first value is written; the stored format stays (AUTO is not decided again).  Synchronous like the set-up.
+  int spmm_refresh_values_dev(int which, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev) override
+  {
+    if (which != 0 && which != 1) { err = "spmm_refresh_values_dev: which must be 0 (the operator) or 1 (the metric)"; return DLA_ERR_ARG; }
+    SparseOp& op = which ? op_b : op_a;
+    if (op.fmt < 0) { err = which ? "spmm_refresh_values_dev: no metric has been set up" : "spmm_refresh_values_dev: no operator has been set up"; return DLA_ERR_ARG; }
+    if (which == 0 && shard.on) { err = "spmm_refresh_values_dev: the operator of this context is row-sharded"; return DLA_ERR_ARG; }
+    if (n <= 0 || !rowptr_dev || !colind_dev || !values_dev) { err = "spmm_refresh_values_dev: bad arguments"; return DLA_ERR_ARG; }
+    if (n != op.n) { err = "spmm_refresh_values_dev: n = " + std::to_string(n) + " differs from the stored " + std::to_string(op.n); return DLA_ERR_ARG; }
+    bind();
+    long long ends[2] = {0, 0}, first_stored = 0;
+    HIPCHK(hipMemcpyAsync(&ends[0], rowptr_dev, sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&ends[1], rowptr_dev + n, sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&first_stored, (const long long*)op.rowptr, sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ends[0] < 0 || ends[1] - ends[0] != op.nnz) {
+      err = "spmm_refresh_values_dev: " + std::to_string(ends[1] - ends[0]) + " entries, the stored matrix has " + std::to_string(op.nnz);
+      return DLA_ERR_ARG;
+    }
+    // (the stored row pointers index the caller's arrays from here on: rowptr[i] + shift, all inside the nnz entries just checked)
+    const long long shift = ends[0] - first_stored;
+    const bool sell = op.fmt == DLA_SPMM_SELL;
+    const SpmmSetupPlan p = spmm_setup_plan(env(), n, op.nnz, sell ? op.sell_slices : 0, sell ? op.sell_long_segments : 0);
+    const int blocks = std::max(p.row_blocks, std::max(p.slice_blocks, p.seg_blocks));
+    unsigned bad = 0;
+    { const int stc = flag_clear(); if (stc) return stc; }
+#define CMP(S) DLA_LAUNCH((pattern_compare_kernel<S>), dim3(blocks), dim3(256), 0, st, n, op.w, op.sell_slices, op.sell_long_segments, op.sell_stored, \
+                          (const long long*)op.sell_ptr, (const int*)op.sell_perm, (const long long*)op.seg_ptr, (const int*)op.seg_row,              \
+                          (const int*)op.long_row, (const long long*)op.long_ptr, (const long long*)op.rowptr, shift, rowptr_dev, colind_dev,       \
+                          (const int*)op.col, (unsigned*)d_setup_flag)
+    if (sell) CMP(true); else CMP(false);
+#undef CMP
+    HIPCHK(hipGetLastError());
+    { const int stc = flag_read(&bad); if (stc) return stc; }
+    if (bad) {
+      err = (bad & 1u) ? "spmm_refresh_values_dev: the row pointers are not the stored pattern's" : "spmm_refresh_values_dev: the columns are not the stored pattern's";
+      return DLA_ERR_ARG;
+    }
+    { const int stc = fill_from_device<true>(op, (const long long*)op.rowptr, shift, colind_dev, values_dev); if (stc) return stc; }
+    HIPCHK(hipStreamSynchronize(st));
     return DLA_OK;
   }
   int spmm_setup_csr_fmt(int n, const long long* rowptr, const int* colind, const double* values, int format) override

@@ -460,6 +460,30 @@ inline LongRowsPlan long_rows_plan(const PlanEnv& env, int long_segments, int mu
   return p;
 }
 
+// ---- set-up of the sparse operator from CSR arrays in device memory (csr_check_cols_kernel, ell_fill_kernel, sell_fill_kernel,
+// tail_copy_kernel, csr_diag_kernel, pattern_compare_kernel)
+// All of them are grid-stride over blocks of 256 threads under the cap of the other operator kernels, 8 blocks per CU: one thread per
+// entry (the column check), one thread per row with a wavefront on 64 consecutive rows (the ELLPACK fill, the diagonal, the row
+// pointers of the comparison), one wavefront per slice and per segment of a tail row, four to a block (the sliced fill, the tail).
+// A function of the counts alone: n rows, nnz entries, and the layout's slices and tail segments (both 0 for ELLPACK).
+struct SpmmSetupPlan {
+  int entry_blocks;      // csr_check_cols_kernel (>= 1)
+  int row_blocks;        // ell_fill_kernel, csr_diag_kernel, the row part of pattern_compare_kernel (>= 1)
+  int slice_blocks;      // sell_fill_kernel; 0: ELLPACK, nothing is launched
+  int seg_blocks;        // tail_copy_kernel; 0: no tail, nothing is launched
+};
+inline SpmmSetupPlan spmm_setup_plan(const PlanEnv& env, long long n, long long nnz, long long slices, long long long_segments)
+{
+  const long long cap = std::max(1LL, (long long)env.ncu * 8);
+  auto blocks = [&](long long items, long long per_block) { return (int)std::max(1LL, std::min(cap, (items + per_block - 1) / per_block)); };
+  SpmmSetupPlan p{};
+  p.entry_blocks = blocks(nnz, 256);
+  p.row_blocks = blocks(n, 256);
+  p.slice_blocks = slices > 0 ? blocks(slices, 4) : 0;
+  p.seg_blocks = long_segments > 0 ? blocks(long_segments, 4) : 0;
+  return p;
+}
+
 // ---- the orthogonalisation chain
 // The sweeps of a chain, as the host plans them and as the tail kernels name the next one in device memory (OrthoDev::phase).
 // OP_GRAMX / OP_GRAMW / OP_XW belong to the pending-factor schedule (k <= 16, even n; see ortho_tail16): X^T U and U^T U in one

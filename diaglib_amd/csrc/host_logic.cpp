@@ -1928,4 +1928,22 @@ void dla_spmm_precnd_pencil(const int* n, const int* m, const double* fac, const
   if (int st = c->eng->spmm_precnd_pencil(*n, *m, *fac, x, px)) callback_failed(st, "dla_spmm_precnd_pencil failed: " + c->eng->err);
 }
 
+// ---- ... either of the two from CSR arrays in device memory, and new values for a stored pattern
+int dla_spmm_setup_csr_dev(dla_ctx* c, int which, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev, int format)
+{
+  DLA_T("dla_spmm_setup_csr_dev");
+  if (!c) return DLA_ERR_ARG;
+  if (which == 0) g_spmm_ctx = c;       // (as dla_spmm_setup_csr_fmt / dla_spmm_setup_metric_csr treat the thread's context)
+  const int st = engfail(c, c->eng->spmm_setup_csr_dev(which, n, rowptr_dev, colind_dev, values_dev, format));
+  if (st == DLA_OK) g_spmm_ctx = c;
+  return st;
+}
+
+int dla_spmm_refresh_values_dev(dla_ctx* c, int which, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev)
+{
+  DLA_T("dla_spmm_refresh_values_dev");
+  if (!c) return DLA_ERR_ARG;
+  return engfail(c, c->eng->spmm_refresh_values_dev(which, n, rowptr_dev, colind_dev, values_dev));
+}
+
 }  // extern "C"

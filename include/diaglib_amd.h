@@ -478,7 +478,27 @@ void dla_set_solve_info(int iters, int matvec_cols, int restarts);   /* used by 
  * (main.f90:491-492, 511-512); dla_spmm_precnd_pencil divides by the diagonal of the pencil, a_ii + fac b_ii, instead and needs
  * both matrices with the same n.  A callback that finds its matrix missing, or another n, fails through the status of
  * dla_call_matvec / dla_call_precnd with a message that names it.  A row-sharded metric is out of scope: the metric is refused
- * on a context whose operator came from dla_spmm_setup_csr_sharded, and that setup is refused while a metric is present. */
+ * on a context whose operator came from dla_spmm_setup_csr_sharded, and that setup is refused while a metric is present.
+ * Arrays that are already in device memory (dla_spmm_setup_csr_dev, single rank; which = 0: the operator A, 1: the metric B), for
+ * callers that assemble on the GPU: the three arrays are DEVICE addresses of the layout above (rowptr n + 1 x int64, colind nnz x
+ * int32, values nnz x double, 0-based).  The result is exactly what dla_spmm_setup_csr_fmt / dla_spmm_setup_metric_csr give for the
+ * same arrays and format: dla_spmm_info / dla_spmm_metric_info equal field by field, and every later dla_spmm_matvec, dla_spmm_bvec,
+ * dla_spmm_precnd and dla_spmm_precnd_pencil returns the same bits; diag[i] is the sum of the (i, i) entries in the caller's order,
+ * duplicates and tail rows included.  Only the row pointers travel to the host (8 (n + 1) bytes), where the layout is decided as
+ * for host arrays; the entries are checked, rearranged and summed by kernels.  Synchronous: the arrays are read on the context's
+ * stream (dla_stream) and the call returns after that stream has been waited for, so the caller may free or overwrite them
+ * afterwards; the caller is responsible for its own producer of the arrays having finished before the call (the library does not
+ * know the stream they were written on).  Refused (DLA_ERR_ARG, the message names dla_spmm_setup_csr_dev) like the host entries:
+ * null pointers, n <= 0, an unknown format, descending row pointers, an empty matrix, a column outside [0, n), which not 0 or 1,
+ * and a metric on a row-sharded operator.  Every check that reads the entries has finished before the slot's blocks are written
+ * or grown: after a refused call the products of the slot's previous matrix are bit-unchanged.
+ * New values for the same pattern (dla_spmm_refresh_values_dev), for callers whose matrix changes per outer iteration while its
+ * pattern does not: rewrites only the stored values and the diagonal of slot `which`, in the stored format (AUTO is not decided
+ * again; the slot may have been set up from host or device arrays).  Afterwards the slot equals, bit for bit, a fresh set-up of
+ * the same arrays in that format.  Refused with DLA_ERR_ARG when the slot is empty, when it is row-sharded, when n or the number
+ * of entries differs from the stored one, or when the pattern -- the length of every row and every column index, in the caller's
+ * order -- is not the stored one; the pattern is compared in a read-only pass before anything is written, so a refused refresh
+ * leaves values and diagonal as they were.  Synchronous like the set-up, with the same rule for the caller's producer. */
 enum { DLA_SPMM_ELL = 0, DLA_SPMM_SELL = 1, DLA_SPMM_AUTO = 2 };
 /* what the calling context's operator occupies (a struct tag only: C keeps tags apart from the function of the same name) */
 struct dla_spmm_info {
@@ -513,6 +533,13 @@ int  dla_spmm_drop_metric(dla_ctx* ctx);                              /* frees B
 void dla_spmm_bvec(const int* n, const int* m, const double* x_dev, double* bx_dev);          /* bx = B x */
 void dla_spmm_precnd_pencil(const int* n, const int* m, const double* fac, const double* x_dev, double* px_dev);
                                           /* px = x / (a_ii + fac b_ii) where |a_ii + fac b_ii| > 1e-5, else x */
+/* which: 0 = the operator A, 1 = the metric B.  All three arrays are DEVICE addresses: rowptr n+1 x int64, colind nnz x int32,
+   values nnz x double; 0-based; format as in dla_spmm_setup_csr_fmt (ELL / SELL / AUTO); single rank. */
+int  dla_spmm_setup_csr_dev(dla_ctx* ctx, int which, int n, const long long* rowptr_dev, const int* colind_dev,
+                            const double* values_dev, int format);
+/* the same matrix pattern with new values: rewrites only the stored values and the diagonal of slot `which` */
+int  dla_spmm_refresh_values_dev(dla_ctx* ctx, int which, int n, const long long* rowptr_dev, const int* colind_dev,
+                                 const double* values_dev);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,8 @@ EXPORTS = [
     "dla_synth_metric", "dla_synth_lrprec1", "dla_synth_lrprec2", "dla_pending_factor", "dla_pending_block", "dla_basis_admit", "dla_basis_fold", "dla_basis_sync", "dla_spmm_setup_csr", "dla_spmm_setup_csr_fmt", "dla_spmm_info", "dla_spmm_setup_csr_sharded", "dla_spmm_matvec", "dla_spmm_precnd",
     "dla_spmm_setup_metric_csr", "dla_spmm_metric_info", "dla_spmm_drop_metric", "dla_spmm_bvec", "dla_spmm_precnd_pencil",
     "dla_spmm_setup_csr_dev", "dla_spmm_refresh_values_dev",
+    "dla_spmm_setup_lr_csr", "dla_spmm_setup_lr_csr_dev", "dla_spmm_refresh_lr_values_dev", "dla_spmm_lr_info", "dla_spmm_drop_lr",
+    "dla_spmm_apbmul", "dla_spmm_ambmul", "dla_spmm_spdmul", "dla_spmm_smdmul", "dla_spmm_lrprec1", "dla_spmm_lrprec2",
     "dla_davidson_driver", "dla_gen_david_driver", "dla_lobpcg_driver", "dla_caslr_eff_driver", "dla_caslr_driver", "dla_call_lrprec",
     "dla_last_solve_info", "dla_set_solve_info",
 ]
@@ -69,6 +71,8 @@ class KernelStat(C.Structure):
 
 SPMM_ELL, SPMM_SELL, SPMM_AUTO = 0, 1, 2
 SPMM_FORMATS = {"ell": SPMM_ELL, "sell": SPMM_SELL, "auto": SPMM_AUTO}
+# the parts of a linear-response pencil (DLA_SPMM_LR_APB .. _SMD): A+B, A-B, S+D, S-D
+SPMM_LR_PARTS = {"apb": 0, "amb": 1, "spd": 2, "smd": 3}
 
 
 class SpmmInfo(C.Structure):
@@ -154,6 +158,12 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dla_spmm_drop_metric": (i, [vp]),
         "dla_spmm_bvec": (None, [c_ip, c_ip, vp, vp]), "dla_spmm_precnd_pencil": (None, [c_ip, c_ip, c_dp, vp, vp]),
         "dla_spmm_setup_csr_dev": (i, [vp, i, i, vp, vp, vp, i]), "dla_spmm_refresh_values_dev": (i, [vp, i, i, vp, vp, vp]),
+        "dla_spmm_setup_lr_csr": (i, [vp, i, i, vp, vp, vp, i]), "dla_spmm_setup_lr_csr_dev": (i, [vp, i, i, vp, vp, vp, i]),
+        "dla_spmm_refresh_lr_values_dev": (i, [vp, i, i, vp, vp, vp]), "dla_spmm_lr_info": (i, [vp, i, C.POINTER(SpmmInfo)]),
+        "dla_spmm_drop_lr": (i, [vp]),
+        "dla_spmm_apbmul": (None, [c_ip, c_ip, vp, vp]), "dla_spmm_ambmul": (None, [c_ip, c_ip, vp, vp]),
+        "dla_spmm_spdmul": (None, [c_ip, c_ip, vp, vp]), "dla_spmm_smdmul": (None, [c_ip, c_ip, vp, vp]),
+        "dla_spmm_lrprec1": (None, [c_ip, c_ip, c_dp, vp, vp, vp, vp]), "dla_spmm_lrprec2": (None, [c_ip, c_ip, c_dp, vp, vp, vp, vp]),
         "dla_davidson_driver": (None, [i, i, i, i, i, d, i, d, vp, vp, vp, vp, c_ip]),
         "dla_lobpcg_driver": (None, [i, i, i, i, i, i, d, d, vp, vp, vp, vp, vp, c_ip]),
         "dla_caslr_eff_driver": (None, [i, i, i, i, i, d, i, vp, vp, vp, vp, vp, vp, vp, c_ip]),
@@ -617,6 +627,55 @@ class Context:
         """new values for the pattern the operator (metric: the metric) was set up with; raises while the pattern differs"""
         crow, col, val = self._device_csr("spmm_refresh_values_device", crow, col, val)
         self._chk(self.lib.dla_spmm_refresh_values_dev(self.h, int(bool(metric)), crow.numel() - 1, crow.data_ptr(), col.data_ptr(), val.data_ptr()))
+
+    # ---- the four sparse parts of a linear-response pencil (dla_spmm_apbmul .. dla_spmm_smdmul, dla_spmm_lrprec1 / 2)
+    @staticmethod
+    def _lr_part(who: str, part) -> int:
+        if isinstance(part, str):
+            if part not in SPMM_LR_PARTS:
+                raise ValueError(f"{who}: part must be one of {sorted(SPMM_LR_PARTS)} or 0 .. 3, not {part!r}")
+            return SPMM_LR_PARTS[part]
+        return int(part)
+
+    def spmm_setup_lr(self, part, a, fmt: str = "ell") -> None:
+        """hand a scipy.sparse matrix (square; need not be symmetric) to this context as one part of the linear-response pencil:
+        part = "apb" (A+B), "amb" (A-B), "spd" (S+D), "smd" (S-D) or 0 .. 3; fmt as in spmm_setup.  Independent of the operator,
+        the metric and the other parts"""
+        if fmt not in SPMM_FORMATS:
+            raise ValueError(f"spmm_setup_lr: fmt must be one of {sorted(SPMM_FORMATS)}, not {fmt!r}")
+        part = self._lr_part("spmm_setup_lr", part)
+        a = a.tocsr()
+        rp = np.ascontiguousarray(a.indptr, dtype=np.int64)
+        ci = np.ascontiguousarray(a.indices, dtype=np.int32)
+        va = np.ascontiguousarray(a.data, dtype=np.float64)
+        self._chk(self.lib.dla_spmm_setup_lr_csr(self.h, part, a.shape[0], rp.ctypes.data, ci.ctypes.data, va.ctypes.data, SPMM_FORMATS[fmt]))
+
+    def spmm_setup_lr_device(self, part, crow, col, val, fmt: str = "ell") -> None:
+        """spmm_setup_lr from CSR arrays that are torch tensors on the GPU (as spmm_setup_device)"""
+        if fmt not in SPMM_FORMATS:
+            raise ValueError(f"spmm_setup_lr_device: fmt must be one of {sorted(SPMM_FORMATS)}, not {fmt!r}")
+        part = self._lr_part("spmm_setup_lr_device", part)
+        crow, col, val = self._device_csr("spmm_setup_lr_device", crow, col, val)
+        self._chk(self.lib.dla_spmm_setup_lr_csr_dev(self.h, part, crow.numel() - 1, crow.data_ptr(), col.data_ptr(), val.data_ptr(),
+                                                     SPMM_FORMATS[fmt]))
+
+    def spmm_refresh_lr_values_device(self, part, crow, col, val) -> None:
+        """new values for the pattern that part was set up with; raises while the pattern differs"""
+        part = self._lr_part("spmm_refresh_lr_values_device", part)
+        crow, col, val = self._device_csr("spmm_refresh_lr_values_device", crow, col, val)
+        self._chk(self.lib.dla_spmm_refresh_lr_values_dev(self.h, part, crow.numel() - 1, crow.data_ptr(), col.data_ptr(), val.data_ptr()))
+
+    def spmm_lr_info(self, part) -> dict:
+        """spmm_info of one part; raises while that part is empty"""
+        o = SpmmInfo()
+        self._chk(self.lib.dla_spmm_lr_info(self.h, self._lr_part("spmm_lr_info", part), C.byref(o)))
+        d = {name: int(getattr(o, name)) for name, _ in SpmmInfo._fields_}
+        d["format"] = {v: k for k, v in SPMM_FORMATS.items()}[d["format"]]
+        return d
+
+    def spmm_drop_lr(self) -> None:
+        """free the device blocks of all four parts (nothing happens without any); operator and metric stay as they are"""
+        self._chk(self.lib.dla_spmm_drop_lr(self.h))
 
     def synth_matvec(self, x: DevPanel, ax: DevPanel) -> None:
         self._chk(self.lib.dla_call_matvec(self.h, fn_address("dla_synth_matvec"), x.n, x.m, x.ptr, ax.ptr))

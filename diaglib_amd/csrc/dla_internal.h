@@ -290,6 +290,19 @@ struct Engine : BlockOps {
                                  int /*format*/) { return DLA_ERR_ARG; }
   virtual int spmm_refresh_values_dev(int /*which*/, int /*n*/, const long long* /*rowptr_dev*/, const int* /*colind_dev*/,
                                       const double* /*values_dev*/) { return DLA_ERR_ARG; }
+  // four more stored matrices: the parts A+B, A-B, S+D, S-D of the linear-response pencil (part: DLA_SPMM_LR_APB .. _SMD; single
+  // rank, any storage format, independent of A, B and each other), their products y = (part) x and the harness' lrprec_1 / lrprec_2
+  // (variant 1 / 2) on the diagonals of A+B, A-B and S+D.  The host-memory test engine keeps the defaults.
+  virtual int spmm_setup_lr(int /*part*/, int /*n*/, const long long* /*rowptr*/, const int* /*colind*/, const double* /*values*/, int /*format*/) { return DLA_ERR_ARG; }
+  virtual int spmm_setup_lr_dev(int /*part*/, int /*n*/, const long long* /*rowptr_dev*/, const int* /*colind_dev*/, const double* /*values_dev*/,
+                                int /*format*/) { return DLA_ERR_ARG; }
+  virtual int spmm_refresh_lr_values_dev(int /*part*/, int /*n*/, const long long* /*rowptr_dev*/, const int* /*colind_dev*/,
+                                         const double* /*values_dev*/) { return DLA_ERR_ARG; }
+  virtual int spmm_lr_info(int /*part*/, struct dla_spmm_info* /*out*/) { return DLA_ERR_ARG; }
+  virtual int spmm_drop_lr() { return DLA_ERR_ARG; }
+  virtual int spmm_lr_mul(int /*part*/, int /*n*/, int /*m*/, const double* /*x*/, double* /*y*/) { return DLA_ERR_ARG; }
+  virtual int spmm_lrprec(int /*variant*/, int /*n*/, int /*m*/, double /*fac*/, const double* /*xp*/, const double* /*xm*/,
+                          double* /*yp*/, double* /*ym*/) { return DLA_ERR_ARG; }
 
   // Staging pipeline of host-mode callbacks: column chunks of a block travel device -> host on one copy stream, the
   // user's routine works on the chunk that has arrived, finished chunks travel host -> device on a second copy stream

@@ -1892,6 +1892,57 @@ __global__ void pencil_precnd_kernel(int n, int m, double fac, const double* __r
   }
 }
 
+// The harness' lrprec_1 / lrprec_2 (main.f90:234-281; synth_lrprec_kernel restates them) on the stored diagonals of the sparse
+// linear-response parts (dla_spmm_setup_lr_csr): aa = ((A+B)_ii + (A-B)_ii) / 2, sg = (S+D)_ii (D is antisymmetric: its diagonal
+// is zero, so S+D carries the diagonal of S).  One thread keeps VEC rows of the three diagonals in registers -- read once -- and
+// walks the m columns of the four blocks; every element of yp / ym has one writer.  Order of operations, every product, sum and
+// quotient rounded on its own (no contraction into a fused multiply-add), products left to right as written:
+//   aa = 0.5 * (apb_ii + amb_ii)
+//   variant 1: den = -1.0 / (aa * aa - fac * fac * sg * sg),  ca = aa,        cs = fac * sg
+//   variant 2: den =  1.0 / (fac * fac * aa * aa - sg * sg),  ca = fac * aa,  cs = sg
+//   yp = den * (ca * xp + cs * xm),  ym = den * (ca * xm + cs * xp)
+// which is what a host caller gets from the harness' expressions (ca, cs and den do not depend on the column: taking them out of
+// the column loop changes no bit).  32 n m bytes of vectors + 24 n bytes of the three diagonals; panel accesses are non-temporal.
+template <int VEC>
+__global__ __launch_bounds__(256) void lr_precnd_kernel(int n, int m, int variant, double fac, const double* __restrict__ apb_diag,
+                                                        const double* __restrict__ amb_diag, const double* __restrict__ spd_diag,
+                                                        const double* __restrict__ xp, const double* __restrict__ xm,
+                                                        double* __restrict__ yp, double* __restrict__ ym)
+{
+#pragma clang fp contract(off)
+  typedef typename VecOf<VEC>::type vec_t;
+  const size_t nv = (size_t)n / VEC;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t iv = (size_t)blockIdx.x * blockDim.x + threadIdx.x; iv < nv; iv += stride) {
+    const size_t i = iv * VEC;
+    const vec_t pv = *(const vec_t*)(apb_diag + i), mv = *(const vec_t*)(amb_diag + i), sv = *(const vec_t*)(spd_diag + i);
+    double den[VEC], ca[VEC], cs[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      const double aa = 0.5 * (vget<VEC>(pv, e) + vget<VEC>(mv, e)), sg = vget<VEC>(sv, e);
+      if (variant == 1) {
+        den[e] = -1.0 / (aa * aa - fac * fac * sg * sg);
+        ca[e] = aa; cs[e] = fac * sg;
+      } else {
+        den[e] = 1.0 / (fac * fac * aa * aa - sg * sg);
+        ca[e] = fac * aa; cs[e] = sg;
+      }
+    }
+    for (int c = 0; c < m; ++c) {
+      const size_t at = (size_t)c * n + i;
+      const vec_t a = pload<VEC, 1>(xp + at), b = pload<VEC, 1>(xm + at);
+      double op[VEC], om[VEC];
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        op[e] = den[e] * (ca[e] * vget<VEC>(a, e) + cs[e] * vget<VEC>(b, e));
+        om[e] = den[e] * (ca[e] * vget<VEC>(b, e) + cs[e] * vget<VEC>(a, e));
+      }
+      pstore<VEC, 2>(yp + at, vmake<VEC>(op[0], op[VEC - 1]));
+      pstore<VEC, 2>(ym + at, vmake<VEC>(om[0], om[VEC - 1]));
+    }
+  }
+}
+
 // The same product on a ROW SHARD of A (dla_spmm_setup_csr_sharded): col[] indexes the extended local vector
 // [last `halo` rows of the previous rank | the shard's n rows | first `halo` rows of the next rank]; the two halo pieces have
 // arrived through the small-product all-reduce (halo_pack_kernel: every rank fills its own two slots of a zeroed buffer, the sum
@@ -5628,9 +5679,10 @@ struct HipEngine : dla::Engine {
   }
 
   // ---- sample sparse operator (ELLPACK; sliced ELLPACK below)
-  // Everything ONE stored sparse matrix consists of.  The context holds two: the operator A (dla_spmm_matvec / dla_spmm_precnd) and
-  // the metric B of a generalised problem (dla_spmm_bvec); the set-up, info and launch functions below take the one they act on,
-  // so the two have independent storage and independent formats and B's products come from the code that forms A's.
+  // Everything ONE stored sparse matrix consists of.  The context holds six: the operator A (dla_spmm_matvec / dla_spmm_precnd), the
+  // metric B of a generalised problem (dla_spmm_bvec) and the four parts of a linear-response pencil (op_lr below); the set-up, info
+  // and launch functions below take the one they act on, so all have independent storage and independent formats and every product
+  // comes from the code that forms A's.
   struct SparseOp {
     DeviceBuffer<int> col; DeviceBuffer<double> val, diag;   // ELLPACK blocks, or the slices followed by the CSR tail; diag[n]
     int n = 0, w = 0;                  // w: ELLPACK width (0 for the sliced format)
@@ -5653,6 +5705,17 @@ struct HipEngine : dla::Engine {
     }
   };
   SparseOp op_a, op_b;
+  // ... and four more: the parts A+B, A-B, S+D, S-D of the linear-response pencil (dla_spmm_setup_lr_csr; DLA_SPMM_LR_APB .. _SMD),
+  // independent of A, B and each other.  slot() is the one place that maps (kind, index) to the storage; the set-up, refresh, info and
+  // product functions take the SparseOp it returns.
+  static constexpr int LR_PARTS = 4;
+  SparseOp op_lr[LR_PARTS];
+  enum SlotKind { SLOT_MAIN, SLOT_LR };      // MAIN: index 0 = the operator A, 1 = the metric B;  LR: index = part
+  SparseOp& slot(SlotKind kind, int index) { return kind == SLOT_LR ? op_lr[index] : (index ? op_b : op_a); }
+  static bool lr_part_ok(int part) { return part >= 0 && part < LR_PARTS; }
+  static const char* lr_name(int part) { static const char* const nm[LR_PARTS] = {"apb (A+B)", "amb (A-B)", "spd (S+D)", "smd (S-D)"}; return nm[part]; }
+  static const char* lr_mul_name(int part) { static const char* const nm[LR_PARTS] = {"spmm_apbmul", "spmm_ambmul", "spmm_spdmul", "spmm_smdmul"}; return nm[part]; }
+  bool lr_present() const { for (const SparseOp& o : op_lr) if (o.fmt >= 0) return true; return false; }
   // A on a row shard (spmm_setup_sharded; A only): whether it is, and the exchange with the neighbouring ranks.  The one place that
   // answers "is A sharded" -- the sharded set-up and the metric's refuse each other by it.
   struct RowShard {
@@ -5873,7 +5936,7 @@ struct HipEngine : dla::Engine {
   {
     if (which != 0 && which != 1) { err = "spmm_setup_csr_dev: which must be 0 (the operator) or 1 (the metric)"; return DLA_ERR_ARG; }
     if (which == 1 && shard.on) { err = "spmm_setup_csr_dev: the operator of this context is row-sharded, and a row-sharded metric is not supported"; return DLA_ERR_ARG; }
-    { const int stc = setup_dev(which ? op_b : op_a, n, rowptr_dev, colind_dev, values_dev, format); if (stc) return stc; }
+    { const int stc = setup_dev(slot(SLOT_MAIN, which), n, rowptr_dev, colind_dev, values_dev, format); if (stc) return stc; }
     if (which == 0) shard.drop();
     return DLA_OK;
   }
@@ -5882,9 +5945,14 @@ struct HipEngine : dla::Engine {
   int spmm_refresh_values_dev(int which, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev) override
   {
     if (which != 0 && which != 1) { err = "spmm_refresh_values_dev: which must be 0 (the operator) or 1 (the metric)"; return DLA_ERR_ARG; }
-    SparseOp& op = which ? op_b : op_a;
+    SparseOp& op = slot(SLOT_MAIN, which);
     if (op.fmt < 0) { err = which ? "spmm_refresh_values_dev: no metric has been set up" : "spmm_refresh_values_dev: no operator has been set up"; return DLA_ERR_ARG; }
     if (which == 0 && shard.on) { err = "spmm_refresh_values_dev: the operator of this context is row-sharded"; return DLA_ERR_ARG; }
+    return refresh_dev(op, n, rowptr_dev, colind_dev, values_dev);
+  }
+  // (op holds a matrix and is not row-sharded)
+  int refresh_dev(SparseOp& op, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev)
+  {
     if (n <= 0 || !rowptr_dev || !colind_dev || !values_dev) { err = "spmm_refresh_values_dev: bad arguments"; return DLA_ERR_ARG; }
     if (n != op.n) { err = "spmm_refresh_values_dev: n = " + std::to_string(n) + " differs from the stored " + std::to_string(op.n); return DLA_ERR_ARG; }
     bind();
@@ -6021,7 +6089,8 @@ struct HipEngine : dla::Engine {
     std::string lerr;
     // (a metric beside a sharded operator would have to be sharded as well: refused like a bad shard, so that every rank agrees)
     if (op_b.fmt >= 0) lerr = "spmm_setup_csr_sharded: this context holds a metric (dla_spmm_setup_metric_csr), and a row-sharded metric is not supported; drop it first";
-    const int bad = (op_b.fmt >= 0 || values == nullptr) ? DLA_ERR_ARG : dla::sharded_ell_need(n, row0, n_global, rowptr, colind, &w, &need, lerr);
+    if (lr_present()) lerr = "spmm_setup_csr_sharded: this context holds linear-response parts (dla_spmm_setup_lr_csr), and row-sharded parts are not supported; drop them first (dla_spmm_drop_lr)";
+    const int bad = (op_b.fmt >= 0 || lr_present() || values == nullptr) ? DLA_ERR_ARG : dla::sharded_ell_need(n, row0, n_global, rowptr, colind, &w, &need, lerr);
     const int nr = std::max(1, nranks);
     // agree on the halo width and check the layout, collectively: [max need | any failure | row0 and n of every rank (slots)]
     std::vector<double> mx{(double)need, bad ? 1.0 : 0.0};
@@ -6149,6 +6218,82 @@ struct HipEngine : dla::Engine {
     Scope s(this, DLA_OP_PRECND, 16.0 * (double)n * m + 16.0 * (double)n, 2.0 * (double)n * m);
     const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
     DLA_LAUNCH(pencil_precnd_kernel, dim3(blocks), dim3(256), 0, st, n, m, fac, (const double*)op_a.diag, (const double*)op_b.diag, x, px);
+    HIPCHK(hipGetLastError());
+    return DLA_OK;
+  }
+
+  // ---- ... and the four parts of the linear-response pencil (A B; B A)(Y Z) = w (S D; -D -S)(Y Z): A+B, A-B, S+D, S-D as the
+  // callbacks apbmul / ambmul / spdmul / smdmul of caslr_eff_driver / caslr_driver apply them (reference diaglib.f90:1024-1025),
+  // single rank.  Set-up, refresh, info and products are the operator's own functions on another SparseOp; nothing here or in the
+  // product kernels assumes a symmetric matrix (S+D and S-D are not).
+  int lr_slot_check(const char* entry, int part)
+  {
+    if (!lr_part_ok(part)) { err = std::string(entry) + ": part must be 0 (A+B), 1 (A-B), 2 (S+D) or 3 (S-D)"; return DLA_ERR_ARG; }
+    if (shard.on) { err = std::string(entry) + ": the operator of this context is row-sharded, and row-sharded linear-response parts are not supported"; return DLA_ERR_ARG; }
+    return DLA_OK;
+  }
+  int spmm_setup_lr(int part, int n, const long long* rowptr, const int* colind, const double* values, int format) override
+  {
+    { const int stc = lr_slot_check("spmm_setup_lr_csr", part); if (stc) return stc; }
+    const int stc = setup_fmt(slot(SLOT_LR, part), n, rowptr, colind, values, format);
+    if (stc == DLA_ERR_ARG) err = std::string("spmm_setup_lr_csr, part ") + lr_name(part) + ": " + err;
+    return stc;
+  }
+  int spmm_setup_lr_dev(int part, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev, int format) override
+  {
+    { const int stc = lr_slot_check("spmm_setup_lr_csr_dev", part); if (stc) return stc; }
+    const int stc = setup_dev(slot(SLOT_LR, part), n, rowptr_dev, colind_dev, values_dev, format);
+    if (stc == DLA_ERR_ARG) err = std::string("spmm_setup_lr_csr_dev, part ") + lr_name(part) + ": " + err;
+    return stc;
+  }
+  int spmm_refresh_lr_values_dev(int part, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev) override
+  {
+    { const int stc = lr_slot_check("spmm_refresh_lr_values_dev", part); if (stc) return stc; }
+    SparseOp& op = slot(SLOT_LR, part);
+    if (op.fmt < 0) { err = std::string("spmm_refresh_lr_values_dev: part ") + lr_name(part) + " has not been set up"; return DLA_ERR_ARG; }
+    const int stc = refresh_dev(op, n, rowptr_dev, colind_dev, values_dev);
+    if (stc == DLA_ERR_ARG) err = std::string("spmm_refresh_lr_values_dev, part ") + lr_name(part) + ": " + err;
+    return stc;
+  }
+  int spmm_lr_info(int part, struct dla_spmm_info* out) override
+  {
+    if (!lr_part_ok(part)) { err = "spmm_lr_info: part must be 0 (A+B), 1 (A-B), 2 (S+D) or 3 (S-D)"; return DLA_ERR_ARG; }
+    if (op_lr[part].fmt < 0 || !out) { err = std::string("spmm_lr_info: part ") + lr_name(part) + " has not been set up"; return DLA_ERR_ARG; }
+    return op_info(slot(SLOT_LR, part), out);
+  }
+  int spmm_drop_lr() override
+  {
+    bool any = false;
+    for (const SparseOp& o : op_lr) any = any || o.fmt >= 0 || o.col;
+    if (!any) return DLA_OK;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipStreamSynchronize(st));     // (products of the parts may still be queued)
+    for (SparseOp& o : op_lr) o.drop();
+    return DLA_OK;
+  }
+  int spmm_lr_mul(int part, int n, int m, const double* x, double* y) override
+  {
+    if (!lr_part_ok(part)) { err = "spmm_lr_mul: bad part"; return DLA_ERR_ARG; }
+    SparseOp& op = slot(SLOT_LR, part);
+    if (op.fmt < 0) { err = std::string(lr_mul_name(part)) + ": part " + lr_name(part) + " has not been set up (dla_spmm_setup_lr_csr)"; return DLA_ERR_ARG; }
+    if (n != op.n) { err = std::string(lr_mul_name(part)) + ": n = " + std::to_string(n) + " differs from the " + std::to_string(op.n) + " rows of part " + lr_name(part); return DLA_ERR_ARG; }
+    return op_matvec(op, n, m, x, y);
+  }
+  int spmm_lrprec(int variant, int n, int m, double fac, const double* xp, const double* xm, double* yp, double* ym) override
+  {
+    const std::string who = variant == 1 ? "spmm_lrprec1" : "spmm_lrprec2";
+    for (int part : {(int)DLA_SPMM_LR_APB, (int)DLA_SPMM_LR_AMB, (int)DLA_SPMM_LR_SPD}) {
+      const SparseOp& op = op_lr[part];
+      if (op.fmt < 0 || !op.diag) { err = who + ": part " + lr_name(part) + " has not been set up (dla_spmm_setup_lr_csr)"; return DLA_ERR_ARG; }
+      if (n != op.n) { err = who + ": n = " + std::to_string(n) + " differs from the " + std::to_string(op.n) + " rows of part " + lr_name(part); return DLA_ERR_ARG; }
+    }
+    Scope s(this, DLA_OP_PRECND, 32.0 * (double)n * m + 24.0 * (double)n, 8.0 * (double)n * m);
+    const bool vec2 = even_rows(n) && (((uintptr_t)xp | (uintptr_t)xm | (uintptr_t)yp | (uintptr_t)ym) % 16 == 0);
+    const size_t nv = (size_t)n / (vec2 ? 2 : 1);
+    const int blocks = (int)std::max((size_t)1, std::min((size_t)ncu * 8, (nv + 255) / 256));
+    const double *da = op_lr[DLA_SPMM_LR_APB].diag, *dm = op_lr[DLA_SPMM_LR_AMB].diag, *ds = op_lr[DLA_SPMM_LR_SPD].diag;
+    if (vec2) DLA_LAUNCH(lr_precnd_kernel<2>, dim3(blocks), dim3(256), 0, st, n, m, variant, fac, da, dm, ds, xp, xm, yp, ym);
+    else      DLA_LAUNCH(lr_precnd_kernel<1>, dim3(blocks), dim3(256), 0, st, n, m, variant, fac, da, dm, ds, xp, xm, yp, ym);
     HIPCHK(hipGetLastError());
     return DLA_OK;
   }

@@ -1228,7 +1228,8 @@ static bool builtin_operator(dla_matvec_fn fn)
 {
   return (void*)fn == (void*)&dla_synth_matvec || (void*)fn == (void*)&dla_spmm_matvec || (void*)fn == (void*)&dla_synth_apbmul ||
          (void*)fn == (void*)&dla_synth_ambmul || (void*)fn == (void*)&dla_synth_spdmul || (void*)fn == (void*)&dla_synth_smdmul ||
-         (void*)fn == (void*)&dla_synth_metric || (void*)fn == (void*)&dla_spmm_bvec;
+         (void*)fn == (void*)&dla_synth_metric || (void*)fn == (void*)&dla_spmm_bvec || (void*)fn == (void*)&dla_spmm_apbmul ||
+         (void*)fn == (void*)&dla_spmm_ambmul || (void*)fn == (void*)&dla_spmm_spdmul || (void*)fn == (void*)&dla_spmm_smdmul;
 }
 
 int dla_call_matvec(dla_ctx* c, dla_matvec_fn fn, int n, int m, const double* x, double* ax)
@@ -1774,7 +1775,8 @@ int dla_call_lrprec(dla_ctx* c, dla_lrprec_fn fn, int n, int m, double fac, cons
   DLA_T("dla_call_lrprec");
   if (m <= 0) return DLA_OK;
   if (c->callbacks_on_device) {
-    const int order = ((void*)fn == (void*)&dla_synth_lrprec1 || (void*)fn == (void*)&dla_synth_lrprec2) ? 2 : c->callback_order;
+    const int order = ((void*)fn == (void*)&dla_synth_lrprec1 || (void*)fn == (void*)&dla_synth_lrprec2 ||
+                       (void*)fn == (void*)&dla_spmm_lrprec1 || (void*)fn == (void*)&dla_spmm_lrprec2) ? 2 : c->callback_order;
     int st = c->eng->callback_begin(order);
     if (st) return engfail(c, st);
     fn(&n, &m, &fac, xp, xm, yp, ym);
@@ -1945,5 +1947,62 @@ int dla_spmm_refresh_values_dev(dla_ctx* c, int which, int n, const long long* r
   if (!c) return DLA_ERR_ARG;
   return engfail(c, c->eng->spmm_refresh_values_dev(which, n, rowptr_dev, colind_dev, values_dev));
 }
+
+// ---- ... and the four parts of a linear-response pencil beside them (apbmul / ambmul / spdmul / smdmul of reference
+// diaglib.f90:1024-1025, lrprec of :1317; the harness' lrprec_1 / lrprec_2, main.f90:234-281)
+int dla_spmm_setup_lr_csr(dla_ctx* c, int part, int n, const long long* rowptr, const int* colind, const double* values, int format)
+{
+  if (!c) return DLA_ERR_ARG;
+  const int st = engfail(c, c->eng->spmm_setup_lr(part, n, rowptr, colind, values, format));
+  if (st == DLA_OK) g_spmm_ctx = c;
+  return st;
+}
+
+int dla_spmm_setup_lr_csr_dev(dla_ctx* c, int part, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev, int format)
+{
+  DLA_T("dla_spmm_setup_lr_csr_dev");
+  if (!c) return DLA_ERR_ARG;
+  const int st = engfail(c, c->eng->spmm_setup_lr_dev(part, n, rowptr_dev, colind_dev, values_dev, format));
+  if (st == DLA_OK) g_spmm_ctx = c;
+  return st;
+}
+
+int dla_spmm_refresh_lr_values_dev(dla_ctx* c, int part, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev)
+{
+  DLA_T("dla_spmm_refresh_lr_values_dev");
+  if (!c) return DLA_ERR_ARG;
+  return engfail(c, c->eng->spmm_refresh_lr_values_dev(part, n, rowptr_dev, colind_dev, values_dev));
+}
+
+int dla_spmm_lr_info(dla_ctx* c, int part, struct dla_spmm_info* out)
+{
+  if (!c || !out) return DLA_ERR_ARG;
+  return engfail(c, c->eng->spmm_lr_info(part, out));
+}
+
+int dla_spmm_drop_lr(dla_ctx* c)
+{
+  if (!c) return DLA_ERR_ARG;
+  return engfail(c, c->eng->spmm_drop_lr());
+}
+
+static void spmm_lr_mul(int part, const char* what, const int* n, const int* m, const double* x, double* y)
+{
+  dla_ctx* c = g_spmm_ctx;
+  if (!c) { callback_failed(DLA_ERR_ARG, std::string(what) + " before dla_spmm_setup_lr_csr"); return; }
+  if (int st = c->eng->spmm_lr_mul(part, *n, *m, x, y)) callback_failed(st, std::string(what) + " failed: " + c->eng->err);
+}
+void dla_spmm_apbmul(const int* n, const int* m, const double* x, double* y) { spmm_lr_mul(DLA_SPMM_LR_APB, "dla_spmm_apbmul", n, m, x, y); }
+void dla_spmm_ambmul(const int* n, const int* m, const double* x, double* y) { spmm_lr_mul(DLA_SPMM_LR_AMB, "dla_spmm_ambmul", n, m, x, y); }
+void dla_spmm_spdmul(const int* n, const int* m, const double* x, double* y) { spmm_lr_mul(DLA_SPMM_LR_SPD, "dla_spmm_spdmul", n, m, x, y); }
+void dla_spmm_smdmul(const int* n, const int* m, const double* x, double* y) { spmm_lr_mul(DLA_SPMM_LR_SMD, "dla_spmm_smdmul", n, m, x, y); }
+static void spmm_lrp(int variant, const char* what, const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym)
+{
+  dla_ctx* c = g_spmm_ctx;
+  if (!c) { callback_failed(DLA_ERR_ARG, std::string(what) + " before dla_spmm_setup_lr_csr"); return; }
+  if (int st = c->eng->spmm_lrprec(variant, *n, *m, *fac, xp, xm, yp, ym)) callback_failed(st, std::string(what) + " failed: " + c->eng->err);
+}
+void dla_spmm_lrprec1(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { spmm_lrp(1, "dla_spmm_lrprec1", n, m, fac, xp, xm, yp, ym); }
+void dla_spmm_lrprec2(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { spmm_lrp(2, "dla_spmm_lrprec2", n, m, fac, xp, xm, yp, ym); }
 
 }  // extern "C"

@@ -90,7 +90,7 @@ enum {
                                       takes another route than planned the operator is called a SECOND time on the finished
                                       block and its first output is dropped -- the reference calls matvec exactly once per
                                       block (diaglib.f90:1685, 394-397), so:
-                                      1 (default): only for the library's own device operators (dla_synth_*, dla_spmm_matvec, dla_spmm_bvec),
+                                      1 (default): only for the library's own device operators (dla_synth_*, dla_spmm_matvec, dla_spmm_bvec, dla_spmm_apbmul .. _smdmul),
                                          which are pure functions of their input; a caller's callback is called once, in order;
                                       2: also for the caller's device-mode callbacks (ordering contract 0 or 2) -- the caller
                                          states that the operator keeps no state between calls;
@@ -498,7 +498,28 @@ void dla_set_solve_info(int iters, int matvec_cols, int restarts);   /* used by 
  * the same arrays in that format.  Refused with DLA_ERR_ARG when the slot is empty, when it is row-sharded, when n or the number
  * of entries differs from the stored one, or when the pattern -- the length of every row and every column index, in the caller's
  * order -- is not the stored one; the pattern is compared in a read-only pass before anything is written, so a refused refresh
- * leaves values and diagonal as they were.  Synchronous like the set-up, with the same rule for the caller's producer. */
+ * leaves values and diagonal as they were.  Synchronous like the set-up, with the same rule for the caller's producer.
+ * The parts of a linear-response problem (A B; B A)(Y Z) = w (S D; -D -S)(Y Z) (dla_spmm_setup_lr_csr, single rank): a context
+ * keeps four more sparse matrices beside A and B -- part DLA_SPMM_LR_APB = A+B, _AMB = A-B, _SPD = S+D, _SMD = S-D -- each handed
+ * over like the operator and stored in any of the formats above, with its own diagonal and its own tail workspace.
+ * dla_spmm_apbmul / _ambmul / _spdmul / _smdmul have the shape of the reference's apbmul / ambmul / spdmul / smdmul (diaglib.f90:
+ * 1024-1025) and dla_spmm_lrprec1 / _lrprec2 the shape of its lrprec (diaglib.f90:1317), so that caslr_eff_driver and caslr_driver
+ * run a whole solve in HBM on the caller's matrices.  The four products run the kernels dla_spmm_matvec runs: for the same arrays
+ * and format they return the bits the operator slot gives.  No matrix is assumed symmetric, here or in the operator and the metric:
+ * every kernel multiplies row i by the entries handed over for row i (S+D and S-D are not symmetric).  dla_spmm_lrprec1 / _lrprec2
+ * are the harness' lrprec_1 / lrprec_2 (main.f90:234-281) on the stored diagonals, with aa = 0.5 * (apb_ii + amb_ii) and
+ * sg = spd_ii (S-D is not read):
+ *   lrprec1: den = -1 / (aa*aa - fac*fac*sg*sg),  yp = den * (aa*xp + fac*sg*xm),      ym = den * (aa*xm + fac*sg*xp)
+ *   lrprec2: den =  1 / (fac*fac*aa*aa - sg*sg),  yp = den * (fac*aa*xp + sg*xm),      ym = den * (fac*aa*xm + sg*xp)
+ * evaluated in double precision with products taken left to right and no fused multiply-add: the bits a host caller gets from
+ * the same expressions.  The parts are independent of each other and of A and B: setting, replacing or dropping one never changes
+ * another slot's blocks, its info or the bits of its products, and a refused set-up replaces nothing.  Every rule above for A / B
+ * holds for a part: dla_spmm_setup_lr_csr_dev gives the host set-up's result field by field and bit by bit, every check finishes
+ * before any write, the calls are synchronous, and dla_spmm_refresh_lr_values_dev is refused while the pattern differs.  A callback
+ * that finds a part it needs missing (lrprec: A+B, A-B or S+D), or another n, fails through the status of dla_call_matvec /
+ * dla_call_lrprec with a message that names the callback and the part.  Row-sharded parts are out of scope: a part is refused on a
+ * context whose operator came from dla_spmm_setup_csr_sharded (the message names the entry), and that set-up is refused while a
+ * part is present.  dla_spmm_drop_lr frees all four. */
 enum { DLA_SPMM_ELL = 0, DLA_SPMM_SELL = 1, DLA_SPMM_AUTO = 2 };
 /* what the calling context's operator occupies (a struct tag only: C keeps tags apart from the function of the same name) */
 struct dla_spmm_info {
@@ -540,6 +561,22 @@ int  dla_spmm_setup_csr_dev(dla_ctx* ctx, int which, int n, const long long* row
 /* the same matrix pattern with new values: rewrites only the stored values and the diagonal of slot `which` */
 int  dla_spmm_refresh_values_dev(dla_ctx* ctx, int which, int n, const long long* rowptr_dev, const int* colind_dev,
                                  const double* values_dev);
+/* the four sparse parts of the linear-response pencil beside A and B (part: one of the four below); arrays and format as in
+   dla_spmm_setup_csr_fmt (host) and dla_spmm_setup_csr_dev / dla_spmm_refresh_values_dev (device); single rank */
+enum { DLA_SPMM_LR_APB = 0, DLA_SPMM_LR_AMB = 1, DLA_SPMM_LR_SPD = 2, DLA_SPMM_LR_SMD = 3 };
+int  dla_spmm_setup_lr_csr(dla_ctx* ctx, int part, int n, const long long* rowptr, const int* colind, const double* values, int format);
+int  dla_spmm_setup_lr_csr_dev(dla_ctx* ctx, int part, int n, const long long* rowptr_dev, const int* colind_dev,
+                               const double* values_dev, int format);
+int  dla_spmm_refresh_lr_values_dev(dla_ctx* ctx, int part, int n, const long long* rowptr_dev, const int* colind_dev,
+                                    const double* values_dev);
+int  dla_spmm_lr_info(dla_ctx* ctx, int part, struct dla_spmm_info* out);   /* DLA_ERR_ARG while that part is empty */
+int  dla_spmm_drop_lr(dla_ctx* ctx);                                        /* frees all four; no-op without any */
+void dla_spmm_apbmul(const int* n, const int* m, const double* x_dev, double* y_dev);          /* y = (A+B) x */
+void dla_spmm_ambmul(const int* n, const int* m, const double* x_dev, double* y_dev);          /* y = (A-B) x */
+void dla_spmm_spdmul(const int* n, const int* m, const double* x_dev, double* y_dev);          /* y = (S+D) x */
+void dla_spmm_smdmul(const int* n, const int* m, const double* x_dev, double* y_dev);          /* y = (S-D) x */
+void dla_spmm_lrprec1(const int* n, const int* m, const double* fac, const double* xp_dev, const double* xm_dev, double* yp_dev, double* ym_dev);
+void dla_spmm_lrprec2(const int* n, const int* m, const double* fac, const double* xp_dev, const double* xm_dev, double* yp_dev, double* ym_dev);
 
 #ifdef __cplusplus
 }

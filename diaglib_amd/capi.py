@@ -533,47 +533,55 @@ class Context:
     def synth_setup(self, n_global: int, row0: int, n_local: int, rank_w: int = 4, sigma: float = 0.5) -> None:
         self._chk(self.lib.dla_synth_setup(self.h, n_global, row0, n_local, rank_w, sigma))
 
+    # ---- the stored sparse matrices: the operator, the metric and the four parts of a linear-response pencil
+    @staticmethod
+    def _host_csr(a, index_dtype=np.int32):
+        """n and the three CSR arrays of a scipy.sparse matrix as the C-ABI wants them (contiguous int64 / index_dtype / float64)"""
+        a = a.tocsr()
+        return (a.shape[0], np.ascontiguousarray(a.indptr, dtype=np.int64), np.ascontiguousarray(a.indices, dtype=index_dtype),
+                np.ascontiguousarray(a.data, dtype=np.float64))
+
+    @staticmethod
+    def _spmm_format(who: str, fmt) -> int:
+        if fmt not in SPMM_FORMATS:
+            raise ValueError(f"{who}: fmt must be one of {sorted(SPMM_FORMATS)}, not {fmt!r}")
+        return SPMM_FORMATS[fmt]
+
+    @staticmethod
+    def _spmm_info_dict(o) -> dict:
+        d = {name: int(getattr(o, name)) for name, _ in SpmmInfo._fields_}
+        d["format"] = {v: k for k, v in SPMM_FORMATS.items()}[d["format"]]
+        return d
+
     def spmm_setup(self, a, fmt: str = "ell") -> None:
         """hand a scipy.sparse matrix (symmetric, square) to the sample sparse operator of this thread's context; fmt = "ell"
         (ELLPACK, padded to the widest row), "sell" (sliced ELLPACK with a CSR tail: storage follows the non-zeros) or "auto" (ELLPACK while its padding is small)"""
-        if fmt not in SPMM_FORMATS:
-            raise ValueError(f"spmm_setup: fmt must be one of {sorted(SPMM_FORMATS)}, not {fmt!r}")
-        a = a.tocsr()
-        rp = np.ascontiguousarray(a.indptr, dtype=np.int64)
-        ci = np.ascontiguousarray(a.indices, dtype=np.int32)
-        va = np.ascontiguousarray(a.data, dtype=np.float64)
+        f = self._spmm_format("spmm_setup", fmt)
+        n, rp, ci, va = self._host_csr(a)
         if fmt == "ell":
-            self._chk(self.lib.dla_spmm_setup_csr(self.h, a.shape[0], rp.ctypes.data, ci.ctypes.data, va.ctypes.data))
+            self._chk(self.lib.dla_spmm_setup_csr(self.h, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data))
         else:
-            self._chk(self.lib.dla_spmm_setup_csr_fmt(self.h, a.shape[0], rp.ctypes.data, ci.ctypes.data, va.ctypes.data, SPMM_FORMATS[fmt]))
+            self._chk(self.lib.dla_spmm_setup_csr_fmt(self.h, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, f))
 
     def spmm_info(self) -> dict:
         """what the operator set up last occupies: format ("ell" / "sell"), n, nnz, stored, slices, long_rows, long_entries,
         long_segments, multi_segments, device_bytes and the layout constants (include/diaglib_amd.h, dla_spmm_info)"""
         o = SpmmInfo()
         self._chk(self.lib.dla_spmm_info(self.h, C.byref(o)))
-        d = {name: int(getattr(o, name)) for name, _ in SpmmInfo._fields_}
-        d["format"] = {v: k for k, v in SPMM_FORMATS.items()}[d["format"]]
-        return d
+        return self._spmm_info_dict(o)
 
     def spmm_setup_metric(self, b, fmt: str = "ell") -> None:
         """hand a scipy.sparse matrix (symmetric positive definite, square) to this context as the metric B of A x = lambda B x,
         beside the operator of spmm_setup and independent of it; fmt as in spmm_setup.  dla_spmm_bvec then applies it"""
-        if fmt not in SPMM_FORMATS:
-            raise ValueError(f"spmm_setup_metric: fmt must be one of {sorted(SPMM_FORMATS)}, not {fmt!r}")
-        b = b.tocsr()
-        rp = np.ascontiguousarray(b.indptr, dtype=np.int64)
-        ci = np.ascontiguousarray(b.indices, dtype=np.int32)
-        va = np.ascontiguousarray(b.data, dtype=np.float64)
-        self._chk(self.lib.dla_spmm_setup_metric_csr(self.h, b.shape[0], rp.ctypes.data, ci.ctypes.data, va.ctypes.data, SPMM_FORMATS[fmt]))
+        f = self._spmm_format("spmm_setup_metric", fmt)
+        n, rp, ci, va = self._host_csr(b)
+        self._chk(self.lib.dla_spmm_setup_metric_csr(self.h, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, f))
 
     def spmm_metric_info(self) -> dict:
         """spmm_info of the metric; raises while none is set"""
         o = SpmmInfo()
         self._chk(self.lib.dla_spmm_metric_info(self.h, C.byref(o)))
-        d = {name: int(getattr(o, name)) for name, _ in SpmmInfo._fields_}
-        d["format"] = {v: k for k, v in SPMM_FORMATS.items()}[d["format"]]
-        return d
+        return self._spmm_info_dict(o)
 
     def spmm_drop_metric(self) -> None:
         """free the metric's device blocks (nothing happens without one); the operator stays as it is"""
@@ -582,11 +590,8 @@ class Context:
     def spmm_setup_sharded(self, a_rows, row0: int, n_global: int) -> None:
         """hand THIS rank's rows (a scipy.sparse matrix of shape n_local x n_global, global column indices) of a banded
         symmetric matrix to the sample operator; collective over the ranks of the context's transport"""
-        a = a_rows.tocsr()
-        rp = np.ascontiguousarray(a.indptr, dtype=np.int64)
-        ci = np.ascontiguousarray(a.indices, dtype=np.int64)
-        va = np.ascontiguousarray(a.data, dtype=np.float64)
-        self._chk(self.lib.dla_spmm_setup_csr_sharded(self.h, a.shape[0], row0, n_global, rp.ctypes.data, ci.ctypes.data, va.ctypes.data))
+        n, rp, ci, va = self._host_csr(a_rows, np.int64)
+        self._chk(self.lib.dla_spmm_setup_csr_sharded(self.h, n, row0, n_global, rp.ctypes.data, ci.ctypes.data, va.ctypes.data))
 
     @staticmethod
     def _device_csr(who: str, crow, col, val):
@@ -617,11 +622,9 @@ class Context:
         """spmm_setup (metric: spmm_setup_metric) from CSR arrays that are torch tensors on the GPU -- e.g. crow_indices(),
         col_indices() and values() of a torch.sparse_csr_tensor: only the row pointers travel to the host.  The tensors may be
         freed or overwritten when the call returns"""
-        if fmt not in SPMM_FORMATS:
-            raise ValueError(f"spmm_setup_device: fmt must be one of {sorted(SPMM_FORMATS)}, not {fmt!r}")
+        f = self._spmm_format("spmm_setup_device", fmt)
         crow, col, val = self._device_csr("spmm_setup_device", crow, col, val)
-        self._chk(self.lib.dla_spmm_setup_csr_dev(self.h, int(bool(metric)), crow.numel() - 1, crow.data_ptr(), col.data_ptr(), val.data_ptr(),
-                                                  SPMM_FORMATS[fmt]))
+        self._chk(self.lib.dla_spmm_setup_csr_dev(self.h, int(bool(metric)), crow.numel() - 1, crow.data_ptr(), col.data_ptr(), val.data_ptr(), f))
 
     def spmm_refresh_values_device(self, crow, col, val, metric: bool = False) -> None:
         """new values for the pattern the operator (metric: the metric) was set up with; raises while the pattern differs"""
@@ -641,23 +644,17 @@ class Context:
         """hand a scipy.sparse matrix (square; need not be symmetric) to this context as one part of the linear-response pencil:
         part = "apb" (A+B), "amb" (A-B), "spd" (S+D), "smd" (S-D) or 0 .. 3; fmt as in spmm_setup.  Independent of the operator,
         the metric and the other parts"""
-        if fmt not in SPMM_FORMATS:
-            raise ValueError(f"spmm_setup_lr: fmt must be one of {sorted(SPMM_FORMATS)}, not {fmt!r}")
+        f = self._spmm_format("spmm_setup_lr", fmt)
         part = self._lr_part("spmm_setup_lr", part)
-        a = a.tocsr()
-        rp = np.ascontiguousarray(a.indptr, dtype=np.int64)
-        ci = np.ascontiguousarray(a.indices, dtype=np.int32)
-        va = np.ascontiguousarray(a.data, dtype=np.float64)
-        self._chk(self.lib.dla_spmm_setup_lr_csr(self.h, part, a.shape[0], rp.ctypes.data, ci.ctypes.data, va.ctypes.data, SPMM_FORMATS[fmt]))
+        n, rp, ci, va = self._host_csr(a)
+        self._chk(self.lib.dla_spmm_setup_lr_csr(self.h, part, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, f))
 
     def spmm_setup_lr_device(self, part, crow, col, val, fmt: str = "ell") -> None:
         """spmm_setup_lr from CSR arrays that are torch tensors on the GPU (as spmm_setup_device)"""
-        if fmt not in SPMM_FORMATS:
-            raise ValueError(f"spmm_setup_lr_device: fmt must be one of {sorted(SPMM_FORMATS)}, not {fmt!r}")
+        f = self._spmm_format("spmm_setup_lr_device", fmt)
         part = self._lr_part("spmm_setup_lr_device", part)
         crow, col, val = self._device_csr("spmm_setup_lr_device", crow, col, val)
-        self._chk(self.lib.dla_spmm_setup_lr_csr_dev(self.h, part, crow.numel() - 1, crow.data_ptr(), col.data_ptr(), val.data_ptr(),
-                                                     SPMM_FORMATS[fmt]))
+        self._chk(self.lib.dla_spmm_setup_lr_csr_dev(self.h, part, crow.numel() - 1, crow.data_ptr(), col.data_ptr(), val.data_ptr(), f))
 
     def spmm_refresh_lr_values_device(self, part, crow, col, val) -> None:
         """new values for the pattern that part was set up with; raises while the pattern differs"""
@@ -669,9 +666,7 @@ class Context:
         """spmm_info of one part; raises while that part is empty"""
         o = SpmmInfo()
         self._chk(self.lib.dla_spmm_lr_info(self.h, self._lr_part("spmm_lr_info", part), C.byref(o)))
-        d = {name: int(getattr(o, name)) for name, _ in SpmmInfo._fields_}
-        d["format"] = {v: k for k, v in SPMM_FORMATS.items()}[d["format"]]
-        return d
+        return self._spmm_info_dict(o)
 
     def spmm_drop_lr(self) -> None:
         """free the device blocks of all four parts (nothing happens without any); operator and metric stay as they are"""

@@ -176,6 +176,15 @@ struct PolicyScope {
   PolicyScope& operator=(const PolicyScope&) = delete;
 };
 
+// The stored sparse matrices of a context (Engine::spmm_* below says what they are and which rules tie them together).  Internal:
+// the public entries number the operator and the metric by `which` and the parts by DLA_SPMM_LR_APB .. _SMD.
+enum SpmmSlot { SPMM_NO_PART = -2, SPMM_NO_WHICH = -1, SPMM_A = 0, SPMM_B, SPMM_APB, SPMM_AMB, SPMM_SPD, SPMM_SMD, SPMM_SLOTS };
+// where the CSR arrays of a set-up live; PLAIN: host arrays through dla_spmm_setup_csr, the entry without a format (A in ELLPACK,
+// its own name in messages)
+enum SpmmVia { SPMM_VIA_PLAIN, SPMM_VIA_HOST, SPMM_VIA_DEVICE };
+inline int spmm_slot_of_which(int which) { return which == 0 ? SPMM_A : which == 1 ? SPMM_B : SPMM_NO_WHICH; }
+inline int spmm_slot_of_part(int part) { return part >= 0 && part < SPMM_SLOTS - SPMM_APB ? SPMM_APB + part : SPMM_NO_PART; }
+
 // What the host logic needs from a device.  All panel pointers are device addresses,
 // column-major, ld = n.  Reductions (gram / residual norms / nrm2) return host-visible,
 // cross-rank-reduced results and imply a stream synchronisation.
@@ -265,42 +274,36 @@ struct Engine : BlockOps {
   virtual int callback_begin(int /*mode*/) { return 0; }
   virtual int callback_end(int /*mode*/) { return 0; }
 
-  // sample sparse operator (ELLPACK or sliced-ELLPACK SpMM + its diagonal preconditioner)
-  virtual int spmm_setup_csr(int /*n*/, const long long* /*rowptr*/, const int* /*colind*/, const double* /*values*/) { return DLA_ERR_ARG; }
-  // the same operator on a row shard: rows row0 .. row0 + n_local - 1 of A with GLOBAL column indices.  Columns outside the
-  // shard must lie within `halo` rows of it (a banded matrix); every rank publishes its first and last `halo` rows of x through
-  // the all-reduce of the small-product transport (disjoint slots: a sum that gathers), see sharded_ell_* below.  Collective:
-  // every rank calls it (the halo width is agreed by a max-reduction).
+  // ---- the stored sparse matrices.  A context stores up to six (SpmmSlot): the sample operator A (dla_spmm_matvec, dla_spmm_precnd),
+  // the metric B of A x = lambda B x (dla_spmm_bvec, dla_spmm_precnd_pencil) and the four parts A+B, A-B, S+D, S-D of the
+  // linear-response pencil (dla_spmm_apbmul .. smdmul, dla_spmm_lrprec1 / 2).  All six are single-rank matrices in any storage format
+  // (DLA_SPMM_ELL / _SELL / _AUTO: sell_build below) with independent storage, set up, refreshed, asked about and multiplied by
+  // through the same functions; setting or dropping one leaves the others alone.  Two rules tie them together: A alone may instead
+  // live on a row shard (spmm_setup_csr_sharded), and while it does B and the parts are refused -- as the sharded set-up is while B
+  // or a part is stored; and an accepted set-up of A through spmm_setup / spmm_setup_dev makes A whole again.  `slot` is an
+  // SpmmSlot, or SPMM_NO_WHICH / SPMM_NO_PART for a public number out of range, which the engine refuses in the entry's words.
+  // The host-memory test engine holds a sharded A only: it overrides spmm_matvec and keeps the defaults for the rest.
+  // set-up from CSR arrays in host or device memory (via: SpmmVia), and new values from device arrays for the pattern a slot holds
+  virtual int spmm_setup(int /*slot*/, int /*via*/, int /*n*/, const long long* /*rowptr*/, const int* /*colind*/, const double* /*values*/,
+                         int /*format*/) { return DLA_ERR_ARG; }
+  virtual int spmm_refresh_dev(int /*slot*/, int /*n*/, const long long* /*rowptr_dev*/, const int* /*colind_dev*/,
+                               const double* /*values_dev*/) { return DLA_ERR_ARG; }
+  // what a slot stores; the device blocks of slots first .. last given back (nothing happens where nothing is stored); y = (slot) x
+  virtual int spmm_info(int /*slot*/, struct dla_spmm_info* /*out*/) { return DLA_ERR_ARG; }
+  virtual int spmm_drop(int /*first*/, int /*last*/) { return DLA_ERR_ARG; }
+  // (an engine that stores no sparse matrix but A overrides the product of A alone)
+  virtual int spmm_mul(int slot, int n, int m, const double* x, double* y) { return slot == SPMM_A ? spmm_matvec(n, m, x, y) : DLA_ERR_ARG; }
+  virtual int spmm_matvec(int /*n*/, int /*m*/, const double* /*x*/, double* /*ax*/) { return DLA_ERR_ARG; }
+  // A on a row shard: rows row0 .. row0 + n_local - 1 of A with GLOBAL column indices.  Columns outside the shard must lie within
+  // `halo` rows of it (a banded matrix); every rank publishes its first and last `halo` rows of x through the all-reduce of the
+  // small-product transport (disjoint slots: a sum that gathers), see sharded_ell_* below.  Collective: every rank calls it (the
+  // halo width is agreed by a max-reduction).
   virtual int spmm_setup_csr_sharded(int /*n_local*/, long long /*row0*/, long long /*n_global*/, const long long* /*rowptr*/,
                                      const long long* /*colind*/, const double* /*values*/) { return DLA_ERR_ARG; }
-  // the single-rank operator in a chosen storage format (DLA_SPMM_ELL / _SELL / _AUTO: sell_build below) and what was stored
-  virtual int spmm_setup_csr_fmt(int /*n*/, const long long* /*rowptr*/, const int* /*colind*/, const double* /*values*/, int /*format*/) { return DLA_ERR_ARG; }
-  virtual int spmm_info(struct dla_spmm_info* /*out*/) { return DLA_ERR_ARG; }
-  virtual int spmm_matvec(int /*n*/, int /*m*/, const double* /*x*/, double* /*ax*/) { return DLA_ERR_ARG; }
+  // the diagonal preconditioners: px = x / (a_ii + fac), px = x / (a_ii + fac b_ii) of the pencil, and the harness' lrprec_1 /
+  // lrprec_2 (variant 1 / 2) on the diagonals of A+B, A-B and S+D
   virtual int spmm_precnd(int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return DLA_ERR_ARG; }
-  // a second sparse matrix beside the operator: the metric B of A x = lambda B x (single rank, any storage format), its product
-  // bx = B x and the diagonal preconditioner of the pencil, px = x / (a_ii + fac b_ii).  Setting or dropping it leaves A alone.
-  virtual int spmm_setup_metric(int /*n*/, const long long* /*rowptr*/, const int* /*colind*/, const double* /*values*/, int /*format*/) { return DLA_ERR_ARG; }
-  virtual int spmm_metric_info(struct dla_spmm_info* /*out*/) { return DLA_ERR_ARG; }
-  virtual int spmm_drop_metric() { return DLA_ERR_ARG; }
-  virtual int spmm_bvec(int /*n*/, int /*m*/, const double* /*x*/, double* /*bx*/) { return DLA_ERR_ARG; }
   virtual int spmm_precnd_pencil(int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return DLA_ERR_ARG; }
-  // either matrix (which: 0 = the operator A, 1 = the metric B) from CSR arrays in DEVICE memory, and new values for a stored pattern
-  virtual int spmm_setup_csr_dev(int /*which*/, int /*n*/, const long long* /*rowptr_dev*/, const int* /*colind_dev*/, const double* /*values_dev*/,
-                                 int /*format*/) { return DLA_ERR_ARG; }
-  virtual int spmm_refresh_values_dev(int /*which*/, int /*n*/, const long long* /*rowptr_dev*/, const int* /*colind_dev*/,
-                                      const double* /*values_dev*/) { return DLA_ERR_ARG; }
-  // four more stored matrices: the parts A+B, A-B, S+D, S-D of the linear-response pencil (part: DLA_SPMM_LR_APB .. _SMD; single
-  // rank, any storage format, independent of A, B and each other), their products y = (part) x and the harness' lrprec_1 / lrprec_2
-  // (variant 1 / 2) on the diagonals of A+B, A-B and S+D.  The host-memory test engine keeps the defaults.
-  virtual int spmm_setup_lr(int /*part*/, int /*n*/, const long long* /*rowptr*/, const int* /*colind*/, const double* /*values*/, int /*format*/) { return DLA_ERR_ARG; }
-  virtual int spmm_setup_lr_dev(int /*part*/, int /*n*/, const long long* /*rowptr_dev*/, const int* /*colind_dev*/, const double* /*values_dev*/,
-                                int /*format*/) { return DLA_ERR_ARG; }
-  virtual int spmm_refresh_lr_values_dev(int /*part*/, int /*n*/, const long long* /*rowptr_dev*/, const int* /*colind_dev*/,
-                                         const double* /*values_dev*/) { return DLA_ERR_ARG; }
-  virtual int spmm_lr_info(int /*part*/, struct dla_spmm_info* /*out*/) { return DLA_ERR_ARG; }
-  virtual int spmm_drop_lr() { return DLA_ERR_ARG; }
-  virtual int spmm_lr_mul(int /*part*/, int /*n*/, int /*m*/, const double* /*x*/, double* /*y*/) { return DLA_ERR_ARG; }
   virtual int spmm_lrprec(int /*variant*/, int /*n*/, int /*m*/, double /*fac*/, const double* /*xp*/, const double* /*xm*/,
                           double* /*yp*/, double* /*ym*/) { return DLA_ERR_ARG; }
 
@@ -469,20 +472,22 @@ struct SellLayout {
   // the rows of more than one segment: the row, and [multi rows + 1] offsets of its slots (part_ptr[j + 1] - part_ptr[j] segments)
   std::vector<int> multi_row, part_ptr;
 };
-// what every single-rank setup checks, in the words of spmm_setup_csr; w = widest row, nnz = entries
+// what every single-rank setup from host arrays checks, in the words of spmm_setup_csr under the name of `entry`; w = widest row,
+// nnz = entries
 inline int spmm_csr_check(int n, const long long* rowptr, const int* colind, const double* values, int format, int* w, long long* nnz,
-                          std::string& err)
+                          std::string& err, const char* entry = "spmm_setup_csr_fmt")
 {
+  const std::string who = std::string(entry) + ": ";
   *w = 0; *nnz = 0;
-  if (format != DLA_SPMM_ELL && format != DLA_SPMM_SELL && format != DLA_SPMM_AUTO) { err = "spmm_setup_csr_fmt: unknown format"; return DLA_ERR_ARG; }
-  if (n <= 0 || !rowptr || !colind || !values) { err = "spmm_setup_csr_fmt: bad arguments"; return DLA_ERR_ARG; }
+  if (format != DLA_SPMM_ELL && format != DLA_SPMM_SELL && format != DLA_SPMM_AUTO) { err = who + "unknown format"; return DLA_ERR_ARG; }
+  if (n <= 0 || !rowptr || !colind || !values) { err = who + "bad arguments"; return DLA_ERR_ARG; }
   for (int i = 0; i < n; ++i) {
-    if (rowptr[i + 1] < rowptr[i]) { err = "spmm_setup_csr_fmt: row pointers not ascending"; return DLA_ERR_ARG; }
+    if (rowptr[i + 1] < rowptr[i]) { err = who + "row pointers not ascending"; return DLA_ERR_ARG; }
     if (rowptr[i + 1] - rowptr[i] > *w) *w = (int)std::min<long long>(rowptr[i + 1] - rowptr[i], 2147483647LL);
   }
-  if (*w <= 0) { err = "spmm_setup_csr_fmt: empty matrix"; return DLA_ERR_ARG; }
+  if (*w <= 0) { err = who + "empty matrix"; return DLA_ERR_ARG; }
   for (long long p = rowptr[0]; p < rowptr[n]; ++p)
-    if (colind[p] < 0 || colind[p] >= n) { err = "spmm_setup_csr_fmt: column index out of range"; return DLA_ERR_ARG; }
+    if (colind[p] < 0 || colind[p] >= n) { err = who + "column index out of range"; return DLA_ERR_ARG; }
   *nnz = rowptr[n] - rowptr[0];
   return DLA_OK;
 }

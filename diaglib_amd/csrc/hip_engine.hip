@@ -5678,11 +5678,10 @@ struct HipEngine : dla::Engine {
     return DLA_OK;
   }
 
-  // ---- sample sparse operator (ELLPACK; sliced ELLPACK below)
-  // Everything ONE stored sparse matrix consists of.  The context holds six: the operator A (dla_spmm_matvec / dla_spmm_precnd), the
-  // metric B of a generalised problem (dla_spmm_bvec) and the four parts of a linear-response pencil (op_lr below); the set-up, info
-  // and launch functions below take the one they act on, so all have independent storage and independent formats and every product
-  // comes from the code that forms A's.
+  // ---- the stored sparse matrices (ELLPACK; sliced ELLPACK below)
+  // Everything ONE stored sparse matrix consists of.  The context holds six, ops[SPMM_A .. SPMM_SMD] (dla_internal.h says what they
+  // are and what ties them together); the set-up, refresh, info and launch functions below take the one they act on, so all have
+  // independent storage and independent formats and every product comes from the code that forms A's.
   struct SparseOp {
     DeviceBuffer<int> col; DeviceBuffer<double> val, diag;   // ELLPACK blocks, or the slices followed by the CSR tail; diag[n]
     int n = 0, w = 0;                  // w: ELLPACK width (0 for the sliced format)
@@ -5704,20 +5703,66 @@ struct HipEngine : dla::Engine {
       sell_long_segments = sell_multi_rows = sell_multi_segments = 0;
     }
   };
-  SparseOp op_a, op_b;
-  // ... and four more: the parts A+B, A-B, S+D, S-D of the linear-response pencil (dla_spmm_setup_lr_csr; DLA_SPMM_LR_APB .. _SMD),
-  // independent of A, B and each other.  slot() is the one place that maps (kind, index) to the storage; the set-up, refresh, info and
-  // product functions take the SparseOp it returns.
-  static constexpr int LR_PARTS = 4;
-  SparseOp op_lr[LR_PARTS];
-  enum SlotKind { SLOT_MAIN, SLOT_LR };      // MAIN: index 0 = the operator A, 1 = the metric B;  LR: index = part
-  SparseOp& slot(SlotKind kind, int index) { return kind == SLOT_LR ? op_lr[index] : (index ? op_b : op_a); }
-  static bool lr_part_ok(int part) { return part >= 0 && part < LR_PARTS; }
-  static const char* lr_name(int part) { static const char* const nm[LR_PARTS] = {"apb (A+B)", "amb (A-B)", "spd (S+D)", "smd (S-D)"}; return nm[part]; }
-  static const char* lr_mul_name(int part) { static const char* const nm[LR_PARTS] = {"spmm_apbmul", "spmm_ambmul", "spmm_spdmul", "spmm_smdmul"}; return nm[part]; }
-  bool lr_present() const { for (const SparseOp& o : op_lr) if (o.fmt >= 0) return true; return false; }
+  SparseOp ops[dla::SPMM_SLOTS];
+  // The words a message about a slot needs: what the slot is called, what is said while it is empty and beside a row-sharded A, and
+  // the name of each public entry that reaches it.  quoted_*: a refusal of the shared set-up / refresh code is passed on behind the
+  // entry's (and a part's) name; whole: the calls that are refused while A is row-sharded.  The differences between the rows are
+  // what callers have read since each family of entries was added.
+  enum SlotCall : unsigned { CALL_SETUP = 1, CALL_REFRESH = 2, CALL_SHARD = 4, NEED_STORED = 8 };
+  struct SlotWords {
+    const char *noun, *missing, *sharded;
+    const char *setup, *setup_dev, *refresh, *info, *mul;
+    bool quoted_host, quoted_dev;
+    unsigned whole;
+  };
+  static const SlotWords& words(int slot)
+  {
+#define LR_WORDS(P, SUM) {"part " P " (" SUM ")", "part " P " (" SUM ") has not been set up", "row-sharded linear-response parts are", "spmm_setup_lr_csr", \
+                          "spmm_setup_lr_csr_dev", "spmm_refresh_lr_values_dev", "spmm_lr_info", "spmm_" P "mul", true, true, CALL_SETUP | CALL_REFRESH}
+    static const SlotWords table[dla::SPMM_SLOTS] = {
+      {"operator", "no operator has been set up", "", "spmm_setup_csr_fmt", "spmm_setup_csr_dev", "spmm_refresh_values_dev", "spmm_info",
+       "spmm_matvec", false, false, CALL_REFRESH},
+      {"metric", "no metric has been set up", "a row-sharded metric is", "spmm_setup_metric_csr", "spmm_setup_csr_dev", "spmm_refresh_values_dev",
+       "spmm_metric_info", "spmm_bvec", true, false, CALL_SETUP},
+      LR_WORDS("apb", "A+B"), LR_WORDS("amb", "A-B"), LR_WORDS("spd", "S+D"), LR_WORDS("smd", "S-D")};
+#undef LR_WORDS
+    // (a number out of range is refused in the words of the entries that take such a number)
+    return table[slot == dla::SPMM_NO_PART ? dla::SPMM_APB : (slot < 0 || slot >= dla::SPMM_SLOTS) ? dla::SPMM_A : slot];
+  }
+  // "<entry>: " or "<entry>, part apb (A+B): " in front of a quoted refusal
+  static std::string quote(int slot, const char* entry)
+  {
+    return std::string(entry) + (slot >= dla::SPMM_APB ? std::string(", ") + words(slot).noun : std::string()) + ": ";
+  }
+  // The one place that decides whether a call on a slot is admitted (call: one SlotCall, with NEED_STORED where the slot must hold a
+  // matrix): the slot exists; while A is row-sharded B and the parts are refused, and so is a refresh of A; the sharded set-up
+  // (CALL_SHARD, slot SPMM_A) is refused while B or a part is stored.  Leaves the refusal in err.
+  int admit(int slot, const char* entry, unsigned call)
+  {
+    const std::string who = std::string(entry) + ": ";
+    if (slot < 0 || slot >= dla::SPMM_SLOTS) {
+      err = who + (slot == dla::SPMM_NO_PART ? "part must be 0 (A+B), 1 (A-B), 2 (S+D) or 3 (S-D)" : "which must be 0 (the operator) or 1 (the metric)");
+      return DLA_ERR_ARG;
+    }
+    const SlotWords& w = words(slot);
+    if (call & CALL_SHARD) {
+      for (int s = dla::SPMM_SLOTS - 1; s > dla::SPMM_A; --s) {
+        if (ops[s].fmt < 0) continue;
+        err = who + (s == dla::SPMM_B ? "this context holds a metric (dla_spmm_setup_metric_csr), and a row-sharded metric is not supported; drop it first"
+                                      : "this context holds linear-response parts (dla_spmm_setup_lr_csr), and row-sharded parts are not supported; drop them first (dla_spmm_drop_lr)");
+        return DLA_ERR_ARG;
+      }
+    }
+    if (shard.on && (call & w.whole) && slot != dla::SPMM_A) {
+      err = who + "the operator of this context is row-sharded, and " + w.sharded + " not supported";
+      return DLA_ERR_ARG;
+    }
+    if ((call & NEED_STORED) && ops[slot].fmt < 0) { err = who + w.missing; return DLA_ERR_ARG; }
+    if (shard.on && (call & w.whole)) { err = who + "the operator of this context is row-sharded"; return DLA_ERR_ARG; }
+    return DLA_OK;
+  }
   // A on a row shard (spmm_setup_sharded; A only): whether it is, and the exchange with the neighbouring ranks.  The one place that
-  // answers "is A sharded" -- the sharded set-up and the metric's refuse each other by it.
+  // answers "is A sharded" (admit above goes by it).
   struct RowShard {
     bool on = false;
     int halo = 0;                      // rows exchanged with each neighbour
@@ -5739,16 +5784,9 @@ struct HipEngine : dla::Engine {
     HIPCHK(hipMemcpy(op.diag, diag.data(), sizeof(double) * diag.size(), hipMemcpyHostToDevice));
     return DLA_OK;
   }
-  int setup_ell(SparseOp& op, int n, const long long* rowptr, const int* colind, const double* values)
+  // (the matrix has passed dla::spmm_csr_check; w: its widest row)
+  int setup_ell(SparseOp& op, int n, int w, const long long* rowptr, const int* colind, const double* values)
   {
-    if (n <= 0 || !rowptr || !colind || !values) { err = "spmm_setup_csr: bad arguments"; return DLA_ERR_ARG; }
-    int w = 0;
-    for (int i = 0; i < n; ++i) {
-      // (as sharded_ell_need: a descending pair used to pass for an empty row)
-      if (rowptr[i + 1] < rowptr[i]) { err = "spmm_setup_csr: row pointers not ascending"; return DLA_ERR_ARG; }
-      w = std::max(w, (int)(rowptr[i + 1] - rowptr[i]));
-    }
-    if (w <= 0) { err = "spmm_setup_csr: empty matrix"; return DLA_ERR_ARG; }
     std::vector<int> col((size_t)w * n);
     std::vector<double> val((size_t)w * n, 0.0), diag((size_t)n, 0.0);
     for (int i = 0; i < n; ++i) {
@@ -5756,7 +5794,6 @@ struct HipEngine : dla::Engine {
       for (int q = 0; q < w; ++q) {
         const bool in = p0 + q < p1;
         const int cj = in ? colind[p0 + q] : i;
-        if (cj < 0 || cj >= n) { err = "spmm_setup_csr: column index out of range"; return DLA_ERR_ARG; }
         col[(size_t)q * n + i] = cj;
         val[(size_t)q * n + i] = in ? values[p0 + q] : 0.0;
         if (in && cj == i) diag[i] += values[p0 + q];
@@ -5770,17 +5807,12 @@ struct HipEngine : dla::Engine {
     op.fmt = DLA_SPMM_ELL; op.nnz = rowptr[n] - rowptr[0];
     return DLA_OK;
   }
-  int spmm_setup_csr(int n, const long long* rowptr, const int* colind, const double* values) override
-  {
-    { const int stc = setup_ell(op_a, n, rowptr, colind, values); if (stc) return stc; }
-    shard.drop();
-    return DLA_OK;
-  }
   // ---- ... as sliced ELLPACK with a CSR tail (dla::sell_build).  The slices and the tail share the ELLPACK blocks -- columns and
   // values of the tail follow the `stored` padded entries of the slices -- so either format replaces the other in place.
   static constexpr int SELL_MC = 8, LONG_MC = 4;   // right-hand sides per load of a matrix entry (sell_spmm_kernel / csr_long_segments_kernel)
   // room for a sliced layout in op's blocks and the layout's small tables (everything but the entries and the diagonal); rowptr: host.
   // The caller has bound the device and waited for the stream.
+  static hipError_t up(void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; }
   int place_sell(SparseOp& op, int n, const dla::SellLayout& L, const long long* rowptr)
   {
     const size_t tot = (size_t)(L.stored + L.long_entries), nl = L.long_row.size(), ns = L.seg_row.size(), nm = L.multi_row.size();
@@ -5797,7 +5829,6 @@ struct HipEngine : dla::Engine {
     HIPCHK(op.part_ptr.reserve(nm + 1));
     HIPCHK(op.rowptr.reserve((size_t)n + 1));
     HIPCHK(op.long_ptr.reserve(nl + 1));
-    auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
     HIPCHK(up(op.sell_ptr, L.slice_ptr.data(), sizeof(long long) * L.slice_ptr.size()));
     HIPCHK(up(op.sell_perm, L.perm.data(), sizeof(int) * (size_t)n));
     HIPCHK(up(op.long_row, L.long_row.data(), sizeof(int) * nl));
@@ -5818,17 +5849,17 @@ struct HipEngine : dla::Engine {
     op.sell_slices = L.slices; op.sell_long_rows = (int)L.long_row.size();
     op.sell_long_segments = L.long_segments; op.sell_multi_rows = (int)L.multi_row.size(); op.sell_multi_segments = L.multi_segments;
   }
-  int setup_fmt(SparseOp& op, int n, const long long* rowptr, const int* colind, const double* values, int format)
+  // entry: the name the checks speak under
+  int setup_fmt(SparseOp& op, int n, const long long* rowptr, const int* colind, const double* values, int format, const char* entry)
   {
     int w = 0; long long nnz = 0;
-    { const int stc = dla::spmm_csr_check(n, rowptr, colind, values, format, &w, &nnz, err); if (stc) return stc; }
-    if (dla::spmm_pick_format(format, w, n, nnz) == DLA_SPMM_ELL) return setup_ell(op, n, rowptr, colind, values);
+    { const int stc = dla::spmm_csr_check(n, rowptr, colind, values, format, &w, &nnz, err, entry); if (stc) return stc; }
+    if (dla::spmm_pick_format(format, w, n, nnz) == DLA_SPMM_ELL) return setup_ell(op, n, w, rowptr, colind, values);
     dla::SellLayout L;
     dla::sell_build(n, rowptr, colind, values, L);
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamSynchronize(st));
     { const int stc = place_sell(op, n, L, rowptr); if (stc) return stc; }
-    auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
     HIPCHK(up(op.col, L.col.data(), sizeof(int) * L.col.size()));
     HIPCHK(up(op.val, L.val.data(), sizeof(double) * L.val.size()));
     HIPCHK(up(op.col + L.stored, L.long_col.data(), sizeof(int) * L.long_col.size()));
@@ -5932,23 +5963,15 @@ struct HipEngine : dla::Engine {
     HIPCHK(hipStreamSynchronize(st));       // (the caller may free or overwrite its arrays from here on)
     return DLA_OK;
   }
-  int spmm_setup_csr_dev(int which, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev, int format) override
-  {
-    if (which != 0 && which != 1) { err = "spmm_setup_csr_dev: which must be 0 (the operator) or 1 (the metric)"; return DLA_ERR_ARG; }
-    if (which == 1 && shard.on) { err = "spmm_setup_csr_dev: the operator of this context is row-sharded, and a row-sharded metric is not supported"; return DLA_ERR_ARG; }
-    { const int stc = setup_dev(slot(SLOT_MAIN, which), n, rowptr_dev, colind_dev, values_dev, format); if (stc) return stc; }
-    if (which == 0) shard.drop();
-    return DLA_OK;
-  }
   // new values for the pattern a slot holds: everything is compared in a read-only pass (pattern_compare_kernel) that is waited
   // for before the first value is written; the stored format stays (AUTO is not decided again).  Synchronous like the set-up.
-  int spmm_refresh_values_dev(int which, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev) override
+  int spmm_refresh_dev(int slot, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev) override
   {
-    if (which != 0 && which != 1) { err = "spmm_refresh_values_dev: which must be 0 (the operator) or 1 (the metric)"; return DLA_ERR_ARG; }
-    SparseOp& op = slot(SLOT_MAIN, which);
-    if (op.fmt < 0) { err = which ? "spmm_refresh_values_dev: no metric has been set up" : "spmm_refresh_values_dev: no operator has been set up"; return DLA_ERR_ARG; }
-    if (which == 0 && shard.on) { err = "spmm_refresh_values_dev: the operator of this context is row-sharded"; return DLA_ERR_ARG; }
-    return refresh_dev(op, n, rowptr_dev, colind_dev, values_dev);
+    const SlotWords& w = words(slot);
+    { const int stc = admit(slot, w.refresh, CALL_REFRESH | NEED_STORED); if (stc) return stc; }
+    const int stc = refresh_dev(ops[slot], n, rowptr_dev, colind_dev, values_dev);
+    if (stc == DLA_ERR_ARG && w.quoted_dev) err = quote(slot, w.refresh) + err;
+    return stc;
   }
   // (op holds a matrix and is not row-sharded)
   int refresh_dev(SparseOp& op, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev)
@@ -5988,11 +6011,18 @@ struct HipEngine : dla::Engine {
     HIPCHK(hipStreamSynchronize(st));
     return DLA_OK;
   }
-  int spmm_setup_csr_fmt(int n, const long long* rowptr, const int* colind, const double* values, int format) override
+  // from CSR arrays in host or device memory (via: dla::SpmmVia; PLAIN stores ELLPACK and speaks under its own name)
+  int spmm_setup(int slot, int via, int n, const long long* rowptr, const int* colind, const double* values, int format) override
   {
-    { const int stc = setup_fmt(op_a, n, rowptr, colind, values, format); if (stc) return stc; }
-    shard.drop();
-    return DLA_OK;
+    const SlotWords& w = words(slot);
+    const bool dev = via == dla::SPMM_VIA_DEVICE, plain = via == dla::SPMM_VIA_PLAIN, quoted = dev ? w.quoted_dev : w.quoted_host;
+    const char* entry = plain ? "spmm_setup_csr" : dev ? w.setup_dev : w.setup;
+    { const int stc = admit(slot, entry, CALL_SETUP); if (stc) return stc; }
+    const int stc = dev ? setup_dev(ops[slot], n, rowptr, colind, values, format)
+                        : setup_fmt(ops[slot], n, rowptr, colind, values, plain ? (int)DLA_SPMM_ELL : format, quoted ? "spmm_setup_csr_fmt" : entry);
+    if (stc == DLA_ERR_ARG && quoted) err = quote(slot, entry) + err;
+    if (!stc && slot == dla::SPMM_A) shard.drop();
+    return stc;
   }
   int op_info(const SparseOp& op, struct dla_spmm_info* out) const
   {
@@ -6012,10 +6042,21 @@ struct HipEngine : dla::Engine {
     }
     return DLA_OK;
   }
-  int spmm_info(struct dla_spmm_info* out) override
+  int spmm_info(int slot, struct dla_spmm_info* out) override
   {
-    if (op_a.fmt < 0 || !out) { err = "spmm_info: no operator has been set up"; return DLA_ERR_ARG; }
-    return op_info(op_a, out);
+    { const int stc = admit(slot, words(slot).info, NEED_STORED); if (stc) return stc; }
+    return op_info(ops[slot], out);
+  }
+  // (nothing stored: neither the device nor the stream is touched)
+  int spmm_drop(int first, int last) override
+  {
+    bool any = false;
+    for (int s = first; s <= last; ++s) any = any || ops[s].fmt >= 0 || ops[s].col;
+    if (!any) return DLA_OK;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipStreamSynchronize(st));     // (products of these slots may still be queued)
+    for (int s = first; s <= last; ++s) ops[s].drop();
+    return DLA_OK;
   }
   // slices kernel, segments kernel, combine kernel; p: the tail's launch shapes and workspace (long_rows_plan)
   int op_matvec_sell(SparseOp& op, const LongRowsPlan& p, int n, int m, const double* x, double* ax)
@@ -6087,10 +6128,10 @@ struct HipEngine : dla::Engine {
   {
     int w = 0; long long need = 0;
     std::string lerr;
-    // (a metric beside a sharded operator would have to be sharded as well: refused like a bad shard, so that every rank agrees)
-    if (op_b.fmt >= 0) lerr = "spmm_setup_csr_sharded: this context holds a metric (dla_spmm_setup_metric_csr), and a row-sharded metric is not supported; drop it first";
-    if (lr_present()) lerr = "spmm_setup_csr_sharded: this context holds linear-response parts (dla_spmm_setup_lr_csr), and row-sharded parts are not supported; drop them first (dla_spmm_drop_lr)";
-    const int bad = (op_b.fmt >= 0 || lr_present() || values == nullptr) ? DLA_ERR_ARG : dla::sharded_ell_need(n, row0, n_global, rowptr, colind, &w, &need, lerr);
+    // (a metric or a part beside a sharded operator would have to be sharded as well: refused like a bad shard, so that every rank agrees)
+    const bool held = admit(dla::SPMM_A, "spmm_setup_csr_sharded", CALL_SHARD) != DLA_OK;
+    if (held) lerr = err;
+    const int bad = (held || values == nullptr) ? DLA_ERR_ARG : dla::sharded_ell_need(n, row0, n_global, rowptr, colind, &w, &need, lerr);
     const int nr = std::max(1, nranks);
     // agree on the halo width and check the layout, collectively: [max need | any failure | row0 and n of every rank (slots)]
     std::vector<double> mx{(double)need, bad ? 1.0 : 0.0};
@@ -6121,10 +6162,10 @@ struct HipEngine : dla::Engine {
     dla::ShardedEll e;
     dla::sharded_ell_build(n, row0, rowptr, colind, values, (int)halo, e);
     bind();
-    stc = upload_ell(op_a, e.col, e.val, e.diag);
+    stc = upload_ell(ops[dla::SPMM_A], e.col, e.val, e.diag);
     if (stc) return stc;
-    op_a.n = n; op_a.w = e.w; shard.halo = (int)halo; shard.on = true;
-    op_a.fmt = DLA_SPMM_ELL; op_a.nnz = rowptr[n] - rowptr[0];
+    ops[dla::SPMM_A].n = n; ops[dla::SPMM_A].w = e.w; shard.halo = (int)halo; shard.on = true;
+    ops[dla::SPMM_A].fmt = DLA_SPMM_ELL; ops[dla::SPMM_A].nnz = rowptr[n] - rowptr[0];
     return DLA_OK;
   }
   int spmm_matvec_sharded(int n, int m, const double* x, double* ax)
@@ -6157,67 +6198,52 @@ struct HipEngine : dla::Engine {
       // (the first / last rank never index their missing neighbour: any valid address serves)
       const double* prev = shard.d_halo + (size_t)((rank > 0 ? (rank - 1) * 2 + 1 : 0) * mcur) * H;
       const double* next = shard.d_halo + (size_t)((rank + 1 < nr ? (rank + 1) * 2 : 0) * mcur) * H;
-#define ELLH(W) DLA_LAUNCH((ell_spmm_halo_kernel<W>), dim3(blocks), dim3(256), 0, st, n, mcur, op_a.w, H, (const int*)op_a.col, (const double*)op_a.val, xc, prev, next, ax + (size_t)c0 * n)
-      if (op_a.w <= 4) ELLH(4); else if (op_a.w <= 8) ELLH(8); else if (op_a.w <= 16) ELLH(16); else if (op_a.w <= 32) ELLH(32); else ELLH(0);
+#define ELLH(W) DLA_LAUNCH((ell_spmm_halo_kernel<W>), dim3(blocks), dim3(256), 0, st, n, mcur, ops[dla::SPMM_A].w, H, (const int*)ops[dla::SPMM_A].col, (const double*)ops[dla::SPMM_A].val, xc, prev, next, ax + (size_t)c0 * n)
+      if (ops[dla::SPMM_A].w <= 4) ELLH(4); else if (ops[dla::SPMM_A].w <= 8) ELLH(8); else if (ops[dla::SPMM_A].w <= 16) ELLH(16); else if (ops[dla::SPMM_A].w <= 32) ELLH(32); else ELLH(0);
 #undef ELLH
       HIPCHK(hipGetLastError());
     }
     return DLA_OK;
   }
-  int spmm_matvec(int n, int m, const double* x, double* ax) override
+  // y = (slot) x; the words of a refusal are the callback's (SlotWords::mul)
+  int spmm_mul(int slot, int n, int m, const double* x, double* y) override
   {
-    if (n != op_a.n || !op_a.col) { err = "spmm_matvec: n differs from setup"; return DLA_ERR_ARG; }
-    if (shard.on) {
-      Scope s(this, DLA_OP_MATVEC, 12.0 * (double)op_a.w * n + 16.0 * (double)n * m, 2.0 * (double)op_a.w * n * m);
-      return spmm_matvec_sharded(n, m, x, ax);
+    { const int stc = admit(slot, words(slot).mul, 0); if (stc) return stc; }
+    const SlotWords& w = words(slot);
+    SparseOp& op = ops[slot];
+    const std::string who = std::string(w.mul) + ": ";
+    if (slot == dla::SPMM_A) {
+      if (n != op.n || !op.col) { err = who + "n differs from setup"; return DLA_ERR_ARG; }
+    } else {
+      if (op.fmt < 0) { err = who + w.missing + " (dla_" + w.setup + ")"; return DLA_ERR_ARG; }
+      if (n != op.n && slot == dla::SPMM_B) { err = who + "n differs from the metric's"; return DLA_ERR_ARG; }
+      if (n != op.n) { err = who + "n = " + std::to_string(n) + " differs from the " + std::to_string(op.n) + " rows of " + w.noun; return DLA_ERR_ARG; }
     }
-    return op_matvec(op_a, n, m, x, ax);
+    if (shard.on && slot == dla::SPMM_A) {
+      Scope s(this, DLA_OP_MATVEC, 12.0 * (double)op.w * n + 16.0 * (double)n * m, 2.0 * (double)op.w * n * m);
+      return spmm_matvec_sharded(n, m, x, y);
+    }
+    return op_matvec(op, n, m, x, y);
   }
   int spmm_precnd(int n, int m, double fac, const double* x, double* px) override
   {
-    if (n != op_a.n || !op_a.diag) { err = "spmm_precnd: n differs from setup"; return DLA_ERR_ARG; }
+    if (n != ops[dla::SPMM_A].n || !ops[dla::SPMM_A].diag) { err = "spmm_precnd: n differs from setup"; return DLA_ERR_ARG; }
     Scope s(this, DLA_OP_PRECND, 8.0 * n * (2.0 * m + 1.0), (double)n * m);
     const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
-    DLA_LAUNCH(diag_precnd_kernel, dim3(blocks), dim3(256), 0, st, n, m, fac, (const double*)op_a.diag, x, px);
+    DLA_LAUNCH(diag_precnd_kernel, dim3(blocks), dim3(256), 0, st, n, m, fac, (const double*)ops[dla::SPMM_A].diag, x, px);
     HIPCHK(hipGetLastError());
     return DLA_OK;
   }
-  // ---- ... and a second matrix beside it: the metric B of A x = lambda B x (bvec of reference diaglib.f90:1855), single rank
-  int spmm_setup_metric(int n, const long long* rowptr, const int* colind, const double* values, int format) override
-  {
-    if (shard.on) { err = "spmm_setup_metric_csr: the operator of this context is row-sharded, and a row-sharded metric is not supported"; return DLA_ERR_ARG; }
-    const int stc = setup_fmt(op_b, n, rowptr, colind, values, format);
-    if (stc == DLA_ERR_ARG) err = "spmm_setup_metric_csr: " + err;
-    return stc;
-  }
-  int spmm_metric_info(struct dla_spmm_info* out) override
-  {
-    if (op_b.fmt < 0 || !out) { err = "spmm_metric_info: no metric has been set up"; return DLA_ERR_ARG; }
-    return op_info(op_b, out);
-  }
-  int spmm_drop_metric() override
-  {
-    if (op_b.fmt < 0 && !op_b.col) return DLA_OK;
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipStreamSynchronize(st));     // (products of B may still be queued)
-    op_b.drop();
-    return DLA_OK;
-  }
-  int spmm_bvec(int n, int m, const double* x, double* bx) override
-  {
-    if (op_b.fmt < 0) { err = "spmm_bvec: no metric has been set up (dla_spmm_setup_metric_csr)"; return DLA_ERR_ARG; }
-    if (n != op_b.n) { err = "spmm_bvec: n differs from the metric's"; return DLA_ERR_ARG; }
-    return op_matvec(op_b, n, m, x, bx);
-  }
+  // ---- ... of the pencil A - lambda B of a generalised problem (the metric B: bvec of reference diaglib.f90:1855)
   int spmm_precnd_pencil(int n, int m, double fac, const double* x, double* px) override
   {
-    if (op_a.fmt < 0 || !op_a.diag) { err = "spmm_precnd_pencil: no operator has been set up"; return DLA_ERR_ARG; }
-    if (op_b.fmt < 0) { err = "spmm_precnd_pencil: no metric has been set up (dla_spmm_setup_metric_csr)"; return DLA_ERR_ARG; }
-    if (op_a.n != op_b.n) { err = "spmm_precnd_pencil: the operator has " + std::to_string(op_a.n) + " rows and the metric " + std::to_string(op_b.n); return DLA_ERR_ARG; }
-    if (n != op_a.n) { err = "spmm_precnd_pencil: n differs from setup"; return DLA_ERR_ARG; }
+    if (ops[dla::SPMM_A].fmt < 0 || !ops[dla::SPMM_A].diag) { err = "spmm_precnd_pencil: no operator has been set up"; return DLA_ERR_ARG; }
+    if (ops[dla::SPMM_B].fmt < 0) { err = "spmm_precnd_pencil: no metric has been set up (dla_spmm_setup_metric_csr)"; return DLA_ERR_ARG; }
+    if (ops[dla::SPMM_A].n != ops[dla::SPMM_B].n) { err = "spmm_precnd_pencil: the operator has " + std::to_string(ops[dla::SPMM_A].n) + " rows and the metric " + std::to_string(ops[dla::SPMM_B].n); return DLA_ERR_ARG; }
+    if (n != ops[dla::SPMM_A].n) { err = "spmm_precnd_pencil: n differs from setup"; return DLA_ERR_ARG; }
     Scope s(this, DLA_OP_PRECND, 16.0 * (double)n * m + 16.0 * (double)n, 2.0 * (double)n * m);
     const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
-    DLA_LAUNCH(pencil_precnd_kernel, dim3(blocks), dim3(256), 0, st, n, m, fac, (const double*)op_a.diag, (const double*)op_b.diag, x, px);
+    DLA_LAUNCH(pencil_precnd_kernel, dim3(blocks), dim3(256), 0, st, n, m, fac, (const double*)ops[dla::SPMM_A].diag, (const double*)ops[dla::SPMM_B].diag, x, px);
     HIPCHK(hipGetLastError());
     return DLA_OK;
   }
@@ -6226,72 +6252,19 @@ struct HipEngine : dla::Engine {
   // callbacks apbmul / ambmul / spdmul / smdmul of caslr_eff_driver / caslr_driver apply them (reference diaglib.f90:1024-1025),
   // single rank.  Set-up, refresh, info and products are the operator's own functions on another SparseOp; nothing here or in the
   // product kernels assumes a symmetric matrix (S+D and S-D are not).
-  int lr_slot_check(const char* entry, int part)
-  {
-    if (!lr_part_ok(part)) { err = std::string(entry) + ": part must be 0 (A+B), 1 (A-B), 2 (S+D) or 3 (S-D)"; return DLA_ERR_ARG; }
-    if (shard.on) { err = std::string(entry) + ": the operator of this context is row-sharded, and row-sharded linear-response parts are not supported"; return DLA_ERR_ARG; }
-    return DLA_OK;
-  }
-  int spmm_setup_lr(int part, int n, const long long* rowptr, const int* colind, const double* values, int format) override
-  {
-    { const int stc = lr_slot_check("spmm_setup_lr_csr", part); if (stc) return stc; }
-    const int stc = setup_fmt(slot(SLOT_LR, part), n, rowptr, colind, values, format);
-    if (stc == DLA_ERR_ARG) err = std::string("spmm_setup_lr_csr, part ") + lr_name(part) + ": " + err;
-    return stc;
-  }
-  int spmm_setup_lr_dev(int part, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev, int format) override
-  {
-    { const int stc = lr_slot_check("spmm_setup_lr_csr_dev", part); if (stc) return stc; }
-    const int stc = setup_dev(slot(SLOT_LR, part), n, rowptr_dev, colind_dev, values_dev, format);
-    if (stc == DLA_ERR_ARG) err = std::string("spmm_setup_lr_csr_dev, part ") + lr_name(part) + ": " + err;
-    return stc;
-  }
-  int spmm_refresh_lr_values_dev(int part, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev) override
-  {
-    { const int stc = lr_slot_check("spmm_refresh_lr_values_dev", part); if (stc) return stc; }
-    SparseOp& op = slot(SLOT_LR, part);
-    if (op.fmt < 0) { err = std::string("spmm_refresh_lr_values_dev: part ") + lr_name(part) + " has not been set up"; return DLA_ERR_ARG; }
-    const int stc = refresh_dev(op, n, rowptr_dev, colind_dev, values_dev);
-    if (stc == DLA_ERR_ARG) err = std::string("spmm_refresh_lr_values_dev, part ") + lr_name(part) + ": " + err;
-    return stc;
-  }
-  int spmm_lr_info(int part, struct dla_spmm_info* out) override
-  {
-    if (!lr_part_ok(part)) { err = "spmm_lr_info: part must be 0 (A+B), 1 (A-B), 2 (S+D) or 3 (S-D)"; return DLA_ERR_ARG; }
-    if (op_lr[part].fmt < 0 || !out) { err = std::string("spmm_lr_info: part ") + lr_name(part) + " has not been set up"; return DLA_ERR_ARG; }
-    return op_info(slot(SLOT_LR, part), out);
-  }
-  int spmm_drop_lr() override
-  {
-    bool any = false;
-    for (const SparseOp& o : op_lr) any = any || o.fmt >= 0 || o.col;
-    if (!any) return DLA_OK;
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipStreamSynchronize(st));     // (products of the parts may still be queued)
-    for (SparseOp& o : op_lr) o.drop();
-    return DLA_OK;
-  }
-  int spmm_lr_mul(int part, int n, int m, const double* x, double* y) override
-  {
-    if (!lr_part_ok(part)) { err = "spmm_lr_mul: bad part"; return DLA_ERR_ARG; }
-    SparseOp& op = slot(SLOT_LR, part);
-    if (op.fmt < 0) { err = std::string(lr_mul_name(part)) + ": part " + lr_name(part) + " has not been set up (dla_spmm_setup_lr_csr)"; return DLA_ERR_ARG; }
-    if (n != op.n) { err = std::string(lr_mul_name(part)) + ": n = " + std::to_string(n) + " differs from the " + std::to_string(op.n) + " rows of part " + lr_name(part); return DLA_ERR_ARG; }
-    return op_matvec(op, n, m, x, y);
-  }
   int spmm_lrprec(int variant, int n, int m, double fac, const double* xp, const double* xm, double* yp, double* ym) override
   {
     const std::string who = variant == 1 ? "spmm_lrprec1" : "spmm_lrprec2";
-    for (int part : {(int)DLA_SPMM_LR_APB, (int)DLA_SPMM_LR_AMB, (int)DLA_SPMM_LR_SPD}) {
-      const SparseOp& op = op_lr[part];
-      if (op.fmt < 0 || !op.diag) { err = who + ": part " + lr_name(part) + " has not been set up (dla_spmm_setup_lr_csr)"; return DLA_ERR_ARG; }
-      if (n != op.n) { err = who + ": n = " + std::to_string(n) + " differs from the " + std::to_string(op.n) + " rows of part " + lr_name(part); return DLA_ERR_ARG; }
+    for (int slot : {(int)dla::SPMM_APB, (int)dla::SPMM_AMB, (int)dla::SPMM_SPD}) {
+      const SparseOp& op = ops[slot];
+      if (op.fmt < 0 || !op.diag) { err = who + ": " + words(slot).missing + " (dla_spmm_setup_lr_csr)"; return DLA_ERR_ARG; }
+      if (n != op.n) { err = who + ": n = " + std::to_string(n) + " differs from the " + std::to_string(op.n) + " rows of " + words(slot).noun; return DLA_ERR_ARG; }
     }
     Scope s(this, DLA_OP_PRECND, 32.0 * (double)n * m + 24.0 * (double)n, 8.0 * (double)n * m);
     const bool vec2 = even_rows(n) && (((uintptr_t)xp | (uintptr_t)xm | (uintptr_t)yp | (uintptr_t)ym) % 16 == 0);
     const size_t nv = (size_t)n / (vec2 ? 2 : 1);
     const int blocks = (int)std::max((size_t)1, std::min((size_t)ncu * 8, (nv + 255) / 256));
-    const double *da = op_lr[DLA_SPMM_LR_APB].diag, *dm = op_lr[DLA_SPMM_LR_AMB].diag, *ds = op_lr[DLA_SPMM_LR_SPD].diag;
+    const double *da = ops[dla::SPMM_APB].diag, *dm = ops[dla::SPMM_AMB].diag, *ds = ops[dla::SPMM_SPD].diag;
     if (vec2) DLA_LAUNCH(lr_precnd_kernel<2>, dim3(blocks), dim3(256), 0, st, n, m, variant, fac, da, dm, ds, xp, xm, yp, ym);
     else      DLA_LAUNCH(lr_precnd_kernel<1>, dim3(blocks), dim3(256), 0, st, n, m, variant, fac, da, dm, ds, xp, xm, yp, ym);
     HIPCHK(hipGetLastError());

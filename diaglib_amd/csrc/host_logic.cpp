@@ -1222,14 +1222,33 @@ static int staged_callback(dla_ctx* c, int n, int m, const double* x, double* y,
   return engfail(c, c->eng->stage_end());
 }
 
-// the library's own device-resident operators: they enqueue on the engine's stream (ordering contract 2 whatever the
-// context says) and are pure functions of their input block (safe to call again on the same block)
+// The library's own device-resident callbacks.  All of them enqueue on the engine's stream (ordering contract 2 whatever the
+// context says); the operators among them are pure functions of their input block (safe to call again on the same block).
+struct OwnCallback { void* fn; bool pure_operator, on_engine_stream; };
+static const OwnCallback* own_callback(void* fn)
+{
+  static const OwnCallback table[] = {
+    {(void*)&dla_synth_matvec, true, true}, {(void*)&dla_synth_apbmul, true, true}, {(void*)&dla_synth_ambmul, true, true},
+    {(void*)&dla_synth_spdmul, true, true}, {(void*)&dla_synth_smdmul, true, true}, {(void*)&dla_synth_metric, true, true},
+    {(void*)&dla_spmm_matvec, true, true}, {(void*)&dla_spmm_bvec, true, true}, {(void*)&dla_spmm_apbmul, true, true},
+    {(void*)&dla_spmm_ambmul, true, true}, {(void*)&dla_spmm_spdmul, true, true}, {(void*)&dla_spmm_smdmul, true, true},
+    {(void*)&dla_synth_precnd, false, true}, {(void*)&dla_spmm_precnd, false, true}, {(void*)&dla_spmm_precnd_pencil, false, true},
+    {(void*)&dla_synth_lrprec1, false, true}, {(void*)&dla_synth_lrprec2, false, true}, {(void*)&dla_spmm_lrprec1, false, true},
+    {(void*)&dla_spmm_lrprec2, false, true}};
+  for (const OwnCallback& r : table)
+    if (r.fn == fn) return &r;
+  return nullptr;
+}
 static bool builtin_operator(dla_matvec_fn fn)
 {
-  return (void*)fn == (void*)&dla_synth_matvec || (void*)fn == (void*)&dla_spmm_matvec || (void*)fn == (void*)&dla_synth_apbmul ||
-         (void*)fn == (void*)&dla_synth_ambmul || (void*)fn == (void*)&dla_synth_spdmul || (void*)fn == (void*)&dla_synth_smdmul ||
-         (void*)fn == (void*)&dla_synth_metric || (void*)fn == (void*)&dla_spmm_bvec || (void*)fn == (void*)&dla_spmm_apbmul ||
-         (void*)fn == (void*)&dla_spmm_ambmul || (void*)fn == (void*)&dla_spmm_spdmul || (void*)fn == (void*)&dla_spmm_smdmul;
+  const OwnCallback* r = own_callback((void*)fn);
+  return r && r->pure_operator;
+}
+// the ordering contract of a device-mode callback: 2 for the library's own, else the context's
+static int callback_order_of(dla_ctx* c, void* fn)
+{
+  const OwnCallback* r = own_callback(fn);
+  return r && r->on_engine_stream ? 2 : c->callback_order;
 }
 
 int dla_call_matvec(dla_ctx* c, dla_matvec_fn fn, int n, int m, const double* x, double* ax)
@@ -1238,7 +1257,7 @@ int dla_call_matvec(dla_ctx* c, dla_matvec_fn fn, int n, int m, const double* x,
   if (m <= 0) return DLA_OK;
   if (c->callbacks_on_device) {
     // the built-in operators run on the engine's own stream: nothing to order
-    const int order = builtin_operator(fn) ? 2 : c->callback_order;
+    const int order = callback_order_of(c, (void*)fn);
     int st = c->eng->callback_begin(order);
     if (st) return engfail(c, st);
     fn(&n, &m, x, ax);
@@ -1754,8 +1773,7 @@ int dla_call_precnd(dla_ctx* c, dla_precnd_fn fn, int n, int m, double fac, cons
   DLA_T("dla_call_precnd");
   if (m <= 0) return DLA_OK;
   if (c->callbacks_on_device) {
-    const int order = ((void*)fn == (void*)&dla_synth_precnd || (void*)fn == (void*)&dla_spmm_precnd ||
-                       (void*)fn == (void*)&dla_spmm_precnd_pencil) ? 2 : c->callback_order;
+    const int order = callback_order_of(c, (void*)fn);
     int st = c->eng->callback_begin(order);
     if (st) return engfail(c, st);
     fn(&n, &m, &fac, x, px);
@@ -1775,8 +1793,7 @@ int dla_call_lrprec(dla_ctx* c, dla_lrprec_fn fn, int n, int m, double fac, cons
   DLA_T("dla_call_lrprec");
   if (m <= 0) return DLA_OK;
   if (c->callbacks_on_device) {
-    const int order = ((void*)fn == (void*)&dla_synth_lrprec1 || (void*)fn == (void*)&dla_synth_lrprec2 ||
-                       (void*)fn == (void*)&dla_spmm_lrprec1 || (void*)fn == (void*)&dla_spmm_lrprec2) ? 2 : c->callback_order;
+    const int order = callback_order_of(c, (void*)fn);
     int st = c->eng->callback_begin(order);
     if (st) return engfail(c, st);
     fn(&n, &m, &fac, xp, xm, yp, ym);
@@ -1851,27 +1868,69 @@ static void synth_lrp(int variant, const int* n, const int* m, const double* fac
 void dla_synth_lrprec1(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { synth_lrp(1, n, m, fac, xp, xm, yp, ym); }
 void dla_synth_lrprec2(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { synth_lrp(2, n, m, fac, xp, xm, yp, ym); }
 
-// ------------------------------------------------------------------ sample sparse operator
-int dla_spmm_setup_csr(dla_ctx* c, int n, const long long* rowptr, const int* colind, const double* values)
+// ------------------------------------------------------------------ the stored sparse matrices (dla_internal.h, SpmmSlot)
+// Every entry below is one of six calls on a slot (set-up, refresh, info, drop, product, preconditioner).  What differs between the entries besides the slot:
+//   * which context the thread's callbacks act on (g_spmm_ctx): a set-up of A binds its context before the engine is asked, so also
+//     when the set-up is refused; a set-up of B or of a part binds it once the set-up is accepted; info, refresh and drop never do;
+//   * the text a callback fails with (the SpmmCallback rows).
+using dla::SPMM_A; using dla::SPMM_B; using dla::SPMM_APB; using dla::SPMM_SMD;
+static int spmm_set_up(dla_ctx* c, int slot, int via, int n, const long long* rowptr, const int* colind, const double* values, int format)
 {
   if (!c) return DLA_ERR_ARG;
-  g_spmm_ctx = c;
-  return engfail(c, c->eng->spmm_setup_csr(n, rowptr, colind, values));
+  if (slot == SPMM_A) g_spmm_ctx = c;
+  const int st = engfail(c, c->eng->spmm_setup(slot, via, n, rowptr, colind, values, format));
+  if (st == DLA_OK) g_spmm_ctx = c;
+  return st;
 }
-
-int dla_spmm_setup_csr_fmt(dla_ctx* c, int n, const long long* rowptr, const int* colind, const double* values, int format)
+static int spmm_refresh(dla_ctx* c, int slot, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev)
 {
   if (!c) return DLA_ERR_ARG;
-  g_spmm_ctx = c;
-  return engfail(c, c->eng->spmm_setup_csr_fmt(n, rowptr, colind, values, format));
+  return engfail(c, c->eng->spmm_refresh_dev(slot, n, rowptr_dev, colind_dev, values_dev));
 }
-
-int dla_spmm_info(dla_ctx* c, struct dla_spmm_info* out)
+static int spmm_slot_info(dla_ctx* c, int slot, struct dla_spmm_info* out)
 {
   if (!c || !out) return DLA_ERR_ARG;
-  return engfail(c, c->eng->spmm_info(out));
+  return engfail(c, c->eng->spmm_info(slot, out));
+}
+static int spmm_slot_drop(dla_ctx* c, int first, int last)
+{
+  if (!c) return DLA_ERR_ARG;
+  return engfail(c, c->eng->spmm_drop(first, last));
+}
+// the callbacks: what each says before any set-up has bound a context, and in front of the engine's refusal
+struct SpmmCallback { const char *unbound, *failed; };
+static const SpmmCallback spmm_mul_words[dla::SPMM_SLOTS] = {
+  {"dla_spmm_matvec before dla_spmm_setup_csr", "spmm_matvec failed: "},
+  {"dla_spmm_bvec before dla_spmm_setup_metric_csr", "dla_spmm_bvec failed: "},
+  {"dla_spmm_apbmul before dla_spmm_setup_lr_csr", "dla_spmm_apbmul failed: "},
+  {"dla_spmm_ambmul before dla_spmm_setup_lr_csr", "dla_spmm_ambmul failed: "},
+  {"dla_spmm_spdmul before dla_spmm_setup_lr_csr", "dla_spmm_spdmul failed: "},
+  {"dla_spmm_smdmul before dla_spmm_setup_lr_csr", "dla_spmm_smdmul failed: "}};
+static void spmm_product(int slot, const int* n, const int* m, const double* x, double* y)
+{
+  dla_ctx* c = g_spmm_ctx;
+  if (!c) { callback_failed(DLA_ERR_ARG, spmm_mul_words[slot].unbound); return; }
+  if (int st = c->eng->spmm_mul(slot, *n, *m, x, y)) callback_failed(st, spmm_mul_words[slot].failed + c->eng->err);
+}
+// kind 0: dla_spmm_precnd, 1: dla_spmm_precnd_pencil, 2 / 3: dla_spmm_lrprec1 / 2 (xm, ym: the second pair of the latter two)
+static void spmm_precondition(int kind, const int* n, const int* m, const double* fac, const double* x, const double* xm, double* y, double* ym)
+{
+  static const SpmmCallback words[4] = {
+    {"dla_spmm_precnd before dla_spmm_setup_csr", "spmm_precnd failed: "},
+    {"dla_spmm_precnd_pencil before dla_spmm_setup_csr and dla_spmm_setup_metric_csr", "dla_spmm_precnd_pencil failed: "},
+    {"dla_spmm_lrprec1 before dla_spmm_setup_lr_csr", "dla_spmm_lrprec1 failed: "},
+    {"dla_spmm_lrprec2 before dla_spmm_setup_lr_csr", "dla_spmm_lrprec2 failed: "}};
+  dla_ctx* c = g_spmm_ctx;
+  if (!c) { callback_failed(DLA_ERR_ARG, words[kind].unbound); return; }
+  const int st = kind == 0 ? c->eng->spmm_precnd(*n, *m, *fac, x, y) : kind == 1 ? c->eng->spmm_precnd_pencil(*n, *m, *fac, x, y)
+                                                                     : c->eng->spmm_lrprec(kind - 1, *n, *m, *fac, x, xm, y, ym);
+  if (st) callback_failed(st, words[kind].failed + c->eng->err);
 }
 
+// ---- the operator A (single rank in a storage format, or on a row shard) ...
+int dla_spmm_setup_csr(dla_ctx* c, int n, const long long* rowptr, const int* colind, const double* values) { return spmm_set_up(c, SPMM_A, dla::SPMM_VIA_PLAIN, n, rowptr, colind, values, DLA_SPMM_ELL); }
+int dla_spmm_setup_csr_fmt(dla_ctx* c, int n, const long long* rowptr, const int* colind, const double* values, int format) { return spmm_set_up(c, SPMM_A, dla::SPMM_VIA_HOST, n, rowptr, colind, values, format); }
+int dla_spmm_info(dla_ctx* c, struct dla_spmm_info* out) { return spmm_slot_info(c, SPMM_A, out); }
 int dla_spmm_setup_csr_sharded(dla_ctx* c, int n_local, long long row0, long long n_global, const long long* rowptr,
                                const long long* colind, const double* values)
 {
@@ -1880,129 +1939,48 @@ int dla_spmm_setup_csr_sharded(dla_ctx* c, int n_local, long long row0, long lon
   g_spmm_ctx = c;
   return engfail(c, c->eng->spmm_setup_csr_sharded(n_local, row0, n_global, rowptr, colind, values));
 }
+void dla_spmm_matvec(const int* n, const int* m, const double* x, double* ax) { spmm_product(SPMM_A, n, m, x, ax); }
+void dla_spmm_precnd(const int* n, const int* m, const double* fac, const double* x, double* px) { spmm_precondition(0, n, m, fac, x, nullptr, px, nullptr); }
 
-void dla_spmm_matvec(const int* n, const int* m, const double* x, double* ax)
-{
-  dla_ctx* c = g_spmm_ctx;
-  if (!c) { callback_failed(DLA_ERR_ARG, "dla_spmm_matvec before dla_spmm_setup_csr"); return; }
-  if (int st = c->eng->spmm_matvec(*n, *m, x, ax)) callback_failed(st, "spmm_matvec failed: " + c->eng->err);
-}
+// ---- ... the metric of a generalised problem beside it (bvec of reference diaglib.f90:1855; the harness' smult, main.f90:115-144) ...
+int dla_spmm_setup_metric_csr(dla_ctx* c, int n, const long long* rowptr, const int* colind, const double* values, int format) { return spmm_set_up(c, SPMM_B, dla::SPMM_VIA_HOST, n, rowptr, colind, values, format); }
+int dla_spmm_metric_info(dla_ctx* c, struct dla_spmm_info* out) { return spmm_slot_info(c, SPMM_B, out); }
+int dla_spmm_drop_metric(dla_ctx* c) { return spmm_slot_drop(c, SPMM_B, SPMM_B); }
+void dla_spmm_bvec(const int* n, const int* m, const double* x, double* bx) { spmm_product(SPMM_B, n, m, x, bx); }
+void dla_spmm_precnd_pencil(const int* n, const int* m, const double* fac, const double* x, double* px) { spmm_precondition(1, n, m, fac, x, nullptr, px, nullptr); }
 
-void dla_spmm_precnd(const int* n, const int* m, const double* fac, const double* x, double* px)
-{
-  dla_ctx* c = g_spmm_ctx;
-  if (!c) { callback_failed(DLA_ERR_ARG, "dla_spmm_precnd before dla_spmm_setup_csr"); return; }
-  if (int st = c->eng->spmm_precnd(*n, *m, *fac, x, px)) callback_failed(st, "spmm_precnd failed: " + c->eng->err);
-}
-
-// ---- ... and the metric of a generalised problem beside it (bvec of reference diaglib.f90:1855; the harness' smult, main.f90:115-144)
-int dla_spmm_setup_metric_csr(dla_ctx* c, int n, const long long* rowptr, const int* colind, const double* values, int format)
-{
-  if (!c) return DLA_ERR_ARG;
-  const int st = engfail(c, c->eng->spmm_setup_metric(n, rowptr, colind, values, format));
-  if (st == DLA_OK) g_spmm_ctx = c;
-  return st;
-}
-
-int dla_spmm_metric_info(dla_ctx* c, struct dla_spmm_info* out)
-{
-  if (!c || !out) return DLA_ERR_ARG;
-  return engfail(c, c->eng->spmm_metric_info(out));
-}
-
-int dla_spmm_drop_metric(dla_ctx* c)
-{
-  if (!c) return DLA_ERR_ARG;
-  return engfail(c, c->eng->spmm_drop_metric());
-}
-
-void dla_spmm_bvec(const int* n, const int* m, const double* x, double* bx)
-{
-  dla_ctx* c = g_spmm_ctx;
-  if (!c) { callback_failed(DLA_ERR_ARG, "dla_spmm_bvec before dla_spmm_setup_metric_csr"); return; }
-  if (int st = c->eng->spmm_bvec(*n, *m, x, bx)) callback_failed(st, "dla_spmm_bvec failed: " + c->eng->err);
-}
-
-void dla_spmm_precnd_pencil(const int* n, const int* m, const double* fac, const double* x, double* px)
-{
-  dla_ctx* c = g_spmm_ctx;
-  if (!c) { callback_failed(DLA_ERR_ARG, "dla_spmm_precnd_pencil before dla_spmm_setup_csr and dla_spmm_setup_metric_csr"); return; }
-  if (int st = c->eng->spmm_precnd_pencil(*n, *m, *fac, x, px)) callback_failed(st, "dla_spmm_precnd_pencil failed: " + c->eng->err);
-}
-
-// ---- ... either of the two from CSR arrays in device memory, and new values for a stored pattern
+// ---- ... either of the two from CSR arrays in device memory, and new values for a stored pattern ...
 int dla_spmm_setup_csr_dev(dla_ctx* c, int which, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev, int format)
 {
   DLA_T("dla_spmm_setup_csr_dev");
-  if (!c) return DLA_ERR_ARG;
-  if (which == 0) g_spmm_ctx = c;       // (as dla_spmm_setup_csr_fmt / dla_spmm_setup_metric_csr treat the thread's context)
-  const int st = engfail(c, c->eng->spmm_setup_csr_dev(which, n, rowptr_dev, colind_dev, values_dev, format));
-  if (st == DLA_OK) g_spmm_ctx = c;
-  return st;
+  return spmm_set_up(c, dla::spmm_slot_of_which(which), dla::SPMM_VIA_DEVICE, n, rowptr_dev, colind_dev, values_dev, format);
 }
-
 int dla_spmm_refresh_values_dev(dla_ctx* c, int which, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev)
 {
   DLA_T("dla_spmm_refresh_values_dev");
-  if (!c) return DLA_ERR_ARG;
-  return engfail(c, c->eng->spmm_refresh_values_dev(which, n, rowptr_dev, colind_dev, values_dev));
+  return spmm_refresh(c, dla::spmm_slot_of_which(which), n, rowptr_dev, colind_dev, values_dev);
 }
 
-// ---- ... and the four parts of a linear-response pencil beside them (apbmul / ambmul / spdmul / smdmul of reference
-// diaglib.f90:1024-1025, lrprec of :1317; the harness' lrprec_1 / lrprec_2, main.f90:234-281)
-int dla_spmm_setup_lr_csr(dla_ctx* c, int part, int n, const long long* rowptr, const int* colind, const double* values, int format)
-{
-  if (!c) return DLA_ERR_ARG;
-  const int st = engfail(c, c->eng->spmm_setup_lr(part, n, rowptr, colind, values, format));
-  if (st == DLA_OK) g_spmm_ctx = c;
-  return st;
-}
-
+// ---- ... and the four parts of a linear-response pencil (apbmul / ambmul / spdmul / smdmul of reference diaglib.f90:1024-1025,
+// lrprec of :1317; the harness' lrprec_1 / lrprec_2, main.f90:234-281)
+int dla_spmm_setup_lr_csr(dla_ctx* c, int part, int n, const long long* rowptr, const int* colind, const double* values, int format) { return spmm_set_up(c, dla::spmm_slot_of_part(part), dla::SPMM_VIA_HOST, n, rowptr, colind, values, format); }
 int dla_spmm_setup_lr_csr_dev(dla_ctx* c, int part, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev, int format)
 {
   DLA_T("dla_spmm_setup_lr_csr_dev");
-  if (!c) return DLA_ERR_ARG;
-  const int st = engfail(c, c->eng->spmm_setup_lr_dev(part, n, rowptr_dev, colind_dev, values_dev, format));
-  if (st == DLA_OK) g_spmm_ctx = c;
-  return st;
+  return spmm_set_up(c, dla::spmm_slot_of_part(part), dla::SPMM_VIA_DEVICE, n, rowptr_dev, colind_dev, values_dev, format);
 }
-
 int dla_spmm_refresh_lr_values_dev(dla_ctx* c, int part, int n, const long long* rowptr_dev, const int* colind_dev, const double* values_dev)
 {
   DLA_T("dla_spmm_refresh_lr_values_dev");
-  if (!c) return DLA_ERR_ARG;
-  return engfail(c, c->eng->spmm_refresh_lr_values_dev(part, n, rowptr_dev, colind_dev, values_dev));
+  return spmm_refresh(c, dla::spmm_slot_of_part(part), n, rowptr_dev, colind_dev, values_dev);
 }
-
-int dla_spmm_lr_info(dla_ctx* c, int part, struct dla_spmm_info* out)
-{
-  if (!c || !out) return DLA_ERR_ARG;
-  return engfail(c, c->eng->spmm_lr_info(part, out));
-}
-
-int dla_spmm_drop_lr(dla_ctx* c)
-{
-  if (!c) return DLA_ERR_ARG;
-  return engfail(c, c->eng->spmm_drop_lr());
-}
-
-static void spmm_lr_mul(int part, const char* what, const int* n, const int* m, const double* x, double* y)
-{
-  dla_ctx* c = g_spmm_ctx;
-  if (!c) { callback_failed(DLA_ERR_ARG, std::string(what) + " before dla_spmm_setup_lr_csr"); return; }
-  if (int st = c->eng->spmm_lr_mul(part, *n, *m, x, y)) callback_failed(st, std::string(what) + " failed: " + c->eng->err);
-}
-void dla_spmm_apbmul(const int* n, const int* m, const double* x, double* y) { spmm_lr_mul(DLA_SPMM_LR_APB, "dla_spmm_apbmul", n, m, x, y); }
-void dla_spmm_ambmul(const int* n, const int* m, const double* x, double* y) { spmm_lr_mul(DLA_SPMM_LR_AMB, "dla_spmm_ambmul", n, m, x, y); }
-void dla_spmm_spdmul(const int* n, const int* m, const double* x, double* y) { spmm_lr_mul(DLA_SPMM_LR_SPD, "dla_spmm_spdmul", n, m, x, y); }
-void dla_spmm_smdmul(const int* n, const int* m, const double* x, double* y) { spmm_lr_mul(DLA_SPMM_LR_SMD, "dla_spmm_smdmul", n, m, x, y); }
-static void spmm_lrp(int variant, const char* what, const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym)
-{
-  dla_ctx* c = g_spmm_ctx;
-  if (!c) { callback_failed(DLA_ERR_ARG, std::string(what) + " before dla_spmm_setup_lr_csr"); return; }
-  if (int st = c->eng->spmm_lrprec(variant, *n, *m, *fac, xp, xm, yp, ym)) callback_failed(st, std::string(what) + " failed: " + c->eng->err);
-}
-void dla_spmm_lrprec1(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { spmm_lrp(1, "dla_spmm_lrprec1", n, m, fac, xp, xm, yp, ym); }
-void dla_spmm_lrprec2(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { spmm_lrp(2, "dla_spmm_lrprec2", n, m, fac, xp, xm, yp, ym); }
+int dla_spmm_lr_info(dla_ctx* c, int part, struct dla_spmm_info* out) { return spmm_slot_info(c, dla::spmm_slot_of_part(part), out); }
+int dla_spmm_drop_lr(dla_ctx* c) { return spmm_slot_drop(c, SPMM_APB, SPMM_SMD); }
+void dla_spmm_apbmul(const int* n, const int* m, const double* x, double* y) { spmm_product(dla::SPMM_APB, n, m, x, y); }
+void dla_spmm_ambmul(const int* n, const int* m, const double* x, double* y) { spmm_product(dla::SPMM_AMB, n, m, x, y); }
+void dla_spmm_spdmul(const int* n, const int* m, const double* x, double* y) { spmm_product(dla::SPMM_SPD, n, m, x, y); }
+void dla_spmm_smdmul(const int* n, const int* m, const double* x, double* y) { spmm_product(dla::SPMM_SMD, n, m, x, y); }
+void dla_spmm_lrprec1(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { spmm_precondition(2, n, m, fac, xp, xm, yp, ym); }
+void dla_spmm_lrprec2(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { spmm_precondition(3, n, m, fac, xp, xm, yp, ym); }
 
 }  // extern "C"

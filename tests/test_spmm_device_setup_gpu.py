@@ -16,10 +16,10 @@ import pytest
 
 from diaglib_amd import capi
 from spmm_cases import LONG_ROW, csr_from_lengths, skewed_csr
-from test_operators_gpu import Guarded, call_matvec, call_precnd, ragged_csr, setup_csr_one_shard
+from spmm_slots import fresh_context, info, poison, precnd, product, refresh_status, same_bits, setup_status, to_device
+from test_operators_gpu import ragged_csr, setup_csr_one_shard
 from test_sell_layout_split import LONG_SEG, special_lengths
 from test_spmm_gpu import _laplacian_2d
-from test_spmm_long_rows_gpu import fresh_context
 
 pytestmark = pytest.mark.gpu
 FMT = capi.SPMM_FORMATS
@@ -89,39 +89,18 @@ def vectors(n, m):
 
 
 # ------------------------------------------------------------------------------------------------------------------ plumbing
-def setup_host(c, which, n, indptr, indices, data, fmt):
-    f = c.lib.dla_spmm_setup_metric_csr if which == B else c.lib.dla_spmm_setup_csr_fmt
-    c._chk(f(c.h, n, indptr.ctypes.data, indices.ctypes.data, data.ctypes.data, FMT[fmt]))
-
-
-def to_device(indptr, indices, data):
-    import torch
-    t = (torch.from_numpy(np.ascontiguousarray(indptr, np.int64)).cuda(), torch.from_numpy(np.ascontiguousarray(indices, np.int32)).cuda(),
-         torch.from_numpy(np.ascontiguousarray(data, np.float64)).cuda())
-    torch.cuda.synchronize()            # the caller's producer has finished
-    return t
-
-
-def poison(tensors):
-    """what a caller may do the moment the call has returned"""
-    import torch
-    crow, col, val = tensors
-    crow.fill_(-1); col.fill_(2 ** 31 - 1); val.fill_(float("nan"))
-    torch.cuda.synchronize()
+def setup_host(c, which, *csr_and_format):
+    c._chk(setup_status(c, which, *csr_and_format))
 
 
 def dev_call(c, entry, which, n, arrays, fmt=None):
     """status of one call of a device-array entry on (indptr, indices, data); the tensors are poisoned after it"""
-    t = to_device(*arrays)
-    f = getattr(c.lib, entry)
-    args = (c.h, which, n, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
-    st = f(*args, fmt) if entry == "dla_spmm_setup_csr_dev" else f(*args)
-    poison(t)
-    return st
+    slot = which if which in (A, B) else ("which", which)
+    return setup_status(c, slot, n, *arrays, fmt, "device") if entry == "dla_spmm_setup_csr_dev" else refresh_status(c, slot, n, *arrays)
 
 
 def setup_dev(c, which, n, indptr, indices, data, fmt):
-    c._chk(dev_call(c, "dla_spmm_setup_csr_dev", which, n, (indptr, indices, data), FMT[fmt] if isinstance(fmt, str) else fmt))
+    c._chk(dev_call(c, "dla_spmm_setup_csr_dev", which, n, (indptr, indices, data), fmt))
 
 
 def refresh_dev(c, which, n, indptr, indices, data):
@@ -135,29 +114,6 @@ def refused(c, entry, which, n, arrays, fmt=None):
     return msg
 
 
-def product(c, name, x):
-    n, m = x.shape
-    gx, gy = Guarded(c, n, m, x), Guarded(c, n, m)
-    call_matvec(c, name, n, m, gx.ptr, gy.ptr)
-    got = gy.body().copy()
-    gx.assert_unchanged()
-    gx.free(); gy.free()
-    return got
-
-
-def precnd(c, name, x, fac=-1.25):
-    n, m = x.shape
-    gx, gy = Guarded(c, n, m, x), Guarded(c, n, m)
-    call_precnd(c, name, n, m, fac, gx.ptr, gy.ptr)
-    got = gy.body().copy()
-    gx.free(); gy.free()
-    return got
-
-
-def info(c, which):
-    return c.spmm_metric_info() if which == B else c.spmm_info()
-
-
 def slot_results(c, which, n, pencil=False):
     """everything the contract names for one slot: info, products for every m of MS, the preconditioner(s)"""
     out = {"info": info(c, which)}
@@ -168,10 +124,6 @@ def slot_results(c, which, n, pencil=False):
     if pencil:
         out["precnd_pencil"] = precnd(c, "dla_spmm_precnd_pencil", vectors(n, 3))
     return out
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
 
 
 def assert_same_results(got, want, what):

@@ -15,6 +15,7 @@ import scipy.sparse.linalg as spl
 
 from diaglib_amd import capi
 from spmm_cases import LONG_ROW, SLICE, WINDOW, csr_from_lengths, skewed_csr
+from spmm_slots import setup
 from test_operators_gpu import (EPS, LD, N_TRIP, SENT, Guarded, _assert_second_trip, assert_within, call_matvec, call_precnd, csr_diagonal,
                                 csr_product_reference, csr_rows, ragged_csr, setup_csr, spmm_product)
 from test_spmm_gpu import _laplacian_2d
@@ -30,9 +31,8 @@ def dev(ctx):
     ctx.set_option(capi.OPT_CALLBACKS_ON_DEVICE, 0)
 
 
-def setup_fmt(ctx, n, indptr, indices, data, fmt):
-    assert indptr.dtype == np.int64 and indices.dtype == np.int32 and data.dtype == np.float64
-    ctx._chk(ctx.lib.dla_spmm_setup_csr_fmt(ctx.h, n, indptr.ctypes.data, indices.ctypes.data, data.ctypes.data, fmt))
+def setup_fmt(ctx, *csr_and_format):
+    setup(ctx, "A", *csr_and_format)
 
 
 def check_product(ctx, n, indptr, indices, data, x, what):

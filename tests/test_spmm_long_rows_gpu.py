@@ -7,8 +7,6 @@ segment is that partial, a longer row is ((part_0 + part_1) + part_2) + ...  The
 exactly that in exact rational arithmetic, bit for bit.  SEG is read from dla_spmm_info, never written here: tuning it moves the
 sizes of this file with it.  The matrix has n = 3 SEG + 70 rows: rows of LONG_ROW + 1, SEG - 1, SEG, SEG + 1, 2 SEG, 2 SEG + 63,
 3 SEG + 1 and n entries on distinct rows, everything else 0 .. 5 entries (conventions of tests/test_spmm_formats_gpu.py)."""
-import contextlib
-import ctypes as C
 from fractions import Fraction
 
 import numpy as np
@@ -18,9 +16,8 @@ import scipy.sparse.linalg as spl
 
 from diaglib_amd import capi
 from spmm_cases import LONG_ROW, csr_from_lengths
+from spmm_slots import fresh_context, product, setup
 from test_operators_gpu import EPS, LD, Guarded, assert_within, call_matvec, csr_product_reference, spmm_product
-from test_spmm_formats_gpu import setup_fmt
-from test_spmm_metric_gpu import product, setup_metric
 
 pytestmark = pytest.mark.gpu
 ELL, SELL = capi.SPMM_ELL, capi.SPMM_SELL
@@ -34,6 +31,14 @@ def dev(ctx):
     yield ctx
     ctx.set_option(capi.OPT_CALLBACKS_ON_DEVICE, 0)
     ctx.spmm_drop_metric()
+
+
+def setup_fmt(ctx, *csr_and_format):
+    setup(ctx, "A", *csr_and_format)
+
+
+def setup_metric(ctx, *csr_and_format):
+    setup(ctx, "B", *csr_and_format)
 
 
 def fma(a, b, c):
@@ -191,20 +196,6 @@ def test_rows_outside_the_tail_keep_the_bits_of_ellpack(dev, case):
 
 
 # ------------------------------------------------------------------------------------------------------------------ 5. determinism, workspace
-@contextlib.contextmanager
-def fresh_context():
-    lib = capi.load()
-    h = C.c_void_p()
-    assert lib.dla_create(C.byref(h), 0) == 0
-    c = capi.Context.__new__(capi.Context)
-    c.lib, c.h, c._keep, c.sync_python_callbacks = lib, h, [], True
-    try:
-        c.set_option(capi.OPT_CALLBACKS_ON_DEVICE, 1)
-        yield c
-    finally:
-        c.destroy()
-
-
 def test_products_are_deterministic_while_the_workspace_grows_and_operators_change(dev, case):
     """m = 1, 13, 1, 37 on one operator (the workspace of multi_segments x m partial sums grows twice and is reused in between), then
     an operator with more segments, then one with fewer: every product twice, bit-identical, and equal to what a context that

@@ -15,11 +15,9 @@ from diaglib_amd import capi
 from spmm_cases import csr_from_lengths
 from spmm_lr_cases import (MUL, PARTS, dense_roots, lrprec_numpy, positive_definite, random_pencil, solve_device_mode, solve_host_mode,
                            tolerance)
+from spmm_slots import CALL, SLOTS, info as _info, product, raw, refresh_status, same_bits, setup, setup_status, to_device, within_scipy_bound
 from test_operators_gpu import Guarded, setup_csr, setup_csr_one_shard
-from test_spmm_device_setup_gpu import poison, same_bits, to_device
-from test_spmm_formats_gpu import setup_fmt
 from test_spmm_gpu import _banded
-from test_spmm_metric_gpu import product, setup_metric, within_scipy_bound
 
 pytestmark = pytest.mark.gpu
 FMT = capi.SPMM_FORMATS
@@ -37,16 +35,17 @@ def dev(ctx):
     ctx.spmm_drop_metric()
 
 
-def setup_lr(ctx, part, n, indptr, indices, data, fmt):
+def _part(part):
+    return part if isinstance(part, str) else ("part", part)
+
+
+def setup_fmt(ctx, *csr_and_format):
+    setup(ctx, "A", *csr_and_format)
+
+
+def setup_lr(ctx, part, *csr_and_format):
     """one part from raw CSR arrays (unsorted columns, duplicates: scipy would clean them)"""
-    assert indptr.dtype == np.int64 and indices.dtype == np.int32 and data.dtype == np.float64
-    ctx._chk(ctx.lib.dla_spmm_setup_lr_csr(ctx.h, PART[part] if isinstance(part, str) else part, n, indptr.ctypes.data, indices.ctypes.data,
-                                           data.ctypes.data, FMT[fmt] if isinstance(fmt, str) else fmt))
-
-
-def raw(a):
-    a = a.tocsr()
-    return a.shape[0], a.indptr.astype(np.int64), a.indices.astype(np.int32), a.data.astype(np.float64)
+    setup(ctx, _part(part), *csr_and_format)
 
 
 # ------------------------------------------------------------------------------------------------------------------ 1. products by bits
@@ -104,22 +103,8 @@ def test_a_non_symmetric_part(dev, fmt):
 
 
 # ------------------------------------------------------------------------------------------------------------------ 2. independence
-SLOTS = ("A", "B") + PARTS
-CALL = dict({"A": "dla_spmm_matvec", "B": "dla_spmm_bvec"}, **MUL)
-
-
 def _set(ctx, slot, mat, fmt):
-    n = len(mat[0]) - 1
-    if slot == "A":
-        setup_fmt(ctx, n, *mat, FMT[fmt])
-    elif slot == "B":
-        setup_metric(ctx, n, *mat, FMT[fmt])
-    else:
-        setup_lr(ctx, slot, n, *mat, fmt)
-
-
-def _info(ctx, slot):
-    return ctx.spmm_info() if slot == "A" else ctx.spmm_metric_info() if slot == "B" else ctx.spmm_lr_info(slot)
+    setup(ctx, slot, len(mat[0]) - 1, *mat, fmt)
 
 
 def _state(ctx, slot, x):
@@ -213,11 +198,9 @@ def test_a_refused_part_setup_replaces_nothing(dev, fmt):
 # ------------------------------------------------------------------------------------------------------------------ 3. device arrays
 def _dev_call(ctx, entry, part, n, arrays, fmt=None):
     """status of one call of a device-array entry; the tensors are poisoned the moment it has returned"""
-    t = to_device(*arrays)
-    args = (ctx.h, PART[part] if isinstance(part, str) else part, n, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
-    st = getattr(ctx.lib, entry)(*args) if fmt is None else getattr(ctx.lib, entry)(*args, FMT[fmt])
-    poison(t)
-    return st
+    if entry == "dla_spmm_setup_lr_csr_dev":
+        return setup_status(ctx, _part(part), n, *arrays, fmt, "device")
+    return refresh_status(ctx, _part(part), n, *arrays)
 
 
 def _dev_mat(kind):

@@ -19,8 +19,8 @@ import scipy.sparse as sp
 
 from diaglib_amd import capi
 from spmm_cases import LONG_ROW, skewed_csr
-from test_operators_gpu import EPS, Guarded, call_matvec, call_precnd, csr_product_reference, setup_csr, setup_csr_one_shard
-from test_spmm_formats_gpu import setup_fmt
+from test_operators_gpu import EPS, Guarded, call_precnd, csr_product_reference, setup_csr, setup_csr_one_shard
+from spmm_slots import product, setup, within_scipy_bound
 from test_spmm_gpu import _banded, _laplacian_2d
 
 pytestmark = pytest.mark.gpu
@@ -36,25 +36,12 @@ def dev(ctx):
     ctx.spmm_drop_metric()
 
 
-def setup_metric(ctx, n, indptr, indices, data, fmt):
-    """the metric from raw CSR arrays (unsorted columns, duplicates: scipy would clean them)"""
-    assert indptr.dtype == np.int64 and indices.dtype == np.int32 and data.dtype == np.float64
-    ctx._chk(ctx.lib.dla_spmm_setup_metric_csr(ctx.h, n, indptr.ctypes.data, indices.ctypes.data, data.ctypes.data, fmt))
+def setup_fmt(ctx, *csr_and_format):
+    setup(ctx, "A", *csr_and_format)
 
 
-def product(ctx, name, x):
-    """one product of the named callback on x, between sentinel columns; the input must come back unchanged"""
-    n, m = x.shape
-    gx, gy = Guarded(ctx, n, m, x), Guarded(ctx, n, m)
-    call_matvec(ctx, name, n, m, gx.ptr, gy.ptr)
-    got = gy.body().copy()
-    gx.assert_unchanged()
-    gx.free(); gy.free()
-    return got
-
-
-def within_scipy_bound(got, a, x):
-    return np.all(np.abs(got - a @ x) <= 64 * EPS * (abs(a) @ np.abs(x)) + 1e-300)
+def setup_metric(ctx, *csr_and_format):
+    setup(ctx, "B", *csr_and_format)
 
 
 def within_bound_raw(got, indptr, indices, data, x):

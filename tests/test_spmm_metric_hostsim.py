@@ -1,6 +1,7 @@
 """CPU: the sparse metric's entry points on the host-memory engine (tests/hostsim.py over oracle/hostsim_engine.cpp).  That engine
-overrides the block-operation interface without the metric's five functions: their default bodies answer DLA_ERR_ARG, the sparse
-operator the engine does implement goes on working, and the callbacks fail through the trampolines' status with their name.
+stores one sparse matrix, a row-sharded operator, and overrides the product of that matrix alone: the default bodies of the slot
+interface answer DLA_ERR_ARG for the product of every other slot and for every set-up, info and drop.  The sparse operator the engine does
+implement goes on working, and the callbacks fail through the trampolines' status with their name.
 (A process of its own: the library a process has loaded cannot be exchanged.)"""
 import os
 import subprocess

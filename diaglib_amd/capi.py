@@ -45,6 +45,7 @@ EXPORTS = [
     "dla_synth_metric", "dla_synth_lrprec1", "dla_synth_lrprec2", "dla_pending_factor", "dla_pending_block", "dla_basis_admit", "dla_basis_fold", "dla_basis_sync", "dla_spmm_setup_csr", "dla_spmm_setup_csr_fmt", "dla_spmm_info", "dla_spmm_setup_csr_sharded", "dla_spmm_matvec", "dla_spmm_precnd",
     "dla_spmm_setup_metric_csr", "dla_spmm_metric_info", "dla_spmm_drop_metric", "dla_spmm_bvec", "dla_spmm_precnd_pencil",
     "dla_spmm_setup_csr_dev", "dla_spmm_refresh_values_dev",
+    "dla_spmm_cheb_config", "dla_spmm_cheb_info", "dla_spmm_precnd_cheb",
     "dla_spmm_setup_lr_csr", "dla_spmm_setup_lr_csr_dev", "dla_spmm_refresh_lr_values_dev", "dla_spmm_lr_info", "dla_spmm_drop_lr",
     "dla_spmm_apbmul", "dla_spmm_ambmul", "dla_spmm_spdmul", "dla_spmm_smdmul", "dla_spmm_lrprec1", "dla_spmm_lrprec2",
     "dla_davidson_driver", "dla_gen_david_driver", "dla_lobpcg_driver", "dla_caslr_eff_driver", "dla_caslr_driver", "dla_call_lrprec",
@@ -80,6 +81,10 @@ class SpmmInfo(C.Structure):
                 ("nnz", C.c_longlong), ("stored", C.c_longlong), ("slices", C.c_int), ("long_rows", C.c_int),
                 ("long_entries", C.c_longlong), ("device_bytes", C.c_longlong), ("long_segment_entries", C.c_int), ("long_segments", C.c_int),
                 ("multi_segments", C.c_int)]
+
+
+class SpmmChebInfo(C.Structure):
+    _fields_ = [("steps", C.c_int), ("lo_fraction", C.c_double), ("upper", C.c_double)]
 
 
 class DlaError(RuntimeError):
@@ -158,6 +163,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dla_spmm_drop_metric": (i, [vp]),
         "dla_spmm_bvec": (None, [c_ip, c_ip, vp, vp]), "dla_spmm_precnd_pencil": (None, [c_ip, c_ip, c_dp, vp, vp]),
         "dla_spmm_setup_csr_dev": (i, [vp, i, i, vp, vp, vp, i]), "dla_spmm_refresh_values_dev": (i, [vp, i, i, vp, vp, vp]),
+        "dla_spmm_cheb_config": (i, [vp, i, d]), "dla_spmm_cheb_info": (i, [vp, C.POINTER(SpmmChebInfo)]),
+        "dla_spmm_precnd_cheb": (None, [c_ip, c_ip, c_dp, vp, vp]),
         "dla_spmm_setup_lr_csr": (i, [vp, i, i, vp, vp, vp, i]), "dla_spmm_setup_lr_csr_dev": (i, [vp, i, i, vp, vp, vp, i]),
         "dla_spmm_refresh_lr_values_dev": (i, [vp, i, i, vp, vp, vp]), "dla_spmm_lr_info": (i, [vp, i, C.POINTER(SpmmInfo)]),
         "dla_spmm_drop_lr": (i, [vp]),
@@ -630,6 +637,20 @@ class Context:
         """new values for the pattern the operator (metric: the metric) was set up with; raises while the pattern differs"""
         crow, col, val = self._device_csr("spmm_refresh_values_device", crow, col, val)
         self._chk(self.lib.dla_spmm_refresh_values_dev(self.h, int(bool(metric)), crow.numel() - 1, crow.data_ptr(), col.data_ptr(), val.data_ptr()))
+
+    # ---- the Chebyshev polynomial preconditioner on the stored operator (dla_spmm_precnd_cheb)
+    def spmm_cheb_config(self, steps: int, lo_fraction: float = 0.02) -> None:
+        """steps of the Chebyshev iteration for A + fac I that ``fn_address("dla_spmm_precnd_cheb")`` applies, on the interval
+        [lo_fraction * hi, hi] under the Gershgorin bound of the stored operator; steps = 0 switches it off and frees its work
+        panels.  Belongs to the context, not to the matrix: it survives set-ups and refreshes"""
+        self._chk(self.lib.dla_spmm_cheb_config(self.h, int(steps), float(lo_fraction)))
+
+    def spmm_cheb_info(self) -> dict:
+        """steps, lo_fraction and upper (the Gershgorin bound of the stored operator); raises while nothing is configured or no
+        operator is stored"""
+        o = SpmmChebInfo()
+        self._chk(self.lib.dla_spmm_cheb_info(self.h, C.byref(o)))
+        return {"steps": int(o.steps), "lo_fraction": float(o.lo_fraction), "upper": float(o.upper)}
 
     # ---- the four sparse parts of a linear-response pencil (dla_spmm_apbmul .. dla_spmm_smdmul, dla_spmm_lrprec1 / 2)
     @staticmethod

@@ -306,6 +306,11 @@ struct Engine : BlockOps {
   virtual int spmm_precnd_pencil(int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return DLA_ERR_ARG; }
   virtual int spmm_lrprec(int /*variant*/, int /*n*/, int /*m*/, double /*fac*/, const double* /*xp*/, const double* /*xm*/,
                           double* /*yp*/, double* /*ym*/) { return DLA_ERR_ARG; }
+  // the Chebyshev polynomial preconditioner on the stored A (the contract: include/diaglib_amd.h, dla_spmm_precnd_cheb): the
+  // configuration belongs to the engine, not to the matrix; steps = 0 switches it off and gives the work panels back
+  virtual int spmm_cheb_config(int /*steps*/, double /*lo_fraction*/) { return DLA_ERR_ARG; }
+  virtual int spmm_cheb_info(struct dla_spmm_cheb_info* /*out*/) { return DLA_ERR_ARG; }
+  virtual int spmm_precnd_cheb(int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return DLA_ERR_ARG; }
 
   // Staging pipeline of host-mode callbacks: column chunks of a block travel device -> host on one copy stream, the
   // user's routine works on the chunk that has arrived, finished chunks travel host -> device on a second copy stream
@@ -571,6 +576,37 @@ inline void sell_build(int n, const long long* rowptr, const int* colind, const 
 {
   sell_layout(n, rowptr, s);
   sell_fill(n, rowptr, colind, values, s);
+}
+
+// ---- the scalars of the Chebyshev preconditioner (include/diaglib_amd.h, dla_spmm_precnd_cheb; Saad, Iterative Methods, Algorithm
+// 12.1 from a zero start).  Host only; the results are doubles.  For the interval [lo, hi] and d steps: theta = (hi + lo) / 2,
+// delta = (hi - lo) / 2, sigma = theta / delta, rho_0 = 1 / sigma, rho_k = 1 / (2 sigma - rho_{k-1}), and step k = 1 .. d - 1 is
+//   z_{k+1} = alpha u + beta v + gamma x + eta (A u)
+// with alpha = 1 + rho_k rho_{k-1} - (2 rho_k / delta) fac, beta = -rho_k rho_{k-1}, gamma = 2 rho_k / delta, eta = -gamma, u = z_k
+// and v = z_{k-1}.  z_1 = x / theta is never stored: step 1 gathers u = x itself with alpha / theta and eta / theta (its beta is
+// 0: z_0 = 0), and step 2 takes v = x with beta / theta.  d = 1 has no step: px = x / theta.
+struct ChebStep { double alpha, beta, gamma, eta; };
+struct ChebCoefficients { double theta = 0.0, delta = 0.0; std::vector<ChebStep> steps; };
+inline ChebCoefficients cheb_coefficients(double hi, double lo, double fac, int d)
+{
+  // The recurrence of rho amplifies a rounding of sigma by 2 sigma / (2 sigma - rho), several-fold when lo_fraction is small, so it
+  // is carried in long double and every coefficient is rounded to double once (tests/test_cheb_ref.py: within 8 ulp).
+  typedef long double ld;
+  ChebCoefficients c;
+  const ld theta = ((ld)hi + (ld)lo) / 2, delta = ((ld)hi - (ld)lo) / 2, sigma = theta / delta;
+  c.theta = (double)theta;
+  c.delta = (double)delta;
+  ld rho_prev = 1 / sigma;
+  for (int k = 1; k < d; ++k) {
+    const ld rho = 1 / (2 * sigma - rho_prev);
+    const ld a = rho * rho_prev, b = 2 * rho / delta;
+    ld alpha = 1 + a - b * (ld)fac, beta = -a, eta = -b;
+    if (k == 1) { alpha /= theta; eta /= theta; beta = 0; }
+    if (k == 2) beta /= theta;
+    c.steps.push_back(ChebStep{(double)alpha, (double)beta, (double)b, (double)eta});
+    rho_prev = rho;
+  }
+  return c;
 }
 
 Engine* make_engine(int device, std::string& err);

@@ -1700,6 +1700,187 @@ __global__ __launch_bounds__(256) void long_rows_combine_kernel(int n, int m, in
   }
 }
 
+// ---- the Chebyshev polynomial preconditioner on the stored operator (the contract: include/diaglib_amd.h, dla_spmm_precnd_cheb).
+// One step is z_{k+1} = alpha u + beta v + gamma x + eta (A u) with u = z_k, v = z_{k-1} (dla::cheb_coefficients): the product
+// kernels above with the combination as their epilogue, so that A u never travels to HBM.  Per step 12 w n bytes of matrix, the
+// gather of u, three coalesced panel reads and one write (32 n m) instead of the 16 n m of the product plus 40 n m of a sweep
+// that combines.  `out` may be the buffer of v (the same thread reads and writes the element); it is never the buffer of u, which
+// other rows gather.  The combination is spelled once, with explicit fused multiply-adds: the same bits from every kernel below.
+struct ChebCoef { double alpha, beta, gamma, eta; };
+__device__ __forceinline__ double cheb_combine(const ChebCoef& k, double u, double v, double x, double au)
+{
+  return fma(k.eta, au, fma(k.gamma, x, fma(k.beta, v, k.alpha * u)));
+}
+// ell_spmm_kernel<W> with that epilogue, on the same width ladder.  The three panel reads of a column are issued before the gather
+// loop, so they are in flight while it runs.
+template <int W>
+__global__ __launch_bounds__(256) void ell_cheb_step_kernel(int n, int m, int w, const int* __restrict__ col,
+                                                            const double* __restrict__ val, ChebCoef k, const double* u,
+                                                            const double* v, const double* x, double* out)
+{
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    if constexpr (W > 0) {
+      int cj[W]; double vj[W];
+#pragma unroll
+      for (int q = 0; q < W; ++q) {
+        const bool in = q < w;
+        cj[q] = in ? col[(size_t)q * n + i] : i;
+        vj[q] = in ? val[(size_t)q * n + i] : 0.0;
+      }
+      for (int c = 0; c < m; ++c) {
+        const size_t o = (size_t)c * n + i;
+        const double* uc = u + (size_t)c * n;
+        const double ui = u[o], vi = v[o], xi = x[o];
+        double s = 0.0;
+#pragma unroll
+        for (int q = 0; q < W; ++q) s += vj[q] * uc[cj[q]];
+        __builtin_nontemporal_store(cheb_combine(k, ui, vi, xi, s), out + o);
+      }
+    } else {
+      for (int c = 0; c < m; ++c) {
+        const size_t o = (size_t)c * n + i;
+        const double* uc = u + (size_t)c * n;
+        const double ui = u[o], vi = v[o], xi = x[o];
+        double s = 0.0;
+        for (int q = 0; q < w; ++q) s += val[(size_t)q * n + i] * uc[col[(size_t)q * n + i]];
+        __builtin_nontemporal_store(cheb_combine(k, ui, vi, xi, s), out + o);
+      }
+    }
+  }
+}
+// sell_spmm_kernel<MC> with the same epilogue for the rows of the slices; tail slots and slots past n store nothing
+template <int MC>
+__global__ __launch_bounds__(256) void sell_cheb_step_kernel(int n, int m, int slices, const long long* __restrict__ slice_ptr,
+                                                             const int* __restrict__ perm, const int* __restrict__ col,
+                                                             const double* __restrict__ val, ChebCoef kc, const double* u,
+                                                             const double* v, const double* x, double* out)
+{
+  const int lane = threadIdx.x & 63;
+  for (int s = blockIdx.x * 4 + (threadIdx.x >> 6); s < slices; s += gridDim.x * 4) {
+    const long long p0 = slice_ptr[s];
+    const int width = (int)((slice_ptr[s + 1] - p0) >> 6);
+    const int slot = s * 64 + lane;
+    const int row = slot < n ? perm[slot] : -1;
+    const int* cs = col + p0 + lane;
+    const double* vs = val + p0 + lane;
+    for (int c0 = 0; c0 < m; c0 += MC) {
+      const double* uc = u + (size_t)c0 * n;
+      double acc[MC], ui[MC], vi[MC], xi[MC];
+#pragma unroll
+      for (int k = 0; k < MC; ++k) {
+        acc[k] = 0.0;
+        const bool live = row >= 0 && c0 + k < m;
+        const size_t o = live ? (size_t)(c0 + k) * n + row : 0;
+        ui[k] = live ? u[o] : 0.0; vi[k] = live ? v[o] : 0.0; xi[k] = live ? x[o] : 0.0;
+      }
+      if (c0 + MC <= m) {
+        for (int q = 0; q < width; ++q) {
+          const int cj = cs[(size_t)q * 64];
+          const double vj = vs[(size_t)q * 64];
+#pragma unroll
+          for (int k = 0; k < MC; ++k) acc[k] = fma(vj, uc[(size_t)k * n + cj], acc[k]);
+        }
+      } else {
+        const int mc = m - c0;
+        for (int q = 0; q < width; ++q) {
+          const int cj = cs[(size_t)q * 64];
+          const double vj = vs[(size_t)q * 64];
+#pragma unroll
+          for (int k = 0; k < MC; ++k) if (k < mc) acc[k] = fma(vj, uc[(size_t)k * n + cj], acc[k]);
+        }
+      }
+      if (row >= 0) {
+#pragma unroll
+        for (int k = 0; k < MC; ++k)
+          if (c0 + k < m) __builtin_nontemporal_store(cheb_combine(kc, ui[k], vi[k], xi[k], acc[k]), out + (size_t)(c0 + k) * n + row);
+      }
+    }
+  }
+}
+// the rows of the CSR tail: csr_long_segments_kernel / long_rows_combine_kernel have left (A u)[row] in the scratch panel au; one
+// thread per (tail row, column) forms the combination for those rows only
+__global__ __launch_bounds__(256) void tail_cheb_combine_kernel(int n, int m, int nlong, const int* __restrict__ long_row, ChebCoef k,
+                                                                const double* u, const double* v, const double* x,
+                                                                const double* __restrict__ au, double* out)
+{
+  const long long total = (long long)nlong * m;
+  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
+    const int j = (int)(t / m), c = (int)(t - (long long)j * m);
+    const size_t o = (size_t)c * n + long_row[j];
+    out[o] = cheb_combine(k, u[o], v[o], x[o], au[o]);
+  }
+}
+// the un-fused step (A/B comparand, Knobs::cheb_unfused): the product kernel has written A u to the panel au; one sweep combines
+__global__ __launch_bounds__(256) void cheb_combine_kernel(size_t total, ChebCoef k, const double* u, const double* v, const double* x,
+                                                           const double* __restrict__ au, double* out)
+{
+  for (size_t o = (size_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (size_t)gridDim.x * 256)
+    out[o] = cheb_combine(k, u[o], v[o], x[o], au[o]);
+}
+// one step (d = 1): px = x / theta
+__global__ __launch_bounds__(256) void cheb_scale_kernel(size_t total, double theta, const double* __restrict__ x, double* __restrict__ px)
+{
+  for (size_t o = (size_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (size_t)gridDim.x * 256) px[o] = x[o] / theta;
+}
+// The Gershgorin bound of the stored matrix: g_i = diag[i] + sum of |v| over the entries of row i whose column is not i, in stored
+// order from 0.0 (padding is a zero on the row's own column).  Every block leaves the maximum over its rows in partial[block]; the
+// host takes the maximum of those.  A maximum does not depend on the order it is taken in, so no atomics and the same bits always.
+__device__ __forceinline__ void block_max_store(double g, double* __restrict__ partial)
+{
+  __shared__ double wave_max[4];
+  for (int off = 32; off > 0; off >>= 1) g = fmax(g, __shfl_xor(g, off, 64));
+  if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = g;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = fmax(fmax(wave_max[0], wave_max[1]), fmax(wave_max[2], wave_max[3]));
+}
+__global__ __launch_bounds__(256) void ell_gershgorin_kernel(int n, int w, const int* __restrict__ col, const double* __restrict__ val,
+                                                             const double* __restrict__ diag, double* __restrict__ partial)
+{
+  double g = -INFINITY;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    double s = 0.0;
+    for (int q = 0; q < w; ++q) if (col[(size_t)q * n + i] != i) s += fabs(val[(size_t)q * n + i]);
+    g = fmax(g, diag[i] + s);
+  }
+  block_max_store(g, partial);
+}
+__global__ __launch_bounds__(256) void sell_gershgorin_kernel(int n, int slices, const long long* __restrict__ slice_ptr,
+                                                              const int* __restrict__ perm, const int* __restrict__ col,
+                                                              const double* __restrict__ val, const double* __restrict__ diag,
+                                                              double* __restrict__ partial)
+{
+  const int lane = threadIdx.x & 63;
+  double g = -INFINITY;
+  for (int s = blockIdx.x * 4 + (threadIdx.x >> 6); s < slices; s += gridDim.x * 4) {
+    const long long p0 = slice_ptr[s];
+    const int width = (int)((slice_ptr[s + 1] - p0) >> 6);
+    const int slot = s * 64 + lane;
+    const int row = slot < n ? perm[slot] : -1;
+    if (row < 0) continue;        // (a tail row: tail_gershgorin_kernel; or a slot past n)
+    double sum = 0.0;
+    for (int q = 0; q < width; ++q) if (col[p0 + (long long)q * 64 + lane] != row) sum += fabs(val[p0 + (long long)q * 64 + lane]);
+    g = fmax(g, diag[row] + sum);
+  }
+  block_max_store(g, partial);
+}
+// ... and the rows of the tail, one wavefront per ROW whatever the number of its segments: lane l takes entries l, l + 64, ... of the
+// row from 0.0, then the butterfly of the product's segments.  col / val: the tail's entries (behind the slices')
+__global__ __launch_bounds__(256) void tail_gershgorin_kernel(int nlong, const long long* __restrict__ long_ptr, const int* __restrict__ long_row,
+                                                              const int* __restrict__ col, const double* __restrict__ val,
+                                                              const double* __restrict__ diag, double* __restrict__ partial)
+{
+  const int lane = threadIdx.x & 63;
+  double g = -INFINITY;
+  for (int r = blockIdx.x * 4 + (threadIdx.x >> 6); r < nlong; r += gridDim.x * 4) {
+    const int row = long_row[r];
+    double sum = 0.0;
+    for (long long p = long_ptr[r] + lane; p < long_ptr[r + 1]; p += 64) if (col[p] != row) sum += fabs(val[p]);
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+    g = fmax(g, diag[row] + sum);
+  }
+  block_max_store(g, partial);
+}
+
 // ---- the same two formats filled from CSR arrays that are already in DEVICE memory (dla_spmm_setup_csr_dev), and new values for a
 // stored pattern (dla_spmm_refresh_values_dev).  The host keeps what depends on the row lengths alone (dla::sell_layout on the
 // downloaded row pointers); everything proportional to the number of entries happens here.  Every output element has one writer; the
@@ -5970,6 +6151,7 @@ struct HipEngine : dla::Engine {
     const SlotWords& w = words(slot);
     { const int stc = admit(slot, w.refresh, CALL_REFRESH | NEED_STORED); if (stc) return stc; }
     const int stc = refresh_dev(ops[slot], n, rowptr_dev, colind_dev, values_dev);
+    if (slot == dla::SPMM_A) cheb.upper_valid = false;
     if (stc == DLA_ERR_ARG && w.quoted_dev) err = quote(slot, w.refresh) + err;
     return stc;
   }
@@ -6021,6 +6203,7 @@ struct HipEngine : dla::Engine {
     const int stc = dev ? setup_dev(ops[slot], n, rowptr, colind, values, format)
                         : setup_fmt(ops[slot], n, rowptr, colind, values, plain ? (int)DLA_SPMM_ELL : format, quoted ? "spmm_setup_csr_fmt" : entry);
     if (stc == DLA_ERR_ARG && quoted) err = quote(slot, entry) + err;
+    if (slot == dla::SPMM_A) cheb.upper_valid = false;
     if (!stc && slot == dla::SPMM_A) shard.drop();
     return stc;
   }
@@ -6056,6 +6239,7 @@ struct HipEngine : dla::Engine {
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamSynchronize(st));     // (products of these slots may still be queued)
     for (int s = first; s <= last; ++s) ops[s].drop();
+    if (first <= dla::SPMM_A && dla::SPMM_A <= last) cheb.upper_valid = false;
     return DLA_OK;
   }
   // slices kernel, segments kernel, combine kernel; p: the tail's launch shapes and workspace (long_rows_plan)
@@ -6162,6 +6346,7 @@ struct HipEngine : dla::Engine {
     dla::ShardedEll e;
     dla::sharded_ell_build(n, row0, rowptr, colind, values, (int)halo, e);
     bind();
+    cheb.upper_valid = false;
     stc = upload_ell(ops[dla::SPMM_A], e.col, e.val, e.diag);
     if (stc) return stc;
     ops[dla::SPMM_A].n = n; ops[dla::SPMM_A].w = e.w; shard.halo = (int)halo; shard.on = true;
@@ -6245,6 +6430,187 @@ struct HipEngine : dla::Engine {
     const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
     DLA_LAUNCH(pencil_precnd_kernel, dim3(blocks), dim3(256), 0, st, n, m, fac, (const double*)ops[dla::SPMM_A].diag, (const double*)ops[dla::SPMM_B].diag, x, px);
     HIPCHK(hipGetLastError());
+    return DLA_OK;
+  }
+
+  // ---- the Chebyshev polynomial of A + fac I as a preconditioner (the contract: include/diaglib_amd.h, dla_spmm_precnd_cheb; the
+  // kernels: beside ell_cheb_step_kernel).  The configuration and the work panels are the context's; the Gershgorin bound is the
+  // stored matrix's and is formed again after every set-up, refresh or drop of slot A (upper_valid).
+  struct Cheb {
+    int steps = 0;
+    double lo_fraction = 0.0;
+    bool upper_valid = false;
+    double upper = 0.0;
+    DeviceBuffer<double> z[2];         // the iterates z_k, z_{k-1}: n x m each
+    DeviceBuffer<double> au;           // A u of the tail rows of a sliced operator, and of every row on the un-fused path: n x m
+    DeviceBuffer<double> partial;      // the block maxima of the Gershgorin kernels
+  } cheb;
+  int spmm_cheb_config(int steps, double lo_fraction) override
+  {
+    if (steps < 0) { err = "spmm_cheb_config: steps = " + std::to_string(steps) + " must not be negative"; return DLA_ERR_ARG; }
+    if (steps > 0 && !(lo_fraction > 0.0 && lo_fraction < 1.0)) {
+      err = "spmm_cheb_config: lo_fraction = " + std::to_string(lo_fraction) + " must lie inside (0, 1)";
+      return DLA_ERR_ARG;
+    }
+    if (steps == 0) {
+      if (cheb.z[0] || cheb.z[1] || cheb.au || cheb.partial) {
+        HIPCHK(hipSetDevice(device));
+        HIPCHK(hipStreamSynchronize(st));     // (a queued call may still use the panels)
+        cheb.z[0].reset(); cheb.z[1].reset(); cheb.au.reset(); cheb.partial.reset();
+      }
+      cheb.steps = 0; cheb.lo_fraction = 0.0;
+      return DLA_OK;
+    }
+    cheb.steps = steps; cheb.lo_fraction = lo_fraction;
+    return DLA_OK;
+  }
+  // g of the stored A (single rank), from the blocks: at most ncu x 8 block maxima come to the host.  Synchronous, once per stored
+  // matrix; like the set-up kernels it is not booked into the statistics.
+  int cheb_upper()
+  {
+    if (cheb.upper_valid) return DLA_OK;
+    SparseOp& op = ops[dla::SPMM_A];
+    bind();
+    const bool sell = op.fmt == DLA_SPMM_SELL;
+    const int cap = std::max(1, ncu * 4);
+    const int b0 = sell ? std::max(1, std::min(cap, (op.sell_slices + 3) / 4)) : std::max(1, std::min(2 * cap, (op.n + 255) / 256));
+    const int b1 = sell && op.sell_long_rows > 0 ? std::max(1, std::min(cap, (op.sell_long_rows + 3) / 4)) : 0;
+    if ((size_t)(b0 + b1) > cheb.partial.capacity()) {
+      HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(cheb.partial.reserve((size_t)2 * cap));
+    }
+    if (sell) {
+      DLA_LAUNCH(sell_gershgorin_kernel, dim3(b0), dim3(256), 0, st, op.n, op.sell_slices, (const long long*)op.sell_ptr, (const int*)op.sell_perm,
+                 (const int*)op.col, (const double*)op.val, (const double*)op.diag, (double*)cheb.partial);
+      HIPCHK(hipGetLastError());
+      if (b1 > 0) {
+        DLA_LAUNCH(tail_gershgorin_kernel, dim3(b1), dim3(256), 0, st, op.sell_long_rows, (const long long*)op.long_ptr, (const int*)op.long_row,
+                   (const int*)op.col + op.sell_stored, (const double*)op.val + op.sell_stored, (const double*)op.diag, (double*)cheb.partial + b0);
+        HIPCHK(hipGetLastError());
+      }
+    } else {
+      DLA_LAUNCH(ell_gershgorin_kernel, dim3(b0), dim3(256), 0, st, op.n, op.w, (const int*)op.col, (const double*)op.val, (const double*)op.diag,
+                 (double*)cheb.partial);
+      HIPCHK(hipGetLastError());
+    }
+    std::vector<double> h((size_t)(b0 + b1));
+    HIPCHK(hipMemcpyAsync(h.data(), (const double*)cheb.partial, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    double g = h[0];
+    for (size_t j = 1; j < h.size(); ++j) g = std::max(g, h[j]);
+    cheb.upper = g; cheb.upper_valid = true;
+    return DLA_OK;
+  }
+  // what both entries refuse first; who: the entry's name
+  int cheb_admit(const char* who)
+  {
+    if (ops[dla::SPMM_A].fmt < 0 || !ops[dla::SPMM_A].diag) { err = std::string(who) + ": no operator has been set up (dla_spmm_setup_csr)"; return DLA_ERR_ARG; }
+    if (shard.on) { err = std::string(who) + ": the operator of this context is row-sharded, and the Chebyshev preconditioner on a row-sharded operator is not supported"; return DLA_ERR_ARG; }
+    if (cheb.steps <= 0) { err = std::string(who) + ": nothing is configured (dla_spmm_cheb_config)"; return DLA_ERR_ARG; }
+    return DLA_OK;
+  }
+  int spmm_cheb_info(struct dla_spmm_cheb_info* out) override
+  {
+    { const int stc = cheb_admit("spmm_cheb_info"); if (stc) return stc; }
+    { const int stc = cheb_upper(); if (stc) return stc; }
+    out->steps = cheb.steps; out->lo_fraction = cheb.lo_fraction; out->upper = cheb.upper;
+    return DLA_OK;
+  }
+  // a work panel of at least `need` doubles, grown behind a stream wait as long_part is
+  int cheb_panel(DeviceBuffer<double>& b, size_t need)
+  {
+    if (need <= b.capacity()) return DLA_OK;
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(b.reserve(need));
+    return DLA_OK;
+  }
+  // one step out = alpha u + beta v + gamma x + eta (A u) on the stored A; out may be v's buffer, never u's
+  int cheb_step(SparseOp& op, int n, int m, const ChebCoef& k, const double* u, const double* v, const double* x, double* out)
+  {
+    const double nm = (double)n * m;
+    if (knobs.cheb_unfused()) {
+      { const int stc = op_matvec(op, n, m, u, cheb.au); if (stc) return stc; }
+      Scope s(this, DLA_OP_PRECND, 40.0 * nm, 7.0 * nm, "cheb_combine_kernel");
+      const size_t total = (size_t)n * m;
+      const int blocks = (int)std::max((size_t)1, std::min((size_t)ncu * 8, (total + 255) / 256));
+      DLA_LAUNCH(cheb_combine_kernel, dim3(blocks), dim3(256), 0, st, total, k, u, v, x, (const double*)cheb.au, out);
+      HIPCHK(hipGetLastError());
+      return DLA_OK;
+    }
+    if (op.fmt == DLA_SPMM_SELL) {
+      const LongRowsPlan p = long_rows_plan(env(), op.sell_long_segments, op.sell_multi_rows, op.sell_multi_segments, m, LONG_MC);
+      // (the tail's partial sums and its rows of the scratch panel are written once and read once)
+      Scope s(this, DLA_OP_PRECND, 12.0 * (double)(op.sell_stored + op.sell_long_entries) + 4.0 * n + 32.0 * nm + 16.0 * (double)p.part_doubles +
+                                       16.0 * (double)op.sell_long_rows * m,
+              2.0 * (double)op.nnz * m + 7.0 * nm, "sell_cheb_step_kernel");
+      if (p.part_doubles > op.long_part.capacity()) {
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(op.long_part.reserve(p.part_doubles));
+      }
+      DLA_LAUNCH((sell_cheb_step_kernel<SELL_MC>), dim3(std::max(1, std::min(ncu * 8, (op.sell_slices + 3) / 4))), dim3(256), 0, st, n, m, op.sell_slices,
+                 (const long long*)op.sell_ptr, (const int*)op.sell_perm, (const int*)op.col, (const double*)op.val, k, u, v, x, out);
+      HIPCHK(hipGetLastError());
+      if (op.sell_long_segments > 0) {
+        DLA_LAUNCH((csr_long_segments_kernel<LONG_MC>), dim3(p.seg_blocks), dim3(256), 0, st, n, m, op.sell_long_segments, (const long long*)op.seg_ptr,
+                   (const int*)op.seg_row, (const int*)op.seg_part, (const int*)op.long_row, (const int*)op.col + op.sell_stored,
+                   (const double*)op.val + op.sell_stored, u, (double*)cheb.au, (double*)op.long_part);
+        HIPCHK(hipGetLastError());
+        if (p.combine_blocks > 0) {
+          DLA_LAUNCH(long_rows_combine_kernel, dim3(p.combine_blocks), dim3(256), 0, st, n, m, op.sell_multi_rows, (const int*)op.multi_row,
+                     (const int*)op.part_ptr, (const double*)op.long_part, (double*)cheb.au);
+          HIPCHK(hipGetLastError());
+        }
+        const long long total = (long long)op.sell_long_rows * m;
+        DLA_LAUNCH(tail_cheb_combine_kernel, dim3((int)std::max(1LL, std::min((long long)ncu * 8, (total + 255) / 256))), dim3(256), 0, st, n, m,
+                   op.sell_long_rows, (const int*)op.long_row, k, u, v, x, (const double*)cheb.au, out);
+        HIPCHK(hipGetLastError());
+      }
+      return DLA_OK;
+    }
+    Scope s(this, DLA_OP_PRECND, 12.0 * (double)op.w * n + 32.0 * nm, 2.0 * (double)op.w * nm + 7.0 * nm, "ell_cheb_step_kernel");
+    const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
+#define ELLC(W) DLA_LAUNCH((ell_cheb_step_kernel<W>), dim3(blocks), dim3(256), 0, st, n, m, op.w, (const int*)op.col, (const double*)op.val, k, u, v, x, out)
+    if (op.w <= 4) ELLC(4); else if (op.w <= 8) ELLC(8); else if (op.w <= 16) ELLC(16); else if (op.w <= 32) ELLC(32); else ELLC(0);
+#undef ELLC
+    HIPCHK(hipGetLastError());
+    return DLA_OK;
+  }
+  int spmm_precnd_cheb(int n, int m, double fac, const double* x, double* px) override
+  {
+    const char* who = "spmm_precnd_cheb";
+    { const int stc = cheb_admit(who); if (stc) return stc; }
+    SparseOp& op = ops[dla::SPMM_A];
+    if (n != op.n) { err = std::string(who) + ": n = " + std::to_string(n) + " differs from the " + std::to_string(op.n) + " rows of the operator"; return DLA_ERR_ARG; }
+    if (m <= 0) return DLA_OK;
+    { const int stc = cheb_upper(); if (stc) return stc; }
+    const int d = cheb.steps;
+    const double hi = cheb.upper + fac, lo = cheb.lo_fraction * hi, nm = (double)n * m;
+    const size_t total = (size_t)n * m;
+    if (hi <= 1.0e-5) {       // (the harness' guard on the interval's upper end: px = x)
+      Scope s(this, DLA_OP_PRECND, 16.0 * nm, 0.0, "cheb_identity_copy");
+      if (!lc.dry) HIPCHK(hipMemcpyAsync(px, x, sizeof(double) * total, hipMemcpyDeviceToDevice, st));
+      return DLA_OK;
+    }
+    const dla::ChebCoefficients cf = dla::cheb_coefficients(hi, lo, fac, d);
+    if (d == 1) {
+      Scope s(this, DLA_OP_PRECND, 16.0 * nm, nm, "cheb_scale_kernel");
+      const int blocks = (int)std::max((size_t)1, std::min((size_t)ncu * 8, (total + 255) / 256));
+      DLA_LAUNCH(cheb_scale_kernel, dim3(blocks), dim3(256), 0, st, total, cf.theta, x, px);
+      HIPCHK(hipGetLastError());
+      return DLA_OK;
+    }
+    // step k writes z_{k+1}: to px when it is the last, else to z[(k - 1) & 1], which held z_{k-1}
+    if (d >= 3) { const int stc = cheb_panel(cheb.z[0], total); if (stc) return stc; }
+    if (d >= 4) { const int stc = cheb_panel(cheb.z[1], total); if (stc) return stc; }
+    if (knobs.cheb_unfused() || (op.fmt == DLA_SPMM_SELL && op.sell_long_segments > 0)) { const int stc = cheb_panel(cheb.au, total); if (stc) return stc; }
+    for (int k = 1; k < d; ++k) {
+      const dla::ChebStep& c = cf.steps[(size_t)k - 1];
+      const double* u = k == 1 ? x : (const double*)cheb.z[(k - 2) & 1];
+      const double* v = k <= 2 ? x : (const double*)cheb.z[(k - 1) & 1];
+      double* out = k == d - 1 ? px : (double*)cheb.z[(k - 1) & 1];
+      const int stc = cheb_step(op, n, m, ChebCoef{c.alpha, c.beta, c.gamma, c.eta}, u, v, x, out);
+      if (stc) return stc;
+    }
     return DLA_OK;
   }
 

@@ -100,6 +100,8 @@ struct Knobs {
   bool own_copy_kernel() const { return tune[7] == 9; }
   // 22 / 23: one first-level group per 16 / 64 block partials (measured r06, DESIGN "Measured and rejected")
   int reduce_group_size() const { return tune[7] == 22 ? 16 : tune[7] == 23 ? 64 : 32; }
+  // 30: a step of the Chebyshev preconditioner as the product kernel plus one combining sweep, not fused (tools/cheb_precnd_ab.py)
+  bool cheb_unfused() const { return tune[7] == 30; }
 };
 
 // Sizes the engine's buffers and the tail kernels' LDS are built with, and that decisions read (one spelling: the engine and its kernels

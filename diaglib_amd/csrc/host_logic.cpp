@@ -1234,7 +1234,7 @@ static const OwnCallback* own_callback(void* fn)
     {(void*)&dla_spmm_ambmul, true, true}, {(void*)&dla_spmm_spdmul, true, true}, {(void*)&dla_spmm_smdmul, true, true},
     {(void*)&dla_synth_precnd, false, true}, {(void*)&dla_spmm_precnd, false, true}, {(void*)&dla_spmm_precnd_pencil, false, true},
     {(void*)&dla_synth_lrprec1, false, true}, {(void*)&dla_synth_lrprec2, false, true}, {(void*)&dla_spmm_lrprec1, false, true},
-    {(void*)&dla_spmm_lrprec2, false, true}};
+    {(void*)&dla_spmm_lrprec2, false, true}, {(void*)&dla_spmm_precnd_cheb, false, true}};
   for (const OwnCallback& r : table)
     if (r.fn == fn) return &r;
   return nullptr;
@@ -1941,6 +1941,24 @@ int dla_spmm_setup_csr_sharded(dla_ctx* c, int n_local, long long row0, long lon
 }
 void dla_spmm_matvec(const int* n, const int* m, const double* x, double* ax) { spmm_product(SPMM_A, n, m, x, ax); }
 void dla_spmm_precnd(const int* n, const int* m, const double* fac, const double* x, double* px) { spmm_precondition(0, n, m, fac, x, nullptr, px, nullptr); }
+// ... and the Chebyshev polynomial of A + fac I as its preconditioner.  The configuration is the context's and binds nothing: like
+// info, refresh and drop it leaves the thread's callbacks on the context they act on.
+int dla_spmm_cheb_config(dla_ctx* c, int steps, double lo_fraction)
+{
+  if (!c) return DLA_ERR_ARG;
+  return engfail(c, c->eng->spmm_cheb_config(steps, lo_fraction));
+}
+int dla_spmm_cheb_info(dla_ctx* c, struct dla_spmm_cheb_info* out)
+{
+  if (!c || !out) return DLA_ERR_ARG;
+  return engfail(c, c->eng->spmm_cheb_info(out));
+}
+void dla_spmm_precnd_cheb(const int* n, const int* m, const double* fac, const double* x, double* px)
+{
+  dla_ctx* c = g_spmm_ctx;
+  if (!c) { callback_failed(DLA_ERR_ARG, "dla_spmm_precnd_cheb before dla_spmm_setup_csr: no operator has been set up"); return; }
+  if (int st = c->eng->spmm_precnd_cheb(*n, *m, *fac, x, px)) callback_failed(st, "dla_spmm_precnd_cheb failed: " + c->eng->err);
+}
 
 // ---- ... the metric of a generalised problem beside it (bvec of reference diaglib.f90:1855; the harness' smult, main.f90:115-144) ...
 int dla_spmm_setup_metric_csr(dla_ctx* c, int n, const long long* rowptr, const int* colind, const double* values, int format) { return spmm_set_up(c, SPMM_B, dla::SPMM_VIA_HOST, n, rowptr, colind, values, format); }

@@ -578,6 +578,50 @@ void dla_spmm_smdmul(const int* n, const int* m, const double* x_dev, double* y_
 void dla_spmm_lrprec1(const int* n, const int* m, const double* fac, const double* xp_dev, const double* xm_dev, double* yp_dev, double* ym_dev);
 void dla_spmm_lrprec2(const int* n, const int* m, const double* fac, const double* xp_dev, const double* xm_dev, double* yp_dev, double* ym_dev);
 
+/* ---------------------------------------------------------------- Chebyshev polynomial preconditioner on the stored operator
+ * dla_spmm_precnd and dla_spmm_precnd_pencil divide by a diagonal, which does nothing for a stencil, FEM or graph matrix whose
+ * diagonal is (nearly) constant.  dla_spmm_precnd_cheb has the same shape precnd(n,m,fac,x,px), expects DEVICE addresses, acts on
+ * the calling thread's context, enqueues on that context's stream and goes where a precnd goes; it applies d steps of the Chebyshev
+ * iteration for M = A + fac I, with A the stored operator (slot A, single rank, any format), d >= 1 the configured number of steps
+ * and 0 < f < 1 the configured lo_fraction (dla_spmm_cheb_config).  The contract:
+ * Upper bound g of the spectrum (Gershgorin): g = max_i g_i with g_i = diag[i] + sum |v_p| over the entries of row i whose
+ * column is not i, in stored order from 0.0; diag[i] is the stored diagonal, which already holds the sum of duplicate (i, i)
+ * entries.  Kernels form g from the stored blocks without atomics and in a fixed order of summation (a tail row: lane l of one
+ * wavefront takes the row's entries l, l + 64, ... from 0.0, then the butterfly of the tail-row contract above, whatever the
+ * number of its segments).  g belongs to the stored matrix: every accepted set-up, refresh or drop of slot A invalidates it, and
+ * the next call of the preconditioner or of dla_spmm_cheb_info computes it again.  For the same arrays in the same format it has
+ * the same bits whether the matrix came from host arrays or device arrays.
+ * Interval: hi = g + fac, lo = f hi.  If hi <= 1e-5 then px = x, bit for bit (the harness' mprec guard, main.f90:161-169, on the
+ * interval's upper end).
+ * Scalars, on the host, each rounded to double once: theta = (hi + lo) / 2, delta = (hi - lo) / 2, sigma = theta / delta, rho_0 = 1 / sigma,
+ * rho_k = 1 / (2 sigma - rho_{k-1}).
+ * Recurrence (Saad, Iterative Methods, Algorithm 12.1 with a zero start, written on the iterate):
+ *   z_0 = 0,  z_1 = x / theta,
+ *   z_{k+1} = z_k + rho_k rho_{k-1} (z_k - z_{k-1}) + (2 rho_k / delta) (x - (A z_k + fac z_k))   for k = 1 .. d - 1,
+ *   px = z_d.
+ * The residual polynomial of z_d is T_d((theta - lambda) / delta) / T_d(sigma).  d = 1 is the scaled identity x / theta; d steps
+ * cost d - 1 sparse products.  Every step is one expression, z_{k+1} = fma(eta, A z_k, fma(gamma, x, fma(beta, z_{k-1}, alpha z_k)))
+ * with alpha = 1 + rho_k rho_{k-1} - (2 rho_k / delta) fac, beta = -rho_k rho_{k-1}, gamma = 2 rho_k / delta, eta = -gamma rounded
+ * on the host (z_1 is folded into the coefficients of steps 1 and 2, so no scaling sweep runs), and A z_k is accumulated as
+ * dla_spmm_matvec accumulates it, in both formats: a matrix stored as ELLPACK and as sliced ELLPACK gives the same bits on every
+ * row outside the CSR tail.  x is not changed; x and px must not overlap; repeated calls are bit-identical; every output element
+ * has one writer.  The iterates live in two work panels of n x m doubles that belong to the context (a sliced operator with a
+ * tail, and the un-fused A/B path, take a third); they grow on demand and are released by steps = 0 and by dla_destroy.
+ * Accuracy: px stays within twice the first-order running bound that tests/cheb_ref.py computes beside its long-double reference.
+ * Configuration (dla_spmm_cheb_config): a property of the context, independent of the matrix -- it survives set-ups and
+ * refreshes -- and deliberately not a dla_set_option option.  steps = 0 switches the preconditioner off; steps < 0 and
+ * lo_fraction outside (0, 1) are refused with DLA_ERR_ARG and leave an earlier configuration in force.  dla_spmm_cheb_info answers
+ * DLA_ERR_ARG while nothing is configured or no A is stored; upper is g of the stored A.
+ * Refusals: the callback fails through the status of dla_call_precnd, with a message that names dla_spmm_precnd_cheb and the
+ * cause, when it finds no operator, another n, nothing configured or a row-sharded operator; a refused call writes nothing.
+ * Out of scope: the pencil A + fac B, the linear-response parts and a row-sharded operator (refused as above); choosing
+ * lo_fraction or the number of steps adaptively (the caller passes both); sanitizer runs of code loaded into an interpreter (the
+ * host-only scalar recurrence is testable from a stand-alone program); any inspection of kernel assembly. */
+struct dla_spmm_cheb_info { int steps; double lo_fraction; double upper; };
+int  dla_spmm_cheb_config(dla_ctx* ctx, int steps, double lo_fraction);
+int  dla_spmm_cheb_info(dla_ctx* ctx, struct dla_spmm_cheb_info* out);
+void dla_spmm_precnd_cheb(const int* n, const int* m, const double* fac, const double* x_dev, double* px_dev);
+
 #ifdef __cplusplus
 }
 #endif

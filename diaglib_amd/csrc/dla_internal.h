@@ -311,6 +311,10 @@ struct Engine : BlockOps {
   virtual int spmm_cheb_config(int /*steps*/, double /*lo_fraction*/) { return DLA_ERR_ARG; }
   virtual int spmm_cheb_info(struct dla_spmm_cheb_info* /*out*/) { return DLA_ERR_ARG; }
   virtual int spmm_precnd_cheb(int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return DLA_ERR_ARG; }
+  // ... and the same iteration on the diagonally scaled operator D^-1 (A + fac I) (dla_spmm_precnd_cheb_jacobi), under the same
+  // configuration; spmm_cheb_jacobi_upper: the upper end hi of its interval for one fac
+  virtual int spmm_precnd_cheb_jacobi(int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return DLA_ERR_ARG; }
+  virtual int spmm_cheb_jacobi_upper(double /*fac*/, double* /*hi*/) { return DLA_ERR_ARG; }
 
   // Staging pipeline of host-mode callbacks: column chunks of a block travel device -> host on one copy stream, the
   // user's routine works on the chunk that has arrived, finished chunks travel host -> device on a second copy stream

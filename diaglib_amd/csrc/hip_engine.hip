@@ -1711,14 +1711,33 @@ __device__ __forceinline__ double cheb_combine(const ChebCoef& k, double u, doub
 {
   return fma(k.eta, au, fma(k.gamma, x, fma(k.beta, v, k.alpha * u)));
 }
+// ... and the step of the diagonally scaled form (dla_spmm_precnd_cheb_jacobi): the same combination on t = r_i ((A u)_i + fac u_i),
+// with y = x o r in the place of x.  fac enters here, through the product, and not through alpha.  ri is the row's 1 / den_i: the
+// kernels below read it once per row and keep it in a register across the m columns.
+__device__ __forceinline__ double cheb_jacobi_combine(const ChebCoef& k, double fac, double ri, double u, double v, double y, double au)
+{
+  const double t = fma(fac, u, au) * ri;
+  return fma(k.eta, t, fma(k.gamma, y, fma(k.beta, v, k.alpha * u)));
+}
+// J: the scaled epilogue; the gather loops of the step kernels are spelled once for both
+template <bool J>
+__device__ __forceinline__ double cheb_epilogue(const ChebCoef& k, double fac, double ri, double u, double v, double x, double au)
+{
+  if constexpr (J) return cheb_jacobi_combine(k, fac, ri, u, v, x, au);
+  else return cheb_combine(k, u, v, x, au);
+}
 // ell_spmm_kernel<W> with that epilogue, on the same width ladder.  The three panel reads of a column are issued before the gather
 // loop, so they are in flight while it runs.
-template <int W>
+// J = true: x is the panel y = x o r, and fac and r (n doubles) feed the scaled epilogue; J = false reads neither.
+template <int W, bool J>
 __global__ __launch_bounds__(256) void ell_cheb_step_kernel(int n, int m, int w, const int* __restrict__ col,
                                                             const double* __restrict__ val, ChebCoef k, const double* u,
-                                                            const double* v, const double* x, double* out)
+                                                            const double* v, const double* x, double* out, double fac,
+                                                            const double* __restrict__ r)
 {
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    double ri = 0.0;
+    if constexpr (J) ri = r[i];
     if constexpr (W > 0) {
       int cj[W]; double vj[W];
 #pragma unroll
@@ -1734,7 +1753,7 @@ __global__ __launch_bounds__(256) void ell_cheb_step_kernel(int n, int m, int w,
         double s = 0.0;
 #pragma unroll
         for (int q = 0; q < W; ++q) s += vj[q] * uc[cj[q]];
-        __builtin_nontemporal_store(cheb_combine(k, ui, vi, xi, s), out + o);
+        __builtin_nontemporal_store(cheb_epilogue<J>(k, fac, ri, ui, vi, xi, s), out + o);
       }
     } else {
       for (int c = 0; c < m; ++c) {
@@ -1743,17 +1762,18 @@ __global__ __launch_bounds__(256) void ell_cheb_step_kernel(int n, int m, int w,
         const double ui = u[o], vi = v[o], xi = x[o];
         double s = 0.0;
         for (int q = 0; q < w; ++q) s += val[(size_t)q * n + i] * uc[col[(size_t)q * n + i]];
-        __builtin_nontemporal_store(cheb_combine(k, ui, vi, xi, s), out + o);
+        __builtin_nontemporal_store(cheb_epilogue<J>(k, fac, ri, ui, vi, xi, s), out + o);
       }
     }
   }
 }
 // sell_spmm_kernel<MC> with the same epilogue for the rows of the slices; tail slots and slots past n store nothing
-template <int MC>
+template <int MC, bool J>
 __global__ __launch_bounds__(256) void sell_cheb_step_kernel(int n, int m, int slices, const long long* __restrict__ slice_ptr,
                                                              const int* __restrict__ perm, const int* __restrict__ col,
                                                              const double* __restrict__ val, ChebCoef kc, const double* u,
-                                                             const double* v, const double* x, double* out)
+                                                             const double* v, const double* x, double* out, double fac,
+                                                             const double* __restrict__ r)
 {
   const int lane = threadIdx.x & 63;
   for (int s = blockIdx.x * 4 + (threadIdx.x >> 6); s < slices; s += gridDim.x * 4) {
@@ -1763,6 +1783,8 @@ __global__ __launch_bounds__(256) void sell_cheb_step_kernel(int n, int m, int s
     const int row = slot < n ? perm[slot] : -1;
     const int* cs = col + p0 + lane;
     const double* vs = val + p0 + lane;
+    double ri = 0.0;
+    if constexpr (J) ri = row >= 0 ? r[row] : 0.0;
     for (int c0 = 0; c0 < m; c0 += MC) {
       const double* uc = u + (size_t)c0 * n;
       double acc[MC], ui[MC], vi[MC], xi[MC];
@@ -1792,22 +1814,27 @@ __global__ __launch_bounds__(256) void sell_cheb_step_kernel(int n, int m, int s
       if (row >= 0) {
 #pragma unroll
         for (int k = 0; k < MC; ++k)
-          if (c0 + k < m) __builtin_nontemporal_store(cheb_combine(kc, ui[k], vi[k], xi[k], acc[k]), out + (size_t)(c0 + k) * n + row);
+          if (c0 + k < m) __builtin_nontemporal_store(cheb_epilogue<J>(kc, fac, ri, ui[k], vi[k], xi[k], acc[k]), out + (size_t)(c0 + k) * n + row);
       }
     }
   }
 }
 // the rows of the CSR tail: csr_long_segments_kernel / long_rows_combine_kernel have left (A u)[row] in the scratch panel au; one
 // thread per (tail row, column) forms the combination for those rows only
+template <bool J>
 __global__ __launch_bounds__(256) void tail_cheb_combine_kernel(int n, int m, int nlong, const int* __restrict__ long_row, ChebCoef k,
                                                                 const double* u, const double* v, const double* x,
-                                                                const double* __restrict__ au, double* out)
+                                                                const double* __restrict__ au, double* out, double fac,
+                                                                const double* __restrict__ r)
 {
   const long long total = (long long)nlong * m;
   for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
     const int j = (int)(t / m), c = (int)(t - (long long)j * m);
-    const size_t o = (size_t)c * n + long_row[j];
-    out[o] = cheb_combine(k, u[o], v[o], x[o], au[o]);
+    const int row = long_row[j];
+    const size_t o = (size_t)c * n + row;
+    double ri = 0.0;
+    if constexpr (J) ri = r[row];
+    out[o] = cheb_epilogue<J>(k, fac, ri, u[o], v[o], x[o], au[o]);
   }
 }
 // the un-fused step (A/B comparand, Knobs::cheb_unfused): the product kernel has written A u to the panel au; one sweep combines
@@ -1816,6 +1843,33 @@ __global__ __launch_bounds__(256) void cheb_combine_kernel(size_t total, ChebCoe
 {
   for (size_t o = (size_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (size_t)gridDim.x * 256)
     out[o] = cheb_combine(k, u[o], v[o], x[o], au[o]);
+}
+// ... of the scaled form: one thread per row, r_i in a register across the m columns
+__global__ __launch_bounds__(256) void cheb_jacobi_combine_kernel(int n, int m, ChebCoef k, double fac, const double* __restrict__ r,
+                                                                  const double* u, const double* v, const double* y,
+                                                                  const double* __restrict__ au, double* out)
+{
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const double ri = r[i];
+    for (int c = 0; c < m; ++c) {
+      const size_t o = (size_t)c * n + i;
+      out[o] = cheb_jacobi_combine(k, fac, ri, u[o], v[o], y[o], au[o]);
+    }
+  }
+}
+// the scale sweep of the scaled form: y = x o r, or with one step (DIV) px = (x o r) / theta at once
+template <bool DIV>
+__global__ __launch_bounds__(256) void cheb_jacobi_scale_kernel(int n, int m, double theta, const double* __restrict__ r,
+                                                                const double* __restrict__ x, double* __restrict__ y)
+{
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const double ri = r[i];
+    for (int c = 0; c < m; ++c) {
+      const size_t o = (size_t)c * n + i;
+      const double t = x[o] * ri;
+      if constexpr (DIV) y[o] = t / theta; else y[o] = t;
+    }
+  }
 }
 // one step (d = 1): px = x / theta
 __global__ __launch_bounds__(256) void cheb_scale_kernel(size_t total, double theta, const double* __restrict__ x, double* __restrict__ px)
@@ -1833,21 +1887,25 @@ __device__ __forceinline__ void block_max_store(double g, double* __restrict__ p
   __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = fmax(fmax(wave_max[0], wave_max[1]), fmax(wave_max[2], wave_max[3]));
 }
+// ROWS: the same sums written per row, off[row] (the scaled form's off-diagonal row sums), in place of the block maximum in `partial`
+template <bool ROWS>
 __global__ __launch_bounds__(256) void ell_gershgorin_kernel(int n, int w, const int* __restrict__ col, const double* __restrict__ val,
-                                                             const double* __restrict__ diag, double* __restrict__ partial)
+                                                             const double* __restrict__ diag, double* __restrict__ partial,
+                                                             double* __restrict__ off)
 {
   double g = -INFINITY;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     double s = 0.0;
     for (int q = 0; q < w; ++q) if (col[(size_t)q * n + i] != i) s += fabs(val[(size_t)q * n + i]);
-    g = fmax(g, diag[i] + s);
+    if constexpr (ROWS) off[i] = s; else g = fmax(g, diag[i] + s);
   }
-  block_max_store(g, partial);
+  if constexpr (!ROWS) block_max_store(g, partial);
 }
+template <bool ROWS>
 __global__ __launch_bounds__(256) void sell_gershgorin_kernel(int n, int slices, const long long* __restrict__ slice_ptr,
                                                               const int* __restrict__ perm, const int* __restrict__ col,
                                                               const double* __restrict__ val, const double* __restrict__ diag,
-                                                              double* __restrict__ partial)
+                                                              double* __restrict__ partial, double* __restrict__ off)
 {
   const int lane = threadIdx.x & 63;
   double g = -INFINITY;
@@ -1859,15 +1917,17 @@ __global__ __launch_bounds__(256) void sell_gershgorin_kernel(int n, int slices,
     if (row < 0) continue;        // (a tail row: tail_gershgorin_kernel; or a slot past n)
     double sum = 0.0;
     for (int q = 0; q < width; ++q) if (col[p0 + (long long)q * 64 + lane] != row) sum += fabs(val[p0 + (long long)q * 64 + lane]);
-    g = fmax(g, diag[row] + sum);
+    if constexpr (ROWS) off[row] = sum; else g = fmax(g, diag[row] + sum);
   }
-  block_max_store(g, partial);
+  if constexpr (!ROWS) block_max_store(g, partial);
 }
 // ... and the rows of the tail, one wavefront per ROW whatever the number of its segments: lane l takes entries l, l + 64, ... of the
 // row from 0.0, then the butterfly of the product's segments.  col / val: the tail's entries (behind the slices')
+template <bool ROWS>
 __global__ __launch_bounds__(256) void tail_gershgorin_kernel(int nlong, const long long* __restrict__ long_ptr, const int* __restrict__ long_row,
                                                               const int* __restrict__ col, const double* __restrict__ val,
-                                                              const double* __restrict__ diag, double* __restrict__ partial)
+                                                              const double* __restrict__ diag, double* __restrict__ partial,
+                                                              double* __restrict__ off)
 {
   const int lane = threadIdx.x & 63;
   double g = -INFINITY;
@@ -1875,8 +1935,22 @@ __global__ __launch_bounds__(256) void tail_gershgorin_kernel(int nlong, const l
     const int row = long_row[r];
     double sum = 0.0;
     for (long long p = long_ptr[r] + lane; p < long_ptr[r + 1]; p += 64) if (col[p] != row) sum += fabs(val[p]);
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
-    g = fmax(g, diag[row] + sum);
+    for (int sh = 32; sh > 0; sh >>= 1) sum += __shfl_xor(sum, sh, 64);
+    if constexpr (ROWS) { if (lane == 0) off[row] = sum; } else g = fmax(g, diag[row] + sum);
+  }
+  if constexpr (!ROWS) block_max_store(g, partial);
+}
+// The bound of the scaled form for one fac (the contract: include/diaglib_amd.h, dla_spmm_precnd_cheb_jacobi): s_i = |diag[i] + fac|,
+// den_i = s_i where s_i > 1e-5 and 1.0 otherwise, r[i] = 1.0 / den_i, q_i = (s_i + off[i]) / den_i; partial[block] = max q_i.
+__global__ __launch_bounds__(256) void cheb_jacobi_bound_kernel(int n, double fac, const double* __restrict__ diag, const double* __restrict__ off,
+                                                                double* __restrict__ r, double* __restrict__ partial)
+{
+  double g = -INFINITY;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const double s = fabs(diag[i] + fac);
+    const double den = s > 1.0e-5 ? s : 1.0;
+    r[i] = 1.0 / den;
+    g = fmax(g, (s + off[i]) / den);
   }
   block_max_store(g, partial);
 }
@@ -6151,7 +6225,7 @@ struct HipEngine : dla::Engine {
     const SlotWords& w = words(slot);
     { const int stc = admit(slot, w.refresh, CALL_REFRESH | NEED_STORED); if (stc) return stc; }
     const int stc = refresh_dev(ops[slot], n, rowptr_dev, colind_dev, values_dev);
-    if (slot == dla::SPMM_A) cheb.upper_valid = false;
+    if (slot == dla::SPMM_A) cheb.upper_valid = cheb.off_valid = false;
     if (stc == DLA_ERR_ARG && w.quoted_dev) err = quote(slot, w.refresh) + err;
     return stc;
   }
@@ -6203,7 +6277,7 @@ struct HipEngine : dla::Engine {
     const int stc = dev ? setup_dev(ops[slot], n, rowptr, colind, values, format)
                         : setup_fmt(ops[slot], n, rowptr, colind, values, plain ? (int)DLA_SPMM_ELL : format, quoted ? "spmm_setup_csr_fmt" : entry);
     if (stc == DLA_ERR_ARG && quoted) err = quote(slot, entry) + err;
-    if (slot == dla::SPMM_A) cheb.upper_valid = false;
+    if (slot == dla::SPMM_A) cheb.upper_valid = cheb.off_valid = false;
     if (!stc && slot == dla::SPMM_A) shard.drop();
     return stc;
   }
@@ -6239,7 +6313,7 @@ struct HipEngine : dla::Engine {
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamSynchronize(st));     // (products of these slots may still be queued)
     for (int s = first; s <= last; ++s) ops[s].drop();
-    if (first <= dla::SPMM_A && dla::SPMM_A <= last) cheb.upper_valid = false;
+    if (first <= dla::SPMM_A && dla::SPMM_A <= last) cheb.upper_valid = cheb.off_valid = false;
     return DLA_OK;
   }
   // slices kernel, segments kernel, combine kernel; p: the tail's launch shapes and workspace (long_rows_plan)
@@ -6346,7 +6420,7 @@ struct HipEngine : dla::Engine {
     dla::ShardedEll e;
     dla::sharded_ell_build(n, row0, rowptr, colind, values, (int)halo, e);
     bind();
-    cheb.upper_valid = false;
+    cheb.upper_valid = cheb.off_valid = false;
     stc = upload_ell(ops[dla::SPMM_A], e.col, e.val, e.diag);
     if (stc) return stc;
     ops[dla::SPMM_A].n = n; ops[dla::SPMM_A].w = e.w; shard.halo = (int)halo; shard.on = true;
@@ -6444,6 +6518,11 @@ struct HipEngine : dla::Engine {
     DeviceBuffer<double> z[2];         // the iterates z_k, z_{k-1}: n x m each
     DeviceBuffer<double> au;           // A u of the tail rows of a sliced operator, and of every row on the un-fused path: n x m
     DeviceBuffer<double> partial;      // the block maxima of the Gershgorin kernels
+    // the diagonally scaled form (dla_spmm_precnd_cheb_jacobi)
+    bool off_valid = false;            // off holds the off-diagonal row sums of the stored A
+    DeviceBuffer<double> off;          // n doubles: the stored matrix's, formed on first use
+    DeviceBuffer<double> r;            // n doubles: 1 / den_i of the last call's fac
+    DeviceBuffer<double> y;            // the panel y = x o r: n x m
   } cheb;
   int spmm_cheb_config(int steps, double lo_fraction) override
   {
@@ -6453,10 +6532,11 @@ struct HipEngine : dla::Engine {
       return DLA_ERR_ARG;
     }
     if (steps == 0) {
-      if (cheb.z[0] || cheb.z[1] || cheb.au || cheb.partial) {
+      if (cheb.z[0] || cheb.z[1] || cheb.au || cheb.partial || cheb.off || cheb.r || cheb.y) {
         HIPCHK(hipSetDevice(device));
         HIPCHK(hipStreamSynchronize(st));     // (a queued call may still use the panels)
         cheb.z[0].reset(); cheb.z[1].reset(); cheb.au.reset(); cheb.partial.reset();
+        cheb.off.reset(); cheb.r.reset(); cheb.y.reset(); cheb.off_valid = false;
       }
       cheb.steps = 0; cheb.lo_fraction = 0.0;
       return DLA_OK;
@@ -6480,17 +6560,18 @@ struct HipEngine : dla::Engine {
       HIPCHK(cheb.partial.reserve((size_t)2 * cap));
     }
     if (sell) {
-      DLA_LAUNCH(sell_gershgorin_kernel, dim3(b0), dim3(256), 0, st, op.n, op.sell_slices, (const long long*)op.sell_ptr, (const int*)op.sell_perm,
-                 (const int*)op.col, (const double*)op.val, (const double*)op.diag, (double*)cheb.partial);
+      DLA_LAUNCH(sell_gershgorin_kernel<false>, dim3(b0), dim3(256), 0, st, op.n, op.sell_slices, (const long long*)op.sell_ptr, (const int*)op.sell_perm,
+                 (const int*)op.col, (const double*)op.val, (const double*)op.diag, (double*)cheb.partial, (double*)nullptr);
       HIPCHK(hipGetLastError());
       if (b1 > 0) {
-        DLA_LAUNCH(tail_gershgorin_kernel, dim3(b1), dim3(256), 0, st, op.sell_long_rows, (const long long*)op.long_ptr, (const int*)op.long_row,
-                   (const int*)op.col + op.sell_stored, (const double*)op.val + op.sell_stored, (const double*)op.diag, (double*)cheb.partial + b0);
+        DLA_LAUNCH(tail_gershgorin_kernel<false>, dim3(b1), dim3(256), 0, st, op.sell_long_rows, (const long long*)op.long_ptr, (const int*)op.long_row,
+                   (const int*)op.col + op.sell_stored, (const double*)op.val + op.sell_stored, (const double*)op.diag, (double*)cheb.partial + b0,
+                   (double*)nullptr);
         HIPCHK(hipGetLastError());
       }
     } else {
-      DLA_LAUNCH(ell_gershgorin_kernel, dim3(b0), dim3(256), 0, st, op.n, op.w, (const int*)op.col, (const double*)op.val, (const double*)op.diag,
-                 (double*)cheb.partial);
+      DLA_LAUNCH(ell_gershgorin_kernel<false>, dim3(b0), dim3(256), 0, st, op.n, op.w, (const int*)op.col, (const double*)op.val, (const double*)op.diag,
+                 (double*)cheb.partial, (double*)nullptr);
       HIPCHK(hipGetLastError());
     }
     std::vector<double> h((size_t)(b0 + b1));
@@ -6525,15 +6606,24 @@ struct HipEngine : dla::Engine {
     return DLA_OK;
   }
   // one step out = alpha u + beta v + gamma x + eta (A u) on the stored A; out may be v's buffer, never u's
-  int cheb_step(SparseOp& op, int n, int m, const ChebCoef& k, const double* u, const double* v, const double* x, double* out)
+  // J: the step of the scaled form, where x is the panel y = x o r and r = cheb.r; booked under its own kernel names with the 8 n
+  // bytes of r and the 3 n m flops of the scaling on top
+  template <bool J>
+  int cheb_step(SparseOp& op, int n, int m, const ChebCoef& k, const double* u, const double* v, const double* x, double* out, double fac = 0.0)
   {
-    const double nm = (double)n * m;
+    const double nm = (double)n * m, rb = J ? 8.0 * n : 0.0, cf = (J ? 10.0 : 7.0) * nm;
+    const double* r = J ? (const double*)cheb.r : nullptr;
     if (knobs.cheb_unfused()) {
       { const int stc = op_matvec(op, n, m, u, cheb.au); if (stc) return stc; }
-      Scope s(this, DLA_OP_PRECND, 40.0 * nm, 7.0 * nm, "cheb_combine_kernel");
+      Scope s(this, DLA_OP_PRECND, 40.0 * nm + rb, cf, J ? "cheb_jacobi_combine_kernel" : "cheb_combine_kernel");
       const size_t total = (size_t)n * m;
-      const int blocks = (int)std::max((size_t)1, std::min((size_t)ncu * 8, (total + 255) / 256));
-      DLA_LAUNCH(cheb_combine_kernel, dim3(blocks), dim3(256), 0, st, total, k, u, v, x, (const double*)cheb.au, out);
+      if constexpr (J) {
+        DLA_LAUNCH(cheb_jacobi_combine_kernel, dim3(std::max(1, std::min(ncu * 8, (n + 255) / 256))), dim3(256), 0, st, n, m, k, fac, r, u, v, x,
+                   (const double*)cheb.au, out);
+      } else {
+        const int blocks = (int)std::max((size_t)1, std::min((size_t)ncu * 8, (total + 255) / 256));
+        DLA_LAUNCH(cheb_combine_kernel, dim3(blocks), dim3(256), 0, st, total, k, u, v, x, (const double*)cheb.au, out);
+      }
       HIPCHK(hipGetLastError());
       return DLA_OK;
     }
@@ -6541,14 +6631,14 @@ struct HipEngine : dla::Engine {
       const LongRowsPlan p = long_rows_plan(env(), op.sell_long_segments, op.sell_multi_rows, op.sell_multi_segments, m, LONG_MC);
       // (the tail's partial sums and its rows of the scratch panel are written once and read once)
       Scope s(this, DLA_OP_PRECND, 12.0 * (double)(op.sell_stored + op.sell_long_entries) + 4.0 * n + 32.0 * nm + 16.0 * (double)p.part_doubles +
-                                       16.0 * (double)op.sell_long_rows * m,
-              2.0 * (double)op.nnz * m + 7.0 * nm, "sell_cheb_step_kernel");
+                                       16.0 * (double)op.sell_long_rows * m + rb,
+              2.0 * (double)op.nnz * m + cf, J ? "sell_cheb_jacobi_step_kernel" : "sell_cheb_step_kernel");
       if (p.part_doubles > op.long_part.capacity()) {
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(op.long_part.reserve(p.part_doubles));
       }
-      DLA_LAUNCH((sell_cheb_step_kernel<SELL_MC>), dim3(std::max(1, std::min(ncu * 8, (op.sell_slices + 3) / 4))), dim3(256), 0, st, n, m, op.sell_slices,
-                 (const long long*)op.sell_ptr, (const int*)op.sell_perm, (const int*)op.col, (const double*)op.val, k, u, v, x, out);
+      DLA_LAUNCH((sell_cheb_step_kernel<SELL_MC, J>), dim3(std::max(1, std::min(ncu * 8, (op.sell_slices + 3) / 4))), dim3(256), 0, st, n, m, op.sell_slices,
+                 (const long long*)op.sell_ptr, (const int*)op.sell_perm, (const int*)op.col, (const double*)op.val, k, u, v, x, out, fac, r);
       HIPCHK(hipGetLastError());
       if (op.sell_long_segments > 0) {
         DLA_LAUNCH((csr_long_segments_kernel<LONG_MC>), dim3(p.seg_blocks), dim3(256), 0, st, n, m, op.sell_long_segments, (const long long*)op.seg_ptr,
@@ -6561,15 +6651,16 @@ struct HipEngine : dla::Engine {
           HIPCHK(hipGetLastError());
         }
         const long long total = (long long)op.sell_long_rows * m;
-        DLA_LAUNCH(tail_cheb_combine_kernel, dim3((int)std::max(1LL, std::min((long long)ncu * 8, (total + 255) / 256))), dim3(256), 0, st, n, m,
-                   op.sell_long_rows, (const int*)op.long_row, k, u, v, x, (const double*)cheb.au, out);
+        DLA_LAUNCH(tail_cheb_combine_kernel<J>, dim3((int)std::max(1LL, std::min((long long)ncu * 8, (total + 255) / 256))), dim3(256), 0, st, n, m,
+                   op.sell_long_rows, (const int*)op.long_row, k, u, v, x, (const double*)cheb.au, out, fac, r);
         HIPCHK(hipGetLastError());
       }
       return DLA_OK;
     }
-    Scope s(this, DLA_OP_PRECND, 12.0 * (double)op.w * n + 32.0 * nm, 2.0 * (double)op.w * nm + 7.0 * nm, "ell_cheb_step_kernel");
+    Scope s(this, DLA_OP_PRECND, 12.0 * (double)op.w * n + 32.0 * nm + rb, 2.0 * (double)op.w * nm + cf,
+            J ? "ell_cheb_jacobi_step_kernel" : "ell_cheb_step_kernel");
     const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
-#define ELLC(W) DLA_LAUNCH((ell_cheb_step_kernel<W>), dim3(blocks), dim3(256), 0, st, n, m, op.w, (const int*)op.col, (const double*)op.val, k, u, v, x, out)
+#define ELLC(W) DLA_LAUNCH((ell_cheb_step_kernel<W, J>), dim3(blocks), dim3(256), 0, st, n, m, op.w, (const int*)op.col, (const double*)op.val, k, u, v, x, out, fac, r)
     if (op.w <= 4) ELLC(4); else if (op.w <= 8) ELLC(8); else if (op.w <= 16) ELLC(16); else if (op.w <= 32) ELLC(32); else ELLC(0);
 #undef ELLC
     HIPCHK(hipGetLastError());
@@ -6608,7 +6699,108 @@ struct HipEngine : dla::Engine {
       const double* u = k == 1 ? x : (const double*)cheb.z[(k - 2) & 1];
       const double* v = k <= 2 ? x : (const double*)cheb.z[(k - 1) & 1];
       double* out = k == d - 1 ? px : (double*)cheb.z[(k - 1) & 1];
-      const int stc = cheb_step(op, n, m, ChebCoef{c.alpha, c.beta, c.gamma, c.eta}, u, v, x, out);
+      const int stc = cheb_step<false>(op, n, m, ChebCoef{c.alpha, c.beta, c.gamma, c.eta}, u, v, x, out);
+      if (stc) return stc;
+    }
+    return DLA_OK;
+  }
+
+  // ---- ... and on the diagonally scaled operator D^-1 (A + fac I), D = |diag(A) + fac| (the contract: include/diaglib_amd.h,
+  // dla_spmm_precnd_cheb_jacobi).  off, the off-diagonal row sums, is the stored matrix's like the Gershgorin bound; r and the
+  // interval depend on fac and are formed by every call.
+  int cheb_off()
+  {
+    if (cheb.off_valid) return DLA_OK;
+    SparseOp& op = ops[dla::SPMM_A];
+    bind();
+    { const int stc = cheb_panel(cheb.off, (size_t)op.n); if (stc) return stc; }
+    const int cap = std::max(1, ncu * 4);
+    if (op.fmt == DLA_SPMM_SELL) {
+      DLA_LAUNCH(sell_gershgorin_kernel<true>, dim3(std::max(1, std::min(cap, (op.sell_slices + 3) / 4))), dim3(256), 0, st, op.n, op.sell_slices,
+                 (const long long*)op.sell_ptr, (const int*)op.sell_perm, (const int*)op.col, (const double*)op.val, (const double*)op.diag,
+                 (double*)nullptr, (double*)cheb.off);
+      HIPCHK(hipGetLastError());
+      if (op.sell_long_rows > 0) {
+        DLA_LAUNCH(tail_gershgorin_kernel<true>, dim3(std::max(1, std::min(cap, (op.sell_long_rows + 3) / 4))), dim3(256), 0, st, op.sell_long_rows,
+                   (const long long*)op.long_ptr, (const int*)op.long_row, (const int*)op.col + op.sell_stored, (const double*)op.val + op.sell_stored,
+                   (const double*)op.diag, (double*)nullptr, (double*)cheb.off);
+        HIPCHK(hipGetLastError());
+      }
+    } else {
+      DLA_LAUNCH(ell_gershgorin_kernel<true>, dim3(std::max(1, std::min(2 * cap, (op.n + 255) / 256))), dim3(256), 0, st, op.n, op.w, (const int*)op.col,
+                 (const double*)op.val, (const double*)op.diag, (double*)nullptr, (double*)cheb.off);
+      HIPCHK(hipGetLastError());
+    }
+    cheb.off_valid = true;
+    return DLA_OK;
+  }
+  // r = 1 / den and hi = max_i q_i for this fac: one kernel, then the block maxima come to the host (one host wait per call)
+  int cheb_jacobi_bound(double fac, double* hi)
+  {
+    SparseOp& op = ops[dla::SPMM_A];
+    const int n = op.n;
+    { const int stc = cheb_off(); if (stc) return stc; }
+    { const int stc = cheb_panel(cheb.r, (size_t)n); if (stc) return stc; }
+    const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
+    { const int stc = cheb_panel(cheb.partial, (size_t)std::max(ncu * 8, 1)); if (stc) return stc; }
+    {
+      Scope s(this, DLA_OP_PRECND, 24.0 * n, 4.0 * n, "cheb_jacobi_bound_kernel");
+      DLA_LAUNCH(cheb_jacobi_bound_kernel, dim3(blocks), dim3(256), 0, st, n, fac, (const double*)op.diag, (const double*)cheb.off, (double*)cheb.r,
+                 (double*)cheb.partial);
+      HIPCHK(hipGetLastError());
+    }
+    std::vector<double> h((size_t)blocks);
+    HIPCHK(hipMemcpyAsync(h.data(), (const double*)cheb.partial, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    stats.host_syncs++;
+    double g = h[0];
+    for (size_t j = 1; j < h.size(); ++j) g = std::max(g, h[j]);
+    *hi = g;
+    return DLA_OK;
+  }
+  int spmm_cheb_jacobi_upper(double fac, double* hi) override
+  {
+    { const int stc = cheb_admit("spmm_cheb_jacobi_upper"); if (stc) return stc; }
+    return cheb_jacobi_bound(fac, hi);
+  }
+  int spmm_precnd_cheb_jacobi(int n, int m, double fac, const double* x, double* px) override
+  {
+    const char* who = "spmm_precnd_cheb_jacobi";
+    { const int stc = cheb_admit(who); if (stc) return stc; }
+    SparseOp& op = ops[dla::SPMM_A];
+    if (n != op.n) { err = std::string(who) + ": n = " + std::to_string(n) + " differs from the " + std::to_string(op.n) + " rows of the operator"; return DLA_ERR_ARG; }
+    if (m <= 0) return DLA_OK;
+    const int d = cheb.steps;
+    const double nm = (double)n * m;
+    const size_t total = (size_t)n * m;
+    // every buffer of the call before its first launch: a growing one waits for the stream
+    if (d >= 2) { const int stc = cheb_panel(cheb.y, total); if (stc) return stc; }
+    if (d >= 3) { const int stc = cheb_panel(cheb.z[0], total); if (stc) return stc; }
+    if (d >= 4) { const int stc = cheb_panel(cheb.z[1], total); if (stc) return stc; }
+    if (d >= 2 && (knobs.cheb_unfused() || (op.fmt == DLA_SPMM_SELL && op.sell_long_segments > 0))) { const int stc = cheb_panel(cheb.au, total); if (stc) return stc; }
+    double hi = 0.0;
+    { const int stc = cheb_jacobi_bound(fac, &hi); if (stc) return stc; }
+    if (hi <= 1.0e-5) {       // (the guard of the plain form, on the scaled interval's upper end: px = x)
+      Scope s(this, DLA_OP_PRECND, 16.0 * nm, 0.0, "cheb_identity_copy");
+      if (!lc.dry) HIPCHK(hipMemcpyAsync(px, x, sizeof(double) * total, hipMemcpyDeviceToDevice, st));
+      return DLA_OK;
+    }
+    const dla::ChebCoefficients cf = dla::cheb_coefficients(hi, cheb.lo_fraction * hi, 0.0, d);
+    const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
+    {
+      Scope s(this, DLA_OP_PRECND, 16.0 * nm + 8.0 * n, (d == 1 ? 2.0 : 1.0) * nm, "cheb_jacobi_scale_kernel");
+      if (d == 1) DLA_LAUNCH(cheb_jacobi_scale_kernel<true>, dim3(blocks), dim3(256), 0, st, n, m, cf.theta, (const double*)cheb.r, x, px);
+      else DLA_LAUNCH(cheb_jacobi_scale_kernel<false>, dim3(blocks), dim3(256), 0, st, n, m, cf.theta, (const double*)cheb.r, x, (double*)cheb.y);
+      HIPCHK(hipGetLastError());
+    }
+    // the plain form's recurrence with y in the place of x: step k writes z_{k+1} to px when it is the last, else to z[(k - 1) & 1]
+    const double* y = cheb.y;
+    for (int k = 1; k < d; ++k) {
+      const dla::ChebStep& c = cf.steps[(size_t)k - 1];
+      const double* u = k == 1 ? y : (const double*)cheb.z[(k - 2) & 1];
+      const double* v = k <= 2 ? y : (const double*)cheb.z[(k - 1) & 1];
+      double* out = k == d - 1 ? px : (double*)cheb.z[(k - 1) & 1];
+      const int stc = cheb_step<true>(op, n, m, ChebCoef{c.alpha, c.beta, c.gamma, c.eta}, u, v, y, out, fac);
       if (stc) return stc;
     }
     return DLA_OK;

@@ -1234,7 +1234,8 @@ static const OwnCallback* own_callback(void* fn)
     {(void*)&dla_spmm_ambmul, true, true}, {(void*)&dla_spmm_spdmul, true, true}, {(void*)&dla_spmm_smdmul, true, true},
     {(void*)&dla_synth_precnd, false, true}, {(void*)&dla_spmm_precnd, false, true}, {(void*)&dla_spmm_precnd_pencil, false, true},
     {(void*)&dla_synth_lrprec1, false, true}, {(void*)&dla_synth_lrprec2, false, true}, {(void*)&dla_spmm_lrprec1, false, true},
-    {(void*)&dla_spmm_lrprec2, false, true}, {(void*)&dla_spmm_precnd_cheb, false, true}};
+    {(void*)&dla_spmm_lrprec2, false, true}, {(void*)&dla_spmm_precnd_cheb, false, true},
+    {(void*)&dla_spmm_precnd_cheb_jacobi, false, true}};
   for (const OwnCallback& r : table)
     if (r.fn == fn) return &r;
   return nullptr;
@@ -1958,6 +1959,18 @@ void dla_spmm_precnd_cheb(const int* n, const int* m, const double* fac, const d
   dla_ctx* c = g_spmm_ctx;
   if (!c) { callback_failed(DLA_ERR_ARG, "dla_spmm_precnd_cheb before dla_spmm_setup_csr: no operator has been set up"); return; }
   if (int st = c->eng->spmm_precnd_cheb(*n, *m, *fac, x, px)) callback_failed(st, "dla_spmm_precnd_cheb failed: " + c->eng->err);
+}
+// ... on the diagonally scaled operator, under the same configuration
+int dla_spmm_cheb_jacobi_upper(dla_ctx* c, double fac, double* hi)
+{
+  if (!c || !hi) return DLA_ERR_ARG;
+  return engfail(c, c->eng->spmm_cheb_jacobi_upper(fac, hi));
+}
+void dla_spmm_precnd_cheb_jacobi(const int* n, const int* m, const double* fac, const double* x, double* px)
+{
+  dla_ctx* c = g_spmm_ctx;
+  if (!c) { callback_failed(DLA_ERR_ARG, "dla_spmm_precnd_cheb_jacobi before dla_spmm_setup_csr: no operator has been set up"); return; }
+  if (int st = c->eng->spmm_precnd_cheb_jacobi(*n, *m, *fac, x, px)) callback_failed(st, "dla_spmm_precnd_cheb_jacobi failed: " + c->eng->err);
 }
 
 // ---- ... the metric of a generalised problem beside it (bvec of reference diaglib.f90:1855; the harness' smult, main.f90:115-144) ...

@@ -622,6 +622,49 @@ int  dla_spmm_cheb_config(dla_ctx* ctx, int steps, double lo_fraction);
 int  dla_spmm_cheb_info(dla_ctx* ctx, struct dla_spmm_cheb_info* out);
 void dla_spmm_precnd_cheb(const int* n, const int* m, const double* fac, const double* x_dev, double* px_dev);
 
+/* ---------------------------------------------------------------- ... on the diagonally scaled operator
+ * The interval [f g, g] of dla_spmm_precnd_cheb is right only while the diagonal is nearly constant.  On a variable-coefficient
+ * stencil, an FEM matrix on a graded mesh or a graph with uneven degrees g follows the largest row while the wanted eigenvectors
+ * live in the smallest rows, and the diagonal preconditioner has the opposite weakness.  dla_spmm_precnd_cheb_jacobi is the same
+ * iteration on D^-1 M with M = A + fac I and D = |diag(A) + fac|, whose spectrum sits in about [0, 2] whatever the coefficients
+ * do; the result p(D^-1 M) D^-1 is symmetric, and it contains both others as limits (d = 1 is the diagonal preconditioner up to
+ * the factor 1 / theta, a constant diagonal gives the plain polynomial).  Same shape precnd(n,m,fac,x,px), DEVICE addresses, the
+ * calling thread's context and stream; it reads the configuration (d, f) of dla_spmm_cheb_config that the plain one reads, and the
+ * caller chooses between the two by the function it passes as precnd.  Slot A, single rank, ELLPACK and sliced ELLPACK including
+ * the CSR tail.  The contract:
+ * 1. Off-diagonal row sums: off_i = sum |v_p| over the entries of row i whose column is not i, in stored order from 0.0 -- the sum
+ *    that the Gershgorin kernels form per row; a tail row as described for g above.  The n doubles belong to the stored matrix and
+ *    are formed by kernels on first use; every accepted set-up, refresh or drop of slot A invalidates them exactly as it
+ *    invalidates g.  Host set-up and device set-up give the same bits.  g itself keeps its bits.
+ * 2. Per call, per row: s_i = |diag[i] + fac|; den_i = s_i where s_i > 1e-5, else 1.0 (the harness' mprec guard, per row);
+ *    r_i = 1.0 / den_i; q_i = (s_i + off_i) / den_i; hi = max_i q_i bounds the infinity norm of D^-1 (A + fac I); lo = f hi.  If
+ *    hi <= 1e-5 then px = x, bit for bit.  One kernel reads diag and off, writes r (n doubles owned by the context) and block
+ *    maxima; the host takes the maximum of those, without atomics.  THIS COSTS ONE HOST WAIT PER CALL: the scalars of the
+ *    recurrence depend on hi, and hi depends on fac.
+ * 3. Scalars: those of dla_spmm_precnd_cheb for the interval [lo, hi] with fac = 0 (fac enters through the product, not through
+ *    alpha): alpha = 1 + rho_k rho_{k-1}, beta = -rho_k rho_{k-1}, gamma = 2 rho_k / delta, eta = -gamma.
+ * 4. Recurrence: y_i = x_i r_i;  z_0 = 0,  z_1 = y / theta,
+ *      z_{k+1} = z_k + rho_k rho_{k-1} (z_k - z_{k-1}) + (2 rho_k / delta) (y - r o (A z_k + fac z_k))   for k = 1 .. d - 1,
+ *    px = z_d.
+ * 5. Each step is one expression per element, with u = z_k and v = z_{k-1}:
+ *      t = fma(fac, u_i, (A u)_i) * r_i,   out = fma(eta, t, fma(gamma, y_i, fma(beta, v_i, alpha u_i)))
+ *    where (A u)_i is accumulated as dla_spmm_matvec accumulates it and z_1 is folded into the coefficients of steps 1 and 2 as
+ *    in the plain form.  d = 1 is px_i = (x_i r_i) / theta.
+ * 6. Bits: ELLPACK and sliced storage give the same bits on every row outside the tail; the un-fused A/B path gives the fused
+ *    bits; repeated calls are bit-identical; every output element has one writer; x is unchanged and must not overlap px.
+ * 7. dla_spmm_cheb_jacobi_upper returns hi for a given fac (one kernel, one host wait), so that a caller or a test can see the
+ *    interval; DLA_ERR_ARG under the conditions of dla_spmm_cheb_info.
+ * 8. Refusals: the four of the plain callback -- no operator, another n, nothing configured, a row-sharded operator -- through the
+ *    status of dla_call_precnd, with a message that names dla_spmm_precnd_cheb_jacobi and the cause; a refused call writes nothing.
+ * Work memory beside the plain form's two or three panels: the panel y (n x m) and the vectors off and r (n each); they belong to
+ * the context, grow behind a stream wait and are released by steps = 0 and by dla_destroy.
+ * Accuracy: px stays within twice the first-order running bound that tests/cheb_jacobi_ref.py computes beside its long-double
+ * reference, wherever that bound is below 1e-9 of the result.
+ * Out of scope: the pencil A + fac B, the linear-response parts, row shards, choosing d or f adaptively, sanitizer runs of code
+ * loaded into an interpreter, any inspection of kernel assembly. */
+int  dla_spmm_cheb_jacobi_upper(dla_ctx* ctx, double fac, double* hi);
+void dla_spmm_precnd_cheb_jacobi(const int* n, const int* m, const double* fac, const double* x_dev, double* px_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1556,36 +1556,65 @@ __global__ void synth_precnd_kernel(int n, int m, double fac, const double* __re
 // neighbouring entries.  HBM-bound: 12 w n bytes of matrix + 16 n m bytes of vectors per call (+ gather overfetch).
 // Padding to the WIDEST row is what makes this format unusable for a matrix with a few long rows: dla_spmm_setup_csr_fmt stores
 // those as sliced ELLPACK with a CSR tail (sell_spmm_kernel / csr_long_segments_kernel below) behind the same two callbacks.
-template <int W>
-__global__ __launch_bounds__(256) void ell_spmm_kernel(int n, int m, int w, const int* __restrict__ col,
-                                                       const double* __restrict__ val, const double* __restrict__ x,
-                                                       double* __restrict__ ax)
+// The row loop is spelled once (ell_rows) for the product, the Chebyshev step (ell_cheb_step_kernel) and the product on a row shard
+// (ell_spmm_halo_kernel).  A GATHER says where entry j of column c of the gathered panel lives and which column a padding entry
+// points at; an EPILOGUE says what a row does with its sum: row(i) once per row, load(o) for element o = c n + i in front of the
+// gather loop -- so that panel reads it needs are in flight while the loop runs -- and store(o, held, sum) behind it.
+struct GatherPlain {
+  const double* x; int n;
+  __device__ __forceinline__ int self(int i) const { return i; }
+  __device__ __forceinline__ const double* column(int c) const { return x + (size_t)c * n; }
+  __device__ __forceinline__ static double at(const double* xc, int j) { return xc[j]; }
+};
+// the product's epilogue: a non-temporal store of the sum
+struct StoreProduct {
+  double* ax;
+  struct Held {};
+  __device__ __forceinline__ void row(int) {}
+  __device__ __forceinline__ Held load(size_t) const { return Held{}; }
+  __device__ __forceinline__ void store(size_t o, Held, double s) const { __builtin_nontemporal_store(s, ax + o); }
+};
+template <int W, class Gather, class Epilogue>
+__device__ __forceinline__ void ell_rows(int n, int m, int w, const int* __restrict__ col, const double* __restrict__ val,
+                                         const Gather gather, Epilogue ep)
 {
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    ep.row(i);
     if constexpr (W > 0) {
       int cj[W]; double vj[W];
 #pragma unroll
       for (int q = 0; q < W; ++q) {
         const bool in = q < w;
-        cj[q] = in ? col[(size_t)q * n + i] : i;
+        cj[q] = in ? col[(size_t)q * n + i] : gather.self(i);
         vj[q] = in ? val[(size_t)q * n + i] : 0.0;
       }
       for (int c = 0; c < m; ++c) {
-        const double* xc = x + (size_t)c * n;
+        const size_t o = (size_t)c * n + i;
+        const auto xc = gather.column(c);
+        const auto held = ep.load(o);
         double s = 0.0;
 #pragma unroll
-        for (int q = 0; q < W; ++q) s += vj[q] * xc[cj[q]];
-        __builtin_nontemporal_store(s, ax + (size_t)c * n + i);
+        for (int q = 0; q < W; ++q) s += vj[q] * Gather::at(xc, cj[q]);
+        ep.store(o, held, s);
       }
     } else {
       for (int c = 0; c < m; ++c) {
-        const double* xc = x + (size_t)c * n;
+        const size_t o = (size_t)c * n + i;
+        const auto xc = gather.column(c);
+        const auto held = ep.load(o);
         double s = 0.0;
-        for (int q = 0; q < w; ++q) s += val[(size_t)q * n + i] * xc[col[(size_t)q * n + i]];
-        __builtin_nontemporal_store(s, ax + (size_t)c * n + i);
+        for (int q = 0; q < w; ++q) s += val[(size_t)q * n + i] * Gather::at(xc, col[(size_t)q * n + i]);
+        ep.store(o, held, s);
       }
     }
   }
+}
+template <int W>
+__global__ __launch_bounds__(256) void ell_spmm_kernel(int n, int m, int w, const int* __restrict__ col,
+                                                       const double* __restrict__ val, const double* __restrict__ x,
+                                                       double* __restrict__ ax)
+{
+  ell_rows<W>(n, m, w, col, val, GatherPlain{x, n}, StoreProduct{ax});
 }
 
 // The same product from sliced ELLPACK (dla::SellLayout, dla_spmm_setup_csr_fmt): one wavefront owns a slice of 64 slots, entry
@@ -1597,6 +1626,8 @@ __global__ __launch_bounds__(256) void ell_spmm_kernel(int n, int m, int w, cons
 // the entries are accumulated in stored order, one fused multiply-add each, from 0.0: the bits of ell_spmm_kernel.
 // perm[slot] is the row a slot computes; negative: the row lives in the CSR tail (csr_long_segments_kernel / long_rows_combine_kernel write it); slots past n
 // in the last slice and tail slots store nothing, so every element of ax has exactly one writer.
+// (This kernel and sell_cheb_step_kernel keep a slice loop each: one loop shared through the epilogues of ell_rows came out 0.6 % slower
+// on skewed matrices with random gathers -- 20.54 against 20.42 ms, outside the run-to-run band, profiles/sparse_shared_loops.txt.)
 template <int MC>
 __global__ __launch_bounds__(256) void sell_spmm_kernel(int n, int m, int slices, const long long* __restrict__ slice_ptr,
                                                         const int* __restrict__ perm, const int* __restrict__ col,
@@ -1706,72 +1737,58 @@ __global__ __launch_bounds__(256) void long_rows_combine_kernel(int n, int m, in
 // gather of u, three coalesced panel reads and one write (32 n m) instead of the 16 n m of the product plus 40 n m of a sweep
 // that combines.  `out` may be the buffer of v (the same thread reads and writes the element); it is never the buffer of u, which
 // other rows gather.  The combination is spelled once, with explicit fused multiply-adds: the same bits from every kernel below.
-struct ChebCoef { double alpha, beta, gamma, eta; };
-__device__ __forceinline__ double cheb_combine(const ChebCoef& k, double u, double v, double x, double au)
+__device__ __forceinline__ double cheb_combine(const dla::ChebStep& k, double u, double v, double x, double au)
 {
   return fma(k.eta, au, fma(k.gamma, x, fma(k.beta, v, k.alpha * u)));
 }
 // ... and the step of the diagonally scaled form (dla_spmm_precnd_cheb_jacobi): the same combination on t = r_i ((A u)_i + fac u_i),
 // with y = x o r in the place of x.  fac enters here, through the product, and not through alpha.  ri is the row's 1 / den_i: the
 // kernels below read it once per row and keep it in a register across the m columns.
-__device__ __forceinline__ double cheb_jacobi_combine(const ChebCoef& k, double fac, double ri, double u, double v, double y, double au)
+__device__ __forceinline__ double cheb_jacobi_combine(const dla::ChebStep& k, double fac, double ri, double u, double v, double y, double au)
 {
   const double t = fma(fac, u, au) * ri;
   return fma(k.eta, t, fma(k.gamma, y, fma(k.beta, v, k.alpha * u)));
 }
 // J: the scaled epilogue; the gather loops of the step kernels are spelled once for both
 template <bool J>
-__device__ __forceinline__ double cheb_epilogue(const ChebCoef& k, double fac, double ri, double u, double v, double x, double au)
+__device__ __forceinline__ double cheb_epilogue(const dla::ChebStep& k, double fac, double ri, double u, double v, double x, double au)
 {
   if constexpr (J) return cheb_jacobi_combine(k, fac, ri, u, v, x, au);
   else return cheb_combine(k, u, v, x, au);
 }
-// ell_spmm_kernel<W> with that epilogue, on the same width ladder.  The three panel reads of a column are issued before the gather
-// loop, so they are in flight while it runs.
-// J = true: x is the panel y = x o r, and fac and r (n doubles) feed the scaled epilogue; J = false reads neither.
+// The step as an epilogue of ell_rows: the three panel reads of an element are issued before the gather loop, so they
+// are in flight while it runs.  J = true: x is the panel y = x o r, and fac and r (n doubles) feed the scaled epilogue -- r_i is
+// read once per row; J = false reads neither.
+template <bool J>
+struct ChebStepEpilogue {
+  dla::ChebStep k;
+  const double *u, *v, *x;
+  double* out;
+  double fac;
+  const double* r;
+  double ri = 0.0;
+  struct Held { double u = 0.0, v = 0.0, x = 0.0; };
+  __device__ __forceinline__ void row(int i) { if constexpr (J) ri = r[i]; }
+  __device__ __forceinline__ Held load(size_t o) const { return Held{u[o], v[o], x[o]}; }
+  __device__ __forceinline__ void store(size_t o, const Held& h, double s) const
+  {
+    __builtin_nontemporal_store(cheb_epilogue<J>(k, fac, ri, h.u, h.v, h.x, s), out + o);
+  }
+};
+// ell_spmm_kernel<W> with that epilogue, on the same width ladder
 template <int W, bool J>
 __global__ __launch_bounds__(256) void ell_cheb_step_kernel(int n, int m, int w, const int* __restrict__ col,
-                                                            const double* __restrict__ val, ChebCoef k, const double* u,
+                                                            const double* __restrict__ val, dla::ChebStep k, const double* u,
                                                             const double* v, const double* x, double* out, double fac,
                                                             const double* __restrict__ r)
 {
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    double ri = 0.0;
-    if constexpr (J) ri = r[i];
-    if constexpr (W > 0) {
-      int cj[W]; double vj[W];
-#pragma unroll
-      for (int q = 0; q < W; ++q) {
-        const bool in = q < w;
-        cj[q] = in ? col[(size_t)q * n + i] : i;
-        vj[q] = in ? val[(size_t)q * n + i] : 0.0;
-      }
-      for (int c = 0; c < m; ++c) {
-        const size_t o = (size_t)c * n + i;
-        const double* uc = u + (size_t)c * n;
-        const double ui = u[o], vi = v[o], xi = x[o];
-        double s = 0.0;
-#pragma unroll
-        for (int q = 0; q < W; ++q) s += vj[q] * uc[cj[q]];
-        __builtin_nontemporal_store(cheb_epilogue<J>(k, fac, ri, ui, vi, xi, s), out + o);
-      }
-    } else {
-      for (int c = 0; c < m; ++c) {
-        const size_t o = (size_t)c * n + i;
-        const double* uc = u + (size_t)c * n;
-        const double ui = u[o], vi = v[o], xi = x[o];
-        double s = 0.0;
-        for (int q = 0; q < w; ++q) s += val[(size_t)q * n + i] * uc[col[(size_t)q * n + i]];
-        __builtin_nontemporal_store(cheb_epilogue<J>(k, fac, ri, ui, vi, xi, s), out + o);
-      }
-    }
-  }
+  ell_rows<W>(n, m, w, col, val, GatherPlain{u, n}, ChebStepEpilogue<J>{k, u, v, x, out, fac, r});
 }
 // sell_spmm_kernel<MC> with the same epilogue for the rows of the slices; tail slots and slots past n store nothing
 template <int MC, bool J>
 __global__ __launch_bounds__(256) void sell_cheb_step_kernel(int n, int m, int slices, const long long* __restrict__ slice_ptr,
                                                              const int* __restrict__ perm, const int* __restrict__ col,
-                                                             const double* __restrict__ val, ChebCoef kc, const double* u,
+                                                             const double* __restrict__ val, dla::ChebStep kc, const double* u,
                                                              const double* v, const double* x, double* out, double fac,
                                                              const double* __restrict__ r)
 {
@@ -1822,7 +1839,7 @@ __global__ __launch_bounds__(256) void sell_cheb_step_kernel(int n, int m, int s
 // the rows of the CSR tail: csr_long_segments_kernel / long_rows_combine_kernel have left (A u)[row] in the scratch panel au; one
 // thread per (tail row, column) forms the combination for those rows only
 template <bool J>
-__global__ __launch_bounds__(256) void tail_cheb_combine_kernel(int n, int m, int nlong, const int* __restrict__ long_row, ChebCoef k,
+__global__ __launch_bounds__(256) void tail_cheb_combine_kernel(int n, int m, int nlong, const int* __restrict__ long_row, dla::ChebStep k,
                                                                 const double* u, const double* v, const double* x,
                                                                 const double* __restrict__ au, double* out, double fac,
                                                                 const double* __restrict__ r)
@@ -1838,14 +1855,14 @@ __global__ __launch_bounds__(256) void tail_cheb_combine_kernel(int n, int m, in
   }
 }
 // the un-fused step (A/B comparand, Knobs::cheb_unfused): the product kernel has written A u to the panel au; one sweep combines
-__global__ __launch_bounds__(256) void cheb_combine_kernel(size_t total, ChebCoef k, const double* u, const double* v, const double* x,
+__global__ __launch_bounds__(256) void cheb_combine_kernel(size_t total, dla::ChebStep k, const double* u, const double* v, const double* x,
                                                            const double* __restrict__ au, double* out)
 {
   for (size_t o = (size_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (size_t)gridDim.x * 256)
     out[o] = cheb_combine(k, u[o], v[o], x[o], au[o]);
 }
 // ... of the scaled form: one thread per row, r_i in a register across the m columns
-__global__ __launch_bounds__(256) void cheb_jacobi_combine_kernel(int n, int m, ChebCoef k, double fac, const double* __restrict__ r,
+__global__ __launch_bounds__(256) void cheb_jacobi_combine_kernel(int n, int m, dla::ChebStep k, double fac, const double* __restrict__ r,
                                                                   const double* u, const double* v, const double* y,
                                                                   const double* __restrict__ au, double* out)
 {
@@ -2202,38 +2219,23 @@ __global__ __launch_bounds__(256) void lr_precnd_kernel(int n, int m, int varian
 // [last `halo` rows of the previous rank | the shard's n rows | first `halo` rows of the next rank]; the two halo pieces have
 // arrived through the small-product all-reduce (halo_pack_kernel: every rank fills its own two slots of a zeroed buffer, the sum
 // gathers).  Only the wavefronts at the two ends of the shard ever take the halo branches.
+struct GatherHalo {
+  const double *x, *prev, *next; int n, halo;
+  struct Column { const double *pc, *xc, *nc; int n, halo; };
+  __device__ __forceinline__ int self(int i) const { return i + halo; }
+  __device__ __forceinline__ Column column(int c) const { return Column{prev + (size_t)c * halo, x + (size_t)c * n, next + (size_t)c * halo, n, halo}; }
+  __device__ __forceinline__ static double at(const Column& k, int idx)
+  {
+    return idx < k.halo ? k.pc[idx] : (idx < k.halo + k.n ? k.xc[idx - k.halo] : k.nc[idx - k.halo - k.n]);
+  }
+};
 template <int W>
 __global__ __launch_bounds__(256) void ell_spmm_halo_kernel(int n, int m, int w, int halo, const int* __restrict__ col,
                                                             const double* __restrict__ val, const double* __restrict__ x,
                                                             const double* __restrict__ prev, const double* __restrict__ next,
                                                             double* __restrict__ ax)
 {
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    constexpr int WW = W > 0 ? W : 1;
-    int cj[WW]; double vj[WW];
-    if constexpr (W > 0) {
-#pragma unroll
-      for (int q = 0; q < W; ++q) {
-        const bool in = q < w;
-        cj[q] = in ? col[(size_t)q * n + i] : i + halo;
-        vj[q] = in ? val[(size_t)q * n + i] : 0.0;
-      }
-    }
-    for (int c = 0; c < m; ++c) {
-      const double* xc = x + (size_t)c * n;
-      const double* pc = prev + (size_t)c * halo;
-      const double* nc = next + (size_t)c * halo;
-      double s = 0.0;
-      auto fetch = [&](int idx) -> double { return idx < halo ? pc[idx] : (idx < halo + n ? xc[idx - halo] : nc[idx - halo - n]); };
-      if constexpr (W > 0) {
-#pragma unroll
-        for (int q = 0; q < W; ++q) s += vj[q] * fetch(cj[q]);
-      } else {
-        for (int q = 0; q < w; ++q) s += val[(size_t)q * n + i] * fetch(col[(size_t)q * n + i]);
-      }
-      __builtin_nontemporal_store(s, ax + (size_t)c * n + i);
-    }
-  }
+  ell_rows<W>(n, m, w, col, val, GatherHalo{x, prev, next, n, halo}, StoreProduct{ax});
 }
 
 // buf[((r * 2 + side) * m + c) * halo + h]: side 0 = the first, side 1 = the last `halo` rows of rank r's x; this rank's slots
@@ -5949,6 +5951,24 @@ struct HipEngine : dla::Engine {
     DeviceBuffer<double> long_part;    // partial sums of the rows of more than one segment: multi_segments x m, grown by the product
     // what only a refresh of the values reads (refresh_dev): the caller's row pointers [n + 1] and the tail rows' offsets [long_rows + 1]
     DeviceBuffer<long long> rowptr, long_ptr;
+    // The device view: the typed const pointers the product kernels read, with their counts.  The tail's entries follow the slices' in
+    // the shared blocks: that offset is formed here and nowhere else.
+    struct Ell { int w; const int* col; const double* val; };
+    struct Slices { int count; const long long* ptr; const int *perm, *col; const double* val; };
+    struct Tail {
+      int rows, segments, multi_rows;
+      const long long *long_ptr, *seg_ptr;
+      const int *long_row, *seg_row, *seg_part, *multi_row, *part_ptr, *col;
+      const double* val;
+    };
+    Ell ell() const { return {w, col, val}; }
+    Slices slices() const { return {sell_slices, sell_ptr, sell_perm, col, val}; }
+    Tail tail() const
+    {
+      return {sell_long_rows, sell_long_segments, sell_multi_rows, long_ptr, seg_ptr, long_row, seg_row, seg_part, multi_row, part_ptr,
+              col + sell_stored, val + sell_stored};
+    }
+    const double* diagonal() const { return diag; }
     // give the device blocks back (the caller has waited for the stream)
     void drop()
     {
@@ -6316,26 +6336,36 @@ struct HipEngine : dla::Engine {
     if (first <= dla::SPMM_A && dla::SPMM_A <= last) cheb.upper_valid = cheb.off_valid = false;
     return DLA_OK;
   }
-  // slices kernel, segments kernel, combine kernel; p: the tail's launch shapes and workspace (long_rows_plan)
-  int op_matvec_sell(SparseOp& op, const LongRowsPlan& p, int n, int m, const double* x, double* ax)
+  // The ELLPACK width ladder, spelled once for the product, the Chebyshev step and the product on a row shard: launch(W) for the
+  // narrowest instance that keeps w (column, value) pairs in registers; W = 0 loops over any width.
+  static constexpr int ELL_WIDTHS[] = {4, 8, 16, 32, 0};
+  template <class F>
+  static void ell_width(int w, F&& launch)
   {
-    const int cap = ncu * 8;
+    first_instance<std::size(ELL_WIDTHS)>([&](auto i) {
+      constexpr int W = ELL_WIDTHS[decltype(i)::value];
+      if (W > 0 && w > W) return false;
+      launch(std::integral_constant<int, W>{});
+      return true;
+    });
+  }
+  // The tail of a sliced product, dst[tail rows] = (the tail of op) x: the segments kernel and, for the rows of more than one segment,
+  // the combine kernel; p: their launch shapes and workspace (long_rows_plan).  Runs behind the slices' kernel on the stream.
+  int tail_product(SparseOp& op, const LongRowsPlan& p, int n, int m, const double* x, double* dst)
+  {
     if (p.part_doubles > op.long_part.capacity()) {
       HIPCHK(hipStreamSynchronize(st));       // (queued products may still use the old block)
       HIPCHK(op.long_part.reserve(p.part_doubles));
     }
-    DLA_LAUNCH((sell_spmm_kernel<SELL_MC>), dim3(std::max(1, std::min(cap, (op.sell_slices + 3) / 4))), dim3(256), 0, st, n, m, op.sell_slices,
-               (const long long*)op.sell_ptr, (const int*)op.sell_perm, (const int*)op.col, (const double*)op.val, x, ax);
-    HIPCHK(hipGetLastError());
-    if (op.sell_long_segments > 0) {
-      DLA_LAUNCH((csr_long_segments_kernel<LONG_MC>), dim3(p.seg_blocks), dim3(256), 0, st, n, m, op.sell_long_segments, (const long long*)op.seg_ptr,
-                 (const int*)op.seg_row, (const int*)op.seg_part, (const int*)op.long_row, (const int*)op.col + op.sell_stored,
-                 (const double*)op.val + op.sell_stored, x, ax, (double*)op.long_part);
+    const SparseOp::Tail t = op.tail();
+    double* part = op.long_part;
+    if (t.segments > 0) {
+      DLA_LAUNCH((csr_long_segments_kernel<LONG_MC>), dim3(p.seg_blocks), dim3(256), 0, st, n, m, t.segments, t.seg_ptr, t.seg_row, t.seg_part,
+                 t.long_row, t.col, t.val, x, dst, part);
       HIPCHK(hipGetLastError());
     }
     if (p.combine_blocks > 0) {
-      DLA_LAUNCH(long_rows_combine_kernel, dim3(p.combine_blocks), dim3(256), 0, st, n, m, op.sell_multi_rows, (const int*)op.multi_row,
-                 (const int*)op.part_ptr, (const double*)op.long_part, ax);
+      DLA_LAUNCH(long_rows_combine_kernel, dim3(p.combine_blocks), dim3(256), 0, st, n, m, t.multi_rows, t.multi_row, t.part_ptr, (const double*)part, dst);
       HIPCHK(hipGetLastError());
     }
     return DLA_OK;
@@ -6348,13 +6378,15 @@ struct HipEngine : dla::Engine {
       // (the partial sums are written once and read once)
       Scope s(this, DLA_OP_MATVEC, 12.0 * (double)(op.sell_stored + op.sell_long_entries) + 4.0 * n + 16.0 * (double)n * m + 16.0 * (double)p.part_doubles,
               2.0 * (double)op.nnz * m, op.sell_long_segments > 0 ? p.name() : std::string());
-      return op_matvec_sell(op, p, n, m, x, ax);
+      const SparseOp::Slices sl = op.slices();
+      DLA_LAUNCH((sell_spmm_kernel<SELL_MC>), dim3(grid_blocks(env(), sl.count, 4)), dim3(256), 0, st, n, m, sl.count, sl.ptr, sl.perm, sl.col, sl.val, x, ax);
+      HIPCHK(hipGetLastError());
+      return tail_product(op, p, n, m, x, ax);
     }
     Scope s(this, DLA_OP_MATVEC, 12.0 * (double)op.w * n + 16.0 * (double)n * m, 2.0 * (double)op.w * n * m);
-    const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
-#define ELL(W) DLA_LAUNCH((ell_spmm_kernel<W>), dim3(blocks), dim3(256), 0, st, n, m, op.w, (const int*)op.col, (const double*)op.val, x, ax)
-    if (op.w <= 4) ELL(4); else if (op.w <= 8) ELL(8); else if (op.w <= 16) ELL(16); else if (op.w <= 32) ELL(32); else ELL(0);
-#undef ELL
+    const SparseOp::Ell e = op.ell();
+    const dim3 grid(grid_blocks(env(), n, 256));
+    ell_width(e.w, [&](auto W) { DLA_LAUNCH((ell_spmm_kernel<decltype(W)::value>), grid, dim3(256), 0, st, n, m, e.w, e.col, e.val, x, ax); });
     HIPCHK(hipGetLastError());
     return DLA_OK;
   }
@@ -6430,7 +6462,8 @@ struct HipEngine : dla::Engine {
   int spmm_matvec_sharded(int n, int m, const double* x, double* ax)
   {
     const int nr = std::max(1, nranks), H = shard.halo;
-    const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
+    const SparseOp::Ell e = ops[dla::SPMM_A].ell();
+    const dim3 grid(grid_blocks(env(), n, 256));
     // columns per exchange: a mailbox slot of the peer-to-peer transport holds P2P_MAX_DOUBLES
     int mc = m;
     if (H > 0 && nr > 1) mc = std::max(1, std::min(m, P2P_MAX_DOUBLES / (nr * 2 * H)));
@@ -6457,9 +6490,9 @@ struct HipEngine : dla::Engine {
       // (the first / last rank never index their missing neighbour: any valid address serves)
       const double* prev = shard.d_halo + (size_t)((rank > 0 ? (rank - 1) * 2 + 1 : 0) * mcur) * H;
       const double* next = shard.d_halo + (size_t)((rank + 1 < nr ? (rank + 1) * 2 : 0) * mcur) * H;
-#define ELLH(W) DLA_LAUNCH((ell_spmm_halo_kernel<W>), dim3(blocks), dim3(256), 0, st, n, mcur, ops[dla::SPMM_A].w, H, (const int*)ops[dla::SPMM_A].col, (const double*)ops[dla::SPMM_A].val, xc, prev, next, ax + (size_t)c0 * n)
-      if (ops[dla::SPMM_A].w <= 4) ELLH(4); else if (ops[dla::SPMM_A].w <= 8) ELLH(8); else if (ops[dla::SPMM_A].w <= 16) ELLH(16); else if (ops[dla::SPMM_A].w <= 32) ELLH(32); else ELLH(0);
-#undef ELLH
+      ell_width(e.w, [&](auto W) {
+        DLA_LAUNCH((ell_spmm_halo_kernel<decltype(W)::value>), grid, dim3(256), 0, st, n, mcur, e.w, H, e.col, e.val, xc, prev, next, ax + (size_t)c0 * n);
+      });
       HIPCHK(hipGetLastError());
     }
     return DLA_OK;
@@ -6488,8 +6521,7 @@ struct HipEngine : dla::Engine {
   {
     if (n != ops[dla::SPMM_A].n || !ops[dla::SPMM_A].diag) { err = "spmm_precnd: n differs from setup"; return DLA_ERR_ARG; }
     Scope s(this, DLA_OP_PRECND, 8.0 * n * (2.0 * m + 1.0), (double)n * m);
-    const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
-    DLA_LAUNCH(diag_precnd_kernel, dim3(blocks), dim3(256), 0, st, n, m, fac, (const double*)ops[dla::SPMM_A].diag, x, px);
+    DLA_LAUNCH(diag_precnd_kernel, dim3(grid_blocks(env(), n, 256)), dim3(256), 0, st, n, m, fac, ops[dla::SPMM_A].diagonal(), x, px);
     HIPCHK(hipGetLastError());
     return DLA_OK;
   }
@@ -6501,8 +6533,7 @@ struct HipEngine : dla::Engine {
     if (ops[dla::SPMM_A].n != ops[dla::SPMM_B].n) { err = "spmm_precnd_pencil: the operator has " + std::to_string(ops[dla::SPMM_A].n) + " rows and the metric " + std::to_string(ops[dla::SPMM_B].n); return DLA_ERR_ARG; }
     if (n != ops[dla::SPMM_A].n) { err = "spmm_precnd_pencil: n differs from setup"; return DLA_ERR_ARG; }
     Scope s(this, DLA_OP_PRECND, 16.0 * (double)n * m + 16.0 * (double)n, 2.0 * (double)n * m);
-    const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
-    DLA_LAUNCH(pencil_precnd_kernel, dim3(blocks), dim3(256), 0, st, n, m, fac, (const double*)ops[dla::SPMM_A].diag, (const double*)ops[dla::SPMM_B].diag, x, px);
+    DLA_LAUNCH(pencil_precnd_kernel, dim3(grid_blocks(env(), n, 256)), dim3(256), 0, st, n, m, fac, ops[dla::SPMM_A].diagonal(), ops[dla::SPMM_B].diagonal(), x, px);
     HIPCHK(hipGetLastError());
     return DLA_OK;
   }
@@ -6544,42 +6575,53 @@ struct HipEngine : dla::Engine {
     cheb.steps = steps; cheb.lo_fraction = lo_fraction;
     return DLA_OK;
   }
+  // The three Gershgorin kernels on the rows of op: a wavefront per slice and per tail row under 4 blocks per compute unit, a thread
+  // per ELLPACK row under 8.  ROWS = false: the block maxima go to partial, *count of them; ROWS = true: the row sums go to off.
+  template <bool ROWS>
+  int gershgorin(const SparseOp& op, double* partial, double* off, int* count = nullptr)
+  {
+    int b0 = 0, b1 = 0;
+    if (op.fmt == DLA_SPMM_SELL) {
+      const SparseOp::Slices sl = op.slices();
+      const SparseOp::Tail t = op.tail();
+      b0 = grid_blocks(env(), sl.count, 4, 4);
+      DLA_LAUNCH(sell_gershgorin_kernel<ROWS>, dim3(b0), dim3(256), 0, st, op.n, sl.count, sl.ptr, sl.perm, sl.col, sl.val, op.diagonal(), partial, off);
+      HIPCHK(hipGetLastError());
+      if (t.rows > 0) {
+        b1 = grid_blocks(env(), t.rows, 4, 4);
+        DLA_LAUNCH(tail_gershgorin_kernel<ROWS>, dim3(b1), dim3(256), 0, st, t.rows, t.long_ptr, t.long_row, t.col, t.val, op.diagonal(),
+                   ROWS ? partial : partial + b0, off);
+        HIPCHK(hipGetLastError());
+      }
+    } else {
+      const SparseOp::Ell e = op.ell();
+      b0 = grid_blocks(env(), op.n, 256);
+      DLA_LAUNCH(ell_gershgorin_kernel<ROWS>, dim3(b0), dim3(256), 0, st, op.n, e.w, e.col, e.val, op.diagonal(), partial, off);
+      HIPCHK(hipGetLastError());
+    }
+    if (count) *count = b0 + b1;
+    return DLA_OK;
+  }
+  // the maximum of `count` block maxima, taken on the host behind what is queued on the stream (one host wait)
+  int max_of_blocks(const double* buffer, int count, double* g)
+  {
+    std::vector<double> h((size_t)count);
+    HIPCHK(hipMemcpyAsync(h.data(), buffer, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *g = *std::max_element(h.begin(), h.end());
+    return DLA_OK;
+  }
   // g of the stored A (single rank), from the blocks: at most ncu x 8 block maxima come to the host.  Synchronous, once per stored
   // matrix; like the set-up kernels it is not booked into the statistics.
   int cheb_upper()
   {
     if (cheb.upper_valid) return DLA_OK;
-    SparseOp& op = ops[dla::SPMM_A];
     bind();
-    const bool sell = op.fmt == DLA_SPMM_SELL;
-    const int cap = std::max(1, ncu * 4);
-    const int b0 = sell ? std::max(1, std::min(cap, (op.sell_slices + 3) / 4)) : std::max(1, std::min(2 * cap, (op.n + 255) / 256));
-    const int b1 = sell && op.sell_long_rows > 0 ? std::max(1, std::min(cap, (op.sell_long_rows + 3) / 4)) : 0;
-    if ((size_t)(b0 + b1) > cheb.partial.capacity()) {
-      HIPCHK(hipStreamSynchronize(st));
-      HIPCHK(cheb.partial.reserve((size_t)2 * cap));
-    }
-    if (sell) {
-      DLA_LAUNCH(sell_gershgorin_kernel<false>, dim3(b0), dim3(256), 0, st, op.n, op.sell_slices, (const long long*)op.sell_ptr, (const int*)op.sell_perm,
-                 (const int*)op.col, (const double*)op.val, (const double*)op.diag, (double*)cheb.partial, (double*)nullptr);
-      HIPCHK(hipGetLastError());
-      if (b1 > 0) {
-        DLA_LAUNCH(tail_gershgorin_kernel<false>, dim3(b1), dim3(256), 0, st, op.sell_long_rows, (const long long*)op.long_ptr, (const int*)op.long_row,
-                   (const int*)op.col + op.sell_stored, (const double*)op.val + op.sell_stored, (const double*)op.diag, (double*)cheb.partial + b0,
-                   (double*)nullptr);
-        HIPCHK(hipGetLastError());
-      }
-    } else {
-      DLA_LAUNCH(ell_gershgorin_kernel<false>, dim3(b0), dim3(256), 0, st, op.n, op.w, (const int*)op.col, (const double*)op.val, (const double*)op.diag,
-                 (double*)cheb.partial, (double*)nullptr);
-      HIPCHK(hipGetLastError());
-    }
-    std::vector<double> h((size_t)(b0 + b1));
-    HIPCHK(hipMemcpyAsync(h.data(), (const double*)cheb.partial, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    double g = h[0];
-    for (size_t j = 1; j < h.size(); ++j) g = std::max(g, h[j]);
-    cheb.upper = g; cheb.upper_valid = true;
+    int count = 0;
+    { const int stc = cheb_panel(cheb.partial, (size_t)grid_cap(env())); if (stc) return stc; }
+    { const int stc = gershgorin<false>(ops[dla::SPMM_A], cheb.partial, nullptr, &count); if (stc) return stc; }
+    { const int stc = max_of_blocks(cheb.partial, count, &cheb.upper); if (stc) return stc; }
+    cheb.upper_valid = true;
     return DLA_OK;
   }
   // what both entries refuse first; who: the entry's name
@@ -6609,21 +6651,16 @@ struct HipEngine : dla::Engine {
   // J: the step of the scaled form, where x is the panel y = x o r and r = cheb.r; booked under its own kernel names with the 8 n
   // bytes of r and the 3 n m flops of the scaling on top
   template <bool J>
-  int cheb_step(SparseOp& op, int n, int m, const ChebCoef& k, const double* u, const double* v, const double* x, double* out, double fac = 0.0)
+  int cheb_step(SparseOp& op, int n, int m, const dla::ChebStep& k, const double* u, const double* v, const double* x, double* out, double fac)
   {
     const double nm = (double)n * m, rb = J ? 8.0 * n : 0.0, cf = (J ? 10.0 : 7.0) * nm;
-    const double* r = J ? (const double*)cheb.r : nullptr;
+    const double *r = J ? (const double*)cheb.r : nullptr, *au = cheb.au;
     if (knobs.cheb_unfused()) {
       { const int stc = op_matvec(op, n, m, u, cheb.au); if (stc) return stc; }
       Scope s(this, DLA_OP_PRECND, 40.0 * nm + rb, cf, J ? "cheb_jacobi_combine_kernel" : "cheb_combine_kernel");
       const size_t total = (size_t)n * m;
-      if constexpr (J) {
-        DLA_LAUNCH(cheb_jacobi_combine_kernel, dim3(std::max(1, std::min(ncu * 8, (n + 255) / 256))), dim3(256), 0, st, n, m, k, fac, r, u, v, x,
-                   (const double*)cheb.au, out);
-      } else {
-        const int blocks = (int)std::max((size_t)1, std::min((size_t)ncu * 8, (total + 255) / 256));
-        DLA_LAUNCH(cheb_combine_kernel, dim3(blocks), dim3(256), 0, st, total, k, u, v, x, (const double*)cheb.au, out);
-      }
+      if constexpr (J) DLA_LAUNCH(cheb_jacobi_combine_kernel, dim3(grid_blocks(env(), n, 256)), dim3(256), 0, st, n, m, k, fac, r, u, v, x, au, out);
+      else DLA_LAUNCH(cheb_combine_kernel, dim3(grid_blocks(env(), (long long)total, 256)), dim3(256), 0, st, total, k, u, v, x, au, out);
       HIPCHK(hipGetLastError());
       return DLA_OK;
     }
@@ -6633,76 +6670,84 @@ struct HipEngine : dla::Engine {
       Scope s(this, DLA_OP_PRECND, 12.0 * (double)(op.sell_stored + op.sell_long_entries) + 4.0 * n + 32.0 * nm + 16.0 * (double)p.part_doubles +
                                        16.0 * (double)op.sell_long_rows * m + rb,
               2.0 * (double)op.nnz * m + cf, J ? "sell_cheb_jacobi_step_kernel" : "sell_cheb_step_kernel");
-      if (p.part_doubles > op.long_part.capacity()) {
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(op.long_part.reserve(p.part_doubles));
-      }
-      DLA_LAUNCH((sell_cheb_step_kernel<SELL_MC, J>), dim3(std::max(1, std::min(ncu * 8, (op.sell_slices + 3) / 4))), dim3(256), 0, st, n, m, op.sell_slices,
-                 (const long long*)op.sell_ptr, (const int*)op.sell_perm, (const int*)op.col, (const double*)op.val, k, u, v, x, out, fac, r);
+      const SparseOp::Slices sl = op.slices();
+      DLA_LAUNCH((sell_cheb_step_kernel<SELL_MC, J>), dim3(grid_blocks(env(), sl.count, 4)), dim3(256), 0, st, n, m, sl.count, sl.ptr, sl.perm, sl.col,
+                 sl.val, k, u, v, x, out, fac, r);
       HIPCHK(hipGetLastError());
       if (op.sell_long_segments > 0) {
-        DLA_LAUNCH((csr_long_segments_kernel<LONG_MC>), dim3(p.seg_blocks), dim3(256), 0, st, n, m, op.sell_long_segments, (const long long*)op.seg_ptr,
-                   (const int*)op.seg_row, (const int*)op.seg_part, (const int*)op.long_row, (const int*)op.col + op.sell_stored,
-                   (const double*)op.val + op.sell_stored, u, (double*)cheb.au, (double*)op.long_part);
-        HIPCHK(hipGetLastError());
-        if (p.combine_blocks > 0) {
-          DLA_LAUNCH(long_rows_combine_kernel, dim3(p.combine_blocks), dim3(256), 0, st, n, m, op.sell_multi_rows, (const int*)op.multi_row,
-                     (const int*)op.part_ptr, (const double*)op.long_part, (double*)cheb.au);
-          HIPCHK(hipGetLastError());
-        }
-        const long long total = (long long)op.sell_long_rows * m;
-        DLA_LAUNCH(tail_cheb_combine_kernel<J>, dim3((int)std::max(1LL, std::min((long long)ncu * 8, (total + 255) / 256))), dim3(256), 0, st, n, m,
-                   op.sell_long_rows, (const int*)op.long_row, k, u, v, x, (const double*)cheb.au, out, fac, r);
+        // (A u) of the tail rows to the scratch panel, then their combination
+        { const int stc = tail_product(op, p, n, m, u, cheb.au); if (stc) return stc; }
+        const SparseOp::Tail t = op.tail();
+        DLA_LAUNCH(tail_cheb_combine_kernel<J>, dim3(grid_blocks(env(), (long long)t.rows * m, 256)), dim3(256), 0, st, n, m, t.rows, t.long_row, k, u, v, x,
+                   au, out, fac, r);
         HIPCHK(hipGetLastError());
       }
       return DLA_OK;
     }
     Scope s(this, DLA_OP_PRECND, 12.0 * (double)op.w * n + 32.0 * nm + rb, 2.0 * (double)op.w * nm + cf,
             J ? "ell_cheb_jacobi_step_kernel" : "ell_cheb_step_kernel");
-    const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
-#define ELLC(W) DLA_LAUNCH((ell_cheb_step_kernel<W, J>), dim3(blocks), dim3(256), 0, st, n, m, op.w, (const int*)op.col, (const double*)op.val, k, u, v, x, out, fac, r)
-    if (op.w <= 4) ELLC(4); else if (op.w <= 8) ELLC(8); else if (op.w <= 16) ELLC(16); else if (op.w <= 32) ELLC(32); else ELLC(0);
-#undef ELLC
+    const SparseOp::Ell e = op.ell();
+    const dim3 grid(grid_blocks(env(), n, 256));
+    ell_width(e.w, [&](auto W) {
+      DLA_LAUNCH((ell_cheb_step_kernel<decltype(W)::value, J>), grid, dim3(256), 0, st, n, m, e.w, e.col, e.val, k, u, v, x, out, fac, r);
+    });
     HIPCHK(hipGetLastError());
     return DLA_OK;
   }
-  int spmm_precnd_cheb(int n, int m, double fac, const double* x, double* px) override
+  // What the two entries share, once.  J: the scaled form.  interval(&hi, &shift) leaves the upper end of the entry's interval and the
+  // shift its coefficients take; first(cf, &y) launches the entry's own sweep -- with one step the whole polynomial, written to px --
+  // and leaves in y the panel that stands in the place of x in the recurrence.
+  template <bool J, class Interval, class First>
+  int cheb_apply(const char* who, int n, int m, double fac, const double* x, double* px, Interval&& interval, First&& first)
   {
-    const char* who = "spmm_precnd_cheb";
     { const int stc = cheb_admit(who); if (stc) return stc; }
     SparseOp& op = ops[dla::SPMM_A];
     if (n != op.n) { err = std::string(who) + ": n = " + std::to_string(n) + " differs from the " + std::to_string(op.n) + " rows of the operator"; return DLA_ERR_ARG; }
     if (m <= 0) return DLA_OK;
-    { const int stc = cheb_upper(); if (stc) return stc; }
     const int d = cheb.steps;
-    const double hi = cheb.upper + fac, lo = cheb.lo_fraction * hi, nm = (double)n * m;
     const size_t total = (size_t)n * m;
+    // every buffer of the call before its first launch: a growing one waits for the stream
+    if (J && d >= 2) { const int stc = cheb_panel(cheb.y, total); if (stc) return stc; }
+    if (d >= 3) { const int stc = cheb_panel(cheb.z[0], total); if (stc) return stc; }
+    if (d >= 4) { const int stc = cheb_panel(cheb.z[1], total); if (stc) return stc; }
+    if (d >= 2 && (knobs.cheb_unfused() || (op.fmt == DLA_SPMM_SELL && op.sell_long_segments > 0))) { const int stc = cheb_panel(cheb.au, total); if (stc) return stc; }
+    double hi = 0.0, shift = 0.0;
+    { const int stc = interval(&hi, &shift); if (stc) return stc; }
     if (hi <= 1.0e-5) {       // (the harness' guard on the interval's upper end: px = x)
-      Scope s(this, DLA_OP_PRECND, 16.0 * nm, 0.0, "cheb_identity_copy");
+      Scope s(this, DLA_OP_PRECND, 16.0 * (double)n * m, 0.0, "cheb_identity_copy");
       if (!lc.dry) HIPCHK(hipMemcpyAsync(px, x, sizeof(double) * total, hipMemcpyDeviceToDevice, st));
       return DLA_OK;
     }
-    const dla::ChebCoefficients cf = dla::cheb_coefficients(hi, lo, fac, d);
-    if (d == 1) {
-      Scope s(this, DLA_OP_PRECND, 16.0 * nm, nm, "cheb_scale_kernel");
-      const int blocks = (int)std::max((size_t)1, std::min((size_t)ncu * 8, (total + 255) / 256));
-      DLA_LAUNCH(cheb_scale_kernel, dim3(blocks), dim3(256), 0, st, total, cf.theta, x, px);
-      HIPCHK(hipGetLastError());
-      return DLA_OK;
-    }
+    const dla::ChebCoefficients cf = dla::cheb_coefficients(hi, cheb.lo_fraction * hi, shift, d);
+    const double* y = x;
+    { const int stc = first(cf, &y); if (stc) return stc; }
     // step k writes z_{k+1}: to px when it is the last, else to z[(k - 1) & 1], which held z_{k-1}
-    if (d >= 3) { const int stc = cheb_panel(cheb.z[0], total); if (stc) return stc; }
-    if (d >= 4) { const int stc = cheb_panel(cheb.z[1], total); if (stc) return stc; }
-    if (knobs.cheb_unfused() || (op.fmt == DLA_SPMM_SELL && op.sell_long_segments > 0)) { const int stc = cheb_panel(cheb.au, total); if (stc) return stc; }
     for (int k = 1; k < d; ++k) {
-      const dla::ChebStep& c = cf.steps[(size_t)k - 1];
-      const double* u = k == 1 ? x : (const double*)cheb.z[(k - 2) & 1];
-      const double* v = k <= 2 ? x : (const double*)cheb.z[(k - 1) & 1];
+      const double* u = k == 1 ? y : (const double*)cheb.z[(k - 2) & 1];
+      const double* v = k <= 2 ? y : (const double*)cheb.z[(k - 1) & 1];
       double* out = k == d - 1 ? px : (double*)cheb.z[(k - 1) & 1];
-      const int stc = cheb_step<false>(op, n, m, ChebCoef{c.alpha, c.beta, c.gamma, c.eta}, u, v, x, out);
+      const int stc = cheb_step<J>(op, n, m, cf.steps[(size_t)k - 1], u, v, y, out, J ? fac : 0.0);
       if (stc) return stc;
     }
     return DLA_OK;
+  }
+  int spmm_precnd_cheb(int n, int m, double fac, const double* x, double* px) override
+  {
+    return cheb_apply<false>(
+        "spmm_precnd_cheb", n, m, fac, x, px,
+        [&](double* hi, double* shift) -> int {
+          const int stc = cheb_upper();
+          *hi = cheb.upper + fac; *shift = fac;
+          return stc;
+        },
+        [&](const dla::ChebCoefficients& cf, const double**) -> int {
+          if (cheb.steps > 1) return DLA_OK;
+          const size_t total = (size_t)n * m;
+          Scope s(this, DLA_OP_PRECND, 16.0 * (double)n * m, (double)n * m, "cheb_scale_kernel");
+          DLA_LAUNCH(cheb_scale_kernel, dim3(grid_blocks(env(), (long long)total, 256)), dim3(256), 0, st, total, cf.theta, x, px);
+          HIPCHK(hipGetLastError());
+          return DLA_OK;
+        });
   }
 
   // ---- ... and on the diagonally scaled operator D^-1 (A + fac I), D = |diag(A) + fac| (the contract: include/diaglib_amd.h,
@@ -6714,23 +6759,7 @@ struct HipEngine : dla::Engine {
     SparseOp& op = ops[dla::SPMM_A];
     bind();
     { const int stc = cheb_panel(cheb.off, (size_t)op.n); if (stc) return stc; }
-    const int cap = std::max(1, ncu * 4);
-    if (op.fmt == DLA_SPMM_SELL) {
-      DLA_LAUNCH(sell_gershgorin_kernel<true>, dim3(std::max(1, std::min(cap, (op.sell_slices + 3) / 4))), dim3(256), 0, st, op.n, op.sell_slices,
-                 (const long long*)op.sell_ptr, (const int*)op.sell_perm, (const int*)op.col, (const double*)op.val, (const double*)op.diag,
-                 (double*)nullptr, (double*)cheb.off);
-      HIPCHK(hipGetLastError());
-      if (op.sell_long_rows > 0) {
-        DLA_LAUNCH(tail_gershgorin_kernel<true>, dim3(std::max(1, std::min(cap, (op.sell_long_rows + 3) / 4))), dim3(256), 0, st, op.sell_long_rows,
-                   (const long long*)op.long_ptr, (const int*)op.long_row, (const int*)op.col + op.sell_stored, (const double*)op.val + op.sell_stored,
-                   (const double*)op.diag, (double*)nullptr, (double*)cheb.off);
-        HIPCHK(hipGetLastError());
-      }
-    } else {
-      DLA_LAUNCH(ell_gershgorin_kernel<true>, dim3(std::max(1, std::min(2 * cap, (op.n + 255) / 256))), dim3(256), 0, st, op.n, op.w, (const int*)op.col,
-                 (const double*)op.val, (const double*)op.diag, (double*)nullptr, (double*)cheb.off);
-      HIPCHK(hipGetLastError());
-    }
+    { const int stc = gershgorin<true>(op, nullptr, cheb.off); if (stc) return stc; }
     cheb.off_valid = true;
     return DLA_OK;
   }
@@ -6741,21 +6770,16 @@ struct HipEngine : dla::Engine {
     const int n = op.n;
     { const int stc = cheb_off(); if (stc) return stc; }
     { const int stc = cheb_panel(cheb.r, (size_t)n); if (stc) return stc; }
-    const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
-    { const int stc = cheb_panel(cheb.partial, (size_t)std::max(ncu * 8, 1)); if (stc) return stc; }
+    const int blocks = grid_blocks(env(), n, 256);
+    { const int stc = cheb_panel(cheb.partial, (size_t)grid_cap(env())); if (stc) return stc; }
     {
       Scope s(this, DLA_OP_PRECND, 24.0 * n, 4.0 * n, "cheb_jacobi_bound_kernel");
-      DLA_LAUNCH(cheb_jacobi_bound_kernel, dim3(blocks), dim3(256), 0, st, n, fac, (const double*)op.diag, (const double*)cheb.off, (double*)cheb.r,
+      DLA_LAUNCH(cheb_jacobi_bound_kernel, dim3(blocks), dim3(256), 0, st, n, fac, op.diagonal(), (const double*)cheb.off, (double*)cheb.r,
                  (double*)cheb.partial);
       HIPCHK(hipGetLastError());
     }
-    std::vector<double> h((size_t)blocks);
-    HIPCHK(hipMemcpyAsync(h.data(), (const double*)cheb.partial, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    { const int stc = max_of_blocks(cheb.partial, blocks, hi); if (stc) return stc; }
     stats.host_syncs++;
-    double g = h[0];
-    for (size_t j = 1; j < h.size(); ++j) g = std::max(g, h[j]);
-    *hi = g;
     return DLA_OK;
   }
   int spmm_cheb_jacobi_upper(double fac, double* hi) override
@@ -6765,45 +6789,20 @@ struct HipEngine : dla::Engine {
   }
   int spmm_precnd_cheb_jacobi(int n, int m, double fac, const double* x, double* px) override
   {
-    const char* who = "spmm_precnd_cheb_jacobi";
-    { const int stc = cheb_admit(who); if (stc) return stc; }
-    SparseOp& op = ops[dla::SPMM_A];
-    if (n != op.n) { err = std::string(who) + ": n = " + std::to_string(n) + " differs from the " + std::to_string(op.n) + " rows of the operator"; return DLA_ERR_ARG; }
-    if (m <= 0) return DLA_OK;
-    const int d = cheb.steps;
-    const double nm = (double)n * m;
-    const size_t total = (size_t)n * m;
-    // every buffer of the call before its first launch: a growing one waits for the stream
-    if (d >= 2) { const int stc = cheb_panel(cheb.y, total); if (stc) return stc; }
-    if (d >= 3) { const int stc = cheb_panel(cheb.z[0], total); if (stc) return stc; }
-    if (d >= 4) { const int stc = cheb_panel(cheb.z[1], total); if (stc) return stc; }
-    if (d >= 2 && (knobs.cheb_unfused() || (op.fmt == DLA_SPMM_SELL && op.sell_long_segments > 0))) { const int stc = cheb_panel(cheb.au, total); if (stc) return stc; }
-    double hi = 0.0;
-    { const int stc = cheb_jacobi_bound(fac, &hi); if (stc) return stc; }
-    if (hi <= 1.0e-5) {       // (the guard of the plain form, on the scaled interval's upper end: px = x)
-      Scope s(this, DLA_OP_PRECND, 16.0 * nm, 0.0, "cheb_identity_copy");
-      if (!lc.dry) HIPCHK(hipMemcpyAsync(px, x, sizeof(double) * total, hipMemcpyDeviceToDevice, st));
-      return DLA_OK;
-    }
-    const dla::ChebCoefficients cf = dla::cheb_coefficients(hi, cheb.lo_fraction * hi, 0.0, d);
-    const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
-    {
-      Scope s(this, DLA_OP_PRECND, 16.0 * nm + 8.0 * n, (d == 1 ? 2.0 : 1.0) * nm, "cheb_jacobi_scale_kernel");
-      if (d == 1) DLA_LAUNCH(cheb_jacobi_scale_kernel<true>, dim3(blocks), dim3(256), 0, st, n, m, cf.theta, (const double*)cheb.r, x, px);
-      else DLA_LAUNCH(cheb_jacobi_scale_kernel<false>, dim3(blocks), dim3(256), 0, st, n, m, cf.theta, (const double*)cheb.r, x, (double*)cheb.y);
-      HIPCHK(hipGetLastError());
-    }
-    // the plain form's recurrence with y in the place of x: step k writes z_{k+1} to px when it is the last, else to z[(k - 1) & 1]
-    const double* y = cheb.y;
-    for (int k = 1; k < d; ++k) {
-      const dla::ChebStep& c = cf.steps[(size_t)k - 1];
-      const double* u = k == 1 ? y : (const double*)cheb.z[(k - 2) & 1];
-      const double* v = k <= 2 ? y : (const double*)cheb.z[(k - 1) & 1];
-      double* out = k == d - 1 ? px : (double*)cheb.z[(k - 1) & 1];
-      const int stc = cheb_step<true>(op, n, m, ChebCoef{c.alpha, c.beta, c.gamma, c.eta}, u, v, y, out, fac);
-      if (stc) return stc;
-    }
-    return DLA_OK;
+    return cheb_apply<true>(
+        "spmm_precnd_cheb_jacobi", n, m, fac, x, px,
+        [&](double* hi, double* shift) -> int { *shift = 0.0; return cheb_jacobi_bound(fac, hi); },
+        [&](const dla::ChebCoefficients& cf, const double** y) -> int {
+          const bool one = cheb.steps == 1;
+          const dim3 grid(grid_blocks(env(), n, 256));
+          const double* r = cheb.r;
+          Scope s(this, DLA_OP_PRECND, 16.0 * (double)n * m + 8.0 * n, (one ? 2.0 : 1.0) * (double)n * m, "cheb_jacobi_scale_kernel");
+          if (one) DLA_LAUNCH(cheb_jacobi_scale_kernel<true>, grid, dim3(256), 0, st, n, m, cf.theta, r, x, px);
+          else DLA_LAUNCH(cheb_jacobi_scale_kernel<false>, grid, dim3(256), 0, st, n, m, cf.theta, r, x, (double*)cheb.y);
+          HIPCHK(hipGetLastError());
+          *y = cheb.y;
+          return DLA_OK;
+        });
   }
 
   // ---- ... and the four parts of the linear-response pencil (A B; B A)(Y Z) = w (S D; -D -S)(Y Z): A+B, A-B, S+D, S-D as the
@@ -6821,7 +6820,7 @@ struct HipEngine : dla::Engine {
     Scope s(this, DLA_OP_PRECND, 32.0 * (double)n * m + 24.0 * (double)n, 8.0 * (double)n * m);
     const bool vec2 = even_rows(n) && (((uintptr_t)xp | (uintptr_t)xm | (uintptr_t)yp | (uintptr_t)ym) % 16 == 0);
     const size_t nv = (size_t)n / (vec2 ? 2 : 1);
-    const int blocks = (int)std::max((size_t)1, std::min((size_t)ncu * 8, (nv + 255) / 256));
+    const int blocks = grid_blocks(env(), (long long)nv, 256);
     const double *da = ops[dla::SPMM_APB].diag, *dm = ops[dla::SPMM_AMB].diag, *ds = ops[dla::SPMM_SPD].diag;
     if (vec2) DLA_LAUNCH(lr_precnd_kernel<2>, dim3(blocks), dim3(256), 0, st, n, m, variant, fac, da, dm, ds, xp, xm, yp, ym);
     else      DLA_LAUNCH(lr_precnd_kernel<1>, dim3(blocks), dim3(256), 0, st, n, m, variant, fac, da, dm, ds, xp, xm, yp, ym);

@@ -114,6 +114,14 @@ constexpr int DMAT_LD = 320, XUG_DOUBLES = 640 * 16, P2P_MAX_DOUBLES = 16384, PE
 // what every planner needs of the engine
 struct PlanEnv { int ncu; size_t lds_limit; const Knobs& knobs; };
 
+// The grid of a grid-stride kernel on blocks of 256 threads: `items` things to do, `per_block` of them to a block (256: one per
+// thread; 4: one per wavefront), at most per_cu blocks per compute unit (grid_cap) and at least one.
+inline int grid_cap(const PlanEnv& env, int per_cu = 8) { return std::max(1, env.ncu * per_cu); }
+inline int grid_blocks(const PlanEnv& env, long long items, long long per_block, int per_cu = 8)
+{
+  return (int)std::max(1LL, std::min((long long)grid_cap(env, per_cu), (items + per_block - 1) / per_block));
+}
+
 template <typename... A>
 inline std::string plan_name(const char* fmt, A... a)
 {
@@ -476,13 +484,11 @@ struct SpmmSetupPlan {
 };
 inline SpmmSetupPlan spmm_setup_plan(const PlanEnv& env, long long n, long long nnz, long long slices, long long long_segments)
 {
-  const long long cap = std::max(1LL, (long long)env.ncu * 8);
-  auto blocks = [&](long long items, long long per_block) { return (int)std::max(1LL, std::min(cap, (items + per_block - 1) / per_block)); };
   SpmmSetupPlan p{};
-  p.entry_blocks = blocks(nnz, 256);
-  p.row_blocks = blocks(n, 256);
-  p.slice_blocks = slices > 0 ? blocks(slices, 4) : 0;
-  p.seg_blocks = long_segments > 0 ? blocks(long_segments, 4) : 0;
+  p.entry_blocks = grid_blocks(env, nnz, 256);
+  p.row_blocks = grid_blocks(env, n, 256);
+  p.slice_blocks = slices > 0 ? grid_blocks(env, slices, 4) : 0;
+  p.seg_blocks = long_segments > 0 ? grid_blocks(env, long_segments, 4) : 0;
   return p;
 }
 

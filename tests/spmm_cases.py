@@ -33,3 +33,16 @@ def csr_from_lengths(rng, n, lens, eighths=False):
 
 def skewed_csr(rng, n, eighths=False):
     return csr_from_lengths(rng, n, skewed_lengths(rng, n), eighths)
+
+
+def fma(a, b, c):
+    """a b + c rounded once: float(Fraction(a) * Fraction(b) + Fraction(c)) without the gcd -- the three as exact ratios over powers
+    of two, and int / int rounds correctly (test_the_emulation_rounds_once of
+    tests/test_spmm_long_rows_gpu.py compares the two)"""
+    na, da = a.as_integer_ratio()
+    nb, db = b.as_integer_ratio()
+    nc, dc = c.as_integer_ratio()
+    d = da * db
+    if dc > d:
+        return (na * nb * (dc // d) + nc) / dc
+    return (na * nb + nc * (d // dc)) / d

@@ -14,7 +14,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spl
 
 from diaglib_amd import capi
-from spmm_cases import LONG_ROW, SLICE, WINDOW, csr_from_lengths, skewed_csr
+from spmm_cases import LONG_ROW, SLICE, WINDOW, csr_from_lengths, fma, skewed_csr
 from spmm_slots import setup
 from test_operators_gpu import (EPS, LD, N_TRIP, SENT, Guarded, _assert_second_trip, assert_within, call_matvec, call_precnd, csr_diagonal,
                                 csr_product_reference, csr_rows, ragged_csr, setup_csr, spmm_product)
@@ -136,6 +136,63 @@ def test_sell_returns_the_bits_of_ellpack(dev, rng, w_max, n):
     setup_fmt(dev, n, indptr, indices, data, ELL)
     assert dev.spmm_info()["format"] == "ell"
     assert np.array_equal(spmm_product(dev, n, 13, x), plain)
+
+
+# widths on both sides of every edge of the ELLPACK width ladder (4, 8, 16, 32) and the loop over any width beyond it; block widths
+# below, at and above the 8 columns a slice entry is loaded for
+SHORT_W_MAX = [1, 4, 5, 8, 9, 16, 17, 32, 33]
+SHORT_M = [1, 8, 9, 13]
+
+
+def chain_rows(indptr, indices, data, x, step):
+    """every (row, column) as one sequential chain over the row's entries in stored order from 0.0: acc = step(value, x[col], acc)"""
+    out = np.zeros((len(indptr) - 1, x.shape[1]))
+    for i in range(len(indptr) - 1):
+        p0, p1 = int(indptr[i]), int(indptr[i + 1])
+        vals, cols = data[p0:p1].tolist(), indices[p0:p1]
+        for c in range(x.shape[1]):
+            acc = 0.0
+            for v, xv in zip(vals, x[cols, c].tolist()):
+                acc = step(v, xv, acc)
+            out[i, c] = acc
+    return out
+
+
+@pytest.fixture(scope="module")
+def short_rows():
+    """n = 300 (two blocks of 256 rows; five slices, the last one partial), ragged rows of 0 .. w_max entries, 13 columns of x and the
+    contract's chain of fused multiply-adds for all 13: computed once per matrix, left unchanged.  The test is sharp only where a
+    separately rounded multiply and add gives other bits, which is asserted here for every matrix whose rows can tell the two apart:
+    a chain of ONE entry rounds v x once either way, so w_max = 1 cannot (there the two are asserted equal instead)."""
+    cases = {}
+    for w_max in SHORT_W_MAX:
+        rng = np.random.default_rng(5100 + w_max)
+        indptr, indices, data = ragged_csr(rng, 300, w_max)
+        x = np.asfortranarray(rng.standard_normal((300, 13)))
+        fused = chain_rows(indptr, indices, data, x, fma)
+        unfused = chain_rows(indptr, indices, data, x, lambda v, xv, acc: v * xv + acc)
+        differ = int((fused != unfused).sum())
+        print(f"w_max={w_max}: {differ} of {fused.size} elements tell a fused chain from a separately rounded one")
+        assert differ > 0 if w_max > 1 else differ == 0, w_max
+        for a in (indptr, indices, data, x, fused):
+            a.flags.writeable = False
+        cases[w_max] = (indptr, indices, data, x, fused)
+    return cases
+
+
+@pytest.mark.parametrize("m", SHORT_M)
+@pytest.mark.parametrize("w_max", SHORT_W_MAX)
+def test_short_rows_have_the_bits_of_the_contract(dev, short_rows, w_max, m):
+    """per row and column the entries are accumulated in stored order, one fused multiply-add each, from 0.0 -- held to an exact
+    emulation, in both formats, so that the two cannot change together unnoticed"""
+    indptr, indices, data, x, fused = short_rows[w_max]
+    n = 300
+    for fmt, name in ((ELL, "ell"), (SELL, "sell")):
+        setup_fmt(dev, n, indptr, indices, data, fmt)
+        assert dev.spmm_info()["format"] == name
+        got = spmm_product(dev, n, m, np.asfortranarray(x[:, :m]))
+        print(f"{name} w_max={w_max} m={m}: {int((got != fused[:, :m]).sum())} of {got.size} elements differ from the emulation")
+        assert np.array_equal(got, fused[:, :m]), (name, w_max, m)
 
 
 def test_consecutive_sell_products_are_bit_identical(dev):

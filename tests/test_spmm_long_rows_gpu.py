@@ -15,7 +15,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spl
 
 from diaglib_amd import capi
-from spmm_cases import LONG_ROW, csr_from_lengths
+from spmm_cases import LONG_ROW, csr_from_lengths, fma
 from spmm_slots import fresh_context, product, setup
 from test_operators_gpu import EPS, LD, Guarded, assert_within, call_matvec, csr_product_reference, spmm_product
 
@@ -39,18 +39,6 @@ def setup_fmt(ctx, *csr_and_format):
 
 def setup_metric(ctx, *csr_and_format):
     setup(ctx, "B", *csr_and_format)
-
-
-def fma(a, b, c):
-    """a b + c rounded once: float(Fraction(a) * Fraction(b) + Fraction(c)) without the gcd -- the three as exact ratios over powers
-    of two, and int / int rounds correctly (test_the_emulation_rounds_once compares the two)"""
-    na, da = a.as_integer_ratio()
-    nb, db = b.as_integer_ratio()
-    nc, dc = c.as_integer_ratio()
-    d = da * db
-    if dc > d:
-        return (na * nb * (dc // d) + nc) / dc
-    return (na * nb + nc * (d // dc)) / d
 
 
 def emulate_row(vals, xs, seg):

@@ -47,6 +47,7 @@ EXPORTS = [
     "dla_spmm_setup_csr_dev", "dla_spmm_refresh_values_dev",
     "dla_spmm_cheb_config", "dla_spmm_cheb_info", "dla_spmm_precnd_cheb",
     "dla_spmm_cheb_jacobi_upper", "dla_spmm_precnd_cheb_jacobi",
+    "dla_spmm_cheb_pencil_upper", "dla_spmm_precnd_cheb_pencil",
     "dla_spmm_setup_lr_csr", "dla_spmm_setup_lr_csr_dev", "dla_spmm_refresh_lr_values_dev", "dla_spmm_lr_info", "dla_spmm_drop_lr",
     "dla_spmm_apbmul", "dla_spmm_ambmul", "dla_spmm_spdmul", "dla_spmm_smdmul", "dla_spmm_lrprec1", "dla_spmm_lrprec2",
     "dla_davidson_driver", "dla_gen_david_driver", "dla_lobpcg_driver", "dla_caslr_eff_driver", "dla_caslr_driver", "dla_call_lrprec",
@@ -167,6 +168,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dla_spmm_cheb_config": (i, [vp, i, d]), "dla_spmm_cheb_info": (i, [vp, C.POINTER(SpmmChebInfo)]),
         "dla_spmm_precnd_cheb": (None, [c_ip, c_ip, c_dp, vp, vp]),
         "dla_spmm_cheb_jacobi_upper": (i, [vp, d, c_dp]), "dla_spmm_precnd_cheb_jacobi": (None, [c_ip, c_ip, c_dp, vp, vp]),
+        "dla_spmm_cheb_pencil_upper": (i, [vp, d, c_dp]), "dla_spmm_precnd_cheb_pencil": (None, [c_ip, c_ip, c_dp, vp, vp]),
         "dla_spmm_setup_lr_csr": (i, [vp, i, i, vp, vp, vp, i]), "dla_spmm_setup_lr_csr_dev": (i, [vp, i, i, vp, vp, vp, i]),
         "dla_spmm_refresh_lr_values_dev": (i, [vp, i, i, vp, vp, vp]), "dla_spmm_lr_info": (i, [vp, i, C.POINTER(SpmmInfo)]),
         "dla_spmm_drop_lr": (i, [vp]),
@@ -659,6 +661,13 @@ class Context:
         diagonally scaled operator; raises in the states in which ``spmm_cheb_info`` does.  One kernel and one host wait"""
         hi = C.c_double(0.0)
         self._chk(self.lib.dla_spmm_cheb_jacobi_upper(self.h, float(fac), C.byref(hi)))
+        return float(hi.value)
+
+    def spmm_cheb_pencil_upper(self, fac: float) -> float:
+        """hi of ``fn_address("dla_spmm_precnd_cheb_pencil")`` for this fac: the bound max_i (|a_ii + fac b_ii| + offA_i + |fac| offB_i) / den_i
+        of the scaled pencil with the stored metric; raises where the callback refuses.  One kernel and one host wait"""
+        hi = C.c_double(0.0)
+        self._chk(self.lib.dla_spmm_cheb_pencil_upper(self.h, float(fac), C.byref(hi)))
         return float(hi.value)
 
     # ---- the four sparse parts of a linear-response pencil (dla_spmm_apbmul .. dla_spmm_smdmul, dla_spmm_lrprec1 / 2)

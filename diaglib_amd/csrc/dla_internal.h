@@ -315,6 +315,9 @@ struct Engine : BlockOps {
   // configuration; spmm_cheb_jacobi_upper: the upper end hi of its interval for one fac
   virtual int spmm_precnd_cheb_jacobi(int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return DLA_ERR_ARG; }
   virtual int spmm_cheb_jacobi_upper(double /*fac*/, double* /*hi*/) { return DLA_ERR_ARG; }
+  // ... and on the scaled pencil D^-1 (A + fac B) with the stored metric B (dla_spmm_precnd_cheb_pencil); spmm_cheb_pencil_upper: hi
+  virtual int spmm_precnd_cheb_pencil(int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return DLA_ERR_ARG; }
+  virtual int spmm_cheb_pencil_upper(double /*fac*/, double* /*hi*/) { return DLA_ERR_ARG; }
 
   // Staging pipeline of host-mode callbacks: column chunks of a block travel device -> host on one copy stream, the
   // user's routine works on the chunk that has arrived, finished chunks travel host -> device on a second copy stream

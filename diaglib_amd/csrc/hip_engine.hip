@@ -1749,48 +1749,124 @@ __device__ __forceinline__ double cheb_jacobi_combine(const dla::ChebStep& k, do
   const double t = fma(fac, u, au) * ri;
   return fma(k.eta, t, fma(k.gamma, y, fma(k.beta, v, k.alpha * u)));
 }
-// J: the scaled epilogue; the gather loops of the step kernels are spelled once for both
-template <bool J>
-__device__ __forceinline__ double cheb_epilogue(const dla::ChebStep& k, double fac, double ri, double u, double v, double x, double au)
+// ... and of the pencil form (dla_spmm_precnd_cheb_pencil): t = r_i ((A u)_i + fac (B u)_i), with the metric's product in the place
+// of u.  With B the identity, (B u)_i = u_i, these are the bits of cheb_jacobi_combine.
+__device__ __forceinline__ double cheb_pencil_combine(const dla::ChebStep& k, double fac, double ri, double u, double v, double y, double au,
+                                                      double bu)
 {
-  if constexpr (J) return cheb_jacobi_combine(k, fac, ri, u, v, x, au);
+  const double t = fma(fac, bu, au) * ri;
+  return fma(k.eta, t, fma(k.gamma, y, fma(k.beta, v, k.alpha * u)));
+}
+// The forms of a step: plain (dla_spmm_precnd_cheb), scaled (dla_spmm_precnd_cheb_jacobi) and the pencil form with B u in a panel
+// (dla_spmm_precnd_cheb_pencil wherever the two matrices do not share a row loop).  The gather loops of the step kernels are spelled
+// once for all three.
+enum ChebForm : int { CHEB_PLAIN = 0, CHEB_SCALED = 1, CHEB_PENCIL = 2 };
+template <int F>
+__device__ __forceinline__ double cheb_epilogue(const dla::ChebStep& k, double fac, double ri, double u, double v, double x, double au, double bu)
+{
+  if constexpr (F == CHEB_PENCIL) return cheb_pencil_combine(k, fac, ri, u, v, x, au, bu);
+  else if constexpr (F == CHEB_SCALED) return cheb_jacobi_combine(k, fac, ri, u, v, x, au);
   else return cheb_combine(k, u, v, x, au);
 }
-// The step as an epilogue of ell_rows: the three panel reads of an element are issued before the gather loop, so they
-// are in flight while it runs.  J = true: x is the panel y = x o r, and fac and r (n doubles) feed the scaled epilogue -- r_i is
-// read once per row; J = false reads neither.
-template <bool J>
+// The step as an epilogue of ell_rows: the panel reads of an element are issued before the gather loop, so they are in flight while
+// it runs.  Scaled and pencil: x is the panel y = x o r, and fac and r (n doubles) feed the epilogue -- r_i is read once per row;
+// pencil: bu is the panel B u; the plain form reads none of them.
+template <int F>
 struct ChebStepEpilogue {
   dla::ChebStep k;
   const double *u, *v, *x;
   double* out;
   double fac;
   const double* r;
+  const double* bu;
   double ri = 0.0;
-  struct Held { double u = 0.0, v = 0.0, x = 0.0; };
-  __device__ __forceinline__ void row(int i) { if constexpr (J) ri = r[i]; }
-  __device__ __forceinline__ Held load(size_t o) const { return Held{u[o], v[o], x[o]}; }
+  struct Held { double u = 0.0, v = 0.0, x = 0.0, bu = 0.0; };
+  __device__ __forceinline__ void row(int i) { if constexpr (F != CHEB_PLAIN) ri = r[i]; }
+  __device__ __forceinline__ Held load(size_t o) const
+  {
+    if constexpr (F == CHEB_PENCIL) return Held{u[o], v[o], x[o], bu[o]};
+    else return Held{u[o], v[o], x[o], 0.0};
+  }
   __device__ __forceinline__ void store(size_t o, const Held& h, double s) const
   {
-    __builtin_nontemporal_store(cheb_epilogue<J>(k, fac, ri, h.u, h.v, h.x, s), out + o);
+    __builtin_nontemporal_store(cheb_epilogue<F>(k, fac, ri, h.u, h.v, h.x, s, h.bu), out + o);
+  }
+  // (the pair loop: both sums come from the row's own gather loops)
+  __device__ __forceinline__ void store(size_t o, const Held& h, double sa, double sb) const
+  {
+    __builtin_nontemporal_store(cheb_pencil_combine(k, fac, ri, h.u, h.v, h.x, sa, sb), out + o);
   }
 };
 // ell_spmm_kernel<W> with that epilogue, on the same width ladder
-template <int W, bool J>
+template <int W, int F>
 __global__ __launch_bounds__(256) void ell_cheb_step_kernel(int n, int m, int w, const int* __restrict__ col,
                                                             const double* __restrict__ val, dla::ChebStep k, const double* u,
                                                             const double* v, const double* x, double* out, double fac,
-                                                            const double* __restrict__ r)
+                                                            const double* __restrict__ r, const double* __restrict__ bu)
 {
-  ell_rows<W>(n, m, w, col, val, GatherPlain{u, n}, ChebStepEpilogue<J>{k, u, v, x, out, fac, r});
+  ell_rows<W>(n, m, w, col, val, GatherPlain{u, n}, ChebStepEpilogue<F>{k, u, v, x, out, fac, r, bu});
+}
+// The step of the pencil form where BOTH matrices are ELLPACK: a row's (column, value) pairs of A and of B, two gather loops over the
+// same u and the pencil epilogue, so that neither A u nor B u travels to HBM.  ell_rows for two matrices: each sum is accumulated
+// as ell_rows accumulates it (in stored order from 0.0; padding is a zero on the row's own column), so the bits are those of the
+// two products.  W: the instance holds max(wa, wb) pairs of each matrix in registers -- twice the footprint of ell_rows<W>, hence the
+// shorter ladder (PAIR_WIDTHS); W = 0 streams both.
+template <int W, class Gather, class Epilogue>
+__device__ __forceinline__ void ell_pair_rows(int n, int m, int wa, const int* __restrict__ cola, const double* __restrict__ vala, int wb,
+                                              const int* __restrict__ colb, const double* __restrict__ valb, const Gather gather, Epilogue ep)
+{
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    ep.row(i);
+    if constexpr (W > 0) {
+      int ca[W], cb[W]; double va[W], vb[W];
+#pragma unroll
+      for (int q = 0; q < W; ++q) {
+        const bool ina = q < wa, inb = q < wb;
+        ca[q] = ina ? cola[(size_t)q * n + i] : gather.self(i);
+        va[q] = ina ? vala[(size_t)q * n + i] : 0.0;
+        cb[q] = inb ? colb[(size_t)q * n + i] : gather.self(i);
+        vb[q] = inb ? valb[(size_t)q * n + i] : 0.0;
+      }
+      for (int c = 0; c < m; ++c) {
+        const size_t o = (size_t)c * n + i;
+        const auto xc = gather.column(c);
+        const auto held = ep.load(o);
+        double sa = 0.0, sb = 0.0;
+#pragma unroll
+        for (int q = 0; q < W; ++q) sa += va[q] * Gather::at(xc, ca[q]);
+#pragma unroll
+        for (int q = 0; q < W; ++q) sb += vb[q] * Gather::at(xc, cb[q]);
+        ep.store(o, held, sa, sb);
+      }
+    } else {
+      for (int c = 0; c < m; ++c) {
+        const size_t o = (size_t)c * n + i;
+        const auto xc = gather.column(c);
+        const auto held = ep.load(o);
+        double sa = 0.0, sb = 0.0;
+        for (int q = 0; q < wa; ++q) sa += vala[(size_t)q * n + i] * Gather::at(xc, cola[(size_t)q * n + i]);
+        for (int q = 0; q < wb; ++q) sb += valb[(size_t)q * n + i] * Gather::at(xc, colb[(size_t)q * n + i]);
+        ep.store(o, held, sa, sb);
+      }
+    }
+  }
+}
+template <int W>
+__global__ __launch_bounds__(256) void ell_cheb_pencil_step_kernel(int n, int m, int wa, const int* __restrict__ cola,
+                                                                   const double* __restrict__ vala, int wb, const int* __restrict__ colb,
+                                                                   const double* __restrict__ valb, dla::ChebStep k, const double* u,
+                                                                   const double* v, const double* y, double* out, double fac,
+                                                                   const double* __restrict__ r)
+{
+  ell_pair_rows<W>(n, m, wa, cola, vala, wb, colb, valb, GatherPlain{u, n}, ChebStepEpilogue<CHEB_SCALED>{k, u, v, y, out, fac, r, nullptr});
 }
 // sell_spmm_kernel<MC> with the same epilogue for the rows of the slices; tail slots and slots past n store nothing
-template <int MC, bool J>
+template <int MC, int F>
 __global__ __launch_bounds__(256) void sell_cheb_step_kernel(int n, int m, int slices, const long long* __restrict__ slice_ptr,
                                                              const int* __restrict__ perm, const int* __restrict__ col,
                                                              const double* __restrict__ val, dla::ChebStep kc, const double* u,
                                                              const double* v, const double* x, double* out, double fac,
-                                                             const double* __restrict__ r)
+                                                             const double* __restrict__ r, const double* __restrict__ bu)
 {
   const int lane = threadIdx.x & 63;
   for (int s = blockIdx.x * 4 + (threadIdx.x >> 6); s < slices; s += gridDim.x * 4) {
@@ -1801,16 +1877,18 @@ __global__ __launch_bounds__(256) void sell_cheb_step_kernel(int n, int m, int s
     const int* cs = col + p0 + lane;
     const double* vs = val + p0 + lane;
     double ri = 0.0;
-    if constexpr (J) ri = row >= 0 ? r[row] : 0.0;
+    if constexpr (F != CHEB_PLAIN) ri = row >= 0 ? r[row] : 0.0;
     for (int c0 = 0; c0 < m; c0 += MC) {
       const double* uc = u + (size_t)c0 * n;
-      double acc[MC], ui[MC], vi[MC], xi[MC];
+      double acc[MC], ui[MC], vi[MC], xi[MC], bi[MC];
 #pragma unroll
       for (int k = 0; k < MC; ++k) {
         acc[k] = 0.0;
         const bool live = row >= 0 && c0 + k < m;
         const size_t o = live ? (size_t)(c0 + k) * n + row : 0;
         ui[k] = live ? u[o] : 0.0; vi[k] = live ? v[o] : 0.0; xi[k] = live ? x[o] : 0.0;
+        bi[k] = 0.0;
+        if constexpr (F == CHEB_PENCIL) bi[k] = live ? bu[o] : 0.0;
       }
       if (c0 + MC <= m) {
         for (int q = 0; q < width; ++q) {
@@ -1831,27 +1909,28 @@ __global__ __launch_bounds__(256) void sell_cheb_step_kernel(int n, int m, int s
       if (row >= 0) {
 #pragma unroll
         for (int k = 0; k < MC; ++k)
-          if (c0 + k < m) __builtin_nontemporal_store(cheb_epilogue<J>(kc, fac, ri, ui[k], vi[k], xi[k], acc[k]), out + (size_t)(c0 + k) * n + row);
+          if (c0 + k < m) __builtin_nontemporal_store(cheb_epilogue<F>(kc, fac, ri, ui[k], vi[k], xi[k], acc[k], bi[k]), out + (size_t)(c0 + k) * n + row);
       }
     }
   }
 }
 // the rows of the CSR tail: csr_long_segments_kernel / long_rows_combine_kernel have left (A u)[row] in the scratch panel au; one
 // thread per (tail row, column) forms the combination for those rows only
-template <bool J>
+template <int F>
 __global__ __launch_bounds__(256) void tail_cheb_combine_kernel(int n, int m, int nlong, const int* __restrict__ long_row, dla::ChebStep k,
                                                                 const double* u, const double* v, const double* x,
                                                                 const double* __restrict__ au, double* out, double fac,
-                                                                const double* __restrict__ r)
+                                                                const double* __restrict__ r, const double* __restrict__ bu)
 {
   const long long total = (long long)nlong * m;
   for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
     const int j = (int)(t / m), c = (int)(t - (long long)j * m);
     const int row = long_row[j];
     const size_t o = (size_t)c * n + row;
-    double ri = 0.0;
-    if constexpr (J) ri = r[row];
-    out[o] = cheb_epilogue<J>(k, fac, ri, u[o], v[o], x[o], au[o]);
+    double ri = 0.0, bo = 0.0;
+    if constexpr (F != CHEB_PLAIN) ri = r[row];
+    if constexpr (F == CHEB_PENCIL) bo = bu[o];
+    out[o] = cheb_epilogue<F>(k, fac, ri, u[o], v[o], x[o], au[o], bo);
   }
 }
 // the un-fused step (A/B comparand, Knobs::cheb_unfused): the product kernel has written A u to the panel au; one sweep combines
@@ -1874,7 +1953,20 @@ __global__ __launch_bounds__(256) void cheb_jacobi_combine_kernel(int n, int m, 
     }
   }
 }
-// the scale sweep of the scaled form: y = x o r, or with one step (DIV) px = (x o r) / theta at once
+// ... of the pencil form: A u and B u both come from panels
+__global__ __launch_bounds__(256) void cheb_pencil_combine_kernel(int n, int m, dla::ChebStep k, double fac, const double* __restrict__ r,
+                                                                  const double* u, const double* v, const double* y,
+                                                                  const double* __restrict__ au, const double* __restrict__ bu, double* out)
+{
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const double ri = r[i];
+    for (int c = 0; c < m; ++c) {
+      const size_t o = (size_t)c * n + i;
+      out[o] = cheb_pencil_combine(k, fac, ri, u[o], v[o], y[o], au[o], bu[o]);
+    }
+  }
+}
+// the scale sweep of the scaled form and of the pencil form: y = x o r, or with one step (DIV) px = (x o r) / theta at once
 template <bool DIV>
 __global__ __launch_bounds__(256) void cheb_jacobi_scale_kernel(int n, int m, double theta, const double* __restrict__ r,
                                                                 const double* __restrict__ x, double* __restrict__ y)
@@ -1968,6 +2060,27 @@ __global__ __launch_bounds__(256) void cheb_jacobi_bound_kernel(int n, double fa
     const double den = s > 1.0e-5 ? s : 1.0;
     r[i] = 1.0 / den;
     g = fmax(g, (s + off[i]) / den);
+  }
+  block_max_store(g, partial);
+}
+// The bound of the pencil form for one fac (the contract: include/diaglib_amd.h, dla_spmm_precnd_cheb_pencil): den0_i = a_ii + fac b_ii
+// with the product rounded before the sum (no contraction: the bits pencil_precnd_kernel divides by), s_i = |den0_i|, den_i and r[i]
+// as above, q_i = fma(|fac|, offB_i, s_i + offA_i) / den_i; partial[block] = max q_i.  With b_ii = 1 and offB = 0 every value has the
+// bits of cheb_jacobi_bound_kernel.
+__global__ __launch_bounds__(256) void cheb_pencil_bound_kernel(int n, double fac, const double* __restrict__ a_diag, const double* __restrict__ b_diag,
+                                                                const double* __restrict__ off_a, const double* __restrict__ off_b,
+                                                                double* __restrict__ r, double* __restrict__ partial)
+{
+#pragma clang fp contract(off)
+  double g = -INFINITY;
+  const double af = fabs(fac);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const double prod = fac * b_diag[i];
+    const double s = fabs(a_diag[i] + prod);
+    const double den = s > 1.0e-5 ? s : 1.0;
+    r[i] = 1.0 / den;
+    const double sa = s + off_a[i];
+    g = fmax(g, fma(af, off_b[i], sa) / den);
   }
   block_max_store(g, partial);
 }
@@ -6246,6 +6359,7 @@ struct HipEngine : dla::Engine {
     { const int stc = admit(slot, w.refresh, CALL_REFRESH | NEED_STORED); if (stc) return stc; }
     const int stc = refresh_dev(ops[slot], n, rowptr_dev, colind_dev, values_dev);
     if (slot == dla::SPMM_A) cheb.upper_valid = cheb.off_valid = false;
+    if (slot == dla::SPMM_B) cheb.offb_valid = false;
     if (stc == DLA_ERR_ARG && w.quoted_dev) err = quote(slot, w.refresh) + err;
     return stc;
   }
@@ -6298,6 +6412,7 @@ struct HipEngine : dla::Engine {
                         : setup_fmt(ops[slot], n, rowptr, colind, values, plain ? (int)DLA_SPMM_ELL : format, quoted ? "spmm_setup_csr_fmt" : entry);
     if (stc == DLA_ERR_ARG && quoted) err = quote(slot, entry) + err;
     if (slot == dla::SPMM_A) cheb.upper_valid = cheb.off_valid = false;
+    if (slot == dla::SPMM_B) cheb.offb_valid = false;
     if (!stc && slot == dla::SPMM_A) shard.drop();
     return stc;
   }
@@ -6334,6 +6449,7 @@ struct HipEngine : dla::Engine {
     HIPCHK(hipStreamSynchronize(st));     // (products of these slots may still be queued)
     for (int s = first; s <= last; ++s) ops[s].drop();
     if (first <= dla::SPMM_A && dla::SPMM_A <= last) cheb.upper_valid = cheb.off_valid = false;
+    if (first <= dla::SPMM_B && dla::SPMM_B <= last) cheb.offb_valid = false;
     return DLA_OK;
   }
   // The ELLPACK width ladder, spelled once for the product, the Chebyshev step and the product on a row shard: launch(W) for the
@@ -6554,6 +6670,10 @@ struct HipEngine : dla::Engine {
     DeviceBuffer<double> off;          // n doubles: the stored matrix's, formed on first use
     DeviceBuffer<double> r;            // n doubles: 1 / den_i of the last call's fac
     DeviceBuffer<double> y;            // the panel y = x o r: n x m
+    // the pencil form (dla_spmm_precnd_cheb_pencil)
+    bool offb_valid = false;           // offb holds the off-diagonal row sums of the stored metric
+    DeviceBuffer<double> offb;         // n doubles: the stored metric's, formed on first use
+    DeviceBuffer<double> bu;           // B u wherever the two matrices do not share a row loop: n x m
   } cheb;
   int spmm_cheb_config(int steps, double lo_fraction) override
   {
@@ -6563,11 +6683,12 @@ struct HipEngine : dla::Engine {
       return DLA_ERR_ARG;
     }
     if (steps == 0) {
-      if (cheb.z[0] || cheb.z[1] || cheb.au || cheb.partial || cheb.off || cheb.r || cheb.y) {
+      if (cheb.z[0] || cheb.z[1] || cheb.au || cheb.partial || cheb.off || cheb.r || cheb.y || cheb.offb || cheb.bu) {
         HIPCHK(hipSetDevice(device));
         HIPCHK(hipStreamSynchronize(st));     // (a queued call may still use the panels)
         cheb.z[0].reset(); cheb.z[1].reset(); cheb.au.reset(); cheb.partial.reset();
         cheb.off.reset(); cheb.r.reset(); cheb.y.reset(); cheb.off_valid = false;
+        cheb.offb.reset(); cheb.bu.reset(); cheb.offb_valid = false;
       }
       cheb.steps = 0; cheb.lo_fraction = 0.0;
       return DLA_OK;
@@ -6648,18 +6769,42 @@ struct HipEngine : dla::Engine {
     return DLA_OK;
   }
   // one step out = alpha u + beta v + gamma x + eta (A u) on the stored A; out may be v's buffer, never u's
-  // J: the step of the scaled form, where x is the panel y = x o r and r = cheb.r; booked under its own kernel names with the 8 n
-  // bytes of r and the 3 n m flops of the scaling on top
-  template <bool J>
+  // F (ChebForm): scaled and pencil are the steps where x is the panel y = x o r and r = cheb.r; booked under their own kernel names
+  // with the 8 n bytes of r and the 3 n m flops of the scaling on top.  Pencil: B u comes from the metric's own product in the panel
+  // cheb.bu (8 n m bytes more) -- or, where both matrices are ELLPACK, from the second gather loop of ell_cheb_pencil_step_kernel.
+  static constexpr int PAIR_WIDTHS[] = {4, 8, 16, 0};
+  bool cheb_pencil_fused() const { return !knobs.cheb_unfused() && ops[dla::SPMM_A].fmt != DLA_SPMM_SELL && ops[dla::SPMM_B].fmt != DLA_SPMM_SELL; }
+  template <int F>
   int cheb_step(SparseOp& op, int n, int m, const dla::ChebStep& k, const double* u, const double* v, const double* x, double* out, double fac)
   {
-    const double nm = (double)n * m, rb = J ? 8.0 * n : 0.0, cf = (J ? 10.0 : 7.0) * nm;
-    const double *r = J ? (const double*)cheb.r : nullptr, *au = cheb.au;
+    constexpr bool J = F != CHEB_PLAIN, P = F == CHEB_PENCIL;
+    const double nm = (double)n * m, rb = (J ? 8.0 * n : 0.0) + (P ? 8.0 * nm : 0.0), cf = (J ? 10.0 : 7.0) * nm;
+    const double *r = J ? (const double*)cheb.r : nullptr, *au = cheb.au, *bu = P ? (const double*)cheb.bu : nullptr;
+    if constexpr (P) {
+      SparseOp& opb = ops[dla::SPMM_B];
+      if (cheb_pencil_fused()) {
+        const SparseOp::Ell ea = op.ell(), eb = opb.ell();
+        Scope s(this, DLA_OP_PRECND, 12.0 * (double)(ea.w + eb.w) * n + 32.0 * nm + 8.0 * n, 2.0 * (double)(ea.w + eb.w) * nm + cf,
+                "ell_cheb_pencil_step_kernel");
+        const dim3 grid(grid_blocks(env(), n, 256));
+        const int wide = std::max(ea.w, eb.w);
+        first_instance<std::size(PAIR_WIDTHS)>([&](auto i) {
+          constexpr int W = PAIR_WIDTHS[decltype(i)::value];
+          if (W > 0 && wide > W) return false;
+          DLA_LAUNCH((ell_cheb_pencil_step_kernel<W>), grid, dim3(256), 0, st, n, m, ea.w, ea.col, ea.val, eb.w, eb.col, eb.val, k, u, v, x, out, fac, r);
+          return true;
+        });
+        HIPCHK(hipGetLastError());
+        return DLA_OK;
+      }
+      { const int stc = op_matvec(opb, n, m, u, cheb.bu); if (stc) return stc; }
+    }
     if (knobs.cheb_unfused()) {
       { const int stc = op_matvec(op, n, m, u, cheb.au); if (stc) return stc; }
-      Scope s(this, DLA_OP_PRECND, 40.0 * nm + rb, cf, J ? "cheb_jacobi_combine_kernel" : "cheb_combine_kernel");
+      Scope s(this, DLA_OP_PRECND, 40.0 * nm + rb, cf, P ? "cheb_pencil_combine_kernel" : J ? "cheb_jacobi_combine_kernel" : "cheb_combine_kernel");
       const size_t total = (size_t)n * m;
-      if constexpr (J) DLA_LAUNCH(cheb_jacobi_combine_kernel, dim3(grid_blocks(env(), n, 256)), dim3(256), 0, st, n, m, k, fac, r, u, v, x, au, out);
+      if constexpr (P) DLA_LAUNCH(cheb_pencil_combine_kernel, dim3(grid_blocks(env(), n, 256)), dim3(256), 0, st, n, m, k, fac, r, u, v, x, au, bu, out);
+      else if constexpr (J) DLA_LAUNCH(cheb_jacobi_combine_kernel, dim3(grid_blocks(env(), n, 256)), dim3(256), 0, st, n, m, k, fac, r, u, v, x, au, out);
       else DLA_LAUNCH(cheb_combine_kernel, dim3(grid_blocks(env(), (long long)total, 256)), dim3(256), 0, st, total, k, u, v, x, au, out);
       HIPCHK(hipGetLastError());
       return DLA_OK;
@@ -6669,38 +6814,39 @@ struct HipEngine : dla::Engine {
       // (the tail's partial sums and its rows of the scratch panel are written once and read once)
       Scope s(this, DLA_OP_PRECND, 12.0 * (double)(op.sell_stored + op.sell_long_entries) + 4.0 * n + 32.0 * nm + 16.0 * (double)p.part_doubles +
                                        16.0 * (double)op.sell_long_rows * m + rb,
-              2.0 * (double)op.nnz * m + cf, J ? "sell_cheb_jacobi_step_kernel" : "sell_cheb_step_kernel");
+              2.0 * (double)op.nnz * m + cf, P ? "sell_cheb_pencil_panel_step_kernel" : J ? "sell_cheb_jacobi_step_kernel" : "sell_cheb_step_kernel");
       const SparseOp::Slices sl = op.slices();
-      DLA_LAUNCH((sell_cheb_step_kernel<SELL_MC, J>), dim3(grid_blocks(env(), sl.count, 4)), dim3(256), 0, st, n, m, sl.count, sl.ptr, sl.perm, sl.col,
-                 sl.val, k, u, v, x, out, fac, r);
+      DLA_LAUNCH((sell_cheb_step_kernel<SELL_MC, F>), dim3(grid_blocks(env(), sl.count, 4)), dim3(256), 0, st, n, m, sl.count, sl.ptr, sl.perm, sl.col,
+                 sl.val, k, u, v, x, out, fac, r, bu);
       HIPCHK(hipGetLastError());
       if (op.sell_long_segments > 0) {
         // (A u) of the tail rows to the scratch panel, then their combination
         { const int stc = tail_product(op, p, n, m, u, cheb.au); if (stc) return stc; }
         const SparseOp::Tail t = op.tail();
-        DLA_LAUNCH(tail_cheb_combine_kernel<J>, dim3(grid_blocks(env(), (long long)t.rows * m, 256)), dim3(256), 0, st, n, m, t.rows, t.long_row, k, u, v, x,
-                   au, out, fac, r);
+        DLA_LAUNCH(tail_cheb_combine_kernel<F>, dim3(grid_blocks(env(), (long long)t.rows * m, 256)), dim3(256), 0, st, n, m, t.rows, t.long_row, k, u, v, x,
+                   au, out, fac, r, bu);
         HIPCHK(hipGetLastError());
       }
       return DLA_OK;
     }
     Scope s(this, DLA_OP_PRECND, 12.0 * (double)op.w * n + 32.0 * nm + rb, 2.0 * (double)op.w * nm + cf,
-            J ? "ell_cheb_jacobi_step_kernel" : "ell_cheb_step_kernel");
+            P ? "ell_cheb_pencil_panel_step_kernel" : J ? "ell_cheb_jacobi_step_kernel" : "ell_cheb_step_kernel");
     const SparseOp::Ell e = op.ell();
     const dim3 grid(grid_blocks(env(), n, 256));
     ell_width(e.w, [&](auto W) {
-      DLA_LAUNCH((ell_cheb_step_kernel<decltype(W)::value, J>), grid, dim3(256), 0, st, n, m, e.w, e.col, e.val, k, u, v, x, out, fac, r);
+      DLA_LAUNCH((ell_cheb_step_kernel<decltype(W)::value, F>), grid, dim3(256), 0, st, n, m, e.w, e.col, e.val, k, u, v, x, out, fac, r, bu);
     });
     HIPCHK(hipGetLastError());
     return DLA_OK;
   }
-  // What the two entries share, once.  J: the scaled form.  interval(&hi, &shift) leaves the upper end of the entry's interval and the
+  // What the three entries share, once.  F: the form (ChebForm); admit(who): what the entry refuses first.  interval(&hi, &shift) leaves the upper end of the entry's interval and the
   // shift its coefficients take; first(cf, &y) launches the entry's own sweep -- with one step the whole polynomial, written to px --
   // and leaves in y the panel that stands in the place of x in the recurrence.
-  template <bool J, class Interval, class First>
+  template <int F, class Interval, class First>
   int cheb_apply(const char* who, int n, int m, double fac, const double* x, double* px, Interval&& interval, First&& first)
   {
-    { const int stc = cheb_admit(who); if (stc) return stc; }
+    constexpr bool J = F != CHEB_PLAIN, P = F == CHEB_PENCIL;
+    { const int stc = P ? cheb_pencil_admit(who) : cheb_admit(who); if (stc) return stc; }
     SparseOp& op = ops[dla::SPMM_A];
     if (n != op.n) { err = std::string(who) + ": n = " + std::to_string(n) + " differs from the " + std::to_string(op.n) + " rows of the operator"; return DLA_ERR_ARG; }
     if (m <= 0) return DLA_OK;
@@ -6711,6 +6857,16 @@ struct HipEngine : dla::Engine {
     if (d >= 3) { const int stc = cheb_panel(cheb.z[0], total); if (stc) return stc; }
     if (d >= 4) { const int stc = cheb_panel(cheb.z[1], total); if (stc) return stc; }
     if (d >= 2 && (knobs.cheb_unfused() || (op.fmt == DLA_SPMM_SELL && op.sell_long_segments > 0))) { const int stc = cheb_panel(cheb.au, total); if (stc) return stc; }
+    if (P && d >= 2 && !cheb_pencil_fused()) {
+      { const int stc = cheb_panel(cheb.bu, total); if (stc) return stc; }
+      // (... and the workspaces of the two tails, which the products would otherwise grow between the launches)
+      for (SparseOp* o : {&op, &ops[dla::SPMM_B]}) {
+        if (o->fmt != DLA_SPMM_SELL) continue;
+        const LongRowsPlan p = long_rows_plan(env(), o->sell_long_segments, o->sell_multi_rows, o->sell_multi_segments, m, LONG_MC);
+        const int stc = cheb_panel(o->long_part, p.part_doubles);
+        if (stc) return stc;
+      }
+    }
     double hi = 0.0, shift = 0.0;
     { const int stc = interval(&hi, &shift); if (stc) return stc; }
     if (hi <= 1.0e-5) {       // (the harness' guard on the interval's upper end: px = x)
@@ -6726,14 +6882,14 @@ struct HipEngine : dla::Engine {
       const double* u = k == 1 ? y : (const double*)cheb.z[(k - 2) & 1];
       const double* v = k <= 2 ? y : (const double*)cheb.z[(k - 1) & 1];
       double* out = k == d - 1 ? px : (double*)cheb.z[(k - 1) & 1];
-      const int stc = cheb_step<J>(op, n, m, cf.steps[(size_t)k - 1], u, v, y, out, J ? fac : 0.0);
+      const int stc = cheb_step<F>(op, n, m, cf.steps[(size_t)k - 1], u, v, y, out, J ? fac : 0.0);
       if (stc) return stc;
     }
     return DLA_OK;
   }
   int spmm_precnd_cheb(int n, int m, double fac, const double* x, double* px) override
   {
-    return cheb_apply<false>(
+    return cheb_apply<CHEB_PLAIN>(
         "spmm_precnd_cheb", n, m, fac, x, px,
         [&](double* hi, double* shift) -> int {
           const int stc = cheb_upper();
@@ -6753,14 +6909,16 @@ struct HipEngine : dla::Engine {
   // ---- ... and on the diagonally scaled operator D^-1 (A + fac I), D = |diag(A) + fac| (the contract: include/diaglib_amd.h,
   // dla_spmm_precnd_cheb_jacobi).  off, the off-diagonal row sums, is the stored matrix's like the Gershgorin bound; r and the
   // interval depend on fac and are formed by every call.
-  int cheb_off()
+  int cheb_off() { return cheb_off_rows(ops[dla::SPMM_A], cheb.off, cheb.off_valid); }
+  // (of the stored metric, for the pencil form: invalidated by every accepted set-up, refresh or drop of slot B)
+  int cheb_off_b() { return cheb_off_rows(ops[dla::SPMM_B], cheb.offb, cheb.offb_valid); }
+  int cheb_off_rows(SparseOp& op, DeviceBuffer<double>& off, bool& valid)
   {
-    if (cheb.off_valid) return DLA_OK;
-    SparseOp& op = ops[dla::SPMM_A];
+    if (valid) return DLA_OK;
     bind();
-    { const int stc = cheb_panel(cheb.off, (size_t)op.n); if (stc) return stc; }
-    { const int stc = gershgorin<true>(op, nullptr, cheb.off); if (stc) return stc; }
-    cheb.off_valid = true;
+    { const int stc = cheb_panel(off, (size_t)op.n); if (stc) return stc; }
+    { const int stc = gershgorin<true>(op, nullptr, off); if (stc) return stc; }
+    valid = true;
     return DLA_OK;
   }
   // r = 1 / den and hi = max_i q_i for this fac: one kernel, then the block maxima come to the host (one host wait per call)
@@ -6787,22 +6945,73 @@ struct HipEngine : dla::Engine {
     { const int stc = cheb_admit("spmm_cheb_jacobi_upper"); if (stc) return stc; }
     return cheb_jacobi_bound(fac, hi);
   }
+  // the scale sweep of the scaled and the pencil form: y = x o r, or with one step px = (x o r) / theta at once
+  int cheb_scale_sweep(int n, int m, const dla::ChebCoefficients& cf, const double* x, double* px, const double** y)
+  {
+    const bool one = cheb.steps == 1;
+    const dim3 grid(grid_blocks(env(), n, 256));
+    const double* r = cheb.r;
+    Scope s(this, DLA_OP_PRECND, 16.0 * (double)n * m + 8.0 * n, (one ? 2.0 : 1.0) * (double)n * m, "cheb_jacobi_scale_kernel");
+    if (one) DLA_LAUNCH(cheb_jacobi_scale_kernel<true>, grid, dim3(256), 0, st, n, m, cf.theta, r, x, px);
+    else DLA_LAUNCH(cheb_jacobi_scale_kernel<false>, grid, dim3(256), 0, st, n, m, cf.theta, r, x, (double*)cheb.y);
+    HIPCHK(hipGetLastError());
+    *y = cheb.y;
+    return DLA_OK;
+  }
   int spmm_precnd_cheb_jacobi(int n, int m, double fac, const double* x, double* px) override
   {
-    return cheb_apply<true>(
+    return cheb_apply<CHEB_SCALED>(
         "spmm_precnd_cheb_jacobi", n, m, fac, x, px,
         [&](double* hi, double* shift) -> int { *shift = 0.0; return cheb_jacobi_bound(fac, hi); },
-        [&](const dla::ChebCoefficients& cf, const double** y) -> int {
-          const bool one = cheb.steps == 1;
-          const dim3 grid(grid_blocks(env(), n, 256));
-          const double* r = cheb.r;
-          Scope s(this, DLA_OP_PRECND, 16.0 * (double)n * m + 8.0 * n, (one ? 2.0 : 1.0) * (double)n * m, "cheb_jacobi_scale_kernel");
-          if (one) DLA_LAUNCH(cheb_jacobi_scale_kernel<true>, grid, dim3(256), 0, st, n, m, cf.theta, r, x, px);
-          else DLA_LAUNCH(cheb_jacobi_scale_kernel<false>, grid, dim3(256), 0, st, n, m, cf.theta, r, x, (double*)cheb.y);
-          HIPCHK(hipGetLastError());
-          *y = cheb.y;
-          return DLA_OK;
-        });
+        [&](const dla::ChebCoefficients& cf, const double** y) -> int { return cheb_scale_sweep(n, m, cf, x, px, y); });
+  }
+
+  // ---- ... and on the scaled pencil D^-1 (A + fac B), D = |diag(A) + fac diag(B)|, B the stored metric (the contract:
+  // include/diaglib_amd.h, dla_spmm_precnd_cheb_pencil).  offB is the stored metric's as off is the stored operator's.
+  int cheb_pencil_admit(const char* who)
+  {
+    const SparseOp &a = ops[dla::SPMM_A], &b = ops[dla::SPMM_B];
+    if (a.fmt < 0 || !a.diag) { err = std::string(who) + ": no operator has been set up (dla_spmm_setup_csr)"; return DLA_ERR_ARG; }
+    if (shard.on) { err = std::string(who) + ": the operator of this context is row-sharded, and the Chebyshev preconditioner on a row-sharded operator is not supported"; return DLA_ERR_ARG; }
+    if (b.fmt < 0 || !b.diag) { err = std::string(who) + ": no metric has been set up (dla_spmm_setup_metric_csr)"; return DLA_ERR_ARG; }
+    if (a.n != b.n) { err = std::string(who) + ": the operator has " + std::to_string(a.n) + " rows and the metric " + std::to_string(b.n); return DLA_ERR_ARG; }
+    if (cheb.steps <= 0) { err = std::string(who) + ": nothing is configured (dla_spmm_cheb_config)"; return DLA_ERR_ARG; }
+    return DLA_OK;
+  }
+  // r = 1 / den and hi = max_i q_i of the pencil for this fac: one kernel, one host wait per call
+  int cheb_pencil_bound(double fac, double* hi)
+  {
+    SparseOp &op = ops[dla::SPMM_A], &opb = ops[dla::SPMM_B];
+    const int n = op.n;
+    { const int stc = cheb_off(); if (stc) return stc; }
+    { const int stc = cheb_off_b(); if (stc) return stc; }
+    { const int stc = cheb_panel(cheb.r, (size_t)n); if (stc) return stc; }
+    const int blocks = grid_blocks(env(), n, 256);
+    { const int stc = cheb_panel(cheb.partial, (size_t)grid_cap(env())); if (stc) return stc; }
+    {
+      Scope s(this, DLA_OP_PRECND, 40.0 * n, 7.0 * n, "cheb_pencil_bound_kernel");
+      DLA_LAUNCH(cheb_pencil_bound_kernel, dim3(blocks), dim3(256), 0, st, n, fac, op.diagonal(), opb.diagonal(), (const double*)cheb.off,
+                 (const double*)cheb.offb, (double*)cheb.r, (double*)cheb.partial);
+      HIPCHK(hipGetLastError());
+    }
+    { const int stc = max_of_blocks(cheb.partial, blocks, hi); if (stc) return stc; }
+    stats.host_syncs++;
+    return DLA_OK;
+  }
+  int spmm_cheb_pencil_upper(double fac, double* hi) override
+  {
+    { const int stc = cheb_pencil_admit("spmm_cheb_pencil_upper"); if (stc) return stc; }
+    double g = 0.0;
+    { const int stc = cheb_pencil_bound(fac, &g); if (stc) return stc; }
+    *hi = g;
+    return DLA_OK;
+  }
+  int spmm_precnd_cheb_pencil(int n, int m, double fac, const double* x, double* px) override
+  {
+    return cheb_apply<CHEB_PENCIL>(
+        "spmm_precnd_cheb_pencil", n, m, fac, x, px,
+        [&](double* hi, double* shift) -> int { *shift = 0.0; return cheb_pencil_bound(fac, hi); },
+        [&](const dla::ChebCoefficients& cf, const double** y) -> int { return cheb_scale_sweep(n, m, cf, x, px, y); });
   }
 
   // ---- ... and the four parts of the linear-response pencil (A B; B A)(Y Z) = w (S D; -D -S)(Y Z): A+B, A-B, S+D, S-D as the

@@ -1235,7 +1235,7 @@ static const OwnCallback* own_callback(void* fn)
     {(void*)&dla_synth_precnd, false, true}, {(void*)&dla_spmm_precnd, false, true}, {(void*)&dla_spmm_precnd_pencil, false, true},
     {(void*)&dla_synth_lrprec1, false, true}, {(void*)&dla_synth_lrprec2, false, true}, {(void*)&dla_spmm_lrprec1, false, true},
     {(void*)&dla_spmm_lrprec2, false, true}, {(void*)&dla_spmm_precnd_cheb, false, true},
-    {(void*)&dla_spmm_precnd_cheb_jacobi, false, true}};
+    {(void*)&dla_spmm_precnd_cheb_jacobi, false, true}, {(void*)&dla_spmm_precnd_cheb_pencil, false, true}};
   for (const OwnCallback& r : table)
     if (r.fn == fn) return &r;
   return nullptr;
@@ -1971,6 +1971,18 @@ void dla_spmm_precnd_cheb_jacobi(const int* n, const int* m, const double* fac, 
   dla_ctx* c = g_spmm_ctx;
   if (!c) { callback_failed(DLA_ERR_ARG, "dla_spmm_precnd_cheb_jacobi before dla_spmm_setup_csr: no operator has been set up"); return; }
   if (int st = c->eng->spmm_precnd_cheb_jacobi(*n, *m, *fac, x, px)) callback_failed(st, "dla_spmm_precnd_cheb_jacobi failed: " + c->eng->err);
+}
+// ... and on the scaled pencil A + fac B with the stored metric
+int dla_spmm_cheb_pencil_upper(dla_ctx* c, double fac, double* hi)
+{
+  if (!c || !hi) return DLA_ERR_ARG;
+  return engfail(c, c->eng->spmm_cheb_pencil_upper(fac, hi));
+}
+void dla_spmm_precnd_cheb_pencil(const int* n, const int* m, const double* fac, const double* x, double* px)
+{
+  dla_ctx* c = g_spmm_ctx;
+  if (!c) { callback_failed(DLA_ERR_ARG, "dla_spmm_precnd_cheb_pencil before dla_spmm_setup_csr: no operator has been set up"); return; }
+  if (int st = c->eng->spmm_precnd_cheb_pencil(*n, *m, *fac, x, px)) callback_failed(st, "dla_spmm_precnd_cheb_pencil failed: " + c->eng->err);
 }
 
 // ---- ... the metric of a generalised problem beside it (bvec of reference diaglib.f90:1855; the harness' smult, main.f90:115-144) ...

@@ -614,8 +614,8 @@ void dla_spmm_lrprec2(const int* n, const int* m, const double* fac, const doubl
  * DLA_ERR_ARG while nothing is configured or no A is stored; upper is g of the stored A.
  * Refusals: the callback fails through the status of dla_call_precnd, with a message that names dla_spmm_precnd_cheb and the
  * cause, when it finds no operator, another n, nothing configured or a row-sharded operator; a refused call writes nothing.
- * Out of scope: the pencil A + fac B, the linear-response parts and a row-sharded operator (refused as above); choosing
- * lo_fraction or the number of steps adaptively (the caller passes both); sanitizer runs of code loaded into an interpreter (the
+ * Out of scope: the pencil A + fac B (dla_spmm_precnd_cheb_pencil below), the linear-response parts and a row-sharded operator
+ * (refused as above); choosing lo_fraction or the number of steps adaptively (the caller passes both); sanitizer runs of code loaded into an interpreter (the
  * host-only scalar recurrence is testable from a stand-alone program); any inspection of kernel assembly. */
 struct dla_spmm_cheb_info { int steps; double lo_fraction; double upper; };
 int  dla_spmm_cheb_config(dla_ctx* ctx, int steps, double lo_fraction);
@@ -660,10 +660,56 @@ void dla_spmm_precnd_cheb(const int* n, const int* m, const double* fac, const d
  * the context, grow behind a stream wait and are released by steps = 0 and by dla_destroy.
  * Accuracy: px stays within twice the first-order running bound that tests/cheb_jacobi_ref.py computes beside its long-double
  * reference, wherever that bound is below 1e-9 of the result.
- * Out of scope: the pencil A + fac B, the linear-response parts, row shards, choosing d or f adaptively, sanitizer runs of code
- * loaded into an interpreter, any inspection of kernel assembly. */
+ * Out of scope: the linear-response parts, row shards, choosing d or f adaptively, sanitizer runs of code loaded into an
+ * interpreter, any inspection of kernel assembly.  The pencil A + fac B: dla_spmm_precnd_cheb_pencil below. */
 int  dla_spmm_cheb_jacobi_upper(dla_ctx* ctx, double fac, double* hi);
 void dla_spmm_precnd_cheb_jacobi(const int* n, const int* m, const double* fac, const double* x_dev, double* px_dev);
+
+/* ---------------------------------------------------------------- ... on the scaled pencil A + fac B of a generalised problem
+ * A stiffness / mass pair A x = lambda B x is where a diagonal preconditioner does nothing: x / (a_ii + fac b_ii) removes the
+ * scaling of the rows and leaves the whole coupling.  dla_spmm_precnd_cheb_pencil is the iteration of the scaled form on D^-1 M
+ * with M = A + fac B and D = |diag(A) + fac diag(B)|, where A is slot A and B is slot B, the stored metric.  Same shape
+ * precnd(n,m,fac,x,px), DEVICE addresses, the calling thread's context and stream; it reads the configuration (d, f) of
+ * dla_spmm_cheb_config that the other two read and goes where a precnd goes (gen_david_driver, lobpcg_driver with gen_eig).
+ * Single rank.  Each slot in any format -- ELLPACK, sliced ELLPACK, sliced ELLPACK with the CSR tail -- independently of the
+ * other.  The contract:
+ * 1. Off-diagonal row sums: offA_i is exactly off_i of the scaled form, the same buffer with the same invalidation.  offB_i is
+ *    the same sum over the stored B, formed by the same Gershgorin kernels; it belongs to the stored metric: every accepted
+ *    set-up, refresh or drop of slot B invalidates it, and nothing else does.  Host set-up and device set-up give the same bits.
+ *    g and off of slot A keep their bits.
+ * 2. Per call, per row: den0_i = a_ii + fac * b_ii, the product and the sum each rounded on their own (no contraction: the bits
+ *    dla_spmm_precnd_pencil divides by); s_i = |den0_i|; den_i = s_i where s_i > 1e-5, else 1.0; r_i = 1.0 / den_i;
+ *    q_i = fma(|fac|, offB_i, s_i + offA_i) / den_i; hi = max_i q_i bounds the infinity norm of D^-1 (A + fac B), because
+ *    |a_ij + fac b_ij| <= |a_ij| + |fac| |b_ij| entry by entry, whatever the two patterns are; lo = f hi.  If hi <= 1e-5 then
+ *    px = x, bit for bit.  One kernel reads the two diagonals and the two off vectors (40 n bytes with r), writes r and block
+ *    maxima; the host takes the maximum of those.  ONE HOST WAIT PER CALL, as in the scaled form and for the same reason.
+ * 3. Scalars: those of the scaled form, dla::cheb_coefficients(hi, f hi, 0.0, d); fac enters through the product.
+ * 4. Recurrence: y = x o r;  z_0 = 0,  z_1 = y / theta,
+ *      z_{k+1} = z_k + rho_k rho_{k-1} (z_k - z_{k-1}) + (2 rho_k / delta) (y - r o (A z_k + fac B z_k))   for k = 1 .. d - 1,
+ *    px = z_d.  d steps cost d - 1 products with each matrix.
+ * 5. Each step is one expression per element, with u = z_k and v = z_{k-1}:
+ *      t = fma(fac, (B u)_i, (A u)_i) * r_i,   out = fma(eta, t, fma(gamma, y_i, fma(beta, v_i, alpha u_i)))
+ *    where (A u)_i and (B u)_i are each accumulated as dla_spmm_matvec and dla_spmm_bvec accumulate them in that slot's stored
+ *    format (tail rows follow the tail-row contract), and z_1 is folded into the coefficients of steps 1 and 2 as in the other
+ *    forms.  d = 1 is px_i = (x_i r_i) / theta.
+ * 6. Bits: two ELLPACK matrices share one row loop (both gathers in one kernel); any other pair of formats forms B u by the
+ *    metric's own product into a panel; the un-fused A/B path forms both products that way.  All three give the same bits.
+ *    ELLPACK and sliced storage of either matrix give the same bits on every row outside that matrix's tail; repeated calls are
+ *    bit-identical; every output element has one writer; x is unchanged and must not overlap px.  With B stored as the identity
+ *    (one entry 1.0 per row), hi and px have the bits of dla_spmm_cheb_jacobi_upper and dla_spmm_precnd_cheb_jacobi for the same
+ *    A, fac and configuration: every formula above reduces to the scaled form's when b_ii = 1 and offB = 0.
+ * 7. Refusals, through the status of dla_call_precnd, with a message that names dla_spmm_precnd_cheb_pencil and the cause; a
+ *    refused call writes nothing: no operator; no metric; n of the call differs from the operator's; the metric's n differs from
+ *    the operator's; nothing configured; a row-sharded operator.  dla_spmm_cheb_pencil_upper returns hi for a given fac (one
+ *    kernel, one host wait); DLA_ERR_ARG in the same states and for a null hi, and *hi is left alone.
+ * 8. Work memory beside the scaled form's: offB (n doubles, the stored metric's) and one panel for B u (n x m), taken only by the
+ *    paths that need it; they belong to the context, grow behind a stream wait and are released by steps = 0 and by dla_destroy.
+ * 9. Accuracy: px stays within twice the first-order running bound that tests/cheb_pencil_ref.py computes beside its long-double
+ *    reference, wherever that bound is below 1e-9 of the result.
+ * Out of scope: the linear-response parts, row shards, a shared gather for two matrices with the same pattern, choosing d or f
+ * adaptively, sanitizer runs of code loaded into an interpreter, any inspection of kernel assembly. */
+int  dla_spmm_cheb_pencil_upper(dla_ctx* ctx, double fac, double* hi);
+void dla_spmm_precnd_cheb_pencil(const int* n, const int* m, const double* fac, const double* x_dev, double* px_dev);
 
 #ifdef __cplusplus
 }

@@ -364,14 +364,24 @@ class Context:
         self._chk(self.lib.dla_set_allreduce_hook(self.h, C.cast(cb, C.c_void_p), None, nranks, rank))
 
     # ---- block algebra
-    def gram(self, x: DevPanel, u: DevPanel) -> np.ndarray:
-        c = np.zeros((x.m, u.m), order="F")
-        self._chk(self.lib.dla_gram(self.h, x.n, x.m, x.ptr, u.m, u.ptr, _dp(c), max(1, x.m)))
+    # Leading dimensions: a host coefficient block (c, linv, w, y, c2) may have more rows than the product reads -- its row count is
+    # passed as the leading dimension; a host result goes into `out` when one is given (Fortran order, float64, at least the
+    # result's rows: its row count is the leading dimension, rows below the result are left alone) and `out` is returned.
+    @staticmethod
+    def _host_out(out: Optional[np.ndarray], rows: int, cols: int) -> np.ndarray:
+        if out is None:
+            return np.zeros((rows, cols), order="F")
+        assert out.dtype == np.float64 and out.ndim == 2 and out.flags.f_contiguous and out.shape[0] >= rows and out.shape[1] == cols, (out.shape, rows, cols)
+        return out
+
+    def gram(self, x: DevPanel, u: DevPanel, out: Optional[np.ndarray] = None) -> np.ndarray:
+        c = self._host_out(out, x.m, u.m)
+        self._chk(self.lib.dla_gram(self.h, x.n, x.m, x.ptr, u.m, u.ptr, _dp(c), max(1, c.shape[0])))
         return c
 
-    def gram_lower(self, x: DevPanel, u: DevPanel) -> np.ndarray:
-        c = np.zeros((x.m, x.m), order="F")
-        self._chk(self.lib.dla_gram_lower(self.h, x.n, x.m, x.ptr, u.ptr, _dp(c), max(1, x.m)))
+    def gram_lower(self, x: DevPanel, u: DevPanel, out: Optional[np.ndarray] = None) -> np.ndarray:
+        c = self._host_out(out, x.m, x.m)
+        self._chk(self.lib.dla_gram_lower(self.h, x.n, x.m, x.ptr, u.ptr, _dp(c), max(1, c.shape[0])))
         return c
 
     def panel_gemm(self, x: DevPanel, c: np.ndarray, z: DevPanel) -> None:
@@ -386,42 +396,47 @@ class Context:
         linv = np.asfortranarray(linv, dtype=np.float64)
         self._chk(self.lib.dla_trmm_linvt(self.h, u.n, u.m, u.ptr, _dp(linv), linv.shape[0]))
 
-    def trmm_gram(self, u: DevPanel, w: np.ndarray) -> np.ndarray:
-        w = np.asfortranarray(w, dtype=np.float64); g = np.zeros((u.m, u.m), order="F")
-        self._chk(self.lib.dla_trmm_gram(self.h, u.n, u.m, u.ptr, _dp(w), w.shape[0], _dp(g), u.m))
+    def trmm_gram(self, u: DevPanel, w: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
+        w = np.asfortranarray(w, dtype=np.float64); g = self._host_out(out, u.m, u.m)
+        self._chk(self.lib.dla_trmm_gram(self.h, u.n, u.m, u.ptr, _dp(w), w.shape[0], _dp(g), g.shape[0]))
         return g
 
-    def update_gram(self, x: DevPanel, c: np.ndarray, u: DevPanel) -> np.ndarray:
-        c = np.asfortranarray(c, dtype=np.float64); g = np.zeros((u.m, u.m), order="F")
-        self._chk(self.lib.dla_update_gram(self.h, x.n, x.m, x.ptr, u.m, _dp(c), c.shape[0], u.ptr, _dp(g), u.m))
+    def update_gram(self, x: DevPanel, c: np.ndarray, u: DevPanel, out: Optional[np.ndarray] = None) -> np.ndarray:
+        c = np.asfortranarray(c, dtype=np.float64); g = self._host_out(out, u.m, u.m)
+        self._chk(self.lib.dla_update_gram(self.h, x.n, x.m, x.ptr, u.m, _dp(c), c.shape[0], u.ptr, _dp(g), g.shape[0]))
         return g
 
-    def combo_gram(self, x: DevPanel, c: np.ndarray, u: DevPanel) -> np.ndarray:
-        c = np.asfortranarray(c, dtype=np.float64); g = np.zeros((u.m, u.m), order="F")
-        self._chk(self.lib.dla_combo_gram(self.h, x.n, x.m, x.ptr, u.m, _dp(c), c.shape[0], u.ptr, _dp(g), u.m))
+    def combo_gram(self, x: DevPanel, c: np.ndarray, u: DevPanel, out: Optional[np.ndarray] = None) -> np.ndarray:
+        c = np.asfortranarray(c, dtype=np.float64); g = self._host_out(out, u.m, u.m)
+        self._chk(self.lib.dla_combo_gram(self.h, x.n, x.m, x.ptr, u.m, _dp(c), c.shape[0], u.ptr, _dp(g), g.shape[0]))
         return g
 
     def ritz_residual(self, v: DevPanel, av: DevPanel, y: np.ndarray, eig: np.ndarray, n_res: int,
-                      skip: np.ndarray, evec: DevPanel, r: DevPanel, avy: Optional[DevPanel] = None) -> np.ndarray:
+                      skip: np.ndarray, evec: Optional[DevPanel], r: DevPanel, avy: Optional[DevPanel] = None,
+                      m: Optional[int] = None) -> np.ndarray:
+        """evec = None: the Ritz vectors are not written (evec_dev == NULL); the block width is then m (default: the columns of y)"""
         y = np.asfortranarray(y, dtype=np.float64)
+        m = evec.m if evec is not None else (y.shape[1] if m is None else int(m))
         eig = np.ascontiguousarray(eig, dtype=np.float64)
         skip = np.ascontiguousarray(skip, dtype=np.int32)
         rn = np.zeros((2, max(1, n_res)), order="F")
-        self._chk(self.lib.dla_ritz_residual(self.h, v.n, v.m, evec.m, v.ptr, av.ptr, _dp(y), y.shape[0], _dp(eig),
-                                             n_res, skip.ctypes.data_as(c_ip), evec.ptr, r.ptr,
+        self._chk(self.lib.dla_ritz_residual(self.h, v.n, v.m, m, v.ptr, av.ptr, _dp(y), y.shape[0], _dp(eig),
+                                             n_res, skip.ctypes.data_as(c_ip), evec.ptr if evec is not None else None, r.ptr,
                                              avy.ptr if avy is not None else None, _dp(rn)))
         return rn
 
     def ritz_residual_p(self, v: DevPanel, av: DevPanel, y: np.ndarray, eig: np.ndarray, n_res: int, skip: np.ndarray,
-                        evec: DevPanel, r: DevPanel, avy: Optional[DevPanel], c2: np.ndarray, p: DevPanel,
-                        ap: DevPanel) -> np.ndarray:
-        """the Ritz sweep with the extra products p = V c2, ap = AV c2 formed from the same pass over V and AV"""
+                        evec: Optional[DevPanel], r: DevPanel, avy: Optional[DevPanel], c2: np.ndarray, p: DevPanel,
+                        ap: DevPanel, m: Optional[int] = None) -> np.ndarray:
+        """the Ritz sweep with the extra products p = V c2, ap = AV c2 formed from the same pass over V and AV; evec = None and m as
+        in ritz_residual"""
         y = np.asfortranarray(y, dtype=np.float64); c2 = np.asfortranarray(c2, dtype=np.float64)
+        m = evec.m if evec is not None else (y.shape[1] if m is None else int(m))
         eig = np.ascontiguousarray(eig, dtype=np.float64)
         skip = np.ascontiguousarray(skip, dtype=np.int32)
         rn = np.zeros((2, max(1, n_res)), order="F")
-        self._chk(self.lib.dla_ritz_residual_p(self.h, v.n, v.m, evec.m, v.ptr, av.ptr, _dp(y), y.shape[0], _dp(eig),
-                                               n_res, skip.ctypes.data_as(c_ip), evec.ptr, r.ptr,
+        self._chk(self.lib.dla_ritz_residual_p(self.h, v.n, v.m, m, v.ptr, av.ptr, _dp(y), y.shape[0], _dp(eig),
+                                               n_res, skip.ctypes.data_as(c_ip), evec.ptr if evec is not None else None, r.ptr,
                                                avy.ptr if avy is not None else None, _dp(rn),
                                                c2.shape[1], _dp(c2), c2.shape[0], p.ptr, ap.ptr))
         return rn

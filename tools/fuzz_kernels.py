@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
-"""Randomised shape sweep of the block kernels against the oracle (float64 dot-product bound).
+"""Randomised shape sweep of the block kernels.  The panel products, the update and the Ritz sweep go through the guarded checkers
+of tests/dense_ref.py (long-double references, sentinel columns around the outputs, NaN columns around the inputs, NaN rows under the
+coefficient blocks); the Gram matrices against the oracle (float64 dot-product bound).
     python tools/fuzz_kernels.py [cases] [seed]"""
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 from diaglib_amd import capi  # noqa: E402
 from oracle.pyoracle import Oracle  # noqa: E402
+import dense_ref as D  # noqa: E402
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
@@ -24,7 +28,6 @@ for it in range(cases):
     k = int(rng.choice([rng.integers(1, 17), rng.integers(17, 49)]))
     x = np.asfortranarray(rng.standard_normal((n, l)))
     u = np.asfortranarray(rng.standard_normal((n, k)))
-    c = np.asfortranarray(rng.standard_normal((l, k)))
     px, pu = ctx.panel(x), ctx.panel(u)
     errs = {}
     got = ctx.gram(px, pu)
@@ -34,33 +37,26 @@ for it in range(cases):
         want = o.gemm_tn(x, np.asfortranarray(x[:, ::-1]))
         low = np.tril(np.ones((l, l), bool))
         errs["gram_lower"] = np.max((np.abs(gl - want) / (64 * EPS * (np.abs(x).T @ np.abs(x[:, ::-1])) + 1e-300))[low])
-    pz = ctx.panel(n, k)
-    ctx.panel_gemm(px, c, pz)
-    bound = 64 * EPS * (np.abs(x) @ np.abs(c)) + 1e-300
-    errs["gemm"] = np.max(np.abs(pz.download() - o.gemm_nn(x, c)) / bound)
-    ctx.panel_update(px, c, pu)
-    errs["update"] = np.max(np.abs(pu.download() - o.gemm_nn(x, c, alpha=-1.0, beta=1.0, z=u)) / (bound + 4 * EPS * np.abs(u)))
+    pad = int(rng.integers(0, 4))
+    off = [None, None, None, "x", "z"][int(rng.integers(0, 5))]
     m = min(k, 48)
-    y = np.asfortranarray(rng.standard_normal((l, m)))
-    av = np.asfortranarray(rng.standard_normal((n, l)))
-    eig = rng.standard_normal(m)
     nres = int(rng.integers(0, m + 1))
     skip = (rng.random(m) < 0.3).astype(np.int32)
-    pe, pr = ctx.panel(n, m), ctx.panel(n, m)
-    rn = ctx.ritz_residual(px, ctx.panel(av), y, eig, nres, skip, pe, pr)
-    ev = x @ y
-    r = av @ y
-    for i in range(nres):
-        if not skip[i]:
-            r[:, i] -= eig[i] * ev[:, i]
-    b2 = 64 * EPS * (np.abs(x) @ np.abs(y) * (1 + np.abs(eig)[None, :]) + np.abs(av) @ np.abs(y)) + 1e-300
-    errs["ritz_evec"] = np.max(np.abs(pe.download() - ev) / b2)
-    errs["ritz_r"] = np.max(np.abs(pr.download() - r) / b2)
+    some = n > 2000                                 # (long panels: the long-double references on every 97th row and the last 300)
+    for name, check in (("gemm", lambda: D.check_product(ctx, rng, n, l, k, "gemm", off=off, pad=pad, sample=some)[1]),
+                        ("update", lambda: D.check_product(ctx, rng, n, l, k, "update", off=off, pad=pad, sample=some)[1]),
+                        ("ritz", lambda: D.check_ritz(ctx, rng, n, l, m, evec=bool(rng.random() < 0.7), avy=bool(rng.random() < 0.5), n_res=nres,
+                                                      skip=skip, ypad=pad, sample=some)["ratio"])):
+        try:
+            errs[name] = check()
+        except AssertionError as e:
+            errs[name] = float("inf")
+            print("FAIL", name, str(e)[:400], flush=True)
     worst = max(errs.values())
     if worst > 1.0 or not np.isfinite(worst):
         bad += 1
-        print("FAIL", dict(n=n, l=l, k=k, nres=nres), {a: float(b) for a, b in errs.items()}, flush=True)
-    for p in (px, pu, pz, pe, pr):
+        print("FAIL", dict(n=n, l=l, k=k, nres=nres, pad=pad, off=off), {a: float(b) for a, b in errs.items()}, flush=True)
+    for p in (px, pu):
         p.free()
 print(f"{cases} cases, {bad} failures", flush=True)
 sys.exit(1 if bad else 0)

@@ -50,6 +50,8 @@ EXPORTS = [
     "dla_spmm_cheb_pencil_upper", "dla_spmm_precnd_cheb_pencil",
     "dla_spmm_setup_lr_csr", "dla_spmm_setup_lr_csr_dev", "dla_spmm_refresh_lr_values_dev", "dla_spmm_lr_info", "dla_spmm_drop_lr",
     "dla_spmm_apbmul", "dla_spmm_ambmul", "dla_spmm_spdmul", "dla_spmm_smdmul", "dla_spmm_lrprec1", "dla_spmm_lrprec2",
+    "dla_dense_setup", "dla_dense_setup_dev", "dla_dense_info", "dla_dense_drop",
+    "dla_dense_matvec", "dla_dense_bvec", "dla_dense_precnd", "dla_dense_precnd_pencil",
     "dla_davidson_driver", "dla_gen_david_driver", "dla_lobpcg_driver", "dla_caslr_eff_driver", "dla_caslr_driver", "dla_call_lrprec",
     "dla_last_solve_info", "dla_set_solve_info",
 ]
@@ -87,6 +89,11 @@ class SpmmInfo(C.Structure):
 
 class SpmmChebInfo(C.Structure):
     _fields_ = [("steps", C.c_int), ("lo_fraction", C.c_double), ("upper", C.c_double)]
+
+
+class DenseInfo(C.Structure):
+    _fields_ = [("n", C.c_int), ("n_pad", C.c_int), ("row_tile", C.c_int), ("k_chunks", C.c_int), ("device_bytes", C.c_longlong),
+                ("workspace_bytes", C.c_longlong)]
 
 
 class DlaError(RuntimeError):
@@ -175,6 +182,10 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dla_spmm_apbmul": (None, [c_ip, c_ip, vp, vp]), "dla_spmm_ambmul": (None, [c_ip, c_ip, vp, vp]),
         "dla_spmm_spdmul": (None, [c_ip, c_ip, vp, vp]), "dla_spmm_smdmul": (None, [c_ip, c_ip, vp, vp]),
         "dla_spmm_lrprec1": (None, [c_ip, c_ip, c_dp, vp, vp, vp, vp]), "dla_spmm_lrprec2": (None, [c_ip, c_ip, c_dp, vp, vp, vp, vp]),
+        "dla_dense_setup": (i, [vp, i, i, vp, i]), "dla_dense_setup_dev": (i, [vp, i, i, vp, i]),
+        "dla_dense_info": (i, [vp, i, C.POINTER(DenseInfo)]), "dla_dense_drop": (i, [vp, i]),
+        "dla_dense_matvec": (None, [c_ip, c_ip, vp, vp]), "dla_dense_bvec": (None, [c_ip, c_ip, vp, vp]),
+        "dla_dense_precnd": (None, [c_ip, c_ip, c_dp, vp, vp]), "dla_dense_precnd_pencil": (None, [c_ip, c_ip, c_dp, vp, vp]),
         "dla_davidson_driver": (None, [i, i, i, i, i, d, i, d, vp, vp, vp, vp, c_ip]),
         "dla_lobpcg_driver": (None, [i, i, i, i, i, i, d, d, vp, vp, vp, vp, vp, c_ip]),
         "dla_caslr_eff_driver": (None, [i, i, i, i, i, d, i, vp, vp, vp, vp, vp, vp, vp, c_ip]),
@@ -725,6 +736,43 @@ class Context:
     def spmm_drop_lr(self) -> None:
         """free the device blocks of all four parts (nothing happens without any); operator and metric stay as they are"""
         self._chk(self.lib.dla_spmm_drop_lr(self.h))
+
+    # ---- the dense operator and metric (dla_dense_matvec, dla_dense_bvec, dla_dense_precnd, dla_dense_precnd_pencil)
+    def dense_setup(self, a, metric: bool = False) -> None:
+        """hand a dense n x n matrix to this context as its dense operator (metric: the metric B of A x = lambda B x); the library
+        keeps a copy of its own, so ``a`` may be freed or overwritten afterwards.  ``a`` is a NumPy array (made float64 and
+        Fortran-ordered) or a two-dimensional float64 torch tensor on the GPU with unit stride along its rows -- a column-major
+        view such as ``buf.T`` of a C-contiguous ``buf`` -- whose other stride is taken as lda; anything else is refused"""
+        which = int(bool(metric))
+        if isinstance(a, np.ndarray):
+            if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 1:
+                raise ValueError(f"dense_setup: a must be a square two-dimensional array, not of shape {a.shape}")
+            a = np.asfortranarray(a, dtype=np.float64)
+            self._chk(self.lib.dla_dense_setup(self.h, which, a.shape[0], a.ctypes.data, a.shape[0]))
+            return
+        import torch
+        if not isinstance(a, torch.Tensor):
+            raise ValueError(f"dense_setup: a must be a NumPy array or a torch tensor, not {type(a).__name__}")
+        if not a.is_cuda or a.dtype != torch.float64 or a.dim() != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 1:
+            raise ValueError("dense_setup: a device matrix must be a square two-dimensional float64 tensor on the GPU, not "
+                             f"{a.dtype} of shape {tuple(a.shape)} on {a.device}")
+        n = a.shape[0]
+        lda = n if n == 1 else a.stride(1)
+        if (n > 1 and a.stride(0) != 1) or lda < n:
+            raise ValueError(f"dense_setup: a device matrix must have unit stride along its rows and lda >= n (column-major); its strides are {a.stride()}")
+        torch.cuda.current_stream(a.device).synchronize()      # the tensor is complete before the library reads it
+        self._chk(self.lib.dla_dense_setup_dev(self.h, which, n, a.data_ptr(), lda))
+
+    def dense_info(self, metric: bool = False) -> dict:
+        """what the dense operator (metric: the metric) occupies: n, n_pad, row_tile, k_chunks, device_bytes, workspace_bytes
+        (include/diaglib_amd.h, dla_dense_info); raises while the slot is empty"""
+        o = DenseInfo()
+        self._chk(self.lib.dla_dense_info(self.h, int(bool(metric)), C.byref(o)))
+        return {name: int(getattr(o, name)) for name, _ in DenseInfo._fields_}
+
+    def dense_drop(self, metric: bool = False) -> None:
+        """free the dense operator's (metric: the metric's) device blocks; nothing happens where nothing is stored"""
+        self._chk(self.lib.dla_dense_drop(self.h, int(bool(metric))))
 
     def synth_matvec(self, x: DevPanel, ax: DevPanel) -> None:
         self._chk(self.lib.dla_call_matvec(self.h, fn_address("dla_synth_matvec"), x.n, x.m, x.ptr, ax.ptr))

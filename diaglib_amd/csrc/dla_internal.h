@@ -319,6 +319,17 @@ struct Engine : BlockOps {
   virtual int spmm_precnd_cheb_pencil(int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return DLA_ERR_ARG; }
   virtual int spmm_cheb_pencil_upper(double /*fac*/, double* /*hi*/) { return DLA_ERR_ARG; }
 
+  // ---- the stored dense matrices (the contract: include/diaglib_amd.h, dla_dense_setup): which = 0 the operator A, 1 the metric B,
+  // each the library's own copy of a column-major a(lda, n) in host (via = SPMM_VIA_HOST) or device memory (SPMM_VIA_DEVICE), with
+  // its diagonal beside it; independent of each other and of the sparse slots.  dense_precnd: x / (a_ii + fac), or with pencil
+  // x / (a_ii + fac b_ii).  An engine without them (the host-memory test engine) refuses every call.
+  int no_dense() { err = "this engine stores no dense matrix"; return DLA_ERR_ARG; }
+  virtual int dense_setup(int /*which*/, int /*via*/, int /*n*/, const double* /*a*/, int /*lda*/) { return no_dense(); }
+  virtual int dense_info(int /*which*/, struct dla_dense_info* /*out*/) { return no_dense(); }
+  virtual int dense_drop(int /*which*/) { return no_dense(); }
+  virtual int dense_mul(int /*which*/, int /*n*/, int /*m*/, const double* /*x*/, double* /*y*/) { return no_dense(); }
+  virtual int dense_precnd(bool /*pencil*/, int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return no_dense(); }
+
   // Staging pipeline of host-mode callbacks: column chunks of a block travel device -> host on one copy stream, the
   // user's routine works on the chunk that has arrived, finished chunks travel host -> device on a second copy stream
   // (PCIe is full duplex), and the engine's own stream only waits for the last upload -- no host wait at the end.

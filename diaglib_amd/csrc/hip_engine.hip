@@ -2277,6 +2277,101 @@ __global__ void pencil_precnd_kernel(int n, int m, double fac, const double* __r
   }
 }
 
+// ---- the dense operator and metric (the contract: include/diaglib_amd.h, dla_dense_setup; layout and plan: hip_plans.h, dense_plan)
+// The library's copy of a column-major a(lda, n) in device memory: one thread per STORED element, so the writes are contiguous and
+// every padded element gets its 0.0; the reads walk 16 consecutive rows of a column.  The same map as dense_pack on the host.
+__global__ void dense_pack_kernel(int n, int n_pad, const double* __restrict__ a, size_t lda, double* __restrict__ stored)
+{
+  const size_t total = (size_t)n_pad * n_pad, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t d = (size_t)blockIdx.x * blockDim.x + threadIdx.x; d < total; d += stride) {
+    const int i = dense_row_of(n_pad, d), k = dense_col_of(n_pad, d);
+    stored[d] = (i < n && k < n) ? a[(size_t)k * lda + i] : 0.0;
+  }
+}
+__global__ void dense_diag_kernel(int n, const double* __restrict__ a, size_t lda, double* __restrict__ diag)
+{
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) diag[i] = a[(size_t)i * lda + i];
+}
+
+// One pass Y(n x m) = A X, m <= 16 G, on the stored copy, RT = DENSE_WAVE_TILES.  Block (bx, by): four wavefronts, wavefront w owns the RT row
+// tiles of row group 4 bx + w and all of them contraction chunk by (groups [by chunk_groups, ...)): the four read the same
+// fragments of X at about the same time.  Per group a wavefront loads RT x 1024 contiguous bytes of A (one 16-byte
+// load per lane and tile, no bounds check: a row group that reaches beyond the last tile reads that tile again and stores
+// nothing for it) and 2 G doubles of X per lane, and issues 2 G RT v_mfma_f64_16x16x4 with X as the A operand
+// (lane: column lane & 15 of the group, contraction index lane >> 4) and the matrix as the B operand: the accumulator of lane l then
+// holds matrix row l & 15 for the columns (l >> 4) + 4 r, so a store writes 16 consecutive rows of four columns.
+// X has leading dimension n, which may be odd: its elements are loaded one by one (8-byte alignment is all they have), and indices
+// at or beyond n -- where the stored copy holds zeros -- are not loaded at all.
+// k_chunks = 1 (gridDim.y == 1): the result goes to y.  Otherwise chunk by goes to ws[by][m][n], for dense_combine_kernel.
+template <int G>
+__global__ __launch_bounds__(256) void dense_mfma_kernel(int n, int m, int n_pad, int chunk_groups, const double* __restrict__ a,
+                                                          const double* __restrict__ x, double* __restrict__ y, double* __restrict__ ws)
+{
+  constexpr int RT = DENSE_WAVE_TILES;
+  const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
+  const int row_tiles = n_pad / DENSE_TILE, groups = n_pad / DENSE_GROUP;
+  const int tile0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RT;
+  if (tile0 >= row_tiles) return;
+  const int g0 = blockIdx.y * chunk_groups, g1 = min(groups, g0 + chunk_groups);
+  const v2d* ap[RT];
+#pragma unroll
+  for (int t = 0; t < RT; ++t) ap[t] = (const v2d*)a + (size_t)min(tile0 + t, row_tiles - 1) * groups * 64 + lane;
+  const double* xp[G];
+  bool xin[G];
+#pragma unroll
+  for (int q = 0; q < G; ++q) {
+    xin[q] = 16 * q + li < m;
+    xp[q] = x + (size_t)(xin[q] ? 16 * q + li : 0) * n + lk;
+  }
+  v4d acc[RT][G];
+#pragma unroll
+  for (int t = 0; t < RT; ++t)
+#pragma unroll
+    for (int q = 0; q < G; ++q) acc[t][q] = v4d{0.0, 0.0, 0.0, 0.0};
+#pragma unroll 2
+  for (int g = g0; g < g1; ++g) {
+    v2d av[RT];
+#pragma unroll
+    for (int t = 0; t < RT; ++t) av[t] = ap[t][(size_t)g * 64];
+    const int k = DENSE_GROUP * g + lk;
+    double xv[G][2];
+#pragma unroll
+    for (int q = 0; q < G; ++q) {
+      xv[q][0] = (xin[q] && k < n) ? xp[q][DENSE_GROUP * g] : 0.0;
+      xv[q][1] = (xin[q] && k + 4 < n) ? xp[q][DENSE_GROUP * g + 4] : 0.0;
+    }
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+      for (int q = 0; q < G; ++q)
+#pragma unroll
+        for (int t = 0; t < RT; ++t) acc[t][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(xv[q][e], av[t][e], acc[t][q], 0, 0, 0);
+  }
+  double* dst = gridDim.y == 1 ? y : ws + (size_t)blockIdx.y * m * n;
+#pragma unroll
+  for (int t = 0; t < RT; ++t) {
+    const int row = (tile0 + t) * DENSE_TILE + li;
+    if (tile0 + t >= row_tiles || row >= n) continue;
+#pragma unroll
+    for (int q = 0; q < G; ++q)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int c = 16 * q + lk + 4 * r;
+        if (c < m) dst[(size_t)c * n + row] = acc[t][q][r];
+      }
+  }
+}
+// y = ((p_0 + p_1) + p_2) + ... over the chunks of a split pass, in ascending chunk order, one thread per element
+__global__ void dense_combine_kernel(size_t total, int k_chunks, const double* __restrict__ ws, double* __restrict__ y)
+{
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    double s = ws[i];
+    for (int c = 1; c < k_chunks; ++c) s += ws[(size_t)c * total + i];
+    y[i] = s;
+  }
+}
+
 // The harness' lrprec_1 / lrprec_2 (main.f90:234-281; synth_lrprec_kernel restates them) on the stored diagonals of the sparse
 // linear-response parts (dla_spmm_setup_lr_csr): aa = ((A+B)_ii + (A-B)_ii) / 2, sg = (S+D)_ii (D is antisymmetric: its diagonal
 // is zero, so S+D carries the diagonal of S).  One thread keeps VEC rows of the three diagonals in registers -- read once -- and
@@ -6650,6 +6745,146 @@ struct HipEngine : dla::Engine {
     if (n != ops[dla::SPMM_A].n) { err = "spmm_precnd_pencil: n differs from setup"; return DLA_ERR_ARG; }
     Scope s(this, DLA_OP_PRECND, 16.0 * (double)n * m + 16.0 * (double)n, 2.0 * (double)n * m);
     DLA_LAUNCH(pencil_precnd_kernel, dim3(grid_blocks(env(), n, 256)), dim3(256), 0, st, n, m, fac, ops[dla::SPMM_A].diagonal(), ops[dla::SPMM_B].diagonal(), x, px);
+    HIPCHK(hipGetLastError());
+    return DLA_OK;
+  }
+
+  // ---- the stored dense matrices (the contract: include/diaglib_amd.h, dla_dense_setup; the kernels: beside dense_mfma_kernel).
+  // Two slots, the operator and the metric, each the packed copy, its diagonal and the workspace of a split product.  The blocks
+  // only grow: a smaller matrix after a larger one keeps the larger blocks (the kernels go by n / n_pad).
+  struct DenseOp {
+    int n = 0;                       // 0: nothing stored
+    int last_m = 1;                  // width of the first pass of the most recent product (what dense_info describes)
+    DeviceBuffer<double> a, diag, ws;
+    void drop() { a.reset(); diag.reset(); ws.reset(); n = 0; last_m = 1; }
+  } dense[2];
+  static const char* dense_noun(int which) { return which ? "dense metric" : "dense operator"; }
+  int dense_setup(int which, int via, int n, const double* a, int lda) override
+  {
+    const bool dev = via == dla::SPMM_VIA_DEVICE;
+    const std::string who = dev ? "dla_dense_setup_dev: " : "dla_dense_setup: ";
+    if (which != 0 && which != 1) { err = who + "which must be 0 (the operator) or 1 (the metric)"; return DLA_ERR_ARG; }
+    if (!a) { err = who + "the matrix is a null pointer"; return DLA_ERR_ARG; }
+    if (n <= 0) { err = who + "n must be positive"; return DLA_ERR_ARG; }
+    if (lda < n) { err = who + "lda = " + std::to_string(lda) + " is below n = " + std::to_string(n); return DLA_ERR_ARG; }
+    DenseOp& op = dense[which];
+    const int n_pad = dense_n_pad(n);
+    const size_t total = (size_t)n_pad * n_pad;
+    std::vector<double> packed, diag;
+    if (!dev) {
+      try { packed.resize(total); diag.resize((size_t)n); }
+      catch (const std::bad_alloc&) { err = who + "no host memory for the packed copy"; return DLA_ERR_ALLOC; }
+      dense_pack(n, a, (size_t)lda, packed.data(), diag.data());
+    }
+    bind();
+    HIPCHK(hipStreamSynchronize(st));      // (queued products may still read the old blocks)
+    // (a block that has to grow is released first: from here on a failure leaves the slot empty, not half replaced)
+    op.n = 0; op.last_m = 1;
+    if (op.a.reserve(total) != hipSuccess || op.diag.reserve((size_t)n) != hipSuccess) {
+      op.drop();
+      err = who + "no device memory for " + std::to_string(8 * total + 8 * (size_t)n) + " bytes";
+      return DLA_ERR_ALLOC;
+    }
+    if (dev) {
+      DLA_LAUNCH(dense_pack_kernel, dim3(grid_blocks(env(), (long long)total, 256)), dim3(256), 0, st, n, n_pad, a, (size_t)lda, (double*)op.a);
+      HIPCHK(hipGetLastError());
+      DLA_LAUNCH(dense_diag_kernel, dim3(grid_blocks(env(), n, 256)), dim3(256), 0, st, n, a, (size_t)lda, (double*)op.diag);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(st));
+    } else {
+      HIPCHK(hipMemcpy(op.a, packed.data(), sizeof(double) * total, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(op.diag, diag.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    }
+    op.n = n;
+    return DLA_OK;
+  }
+  int dense_info(int which, struct dla_dense_info* out) override
+  {
+    if (which != 0 && which != 1) { err = "dla_dense_info: which must be 0 (the operator) or 1 (the metric)"; return DLA_ERR_ARG; }
+    if (!out) { err = "dla_dense_info: out is a null pointer"; return DLA_ERR_ARG; }
+    const DenseOp& op = dense[which];
+    if (op.n <= 0) { err = std::string("dla_dense_info: no ") + dense_noun(which) + " has been set up"; return DLA_ERR_ARG; }
+    const DensePlan p = dense_plan(ncu, op.n, op.last_m);
+    out->n = op.n; out->n_pad = p.n_pad; out->row_tile = DENSE_TILE * DENSE_WAVE_TILES; out->k_chunks = p.k_chunks;
+    out->device_bytes = 8LL * p.n_pad * p.n_pad + 8LL * op.n;
+    out->workspace_bytes = 8LL * (long long)p.ws_doubles;
+    return DLA_OK;
+  }
+  // (nothing stored: neither the device nor the stream is touched)
+  int dense_drop(int which) override
+  {
+    if (which != 0 && which != 1) { err = "dla_dense_drop: which must be 0 (the operator) or 1 (the metric)"; return DLA_ERR_ARG; }
+    if (dense[which].n <= 0 && !dense[which].a) return DLA_OK;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipStreamSynchronize(st));     // (products of this slot may still be queued)
+    dense[which].drop();
+    return DLA_OK;
+  }
+  // what a dense callback needs of its slot; who: the callback's name
+  int dense_admit(const std::string& who, int which, int n)
+  {
+    const DenseOp& op = dense[which];
+    if (op.n <= 0) { err = who + ": no " + dense_noun(which) + " has been set up (dla_dense_setup)"; return DLA_ERR_ARG; }
+    if (n != op.n) { err = who + ": n = " + std::to_string(n) + " differs from the " + std::to_string(op.n) + " rows of the " + dense_noun(which); return DLA_ERR_ARG; }
+    return DLA_OK;
+  }
+  int dense_mul(int which, int n, int m, const double* x, double* y) override
+  {
+    if (which != 0 && which != 1) { err = "dense product: no such slot"; return DLA_ERR_ARG; }
+    { const int stc = dense_admit(which ? "dense_bvec" : "dense_matvec", which, n); if (stc) return stc; }
+    if (m <= 0) return DLA_OK;
+    DenseOp& op = dense[which];
+    op.last_m = std::min(m, DENSE_MAX_COLS);
+    for (int c0 = 0; c0 < m; c0 += DENSE_MAX_COLS) {
+      const int mp = std::min(DENSE_MAX_COLS, m - c0);
+      const DensePlan p = dense_plan(ncu, n, mp);
+      if (p.ws_doubles > op.ws.capacity()) {
+        bind();
+        HIPCHK(hipStreamSynchronize(st));       // (queued products may still use the old block)
+        HIPCHK(op.ws.reserve(p.ws_doubles));
+      }
+      const double* xc = x + (size_t)c0 * n;
+      double* yc = y + (size_t)c0 * n;
+      const dim3 grid((p.row_groups + 3) / 4, p.k_chunks);
+      {
+        Scope s(this, DLA_OP_MATVEC, 8.0 * (double)n * n + 16.0 * (double)n * mp, 2.0 * (double)n * n * mp, p.name());
+        const bool hit = first_instance<DENSE_MAX_COLS / 16>([&](auto i) {
+          constexpr int G = (int)decltype(i)::value + 1;
+          if (p.acc_groups != G) return false;
+          DLA_LAUNCH((dense_mfma_kernel<G>), grid, dim3(256), 0, st, n, mp, p.n_pad, p.chunk_groups, (const double*)op.a, xc, yc, (double*)op.ws);
+          return true;
+        });
+        if (!hit) { err = "dense product: no kernel instance"; return DLA_ERR_RUNTIME; }
+        HIPCHK(hipGetLastError());
+      }
+      if (p.k_chunks > 1) {
+        // (the partial sums are not compulsory traffic: the launch is booked without algorithmic bytes)
+        Scope s(this, DLA_OP_MATVEC, 0.0, 0.0, "dense_combine_kernel");
+        const size_t total = (size_t)n * mp;
+        DLA_LAUNCH(dense_combine_kernel, dim3(grid_blocks(env(), (long long)total, 256)), dim3(256), 0, st, total, p.k_chunks, (const double*)op.ws, yc);
+        HIPCHK(hipGetLastError());
+      }
+    }
+    return DLA_OK;
+  }
+  // the diagonal kernels of the sparse operator on the stored dense diagonals
+  int dense_precnd(bool pencil, int n, int m, double fac, const double* x, double* px) override
+  {
+    const std::string who = pencil ? "dense_precnd_pencil" : "dense_precnd";
+    { const int stc = dense_admit(who, 0, n); if (stc) return stc; }
+    if (pencil) {
+      if (dense[1].n <= 0) { err = who + ": no dense metric has been set up (dla_dense_setup with which = 1)"; return DLA_ERR_ARG; }
+      if (dense[1].n != dense[0].n) { err = who + ": the operator has " + std::to_string(dense[0].n) + " rows and the metric " + std::to_string(dense[1].n); return DLA_ERR_ARG; }
+    }
+    if (m <= 0) return DLA_OK;
+    const dim3 grid(grid_blocks(env(), n, 256));
+    if (pencil) {
+      Scope s(this, DLA_OP_PRECND, 16.0 * (double)n * m + 16.0 * (double)n, 2.0 * (double)n * m, "pencil_precnd_kernel");
+      DLA_LAUNCH(pencil_precnd_kernel, grid, dim3(256), 0, st, n, m, fac, (const double*)dense[0].diag, (const double*)dense[1].diag, x, px);
+    } else {
+      Scope s(this, DLA_OP_PRECND, 8.0 * n * (2.0 * m + 1.0), (double)n * m, "diag_precnd_kernel");
+      DLA_LAUNCH(diag_precnd_kernel, grid, dim3(256), 0, st, n, m, fac, (const double*)dense[0].diag, x, px);
+    }
     HIPCHK(hipGetLastError());
     return DLA_OK;
   }

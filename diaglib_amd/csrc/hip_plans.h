@@ -621,4 +621,76 @@ inline std::vector<int> close_plan(std::vector<int> plan, bool lean, bool x3)
   return plan;
 }
 
+// ---- the dense operator and metric (include/diaglib_amd.h, dla_dense_setup): the stored layout and the plan of a product
+// The library's copy of a(lda, n) is laid out for the B operand of v_mfma_f64_16x16x4 (one f64 per lane, element [k = lane >> 4]
+// [j = lane & 15]): the matrix is cut into tiles of DENSE_TILE = 16 rows, every tile into groups of DENSE_GROUP = 8 consecutive
+// contraction indices, and a group stores 128 doubles, lane-major -- lane l = 16 (k mod 4) + (i mod 16) holds the pair
+// [a(i, 8 g + l / 16), a(i, 8 g + 4 + l / 16)], the operands of two consecutive MFMA steps.  A wavefront's load of a group is one
+// 16-byte load per lane over 1024 contiguous bytes with no bounds check: rows and contraction indices are zero-padded to
+// n_pad = n rounded up to 16 (zeros add no rounding).  Groups of a tile are consecutive, tiles follow each other.
+constexpr int DENSE_TILE = 16, DENSE_GROUP = 8, DENSE_MAX_COLS = 48;
+// row tiles a wavefront multiplies with one X fragment (64 rows).  A starting value.  The one alternative measured so far, two
+// tiles for passes of two and three accumulator groups (fewer registers, more wavefronts per SIMD), was slower at n = 8192 and 32768,
+// m = 37 (0.32 against 0.23 ms, 4.66 against 3.28 ms): such a pass reads more bytes of X fragments through the caches than of A
+// from HBM, and halving the tiles doubles them.
+constexpr int DENSE_WAVE_TILES = 4;
+// a contraction chunk is at least this many groups (64 indices), and the partial sums of a split product may move at most
+// 1 / DENSE_WS_SHARE of the matrix's bytes.  Starting values as well.
+constexpr int DENSE_MIN_CHUNK_GROUPS = 8, DENSE_WS_SHARE = 8;
+
+constexpr int dense_n_pad(int n) { return (n + DENSE_TILE - 1) / DENSE_TILE * DENSE_TILE; }
+// where a(i, k) lives in the stored copy (0-based, both below n_pad)
+constexpr size_t dense_index(int n_pad, int i, int k)
+{
+  return (((size_t)(i / DENSE_TILE) * (size_t)(n_pad / DENSE_GROUP) + (size_t)(k / DENSE_GROUP)) * 64 + (size_t)((k % 4) * 16 + i % DENSE_TILE)) * 2 +
+         (size_t)((k % DENSE_GROUP) / 4);
+}
+// ... and back: the row and the contraction index of stored element d (what the pack kernel runs, one thread per element)
+constexpr int dense_row_of(int n_pad, size_t d) { return (int)(d / 128 / (size_t)(n_pad / DENSE_GROUP)) * DENSE_TILE + (int)((d >> 1) & 15); }
+constexpr int dense_col_of(int n_pad, size_t d)
+{
+  return (int)(d / 128 % (size_t)(n_pad / DENSE_GROUP)) * DENSE_GROUP + (int)(d & 1) * 4 + (int)((d >> 5) & 3);
+}
+// the copy (n_pad x n_pad doubles) and the diagonal (n doubles) of a column-major host array: what dla_dense_setup uploads
+inline void dense_pack(int n, const double* a, size_t lda, double* stored, double* diag)
+{
+  const int n_pad = dense_n_pad(n);
+  std::fill(stored, stored + (size_t)n_pad * n_pad, 0.0);
+  for (int k = 0; k < n; ++k)
+    for (int i = 0; i < n; ++i) stored[dense_index(n_pad, i, k)] = a[(size_t)k * lda + i];
+  for (int i = 0; i < n; ++i) diag[i] = a[(size_t)i * lda + i];
+}
+
+// One pass of a product Y(n x m) = A X, m <= DENSE_MAX_COLS: a pure function of n, m and the CU count.
+// A wavefront owns DENSE_WAVE_TILES row tiles and one chunk of the contraction, so there are row_groups x k_chunks of them.  The rule
+// for k_chunks: as many as give every SIMD of the device a wavefront (4 ncu / row_groups, rounded up), but
+//   * the partial sums are written and read once, 2 k_chunks n m 8 bytes, and that may be at most 1 / DENSE_WS_SHARE of the 8 n^2
+//     bytes of the matrix: k_chunks <= n / (2 DENSE_WS_SHARE m);
+//   * a chunk keeps at least DENSE_MIN_CHUNK_GROUPS groups: k_chunks <= groups / DENSE_MIN_CHUNK_GROUPS;
+// and never less than 1.  Chunks are chunk_groups = ceil(groups / k_chunks) groups long -- chunk c covers the contraction indices
+// [8 c chunk_groups, min(n_pad, 8 (c + 1) chunk_groups)) -- and k_chunks is then the number of chunks that are not empty.
+struct DensePlan {
+  int n_pad, row_tiles, row_groups, groups;   // groups: n_pad / DENSE_GROUP
+  int acc_groups;                             // accumulator groups of 16 columns (the kernel's instance): 1 .. 3
+  int k_chunks, chunk_groups;
+  size_t ws_doubles;                          // the workspace of partial sums: k_chunks x m x n, 0 with one chunk
+  std::string name() const { return plan_name("dense_mfma_kernel<%d>", acc_groups); }
+};
+inline DensePlan dense_plan(int ncu, int n, int m)
+{
+  DensePlan p{};
+  p.n_pad = dense_n_pad(n);
+  p.row_tiles = p.n_pad / DENSE_TILE;
+  p.acc_groups = (m + 15) / 16;
+  p.row_groups = (p.row_tiles + DENSE_WAVE_TILES - 1) / DENSE_WAVE_TILES;
+  p.groups = p.n_pad / DENSE_GROUP;
+  const long long want = (4LL * std::max(1, ncu) + p.row_groups - 1) / p.row_groups;
+  const long long traffic = (long long)n / (2LL * DENSE_WS_SHARE * m), length = p.groups / DENSE_MIN_CHUNK_GROUPS;
+  const int chunks = (int)std::max(1LL, std::min(want, std::min(traffic, length)));
+  p.chunk_groups = (p.groups + chunks - 1) / chunks;
+  p.k_chunks = (p.groups + p.chunk_groups - 1) / p.chunk_groups;
+  p.ws_doubles = p.k_chunks > 1 ? (size_t)p.k_chunks * (size_t)m * (size_t)n : 0;
+  return p;
+}
+
 }  // namespace dla_plans

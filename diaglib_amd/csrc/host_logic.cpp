@@ -67,6 +67,7 @@ thread_local DefaultCtxOwner g_default_owner;
 // built-in operator callbacks have the reference's context-free shape; they act on the calling thread's setup
 thread_local dla_ctx* g_synth_ctx = nullptr;
 thread_local dla_ctx* g_spmm_ctx = nullptr;
+thread_local dla_ctx* g_dense_ctx = nullptr;   // the dense operator / metric (dla_dense_setup): a binding of its own
 // The sample operators have the reference's callback shape -- void, no status (README.md:34-35) -- so a failure inside one (used before
 // its setup, an engine error) is left here for the trampoline that called it: dla_call_matvec / dla_call_precnd / dla_call_lrprec
 // return it as their own status (the Fortran drivers then end the program the way they end it for every engine failure).  Nothing
@@ -160,6 +161,7 @@ int dla_destroy(dla_ctx* c)
   if (g_default == c) g_default = nullptr;
   if (g_synth_ctx == c) g_synth_ctx = nullptr;
   if (g_spmm_ctx == c) g_spmm_ctx = nullptr;
+  if (g_dense_ctx == c) g_dense_ctx = nullptr;
   delete c;
   return DLA_OK;
 }
@@ -1235,7 +1237,9 @@ static const OwnCallback* own_callback(void* fn)
     {(void*)&dla_synth_precnd, false, true}, {(void*)&dla_spmm_precnd, false, true}, {(void*)&dla_spmm_precnd_pencil, false, true},
     {(void*)&dla_synth_lrprec1, false, true}, {(void*)&dla_synth_lrprec2, false, true}, {(void*)&dla_spmm_lrprec1, false, true},
     {(void*)&dla_spmm_lrprec2, false, true}, {(void*)&dla_spmm_precnd_cheb, false, true},
-    {(void*)&dla_spmm_precnd_cheb_jacobi, false, true}, {(void*)&dla_spmm_precnd_cheb_pencil, false, true}};
+    {(void*)&dla_spmm_precnd_cheb_jacobi, false, true}, {(void*)&dla_spmm_precnd_cheb_pencil, false, true},
+    {(void*)&dla_dense_matvec, true, true}, {(void*)&dla_dense_bvec, true, true},
+    {(void*)&dla_dense_precnd, false, true}, {(void*)&dla_dense_precnd_pencil, false, true}};
   for (const OwnCallback& r : table)
     if (r.fn == fn) return &r;
   return nullptr;
@@ -2025,5 +2029,56 @@ void dla_spmm_spdmul(const int* n, const int* m, const double* x, double* y) { s
 void dla_spmm_smdmul(const int* n, const int* m, const double* x, double* y) { spmm_product(dla::SPMM_SMD, n, m, x, y); }
 void dla_spmm_lrprec1(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { spmm_precondition(2, n, m, fac, xp, xm, yp, ym); }
 void dla_spmm_lrprec2(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { spmm_precondition(3, n, m, fac, xp, xm, yp, ym); }
+
+// ------------------------------------------------------------------ the stored dense matrices (include/diaglib_amd.h, dla_dense_setup)
+// which = 0 the operator A, 1 the metric B.  An accepted set-up binds its context to the calling thread's dense callbacks
+// (g_dense_ctx); info and drop never do.
+static int dense_set_up(dla_ctx* c, int which, int via, int n, const double* a, int lda)
+{
+  if (!c) return DLA_ERR_ARG;
+  const int st = engfail(c, c->eng->dense_setup(which, via, n, a, lda));
+  if (st == DLA_OK) g_dense_ctx = c;
+  return st;
+}
+int dla_dense_setup(dla_ctx* c, int which, int n, const double* a_host, int lda)
+{
+  DLA_T("dla_dense_setup");
+  return dense_set_up(c, which, dla::SPMM_VIA_HOST, n, a_host, lda);
+}
+int dla_dense_setup_dev(dla_ctx* c, int which, int n, const double* a_dev, int lda)
+{
+  DLA_T("dla_dense_setup_dev");
+  return dense_set_up(c, which, dla::SPMM_VIA_DEVICE, n, a_dev, lda);
+}
+int dla_dense_info(dla_ctx* c, int which, struct dla_dense_info* out)
+{
+  if (!c) return DLA_ERR_ARG;
+  return engfail(c, c->eng->dense_info(which, out));
+}
+int dla_dense_drop(dla_ctx* c, int which)
+{
+  if (!c) return DLA_ERR_ARG;
+  return engfail(c, c->eng->dense_drop(which));
+}
+static void dense_product(int which, const int* n, const int* m, const double* x, double* y)
+{
+  static const SpmmCallback words[2] = {{"dla_dense_matvec before dla_dense_setup: no dense operator has been set up", "dla_dense_matvec failed: "},
+                                        {"dla_dense_bvec before dla_dense_setup: no dense metric has been set up", "dla_dense_bvec failed: "}};
+  dla_ctx* c = g_dense_ctx;
+  if (!c) { callback_failed(DLA_ERR_ARG, words[which].unbound); return; }
+  if (int st = c->eng->dense_mul(which, *n, *m, x, y)) callback_failed(st, words[which].failed + c->eng->err);
+}
+static void dense_precondition(bool pencil, const int* n, const int* m, const double* fac, const double* x, double* px)
+{
+  static const SpmmCallback words[2] = {{"dla_dense_precnd before dla_dense_setup: no dense operator has been set up", "dla_dense_precnd failed: "},
+                                        {"dla_dense_precnd_pencil before dla_dense_setup: no dense operator has been set up", "dla_dense_precnd_pencil failed: "}};
+  dla_ctx* c = g_dense_ctx;
+  if (!c) { callback_failed(DLA_ERR_ARG, words[pencil].unbound); return; }
+  if (int st = c->eng->dense_precnd(pencil, *n, *m, *fac, x, px)) callback_failed(st, words[pencil].failed + c->eng->err);
+}
+void dla_dense_matvec(const int* n, const int* m, const double* x, double* ax) { dense_product(0, n, m, x, ax); }
+void dla_dense_bvec(const int* n, const int* m, const double* x, double* bx) { dense_product(1, n, m, x, bx); }
+void dla_dense_precnd(const int* n, const int* m, const double* fac, const double* x, double* px) { dense_precondition(false, n, m, fac, x, px); }
+void dla_dense_precnd_pencil(const int* n, const int* m, const double* fac, const double* x, double* px) { dense_precondition(true, n, m, fac, x, px); }
 
 }  // extern "C"

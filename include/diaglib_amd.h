@@ -90,7 +90,7 @@ enum {
                                       takes another route than planned the operator is called a SECOND time on the finished
                                       block and its first output is dropped -- the reference calls matvec exactly once per
                                       block (diaglib.f90:1685, 394-397), so:
-                                      1 (default): only for the library's own device operators (dla_synth_*, dla_spmm_matvec, dla_spmm_bvec, dla_spmm_apbmul .. _smdmul),
+                                      1 (default): only for the library's own device operators (dla_synth_*, dla_spmm_matvec, dla_spmm_bvec, dla_spmm_apbmul .. _smdmul, dla_dense_matvec, dla_dense_bvec),
                                          which are pure functions of their input; a caller's callback is called once, in order;
                                       2: also for the caller's device-mode callbacks (ordering contract 0 or 2) -- the caller
                                          states that the operator keeps no state between calls;
@@ -710,6 +710,67 @@ void dla_spmm_precnd_cheb_jacobi(const int* n, const int* m, const double* fac, 
  * adaptively, sanitizer runs of code loaded into an interpreter, any inspection of kernel assembly. */
 int  dla_spmm_cheb_pencil_upper(dla_ctx* ctx, double fac, double* hi);
 void dla_spmm_precnd_cheb_pencil(const int* n, const int* m, const double* fac, const double* x_dev, double* px_dev);
+
+/* ---------------------------------------------------------------- dense device operator and metric
+ * The reference's own test problem is a DENSE symmetric matrix (main.f90:311-317: a_ii = i + 1, a_ij = 1 / (i + j)) applied by
+ * mmult, preconditioned by mprec and paired with a dense SPD metric (smult).  A caller that holds a(n,n) in memory hands it over
+ * once; dla_dense_matvec / dla_dense_bvec / dla_dense_precnd / dla_dense_precnd_pencil then have the reference's callback shapes
+ * matvec(n,m,x,ax) / bvec(n,m,x,bx) / precnd(n,m,fac,x,px), expect DEVICE addresses (DLA_OPT_CALLBACKS_ON_DEVICE = 1) and go where
+ * the host routines go in davidson_driver, lobpcg_driver, gen_david_driver and lobpcg_driver(gen_eig): the whole solve stays in HBM.
+ * Set-up and storage.  a is column-major, n x n, leading dimension lda >= n: the Fortran a(lda, n); which = 0 is the operator A,
+ * 1 the metric B.  The library keeps ITS OWN COPY in a layout of its choosing (below), so the caller may free or overwrite the
+ * array when the call returns.  The call is synchronous like dla_spmm_setup_csr_dev: a device array is read on the context's
+ * stream (dla_stream) and the call returns after that stream has been waited for; the caller is responsible for its own producer
+ * of the array having finished before the call.  Host set-up and device set-up of the same values store the same bits, and every
+ * later call returns the same bits.  A second set-up of a slot replaces it; allocations only grow; a refused set-up replaces
+ * nothing.  dla_dense_info answers DLA_ERR_ARG while the slot is empty.  diag[i] = a(i,i) is stored beside the matrix (n doubles):
+ * the two preconditioners are the kernels of dla_spmm_precnd / dla_spmm_precnd_pencil on these vectors -- x / (a_ii + fac) resp.
+ * x / (a_ii + fac b_ii) where the magnitude of the denominator exceeds 1e-5, else x (mprec, main.f90:146-171) -- and return the
+ * bits a host caller gets from the same expressions (the product fac b_ii rounded before the sum).
+ * Layout.  Rows and contraction indices are zero-padded to n_pad = n rounded up to 16.  The matrix is cut into tiles of 16 rows and
+ * every tile into groups of 8 contraction indices; a group is 128 doubles in the order of the B operand of v_mfma_f64_16x16x4,
+ * lane l = 16 (k mod 4) + (i mod 16) holding the pair [a(i, 8 g + l / 16), a(i, 8 g + 4 + l / 16)]: a wavefront loads a group as
+ * 1024 contiguous bytes with no bounds check.  device_bytes = 8 n_pad^2 + 8 n.  row_tile = 64: the rows a wavefront multiplies
+ * with one fragment of x (four tiles).
+ * No symmetry assumed: row i of the result is row i of what was handed over times x.
+ * The product.  One pass takes up to 48 columns of x and reads the matrix once; a wider block takes further passes of up to 48
+ * columns each.  A pass may split the contraction into k_chunks chunks of whole groups (boundaries are multiples of 8), chosen
+ * by a planner from n, the width of the pass and the number of compute units alone (dense_plan in diaglib_amd/csrc/hip_plans.h
+ * states the rule); each chunk is summed in ascending index by the MFMA chain of one wavefront, and with k_chunks > 1 the partials
+ * go to a workspace of k_chunks x m x n doubles that belongs to the stored matrix (it grows with m and is not counted in
+ * device_bytes) and are added in ascending chunk order, ((p_0 + p_1) + p_2) + ..., by one thread per element -- the rule of the
+ * sparse tail's segments.  No atomics; every element of the result and of the workspace has exactly one writer; repeated products
+ * are bit-identical.  (The split depends on the width of the pass, so the bits of a column may differ between blocks of different
+ * width.)  k_chunks and workspace_bytes of dla_dense_info describe the first pass of the slot's most recent product, and a
+ * product of one column before any.
+ * Accuracy: every element stays within (n + 2) eps (|A| |x|)_i of the exact product, the bound of the tail-row contract, which
+ * holds for any order of summation.
+ * Shapes: any n >= 1, any m >= 1.  x and the result must not overlap; x is unchanged; nothing outside the n x m result is written.
+ * Independence: A and B are independent of each other and of the six sparse slots -- setting, dropping or replacing one never
+ * changes another's blocks, info or bits.  A context may hold a sparse A and a dense A at once; the caller chooses by the function
+ * it passes.
+ * Callbacks: they act on the context whose dense set-up the calling thread had accepted last (a thread-local binding of their own,
+ * cleared by dla_destroy) and enqueue on dla_stream.  A callback that finds its matrix missing, another n, or -- the pencil form --
+ * no metric or a metric of another n fails through the status of dla_call_matvec / dla_call_precnd with a message that names it
+ * and the cause; a refused call writes nothing.  dla_dense_matvec and dla_dense_bvec are pure functions of their input, so
+ * DLA_OPT_RUN_AHEAD = 1 covers them.
+ * Refused with DLA_ERR_ARG, the message naming the entry: a null pointer, n <= 0, lda < n, which not 0 or 1.
+ * Statistics: a pass books one launch under DLA_OP_MATVEC with alg_bytes = 8 n^2 + 16 n m and flops = 2 n^2 m (m: its columns)
+ * under the name of its kernel, dense_mfma_kernel<G> with G accumulator groups of 16 columns; the combining kernel of a split pass
+ * books a launch of its own with no algorithmic bytes (the workspace is not compulsory traffic).  The preconditioners book under
+ * DLA_OP_PRECND as the sparse ones do.
+ * Out of scope: the four linear-response parts as dense matrices; row shards; halving the traffic through symmetry; aliasing the
+ * caller's array instead of copying it; sanitizer runs of code loaded into an interpreter (the layout and the planner are host-only
+ * code, testable from a stand-alone program); any inspection of kernel assembly. */
+struct dla_dense_info { int n; int n_pad; int row_tile; int k_chunks; long long device_bytes; long long workspace_bytes; };
+int  dla_dense_setup    (dla_ctx* ctx, int which, int n, const double* a_host, int lda);   /* which: 0 = operator A, 1 = metric B */
+int  dla_dense_setup_dev(dla_ctx* ctx, int which, int n, const double* a_dev,  int lda);
+int  dla_dense_info     (dla_ctx* ctx, int which, struct dla_dense_info* out);
+int  dla_dense_drop     (dla_ctx* ctx, int which);                                        /* no-op where nothing is stored */
+void dla_dense_matvec(const int* n, const int* m, const double* x_dev, double* ax_dev);           /* ax = A x */
+void dla_dense_bvec  (const int* n, const int* m, const double* x_dev, double* bx_dev);           /* bx = B x */
+void dla_dense_precnd(const int* n, const int* m, const double* fac, const double* x_dev, double* px_dev);         /* x / (a_ii + fac), guard 1e-5: mprec */
+void dla_dense_precnd_pencil(const int* n, const int* m, const double* fac, const double* x_dev, double* px_dev);  /* x / (a_ii + fac b_ii), same guard */
 
 #ifdef __cplusplus
 }

@@ -52,6 +52,9 @@ EXPORTS = [
     "dla_spmm_apbmul", "dla_spmm_ambmul", "dla_spmm_spdmul", "dla_spmm_smdmul", "dla_spmm_lrprec1", "dla_spmm_lrprec2",
     "dla_dense_setup", "dla_dense_setup_dev", "dla_dense_info", "dla_dense_drop",
     "dla_dense_matvec", "dla_dense_bvec", "dla_dense_precnd", "dla_dense_precnd_pencil",
+    "dla_dense_setup_lr", "dla_dense_setup_lr_dev", "dla_dense_setup_lr_pair", "dla_dense_setup_lr_pair_dev", "dla_dense_lr_info",
+    "dla_dense_drop_lr", "dla_dense_apbmul", "dla_dense_ambmul", "dla_dense_spdmul", "dla_dense_smdmul", "dla_dense_lrprec1",
+    "dla_dense_lrprec2",
     "dla_davidson_driver", "dla_gen_david_driver", "dla_lobpcg_driver", "dla_caslr_eff_driver", "dla_caslr_driver", "dla_call_lrprec",
     "dla_last_solve_info", "dla_set_solve_info",
 ]
@@ -78,6 +81,7 @@ SPMM_ELL, SPMM_SELL, SPMM_AUTO = 0, 1, 2
 SPMM_FORMATS = {"ell": SPMM_ELL, "sell": SPMM_SELL, "auto": SPMM_AUTO}
 # the parts of a linear-response pencil (DLA_SPMM_LR_APB .. _SMD): A+B, A-B, S+D, S-D
 SPMM_LR_PARTS = {"apb": 0, "amb": 1, "spd": 2, "smd": 3}
+DENSE_LR_PAIRS = {"ab": 0, "sd": 1}      # dla_dense_setup_lr_pair: A, B -> A+B, A-B and S, D -> S+D, S-D
 
 
 class SpmmInfo(C.Structure):
@@ -186,6 +190,12 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dla_dense_info": (i, [vp, i, C.POINTER(DenseInfo)]), "dla_dense_drop": (i, [vp, i]),
         "dla_dense_matvec": (None, [c_ip, c_ip, vp, vp]), "dla_dense_bvec": (None, [c_ip, c_ip, vp, vp]),
         "dla_dense_precnd": (None, [c_ip, c_ip, c_dp, vp, vp]), "dla_dense_precnd_pencil": (None, [c_ip, c_ip, c_dp, vp, vp]),
+        "dla_dense_setup_lr": (i, [vp, i, i, vp, i]), "dla_dense_setup_lr_dev": (i, [vp, i, i, vp, i]),
+        "dla_dense_setup_lr_pair": (i, [vp, i, i, vp, i, vp, i]), "dla_dense_setup_lr_pair_dev": (i, [vp, i, i, vp, i, vp, i]),
+        "dla_dense_lr_info": (i, [vp, i, C.POINTER(DenseInfo)]), "dla_dense_drop_lr": (i, [vp]),
+        "dla_dense_apbmul": (None, [c_ip, c_ip, vp, vp]), "dla_dense_ambmul": (None, [c_ip, c_ip, vp, vp]),
+        "dla_dense_spdmul": (None, [c_ip, c_ip, vp, vp]), "dla_dense_smdmul": (None, [c_ip, c_ip, vp, vp]),
+        "dla_dense_lrprec1": (None, [c_ip, c_ip, c_dp, vp, vp, vp, vp]), "dla_dense_lrprec2": (None, [c_ip, c_ip, c_dp, vp, vp, vp, vp]),
         "dla_davidson_driver": (None, [i, i, i, i, i, d, i, d, vp, vp, vp, vp, c_ip]),
         "dla_lobpcg_driver": (None, [i, i, i, i, i, i, d, d, vp, vp, vp, vp, vp, c_ip]),
         "dla_caslr_eff_driver": (None, [i, i, i, i, i, d, i, vp, vp, vp, vp, vp, vp, vp, c_ip]),
@@ -744,24 +754,32 @@ class Context:
         Fortran-ordered) or a two-dimensional float64 torch tensor on the GPU with unit stride along its rows -- a column-major
         view such as ``buf.T`` of a C-contiguous ``buf`` -- whose other stride is taken as lda; anything else is refused"""
         which = int(bool(metric))
+        dev, a, n, lda = self._dense_array("dense_setup", "a", a)
+        if dev:
+            self._chk(self.lib.dla_dense_setup_dev(self.h, which, n, a.data_ptr(), lda))
+        else:
+            self._chk(self.lib.dla_dense_setup(self.h, which, n, a.ctypes.data, lda))
+
+    @staticmethod
+    def _dense_array(who: str, name: str, a):
+        """(on the device?, the array to keep alive, n, lda) of a dense matrix as dense_setup takes it"""
         if isinstance(a, np.ndarray):
             if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 1:
-                raise ValueError(f"dense_setup: a must be a square two-dimensional array, not of shape {a.shape}")
+                raise ValueError(f"{who}: {name} must be a square two-dimensional array, not of shape {a.shape}")
             a = np.asfortranarray(a, dtype=np.float64)
-            self._chk(self.lib.dla_dense_setup(self.h, which, a.shape[0], a.ctypes.data, a.shape[0]))
-            return
+            return False, a, a.shape[0], a.shape[0]
         import torch
         if not isinstance(a, torch.Tensor):
-            raise ValueError(f"dense_setup: a must be a NumPy array or a torch tensor, not {type(a).__name__}")
+            raise ValueError(f"{who}: {name} must be a NumPy array or a torch tensor, not {type(a).__name__}")
         if not a.is_cuda or a.dtype != torch.float64 or a.dim() != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 1:
-            raise ValueError("dense_setup: a device matrix must be a square two-dimensional float64 tensor on the GPU, not "
+            raise ValueError(f"{who}: a device matrix must be a square two-dimensional float64 tensor on the GPU, not "
                              f"{a.dtype} of shape {tuple(a.shape)} on {a.device}")
         n = a.shape[0]
         lda = n if n == 1 else a.stride(1)
         if (n > 1 and a.stride(0) != 1) or lda < n:
-            raise ValueError(f"dense_setup: a device matrix must have unit stride along its rows and lda >= n (column-major); its strides are {a.stride()}")
+            raise ValueError(f"{who}: a device matrix must have unit stride along its rows and lda >= n (column-major); its strides are {a.stride()}")
         torch.cuda.current_stream(a.device).synchronize()      # the tensor is complete before the library reads it
-        self._chk(self.lib.dla_dense_setup_dev(self.h, which, n, a.data_ptr(), lda))
+        return True, a, n, lda
 
     def dense_info(self, metric: bool = False) -> dict:
         """what the dense operator (metric: the metric) occupies: n, n_pad, row_tile, k_chunks, device_bytes, workspace_bytes
@@ -773,6 +791,45 @@ class Context:
     def dense_drop(self, metric: bool = False) -> None:
         """free the dense operator's (metric: the metric's) device blocks; nothing happens where nothing is stored"""
         self._chk(self.lib.dla_dense_drop(self.h, int(bool(metric))))
+
+    # ---- the four dense parts of a linear-response pencil (dla_dense_apbmul .. dla_dense_smdmul, dla_dense_lrprec1 / 2)
+    def dense_setup_lr(self, part, a) -> None:
+        """hand a dense n x n matrix (need not be symmetric) to this context as one part of the linear-response pencil: part = "apb"
+        (A+B), "amb" (A-B), "spd" (S+D), "smd" (S-D) or 0 .. 3; ``a`` as dense_setup takes it.  Independent of the dense operator,
+        the metric, the other parts and the sparse slots"""
+        part = self._lr_part("dense_setup_lr", part)
+        dev, a, n, lda = self._dense_array("dense_setup_lr", "a", a)
+        if dev:
+            self._chk(self.lib.dla_dense_setup_lr_dev(self.h, part, n, a.data_ptr(), lda))
+        else:
+            self._chk(self.lib.dla_dense_setup_lr(self.h, part, n, a.ctypes.data, lda))
+
+    def dense_setup_lr_pair(self, pair, p, q) -> None:
+        """fill two parts from the matrices a caller holds: pair = "ab" (or 0) stores p + q as A+B and p - q as A-B for p = A, q = B;
+        pair = "sd" (or 1) stores S+D and S-D for p = S, q = D.  p and q as dense_setup takes them, both NumPy arrays or both
+        torch tensors on the GPU, of the same n; both parts are replaced or neither"""
+        if isinstance(pair, str):
+            if pair not in DENSE_LR_PAIRS:
+                raise ValueError(f"dense_setup_lr_pair: pair must be one of {sorted(DENSE_LR_PAIRS)} or 0, 1, not {pair!r}")
+            pair = DENSE_LR_PAIRS[pair]
+        dev_p, p, n, ldp = self._dense_array("dense_setup_lr_pair", "p", p)
+        dev_q, q, nq, ldq = self._dense_array("dense_setup_lr_pair", "q", q)
+        if dev_p != dev_q or n != nq:
+            raise ValueError(f"dense_setup_lr_pair: p and q must both be NumPy arrays or both device tensors, of the same n (n = {n} and {nq})")
+        if dev_p:
+            self._chk(self.lib.dla_dense_setup_lr_pair_dev(self.h, int(pair), n, p.data_ptr(), ldp, q.data_ptr(), ldq))
+        else:
+            self._chk(self.lib.dla_dense_setup_lr_pair(self.h, int(pair), n, p.ctypes.data, ldp, q.ctypes.data, ldq))
+
+    def dense_lr_info(self, part) -> dict:
+        """dense_info of one part; raises while that part is empty"""
+        o = DenseInfo()
+        self._chk(self.lib.dla_dense_lr_info(self.h, self._lr_part("dense_lr_info", part), C.byref(o)))
+        return {name: int(getattr(o, name)) for name, _ in DenseInfo._fields_}
+
+    def dense_drop_lr(self) -> None:
+        """free the device blocks of all four dense parts (nothing happens without any); everything else stays as it is"""
+        self._chk(self.lib.dla_dense_drop_lr(self.h))
 
     def synth_matvec(self, x: DevPanel, ax: DevPanel) -> None:
         self._chk(self.lib.dla_call_matvec(self.h, fn_address("dla_synth_matvec"), x.n, x.m, x.ptr, ax.ptr))

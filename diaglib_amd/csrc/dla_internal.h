@@ -329,6 +329,17 @@ struct Engine : BlockOps {
   virtual int dense_drop(int /*which*/) { return no_dense(); }
   virtual int dense_mul(int /*which*/, int /*n*/, int /*m*/, const double* /*x*/, double* /*y*/) { return no_dense(); }
   virtual int dense_precnd(bool /*pencil*/, int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return no_dense(); }
+  // ... and the four dense parts of the linear-response pencil (dla_dense_setup_lr): part = DLA_DENSE_LR_APB .. _SMD, stored, asked
+  // about and multiplied by as the two above, independent of them and of each other.  dense_setup_lr_pair fills two of them with
+  // p + q and p - q (pair 0: A+B and A-B of A, B; pair 1: S+D and S-D of S, D), both or neither; dense_drop_lr frees all four;
+  // dense_lrprec is the harness' lrprec_1 / lrprec_2 (variant 1 / 2) on the stored diagonals of A+B, A-B and S+D.
+  virtual int dense_setup_lr(int /*part*/, int /*via*/, int /*n*/, const double* /*a*/, int /*lda*/) { return no_dense(); }
+  virtual int dense_setup_lr_pair(int /*pair*/, int /*via*/, int /*n*/, const double* /*p*/, int /*ldp*/, const double* /*q*/, int /*ldq*/) { return no_dense(); }
+  virtual int dense_lr_info(int /*part*/, struct dla_dense_info* /*out*/) { return no_dense(); }
+  virtual int dense_drop_lr() { return no_dense(); }
+  virtual int dense_lr_mul(int /*part*/, int /*n*/, int /*m*/, const double* /*x*/, double* /*y*/) { return no_dense(); }
+  virtual int dense_lrprec(int /*variant*/, int /*n*/, int /*m*/, double /*fac*/, const double* /*xp*/, const double* /*xm*/,
+                           double* /*yp*/, double* /*ym*/) { return no_dense(); }
 
   // Staging pipeline of host-mode callbacks: column chunks of a block travel device -> host on one copy stream, the
   // user's routine works on the chunk that has arrived, finished chunks travel host -> device on a second copy stream

@@ -2292,6 +2292,30 @@ __global__ void dense_diag_kernel(int n, const double* __restrict__ a, size_t ld
 {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) diag[i] = a[(size_t)i * lda + i];
 }
+// The copies of p + q and p - q of two column-major arrays p(ldp, n), q(ldq, n) at once (dla_dense_setup_lr_pair_dev): the same
+// thread-to-element map as dense_pack_kernel, every source element loaded once and used for both copies, one rounded addition and
+// one rounded subtraction (nothing here can contract), both writes contiguous, 0.0 in the padding.  The host twin: dense_pack_pair.
+__global__ void dense_pack_pair_kernel(int n, int n_pad, const double* __restrict__ p, size_t ldp, const double* __restrict__ q, size_t ldq,
+                                       double* __restrict__ sum, double* __restrict__ dif)
+{
+  const size_t total = (size_t)n_pad * n_pad, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t d = (size_t)blockIdx.x * blockDim.x + threadIdx.x; d < total; d += stride) {
+    const int i = dense_row_of(n_pad, d), k = dense_col_of(n_pad, d);
+    const bool in = i < n && k < n;
+    const double pv = in ? p[(size_t)k * ldp + i] : 0.0, qv = in ? q[(size_t)k * ldq + i] : 0.0;
+    sum[d] = in ? pv + qv : 0.0;
+    dif[d] = in ? pv - qv : 0.0;
+  }
+}
+__global__ void dense_diag_pair_kernel(int n, const double* __restrict__ p, size_t ldp, const double* __restrict__ q, size_t ldq,
+                                       double* __restrict__ sum_diag, double* __restrict__ dif_diag)
+{
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const double pv = p[(size_t)i * ldp + i], qv = q[(size_t)i * ldq + i];
+    sum_diag[i] = pv + qv;
+    dif_diag[i] = pv - qv;
+  }
+}
 
 // One pass Y(n x m) = A X, m <= 16 G, on the stored copy, RT = DENSE_WAVE_TILES.  Block (bx, by): four wavefronts, wavefront w owns the RT row
 // tiles of row group 4 bx + w and all of them contraction chunk by (groups [by chunk_groups, ...)): the four read the same
@@ -6749,25 +6773,34 @@ struct HipEngine : dla::Engine {
     return DLA_OK;
   }
 
-  // ---- the stored dense matrices (the contract: include/diaglib_amd.h, dla_dense_setup; the kernels: beside dense_mfma_kernel).
-  // Two slots, the operator and the metric, each the packed copy, its diagonal and the workspace of a split product.  The blocks
-  // only grow: a smaller matrix after a larger one keeps the larger blocks (the kernels go by n / n_pad).
+  // ---- the stored dense matrices (the contract: include/diaglib_amd.h, dla_dense_setup and dla_dense_setup_lr; the kernels: beside
+  // dense_mfma_kernel).  Six slots -- the operator, the metric and the four parts A+B, A-B, S+D, S-D of the linear-response pencil
+  // (slot DENSE_LR0 + part) -- each the packed copy, its diagonal and the workspace of a split product.  The blocks only grow: a
+  // smaller matrix after a larger one keeps the larger blocks (the kernels go by n / n_pad).
+  static constexpr int DENSE_LR0 = 2, DENSE_SLOTS = 6;
   struct DenseOp {
     int n = 0;                       // 0: nothing stored
     int last_m = 1;                  // width of the first pass of the most recent product (what dense_info describes)
     DeviceBuffer<double> a, diag, ws;
     void drop() { a.reset(); diag.reset(); ws.reset(); n = 0; last_m = 1; }
-  } dense[2];
-  static const char* dense_noun(int which) { return which ? "dense metric" : "dense operator"; }
-  int dense_setup(int which, int via, int n, const double* a, int lda) override
+  } dense[DENSE_SLOTS];
+  static const char* dense_noun(int slot)
   {
-    const bool dev = via == dla::SPMM_VIA_DEVICE;
-    const std::string who = dev ? "dla_dense_setup_dev: " : "dla_dense_setup: ";
-    if (which != 0 && which != 1) { err = who + "which must be 0 (the operator) or 1 (the metric)"; return DLA_ERR_ARG; }
-    if (!a) { err = who + "the matrix is a null pointer"; return DLA_ERR_ARG; }
+    static const char* const nouns[DENSE_SLOTS] = {"dense operator", "dense metric", "dense part apb (A+B)", "dense part amb (A-B)",
+                                                   "dense part spd (S+D)", "dense part smd (S-D)"};
+    return nouns[slot];
+  }
+  // what every dense set-up refuses of one array; who: the entry's name with ": ", what: the array's name in the message
+  int dense_array_ok(const std::string& who, const char* what, const char* ld, int n, const double* a, int lda)
+  {
+    if (!a) { err = who + "the " + what + " is a null pointer"; return DLA_ERR_ARG; }
     if (n <= 0) { err = who + "n must be positive"; return DLA_ERR_ARG; }
-    if (lda < n) { err = who + "lda = " + std::to_string(lda) + " is below n = " + std::to_string(n); return DLA_ERR_ARG; }
-    DenseOp& op = dense[which];
+    if (lda < n) { err = who + ld + " = " + std::to_string(lda) + " is below n = " + std::to_string(n); return DLA_ERR_ARG; }
+    return DLA_OK;
+  }
+  // the copy and the diagonal of a checked array into one slot
+  int dense_store(const std::string& who, DenseOp& op, bool dev, int n, const double* a, int lda)
+  {
     const int n_pad = dense_n_pad(n);
     const size_t total = (size_t)n_pad * n_pad;
     std::vector<double> packed, diag;
@@ -6798,17 +6831,92 @@ struct HipEngine : dla::Engine {
     op.n = n;
     return DLA_OK;
   }
-  int dense_info(int which, struct dla_dense_info* out) override
+  int dense_setup(int which, int via, int n, const double* a, int lda) override
   {
-    if (which != 0 && which != 1) { err = "dla_dense_info: which must be 0 (the operator) or 1 (the metric)"; return DLA_ERR_ARG; }
-    if (!out) { err = "dla_dense_info: out is a null pointer"; return DLA_ERR_ARG; }
-    const DenseOp& op = dense[which];
-    if (op.n <= 0) { err = std::string("dla_dense_info: no ") + dense_noun(which) + " has been set up"; return DLA_ERR_ARG; }
+    const bool dev = via == dla::SPMM_VIA_DEVICE;
+    const std::string who = dev ? "dla_dense_setup_dev: " : "dla_dense_setup: ";
+    if (which != 0 && which != 1) { err = who + "which must be 0 (the operator) or 1 (the metric)"; return DLA_ERR_ARG; }
+    { const int stc = dense_array_ok(who, "matrix", "lda", n, a, lda); if (stc) return stc; }
+    return dense_store(who, dense[which], dev, n, a, lda);
+  }
+  static bool dense_part_ok(int part) { return part >= 0 && part < DENSE_SLOTS - DENSE_LR0; }
+  static constexpr const char* DENSE_PART_RULE = "part must be 0 (A+B), 1 (A-B), 2 (S+D) or 3 (S-D)";
+  int dense_setup_lr(int part, int via, int n, const double* a, int lda) override
+  {
+    const bool dev = via == dla::SPMM_VIA_DEVICE;
+    const std::string who = dev ? "dla_dense_setup_lr_dev: " : "dla_dense_setup_lr: ";
+    if (!dense_part_ok(part)) { err = who + DENSE_PART_RULE; return DLA_ERR_ARG; }
+    { const int stc = dense_array_ok(who, "matrix", "lda", n, a, lda); if (stc) return stc; }
+    return dense_store(who, dense[DENSE_LR0 + part], dev, n, a, lda);
+  }
+  // p + q and p - q into the two slots of a pair, both or neither: every check and both allocations come before the first write.
+  // A slot whose blocks have to grow gets new ones while it still holds the old, so a failed allocation leaves both slots as they were.
+  int dense_setup_lr_pair(int pair, int via, int n, const double* p, int ldp, const double* q, int ldq) override
+  {
+    const bool dev = via == dla::SPMM_VIA_DEVICE;
+    const std::string who = dev ? "dla_dense_setup_lr_pair_dev: " : "dla_dense_setup_lr_pair: ";
+    if (pair != 0 && pair != 1) { err = who + "pair must be 0 (A and B: fills A+B, A-B) or 1 (S and D: fills S+D, S-D)"; return DLA_ERR_ARG; }
+    { const int stc = dense_array_ok(who, "first matrix (p)", "ldp", n, p, ldp); if (stc) return stc; }
+    { const int stc = dense_array_ok(who, "second matrix (q)", "ldq", n, q, ldq); if (stc) return stc; }
+    DenseOp* op[2] = {&dense[DENSE_LR0 + 2 * pair], &dense[DENSE_LR0 + 2 * pair + 1]};
+    const int n_pad = dense_n_pad(n);
+    const size_t total = (size_t)n_pad * n_pad;
+    std::vector<double> packed[2], diag[2];
+    if (!dev) {
+      try { for (int s = 0; s < 2; ++s) { packed[s].resize(total); diag[s].resize((size_t)n); } }
+      catch (const std::bad_alloc&) { err = who + "no host memory for the packed copies"; return DLA_ERR_ALLOC; }
+      dense_pack_pair(n, p, (size_t)ldp, q, (size_t)ldq, packed[0].data(), diag[0].data(), packed[1].data(), diag[1].data());
+    }
+    bind();
+    DeviceBuffer<double> grown_a[2], grown_diag[2];
+    for (int s = 0; s < 2; ++s) {
+      const bool ok = (total <= op[s]->a.capacity() || grown_a[s].reserve(total) == hipSuccess) &&
+                      ((size_t)n <= op[s]->diag.capacity() || grown_diag[s].reserve((size_t)n) == hipSuccess);
+      if (!ok) { err = who + "no device memory for " + std::to_string(2 * (8 * total + 8 * (size_t)n)) + " bytes"; return DLA_ERR_ALLOC; }
+    }
+    HIPCHK(hipStreamSynchronize(st));      // (queued products may still read the old blocks)
+    for (int s = 0; s < 2; ++s) {
+      op[s]->n = 0; op[s]->last_m = 1;
+      if (grown_a[s]) op[s]->a.swap(grown_a[s]);
+      if (grown_diag[s]) op[s]->diag.swap(grown_diag[s]);
+    }
+    if (dev) {
+      DLA_LAUNCH(dense_pack_pair_kernel, dim3(grid_blocks(env(), (long long)total, 256)), dim3(256), 0, st, n, n_pad, p, (size_t)ldp, q, (size_t)ldq,
+                 (double*)op[0]->a, (double*)op[1]->a);
+      HIPCHK(hipGetLastError());
+      DLA_LAUNCH(dense_diag_pair_kernel, dim3(grid_blocks(env(), n, 256)), dim3(256), 0, st, n, p, (size_t)ldp, q, (size_t)ldq,
+                 (double*)op[0]->diag, (double*)op[1]->diag);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(st));
+    } else {
+      for (int s = 0; s < 2; ++s) {
+        HIPCHK(hipMemcpy(op[s]->a, packed[s].data(), sizeof(double) * total, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(op[s]->diag, diag[s].data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+      }
+    }
+    op[0]->n = op[1]->n = n;
+    return DLA_OK;
+  }
+  int dense_info_of(const char* who, int slot, struct dla_dense_info* out)
+  {
+    if (!out) { err = std::string(who) + ": out is a null pointer"; return DLA_ERR_ARG; }
+    const DenseOp& op = dense[slot];
+    if (op.n <= 0) { err = std::string(who) + ": no " + dense_noun(slot) + " has been set up"; return DLA_ERR_ARG; }
     const DensePlan p = dense_plan(ncu, op.n, op.last_m);
     out->n = op.n; out->n_pad = p.n_pad; out->row_tile = DENSE_TILE * DENSE_WAVE_TILES; out->k_chunks = p.k_chunks;
     out->device_bytes = 8LL * p.n_pad * p.n_pad + 8LL * op.n;
     out->workspace_bytes = 8LL * (long long)p.ws_doubles;
     return DLA_OK;
+  }
+  int dense_info(int which, struct dla_dense_info* out) override
+  {
+    if (which != 0 && which != 1) { err = "dla_dense_info: which must be 0 (the operator) or 1 (the metric)"; return DLA_ERR_ARG; }
+    return dense_info_of("dla_dense_info", which, out);
+  }
+  int dense_lr_info(int part, struct dla_dense_info* out) override
+  {
+    if (!dense_part_ok(part)) { err = std::string("dla_dense_lr_info: ") + DENSE_PART_RULE; return DLA_ERR_ARG; }
+    return dense_info_of("dla_dense_lr_info", DENSE_LR0 + part, out);
   }
   // (nothing stored: neither the device nor the stream is touched)
   int dense_drop(int which) override
@@ -6820,20 +6928,41 @@ struct HipEngine : dla::Engine {
     dense[which].drop();
     return DLA_OK;
   }
-  // what a dense callback needs of its slot; who: the callback's name
-  int dense_admit(const std::string& who, int which, int n)
+  int dense_drop_lr() override
   {
-    const DenseOp& op = dense[which];
-    if (op.n <= 0) { err = who + ": no " + dense_noun(which) + " has been set up (dla_dense_setup)"; return DLA_ERR_ARG; }
-    if (n != op.n) { err = who + ": n = " + std::to_string(n) + " differs from the " + std::to_string(op.n) + " rows of the " + dense_noun(which); return DLA_ERR_ARG; }
+    bool any = false;
+    for (int s = DENSE_LR0; s < DENSE_SLOTS; ++s) any = any || dense[s].n > 0 || dense[s].a;
+    if (!any) return DLA_OK;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipStreamSynchronize(st));     // (products of the parts may still be queued)
+    for (int s = DENSE_LR0; s < DENSE_SLOTS; ++s) dense[s].drop();
+    return DLA_OK;
+  }
+  // what a dense callback needs of its slot; who: the callback's name
+  int dense_admit(const std::string& who, int slot, int n)
+  {
+    const DenseOp& op = dense[slot];
+    if (op.n <= 0) { err = who + ": no " + dense_noun(slot) + " has been set up (" + (slot < DENSE_LR0 ? "dla_dense_setup" : "dla_dense_setup_lr") + ")"; return DLA_ERR_ARG; }
+    if (n != op.n) { err = who + ": n = " + std::to_string(n) + " differs from the " + std::to_string(op.n) + " rows of the " + dense_noun(slot); return DLA_ERR_ARG; }
     return DLA_OK;
   }
   int dense_mul(int which, int n, int m, const double* x, double* y) override
   {
     if (which != 0 && which != 1) { err = "dense product: no such slot"; return DLA_ERR_ARG; }
-    { const int stc = dense_admit(which ? "dense_bvec" : "dense_matvec", which, n); if (stc) return stc; }
+    return dense_multiply(which ? "dense_bvec" : "dense_matvec", which, n, m, x, y);
+  }
+  int dense_lr_mul(int part, int n, int m, const double* x, double* y) override
+  {
+    static const char* const names[DENSE_SLOTS - DENSE_LR0] = {"dense_apbmul", "dense_ambmul", "dense_spdmul", "dense_smdmul"};
+    if (!dense_part_ok(part)) { err = "dense product: no such part"; return DLA_ERR_ARG; }
+    return dense_multiply(names[part], DENSE_LR0 + part, n, m, x, y);
+  }
+  // y = (slot) x: the passes of one product on the slot's copy and the slot's own workspace
+  int dense_multiply(const char* who, int slot, int n, int m, const double* x, double* y)
+  {
+    { const int stc = dense_admit(who, slot, n); if (stc) return stc; }
     if (m <= 0) return DLA_OK;
-    DenseOp& op = dense[which];
+    DenseOp& op = dense[slot];
     op.last_m = std::min(m, DENSE_MAX_COLS);
     for (int c0 = 0; c0 < m; c0 += DENSE_MAX_COLS) {
       const int mp = std::min(DENSE_MAX_COLS, m - c0);
@@ -6885,6 +7014,25 @@ struct HipEngine : dla::Engine {
       Scope s(this, DLA_OP_PRECND, 8.0 * n * (2.0 * m + 1.0), (double)n * m, "diag_precnd_kernel");
       DLA_LAUNCH(diag_precnd_kernel, grid, dim3(256), 0, st, n, m, fac, (const double*)dense[0].diag, x, px);
     }
+    HIPCHK(hipGetLastError());
+    return DLA_OK;
+  }
+  // lr_precnd_kernel, as spmm_lrprec launches it, on the stored diagonals of the dense parts A+B, A-B and S+D (S-D is not read)
+  int dense_lrprec(int variant, int n, int m, double fac, const double* xp, const double* xm, double* yp, double* ym) override
+  {
+    const std::string who = variant == 1 ? "dense_lrprec1" : "dense_lrprec2";
+    for (int part : {(int)DLA_DENSE_LR_APB, (int)DLA_DENSE_LR_AMB, (int)DLA_DENSE_LR_SPD}) {
+      const int stc = dense_admit(who, DENSE_LR0 + part, n);
+      if (stc) return stc;
+    }
+    if (m <= 0) return DLA_OK;
+    Scope s(this, DLA_OP_PRECND, 32.0 * (double)n * m + 24.0 * (double)n, 8.0 * (double)n * m);
+    const bool vec2 = even_rows(n) && (((uintptr_t)xp | (uintptr_t)xm | (uintptr_t)yp | (uintptr_t)ym) % 16 == 0);
+    const size_t nv = (size_t)n / (vec2 ? 2 : 1);
+    const int blocks = grid_blocks(env(), (long long)nv, 256);
+    const double *da = dense[DENSE_LR0 + DLA_DENSE_LR_APB].diag, *dm = dense[DENSE_LR0 + DLA_DENSE_LR_AMB].diag, *ds = dense[DENSE_LR0 + DLA_DENSE_LR_SPD].diag;
+    if (vec2) DLA_LAUNCH(lr_precnd_kernel<2>, dim3(blocks), dim3(256), 0, st, n, m, variant, fac, da, dm, ds, xp, xm, yp, ym);
+    else      DLA_LAUNCH(lr_precnd_kernel<1>, dim3(blocks), dim3(256), 0, st, n, m, variant, fac, da, dm, ds, xp, xm, yp, ym);
     HIPCHK(hipGetLastError());
     return DLA_OK;
   }

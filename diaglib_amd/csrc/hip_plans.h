@@ -660,6 +660,24 @@ inline void dense_pack(int n, const double* a, size_t lda, double* stored, doubl
     for (int i = 0; i < n; ++i) stored[dense_index(n_pad, i, k)] = a[(size_t)k * lda + i];
   for (int i = 0; i < n; ++i) diag[i] = a[(size_t)i * lda + i];
 }
+// ... and of the sum and the difference of two column-major host arrays p(ldp, n), q(ldq, n) at once (include/diaglib_amd.h,
+// dla_dense_setup_lr_pair): what dense_pack stores for the arrays p + q and p - q, every element one rounded addition or one rounded
+// subtraction, the padding 0.0, every source element read once
+inline void dense_pack_pair(int n, const double* p, size_t ldp, const double* q, size_t ldq, double* sum, double* sum_diag, double* dif,
+                            double* dif_diag)
+{
+  const int n_pad = dense_n_pad(n);
+  std::fill(sum, sum + (size_t)n_pad * n_pad, 0.0);
+  std::fill(dif, dif + (size_t)n_pad * n_pad, 0.0);
+  for (int k = 0; k < n; ++k)
+    for (int i = 0; i < n; ++i) {
+      const double pv = p[(size_t)k * ldp + i], qv = q[(size_t)k * ldq + i];
+      const size_t d = dense_index(n_pad, i, k);
+      sum[d] = pv + qv;
+      dif[d] = pv - qv;
+      if (i == k) { sum_diag[i] = pv + qv; dif_diag[i] = pv - qv; }
+    }
+}
 
 // One pass of a product Y(n x m) = A X, m <= DENSE_MAX_COLS: a pure function of n, m and the CU count.
 // A wavefront owns DENSE_WAVE_TILES row tiles and one chunk of the contraction, so there are row_groups x k_chunks of them.  The rule

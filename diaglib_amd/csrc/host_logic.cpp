@@ -1239,7 +1239,10 @@ static const OwnCallback* own_callback(void* fn)
     {(void*)&dla_spmm_lrprec2, false, true}, {(void*)&dla_spmm_precnd_cheb, false, true},
     {(void*)&dla_spmm_precnd_cheb_jacobi, false, true}, {(void*)&dla_spmm_precnd_cheb_pencil, false, true},
     {(void*)&dla_dense_matvec, true, true}, {(void*)&dla_dense_bvec, true, true},
-    {(void*)&dla_dense_precnd, false, true}, {(void*)&dla_dense_precnd_pencil, false, true}};
+    {(void*)&dla_dense_apbmul, true, true}, {(void*)&dla_dense_ambmul, true, true}, {(void*)&dla_dense_spdmul, true, true},
+    {(void*)&dla_dense_smdmul, true, true},
+    {(void*)&dla_dense_precnd, false, true}, {(void*)&dla_dense_precnd_pencil, false, true},
+    {(void*)&dla_dense_lrprec1, false, true}, {(void*)&dla_dense_lrprec2, false, true}};
   for (const OwnCallback& r : table)
     if (r.fn == fn) return &r;
   return nullptr;
@@ -2080,5 +2083,73 @@ void dla_dense_matvec(const int* n, const int* m, const double* x, double* ax) {
 void dla_dense_bvec(const int* n, const int* m, const double* x, double* bx) { dense_product(1, n, m, x, bx); }
 void dla_dense_precnd(const int* n, const int* m, const double* fac, const double* x, double* px) { dense_precondition(false, n, m, fac, x, px); }
 void dla_dense_precnd_pencil(const int* n, const int* m, const double* fac, const double* x, double* px) { dense_precondition(true, n, m, fac, x, px); }
+
+// ... and the four dense parts of the linear-response pencil (include/diaglib_amd.h, dla_dense_setup_lr).  An accepted set-up of a
+// part or of a pair binds its context to the thread's dense callbacks like dla_dense_setup does; info and drop never do.
+static int dense_bound(dla_ctx* c, int st)
+{
+  st = engfail(c, st);
+  if (st == DLA_OK) g_dense_ctx = c;
+  return st;
+}
+int dla_dense_setup_lr(dla_ctx* c, int part, int n, const double* a_host, int lda)
+{
+  DLA_T("dla_dense_setup_lr");
+  if (!c) return DLA_ERR_ARG;
+  return dense_bound(c, c->eng->dense_setup_lr(part, dla::SPMM_VIA_HOST, n, a_host, lda));
+}
+int dla_dense_setup_lr_dev(dla_ctx* c, int part, int n, const double* a_dev, int lda)
+{
+  DLA_T("dla_dense_setup_lr_dev");
+  if (!c) return DLA_ERR_ARG;
+  return dense_bound(c, c->eng->dense_setup_lr(part, dla::SPMM_VIA_DEVICE, n, a_dev, lda));
+}
+int dla_dense_setup_lr_pair(dla_ctx* c, int pair, int n, const double* p_host, int ldp, const double* q_host, int ldq)
+{
+  DLA_T("dla_dense_setup_lr_pair");
+  if (!c) return DLA_ERR_ARG;
+  return dense_bound(c, c->eng->dense_setup_lr_pair(pair, dla::SPMM_VIA_HOST, n, p_host, ldp, q_host, ldq));
+}
+int dla_dense_setup_lr_pair_dev(dla_ctx* c, int pair, int n, const double* p_dev, int ldp, const double* q_dev, int ldq)
+{
+  DLA_T("dla_dense_setup_lr_pair_dev");
+  if (!c) return DLA_ERR_ARG;
+  return dense_bound(c, c->eng->dense_setup_lr_pair(pair, dla::SPMM_VIA_DEVICE, n, p_dev, ldp, q_dev, ldq));
+}
+int dla_dense_lr_info(dla_ctx* c, int part, struct dla_dense_info* out)
+{
+  if (!c) return DLA_ERR_ARG;
+  return engfail(c, c->eng->dense_lr_info(part, out));
+}
+int dla_dense_drop_lr(dla_ctx* c)
+{
+  if (!c) return DLA_ERR_ARG;
+  return engfail(c, c->eng->dense_drop_lr());
+}
+static void dense_lr_product(int part, const int* n, const int* m, const double* x, double* y)
+{
+  static const SpmmCallback words[4] = {
+    {"dla_dense_apbmul before dla_dense_setup_lr: no dense part apb (A+B) has been set up", "dla_dense_apbmul failed: "},
+    {"dla_dense_ambmul before dla_dense_setup_lr: no dense part amb (A-B) has been set up", "dla_dense_ambmul failed: "},
+    {"dla_dense_spdmul before dla_dense_setup_lr: no dense part spd (S+D) has been set up", "dla_dense_spdmul failed: "},
+    {"dla_dense_smdmul before dla_dense_setup_lr: no dense part smd (S-D) has been set up", "dla_dense_smdmul failed: "}};
+  dla_ctx* c = g_dense_ctx;
+  if (!c) { callback_failed(DLA_ERR_ARG, words[part].unbound); return; }
+  if (int st = c->eng->dense_lr_mul(part, *n, *m, x, y)) callback_failed(st, words[part].failed + c->eng->err);
+}
+static void dense_lr_precondition(int variant, const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym)
+{
+  static const SpmmCallback words[2] = {{"dla_dense_lrprec1 before dla_dense_setup_lr: no dense part has been set up", "dla_dense_lrprec1 failed: "},
+                                        {"dla_dense_lrprec2 before dla_dense_setup_lr: no dense part has been set up", "dla_dense_lrprec2 failed: "}};
+  dla_ctx* c = g_dense_ctx;
+  if (!c) { callback_failed(DLA_ERR_ARG, words[variant - 1].unbound); return; }
+  if (int st = c->eng->dense_lrprec(variant, *n, *m, *fac, xp, xm, yp, ym)) callback_failed(st, words[variant - 1].failed + c->eng->err);
+}
+void dla_dense_apbmul(const int* n, const int* m, const double* x, double* y) { dense_lr_product(DLA_DENSE_LR_APB, n, m, x, y); }
+void dla_dense_ambmul(const int* n, const int* m, const double* x, double* y) { dense_lr_product(DLA_DENSE_LR_AMB, n, m, x, y); }
+void dla_dense_spdmul(const int* n, const int* m, const double* x, double* y) { dense_lr_product(DLA_DENSE_LR_SPD, n, m, x, y); }
+void dla_dense_smdmul(const int* n, const int* m, const double* x, double* y) { dense_lr_product(DLA_DENSE_LR_SMD, n, m, x, y); }
+void dla_dense_lrprec1(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { dense_lr_precondition(1, n, m, fac, xp, xm, yp, ym); }
+void dla_dense_lrprec2(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { dense_lr_precondition(2, n, m, fac, xp, xm, yp, ym); }
 
 }  // extern "C"

@@ -90,7 +90,7 @@ enum {
                                       takes another route than planned the operator is called a SECOND time on the finished
                                       block and its first output is dropped -- the reference calls matvec exactly once per
                                       block (diaglib.f90:1685, 394-397), so:
-                                      1 (default): only for the library's own device operators (dla_synth_*, dla_spmm_matvec, dla_spmm_bvec, dla_spmm_apbmul .. _smdmul, dla_dense_matvec, dla_dense_bvec),
+                                      1 (default): only for the library's own device operators (dla_synth_*, dla_spmm_matvec, dla_spmm_bvec, dla_spmm_apbmul .. _smdmul, dla_dense_matvec, dla_dense_bvec, dla_dense_apbmul .. _smdmul),
                                          which are pure functions of their input; a caller's callback is called once, in order;
                                       2: also for the caller's device-mode callbacks (ordering contract 0 or 2) -- the caller
                                          states that the operator keeps no state between calls;
@@ -759,7 +759,7 @@ void dla_spmm_precnd_cheb_pencil(const int* n, const int* m, const double* fac, 
  * under the name of its kernel, dense_mfma_kernel<G> with G accumulator groups of 16 columns; the combining kernel of a split pass
  * books a launch of its own with no algorithmic bytes (the workspace is not compulsory traffic).  The preconditioners book under
  * DLA_OP_PRECND as the sparse ones do.
- * Out of scope: the four linear-response parts as dense matrices; row shards; halving the traffic through symmetry; aliasing the
+ * Out of scope (the four linear-response parts as dense matrices: the next block): row shards; halving the traffic through symmetry; aliasing the
  * caller's array instead of copying it; sanitizer runs of code loaded into an interpreter (the layout and the planner are host-only
  * code, testable from a stand-alone program); any inspection of kernel assembly. */
 struct dla_dense_info { int n; int n_pad; int row_tile; int k_chunks; long long device_bytes; long long workspace_bytes; };
@@ -771,6 +771,61 @@ void dla_dense_matvec(const int* n, const int* m, const double* x_dev, double* a
 void dla_dense_bvec  (const int* n, const int* m, const double* x_dev, double* bx_dev);           /* bx = B x */
 void dla_dense_precnd(const int* n, const int* m, const double* fac, const double* x_dev, double* px_dev);         /* x / (a_ii + fac), guard 1e-5: mprec */
 void dla_dense_precnd_pencil(const int* n, const int* m, const double* fac, const double* x_dev, double* px_dev);  /* x / (a_ii + fac b_ii), same guard */
+
+/* ---------------------------------------------------------------- dense linear-response parts
+ * The reference harness' linear-response problems are DENSE (main.f90:528-760): A+B, A-B, S+D and S-D of the pencil
+ * (A B; B A)(Y Z) = w (S D; -D -S)(Y Z) applied by dgemm in host callbacks.  A context stores four dense parts beside the dense
+ * operator and metric; dla_dense_apbmul / ambmul / spdmul / smdmul have the shape of the reference's apbmul / ambmul / spdmul /
+ * smdmul (diaglib.f90:1024-1025) and dla_dense_lrprec1 / _lrprec2 the shape of its lrprec (:1317), expect DEVICE addresses
+ * (DLA_OPT_CALLBACKS_ON_DEVICE = 1) and go where the host routines go in caslr_eff_driver and caslr_driver: the whole solve stays
+ * in HBM.  part: DLA_DENSE_LR_APB .. _SMD, the numbering and the meaning of DLA_SPMM_LR_*.
+ * Set-up and storage: every rule of dla_dense_setup holds for a part.  a is column-major, n x n, lda >= n; the library keeps its own
+ * copy in the stored layout above (tiles of 16 rows, groups of 8 contraction indices, zero-padded to n_pad) with the diagonal
+ * beside it, device_bytes = 8 n_pad^2 + 8 n per part; the call is synchronous like dla_dense_setup_dev; host and device set-up of
+ * the same values store the same bits; allocations only grow; a refused set-up replaces nothing.  dla_dense_lr_info answers
+ * DLA_ERR_ARG while that part is empty; dla_dense_drop_lr frees all four and does nothing without any.
+ * No symmetry assumed (S+D and S-D are not symmetric): row i of the result is row i of what was handed over times x.
+ * Set-up from the caller's pairs.  A caller holds A, B, S, D, not their sums: dla_dense_setup_lr_pair takes p(ldp, n) and q(ldq, n)
+ * -- pair DLA_DENSE_LR_PAIR_AB: p = A, q = B, fills APB with p + q and AMB with p - q; DLA_DENSE_LR_PAIR_SD: p = S, q = D, fills
+ * SPD and SMD -- and forms both while packing: every stored element is ONE rounded addition or ONE rounded subtraction of the two
+ * source elements, the padding is 0.0, the two diagonals are formed the same way, and both slots then equal, bit for bit and field
+ * by field of dla_dense_lr_info, what dla_dense_setup_lr stores for the host arrays p + q and p - q.  ldp and ldq are independent,
+ * both >= n; the sources are only read, each element once.  All or nothing: every check and both allocations happen before either
+ * slot is written, so after a refusal or a failed allocation both slots keep their blocks, their info and the bits of their
+ * products.
+ * Products: the kernels and the plan of dla_dense_matvec (dense_mfma_kernel<G>, dense_combine_kernel, dense_plan), so for the same
+ * array a part returns the bits the operator slot returns; each part owns its workspace of partial sums; statistics book as a
+ * dense pass does; k_chunks and workspace_bytes of dla_dense_lr_info describe the first pass of that part's most recent product.
+ * Preconditioners: dla_dense_lrprec1 / _lrprec2 are the kernel of dla_spmm_lrprec1 / 2 on the stored dense diagonals, with
+ * aa = 0.5 * (apb_ii + amb_ii) and sg = spd_ii (S-D is not read), the expressions and the order of operations stated for
+ * dla_spmm_lrprec1 / 2 above -- bit for bit what a host caller gets from them -- booked under DLA_OP_PRECND.
+ * Independence: the four parts are independent of each other, of the dense operator and metric and of the six sparse slots --
+ * blocks, info and product bits alike.
+ * Callbacks: they act on the context whose dense set-up (any of dla_dense_setup*, these included) the calling thread had accepted
+ * last and enqueue on dla_stream.  A product that finds its part missing or another n, and a preconditioner that finds A+B, A-B
+ * or S+D missing or parts of unequal n, fail through the status of dla_call_matvec / dla_call_lrprec with a message that names the
+ * callback and the cause; a refused call writes nothing.  The four products are pure functions of their input, so
+ * DLA_OPT_RUN_AHEAD = 1 covers them.
+ * Refused with DLA_ERR_ARG, the message naming the entry: a null pointer, n <= 0, lda (ldp, ldq) < n, a part outside 0 .. 3, a pair
+ * outside 0 and 1.
+ * Out of scope: one batched launch for the four independent products of an iteration; storing S-D as the transpose of S+D; row
+ * shards; halving the traffic through symmetry; aliasing the caller's arrays; a polynomial preconditioner for the pencil;
+ * sanitizer runs of code loaded into an interpreter (the packing twin dense_pack_pair is host-only code, testable from a
+ * stand-alone program); any inspection of kernel assembly. */
+enum { DLA_DENSE_LR_APB = 0, DLA_DENSE_LR_AMB = 1, DLA_DENSE_LR_SPD = 2, DLA_DENSE_LR_SMD = 3 };
+enum { DLA_DENSE_LR_PAIR_AB = 0, DLA_DENSE_LR_PAIR_SD = 1 };
+int  dla_dense_setup_lr    (dla_ctx* ctx, int part, int n, const double* a_host, int lda);
+int  dla_dense_setup_lr_dev(dla_ctx* ctx, int part, int n, const double* a_dev,  int lda);
+int  dla_dense_setup_lr_pair    (dla_ctx* ctx, int pair, int n, const double* p_host, int ldp, const double* q_host, int ldq);
+int  dla_dense_setup_lr_pair_dev(dla_ctx* ctx, int pair, int n, const double* p_dev,  int ldp, const double* q_dev,  int ldq);
+int  dla_dense_lr_info     (dla_ctx* ctx, int part, struct dla_dense_info* out);   /* DLA_ERR_ARG while that part is empty */
+int  dla_dense_drop_lr     (dla_ctx* ctx);                                         /* frees all four; no-op without any */
+void dla_dense_apbmul(const int* n, const int* m, const double* x_dev, double* y_dev);          /* y = (A+B) x */
+void dla_dense_ambmul(const int* n, const int* m, const double* x_dev, double* y_dev);          /* y = (A-B) x */
+void dla_dense_spdmul(const int* n, const int* m, const double* x_dev, double* y_dev);          /* y = (S+D) x */
+void dla_dense_smdmul(const int* n, const int* m, const double* x_dev, double* y_dev);          /* y = (S-D) x */
+void dla_dense_lrprec1(const int* n, const int* m, const double* fac, const double* xp_dev, const double* xm_dev, double* yp_dev, double* ym_dev);
+void dla_dense_lrprec2(const int* n, const int* m, const double* fac, const double* xp_dev, const double* xm_dev, double* yp_dev, double* ym_dev);
 
 #ifdef __cplusplus
 }

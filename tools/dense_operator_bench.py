@@ -12,9 +12,17 @@ users' sizes, beside torch.matmul and the triad rate of the same process.
    (the oracle's orc_dense_matvec / orc_dense_precnd through host callbacks) and in device mode (dla_dense_matvec / dla_dense_precnd):
    wall time per solve, iterations, eigenvalue difference.
 
+3. With --lr, the dense linear-response parts instead (record: profiles/dense_lr_operator.txt): one caslr_eff_driver solve and one
+   caslr_driver solve of the reference harness' linear-response problem (orc_lr_setup; 4 roots, n_max 8, tol 1e-9, max_dav 20, unit
+   guess) at n = 2000 in device mode (dla_dense_apbmul .. smdmul, dla_dense_lrprec2 / 1) and the same solves through host callbacks
+   (the oracle's orc_lr_* routines); and the pair set-up dla_dense_setup_lr_pair_dev at n = 8192 -- wall time of the synchronous
+   call, in ms and in GB/s of its 16 n^2 + 16 n_pad^2 bytes (two sources read, two copies written), beside the triad rate of the
+   process.  Recorded figures, no thresholds.
+
 Every leg is a process of its own under `timeout`; the first leg that fails ends the run.
 
-    python tools/dense_operator_bench.py [rounds] [record]     (defaults 10, profiles/dense_operator.txt)
+    python tools/dense_operator_bench.py [rounds] [record]          (defaults 10, profiles/dense_operator.txt)
+    python tools/dense_operator_bench.py --lr [rounds] [record]     (defaults 10, profiles/dense_lr_operator.txt)
 """
 import os
 import subprocess
@@ -28,6 +36,7 @@ import numpy as np  # noqa: E402
 
 CALLS_PER_ROUND, WIDTHS = 5, (1, 8, 13, 37)
 LEGS = [("product 2048", 300), ("product 8192", 300), ("product 32768", 420), ("solve 2000", 420)]
+LR_LEGS = [("lrsolve 2000", 420), ("lrpair 8192", 300)]
 
 
 def leg_product(n, rounds):
@@ -113,15 +122,76 @@ def leg_solve(n):
     ctx.dense_drop()
 
 
+def leg_lr_solve(n):
+    from diaglib_amd import capi
+    from oracle.pyoracle import Oracle
+    ctx, o = capi.Context(), Oracle()
+    t, m, tol, max_dav = 4, 8, 1e-9, 20
+    parts = ("apb", "amb", "spd", "smd")
+    for part, a in zip(parts, o.lr_setup(n)):
+        ctx.dense_setup_lr(part, a)
+    g = np.zeros((2 * n, m), order="F")
+    g[np.arange(m), np.arange(m)] = 1.0
+    for driver, trad in (("caslr_eff_driver", False), ("caslr_driver", True)):
+        out = {}
+        host = [o.fn(k) for k in ("orc_lr_apb", "orc_lr_amb", "orc_lr_spd", "orc_lr_smd", "orc_lr_prec1" if trad else "orc_lr_prec")]
+        device = [capi.fn_address(f"dla_dense_{p}mul") for p in parts] + [capi.fn_address("dla_dense_lrprec1" if trad else "dla_dense_lrprec2")]
+        for mode, on_device, fns in (("host callbacks (orc_lr_*)", 0, host), ("device callbacks (dla_dense_*)", 1, device)):
+            ctx.set_option(capi.OPT_CALLBACKS_ON_DEVICE, on_device)
+            solve = ctx.caslr_driver if trad else ctx.caslr_eff_driver
+            times = []
+            for _ in range(5):
+                ctx.sync()
+                t0 = time.perf_counter()
+                eig, _, ok, info = solve(n, t, m, 200, tol, max_dav, *fns, g)
+                times.append((time.perf_counter() - t0) * 1e3)
+            out[mode] = eig[:t].copy()
+            print(f"n = {n} {driver}, {mode}: median {np.median(times[1:]):8.2f} ms per solve (min {min(times[1:]):.2f}), {info['iters']} iterations, ok = {ok}", flush=True)
+        e0, e1 = out.values()
+        print(f"  largest relative eigenvalue difference between the two modes: {float(np.abs(e0 / e1 - 1.0).max()):.2e}")
+    ctx.set_option(capi.OPT_CALLBACKS_ON_DEVICE, 0)
+    ctx.dense_drop_lr()
+
+
+def leg_lr_pair(n, rounds):
+    import torch
+    from diaglib_amd import capi
+    ctx = capi.Context()
+    gen = torch.Generator(device="cuda").manual_seed(n)
+    p, q = (torch.rand((n, n), dtype=torch.float64, device="cuda", generator=gen).T for _ in range(2))      # column-major
+    torch.cuda.synchronize()
+    triad = ctx.stream_triad(max(1 << 24, n * n // 4))
+    ctx._chk(ctx.lib.dla_dense_setup_lr_pair_dev(ctx.h, 0, n, p.data_ptr(), n, q.data_ptr(), n))      # (the blocks are allocated here)
+    n_pad = ctx.dense_lr_info("apb")["n_pad"]
+    times = []
+    for _ in range(rounds):
+        t0 = time.perf_counter()
+        ctx._chk(ctx.lib.dla_dense_setup_lr_pair_dev(ctx.h, 0, n, p.data_ptr(), n, q.data_ptr(), n))
+        times.append((time.perf_counter() - t0) * 1e3)
+    med = float(np.median(times))
+    moved = 16.0 * n * n + 16.0 * n_pad * n_pad
+    print(f"n = {n} dla_dense_setup_lr_pair_dev (synchronous call, blocks in place): median {med:8.3f} ms (min {min(times):.3f}, max {max(times):.3f}) over "
+          f"{rounds} calls, {moved / 1e9:.2f} GB moved = {moved / (med * 1e-3) / 1e9:6.0f} GB/s = {moved / (med * 1e-3) / 1e9 / triad:5.2f} of the triad rate "
+          f"({triad:.0f} GB/s)", flush=True)
+    ctx.dense_drop_lr()
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--leg":
         kind, n, rounds = sys.argv[2], int(sys.argv[3]), int(sys.argv[4])
-        leg_product(n, rounds) if kind == "product" else leg_solve(n)
+        {"product": lambda: leg_product(n, rounds), "solve": lambda: leg_solve(n), "lrsolve": lambda: leg_lr_solve(n),
+         "lrpair": lambda: leg_lr_pair(n, rounds)}[kind]()
         return 0
-    rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-    record = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "dense_operator.txt")
-    text = [f"tools/dense_operator_bench.py {rounds}: dla_dense_matvec beside torch.matmul and the triad rate; {rounds * CALLS_PER_ROUND} timed calls each per shape"]
-    for leg, limit in LEGS:
+    args = [a for a in sys.argv[1:] if a != "--lr"]
+    lr = "--lr" in sys.argv[1:]
+    rounds = int(args[0]) if args else 10
+    record = args[1] if len(args) > 1 else os.path.join(ROOT, "profiles", "dense_lr_operator.txt" if lr else "dense_operator.txt")
+    if lr:
+        text = [f"tools/dense_operator_bench.py --lr {rounds}: the linear-response drivers on dense parts in device mode beside host callbacks (4 timed solves "
+                f"each), and the pair set-up ({rounds} timed calls) beside the triad rate"]
+    else:
+        text = [f"tools/dense_operator_bench.py {rounds}: dla_dense_matvec beside torch.matmul and the triad rate; {rounds * CALLS_PER_ROUND} timed calls each per shape"]
+    for leg, limit in (LR_LEGS if lr else LEGS):
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg"] + leg.split() + [str(rounds)]
         p = subprocess.Popen(cmd, stdout=subprocess.PIPE, text=True)
         for line in p.stdout:                             # (as it comes: a long leg is not silent)

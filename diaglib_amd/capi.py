@@ -753,12 +753,13 @@ class Context:
         keeps a copy of its own, so ``a`` may be freed or overwritten afterwards.  ``a`` is a NumPy array (made float64 and
         Fortran-ordered) or a two-dimensional float64 torch tensor on the GPU with unit stride along its rows -- a column-major
         view such as ``buf.T`` of a C-contiguous ``buf`` -- whose other stride is taken as lda; anything else is refused"""
-        which = int(bool(metric))
-        dev, a, n, lda = self._dense_array("dense_setup", "a", a)
-        if dev:
-            self._chk(self.lib.dla_dense_setup_dev(self.h, which, n, a.data_ptr(), lda))
-        else:
-            self._chk(self.lib.dla_dense_setup(self.h, which, n, a.ctypes.data, lda))
+        self._dense_set_up("dense_setup", int(bool(metric)), a)
+
+    def _dense_set_up(self, who: str, k: int, a) -> None:
+        """slot number k through dla_<who>, or through dla_<who>_dev where ``a`` is on the device"""
+        dev, a, n, lda = self._dense_array(who, "a", a)
+        entry = getattr(self.lib, f"dla_{who}_dev" if dev else f"dla_{who}")
+        self._chk(entry(self.h, k, n, a.data_ptr() if dev else a.ctypes.data, lda))
 
     @staticmethod
     def _dense_array(who: str, name: str, a):
@@ -797,12 +798,7 @@ class Context:
         """hand a dense n x n matrix (need not be symmetric) to this context as one part of the linear-response pencil: part = "apb"
         (A+B), "amb" (A-B), "spd" (S+D), "smd" (S-D) or 0 .. 3; ``a`` as dense_setup takes it.  Independent of the dense operator,
         the metric, the other parts and the sparse slots"""
-        part = self._lr_part("dense_setup_lr", part)
-        dev, a, n, lda = self._dense_array("dense_setup_lr", "a", a)
-        if dev:
-            self._chk(self.lib.dla_dense_setup_lr_dev(self.h, part, n, a.data_ptr(), lda))
-        else:
-            self._chk(self.lib.dla_dense_setup_lr(self.h, part, n, a.ctypes.data, lda))
+        self._dense_set_up("dense_setup_lr", self._lr_part("dense_setup_lr", part), a)
 
     def dense_setup_lr_pair(self, pair, p, q) -> None:
         """fill two parts from the matrices a caller holds: pair = "ab" (or 0) stores p + q as A+B and p - q as A-B for p = A, q = B;

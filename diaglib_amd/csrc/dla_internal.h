@@ -184,6 +184,10 @@ enum SpmmSlot { SPMM_NO_PART = -2, SPMM_NO_WHICH = -1, SPMM_A = 0, SPMM_B, SPMM_
 enum SpmmVia { SPMM_VIA_PLAIN, SPMM_VIA_HOST, SPMM_VIA_DEVICE };
 inline int spmm_slot_of_which(int which) { return which == 0 ? SPMM_A : which == 1 ? SPMM_B : SPMM_NO_WHICH; }
 inline int spmm_slot_of_part(int part) { return part >= 0 && part < SPMM_SLOTS - SPMM_APB ? SPMM_APB + part : SPMM_NO_PART; }
+// ... and the six stored dense matrices, numbered the same way (dla_dense_setup: which, dla_dense_setup_lr: part)
+enum DenseSlot { DENSE_NO_PART = -2, DENSE_NO_WHICH = -1, DENSE_A = 0, DENSE_B, DENSE_APB, DENSE_AMB, DENSE_SPD, DENSE_SMD, DENSE_SLOTS };
+inline int dense_slot_of_which(int which) { return which == 0 ? DENSE_A : which == 1 ? DENSE_B : DENSE_NO_WHICH; }
+inline int dense_slot_of_part(int part) { return part >= 0 && part < DENSE_SLOTS - DENSE_APB ? DENSE_APB + part : DENSE_NO_PART; }
 
 // What the host logic needs from a device.  All panel pointers are device addresses,
 // column-major, ld = n.  Reductions (gram / residual norms / nrm2) return host-visible,
@@ -319,25 +323,22 @@ struct Engine : BlockOps {
   virtual int spmm_precnd_cheb_pencil(int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return DLA_ERR_ARG; }
   virtual int spmm_cheb_pencil_upper(double /*fac*/, double* /*hi*/) { return DLA_ERR_ARG; }
 
-  // ---- the stored dense matrices (the contract: include/diaglib_amd.h, dla_dense_setup): which = 0 the operator A, 1 the metric B,
-  // each the library's own copy of a column-major a(lda, n) in host (via = SPMM_VIA_HOST) or device memory (SPMM_VIA_DEVICE), with
-  // its diagonal beside it; independent of each other and of the sparse slots.  dense_precnd: x / (a_ii + fac), or with pencil
-  // x / (a_ii + fac b_ii).  An engine without them (the host-memory test engine) refuses every call.
+  // ---- the stored dense matrices (the contract: include/diaglib_amd.h, dla_dense_setup and dla_dense_setup_lr).  A context stores up
+  // to six (DenseSlot): the operator A, the metric B and the four parts A+B, A-B, S+D, S-D of the linear-response pencil, each the
+  // library's own copy of a column-major a(lda, n) in host (via = SPMM_VIA_HOST) or device memory (SPMM_VIA_DEVICE) with its diagonal
+  // beside it; independent of each other and of the sparse slots.  `slot` is a DenseSlot, or DENSE_NO_WHICH / DENSE_NO_PART for a
+  // public number out of range, which the engine refuses in the entry's words.  dense_setup_pair fills two parts with p + q and
+  // p - q (pair 0: A+B and A-B of A, B; pair 1: S+D and S-D of S, D), both or neither; dense_drop gives back slots first .. last
+  // (nothing happens where nothing is stored).  dense_precnd: x / (a_ii + fac), or with pencil x / (a_ii + fac b_ii); dense_lrprec:
+  // the harness' lrprec_1 / lrprec_2 (variant 1 / 2) on the stored diagonals of A+B, A-B and S+D.  An engine without them (the
+  // host-memory test engine) refuses every call.
   int no_dense() { err = "this engine stores no dense matrix"; return DLA_ERR_ARG; }
-  virtual int dense_setup(int /*which*/, int /*via*/, int /*n*/, const double* /*a*/, int /*lda*/) { return no_dense(); }
-  virtual int dense_info(int /*which*/, struct dla_dense_info* /*out*/) { return no_dense(); }
-  virtual int dense_drop(int /*which*/) { return no_dense(); }
-  virtual int dense_mul(int /*which*/, int /*n*/, int /*m*/, const double* /*x*/, double* /*y*/) { return no_dense(); }
+  virtual int dense_setup(int /*slot*/, int /*via*/, int /*n*/, const double* /*a*/, int /*lda*/) { return no_dense(); }
+  virtual int dense_setup_pair(int /*pair*/, int /*via*/, int /*n*/, const double* /*p*/, int /*ldp*/, const double* /*q*/, int /*ldq*/) { return no_dense(); }
+  virtual int dense_info(int /*slot*/, struct dla_dense_info* /*out*/) { return no_dense(); }
+  virtual int dense_drop(int /*first*/, int /*last*/) { return no_dense(); }
+  virtual int dense_mul(int /*slot*/, int /*n*/, int /*m*/, const double* /*x*/, double* /*y*/) { return no_dense(); }
   virtual int dense_precnd(bool /*pencil*/, int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return no_dense(); }
-  // ... and the four dense parts of the linear-response pencil (dla_dense_setup_lr): part = DLA_DENSE_LR_APB .. _SMD, stored, asked
-  // about and multiplied by as the two above, independent of them and of each other.  dense_setup_lr_pair fills two of them with
-  // p + q and p - q (pair 0: A+B and A-B of A, B; pair 1: S+D and S-D of S, D), both or neither; dense_drop_lr frees all four;
-  // dense_lrprec is the harness' lrprec_1 / lrprec_2 (variant 1 / 2) on the stored diagonals of A+B, A-B and S+D.
-  virtual int dense_setup_lr(int /*part*/, int /*via*/, int /*n*/, const double* /*a*/, int /*lda*/) { return no_dense(); }
-  virtual int dense_setup_lr_pair(int /*pair*/, int /*via*/, int /*n*/, const double* /*p*/, int /*ldp*/, const double* /*q*/, int /*ldq*/) { return no_dense(); }
-  virtual int dense_lr_info(int /*part*/, struct dla_dense_info* /*out*/) { return no_dense(); }
-  virtual int dense_drop_lr() { return no_dense(); }
-  virtual int dense_lr_mul(int /*part*/, int /*n*/, int /*m*/, const double* /*x*/, double* /*y*/) { return no_dense(); }
   virtual int dense_lrprec(int /*variant*/, int /*n*/, int /*m*/, double /*fac*/, const double* /*xp*/, const double* /*xm*/,
                            double* /*yp*/, double* /*ym*/) { return no_dense(); }
 

@@ -6752,13 +6752,39 @@ struct HipEngine : dla::Engine {
     }
     return op_matvec(op, n, m, x, y);
   }
+  // The three elementwise preconditioner launches, on the stored diagonals of the sparse or of the dense slots (the callers have
+  // admitted the call): px = x / (d + fac); px = x / (da + fac db) of the pencil; the harness' lrprec_1 / lrprec_2 (variant 1 / 2)
+  // on the diagonals of A+B, A-B and S+D.  kname: the kernel name the launch is booked under, empty for none.
+  int launch_diag_precnd(const char* kname, int n, int m, double fac, const double* d, const double* x, double* px)
+  {
+    Scope s(this, DLA_OP_PRECND, 8.0 * n * (2.0 * m + 1.0), (double)n * m, kname);
+    DLA_LAUNCH(diag_precnd_kernel, dim3(grid_blocks(env(), n, 256)), dim3(256), 0, st, n, m, fac, d, x, px);
+    HIPCHK(hipGetLastError());
+    return DLA_OK;
+  }
+  int launch_pencil_precnd(const char* kname, int n, int m, double fac, const double* da, const double* db, const double* x, double* px)
+  {
+    Scope s(this, DLA_OP_PRECND, 16.0 * (double)n * m + 16.0 * (double)n, 2.0 * (double)n * m, kname);
+    DLA_LAUNCH(pencil_precnd_kernel, dim3(grid_blocks(env(), n, 256)), dim3(256), 0, st, n, m, fac, da, db, x, px);
+    HIPCHK(hipGetLastError());
+    return DLA_OK;
+  }
+  int launch_lr_precnd(const char* kname, int variant, int n, int m, double fac, const double* da, const double* dm, const double* ds,
+                       const double* xp, const double* xm, double* yp, double* ym)
+  {
+    Scope s(this, DLA_OP_PRECND, 32.0 * (double)n * m + 24.0 * (double)n, 8.0 * (double)n * m, kname);
+    const bool vec2 = even_rows(n) && (((uintptr_t)xp | (uintptr_t)xm | (uintptr_t)yp | (uintptr_t)ym) % 16 == 0);
+    const size_t nv = (size_t)n / (vec2 ? 2 : 1);
+    const int blocks = grid_blocks(env(), (long long)nv, 256);
+    if (vec2) DLA_LAUNCH(lr_precnd_kernel<2>, dim3(blocks), dim3(256), 0, st, n, m, variant, fac, da, dm, ds, xp, xm, yp, ym);
+    else      DLA_LAUNCH(lr_precnd_kernel<1>, dim3(blocks), dim3(256), 0, st, n, m, variant, fac, da, dm, ds, xp, xm, yp, ym);
+    HIPCHK(hipGetLastError());
+    return DLA_OK;
+  }
   int spmm_precnd(int n, int m, double fac, const double* x, double* px) override
   {
     if (n != ops[dla::SPMM_A].n || !ops[dla::SPMM_A].diag) { err = "spmm_precnd: n differs from setup"; return DLA_ERR_ARG; }
-    Scope s(this, DLA_OP_PRECND, 8.0 * n * (2.0 * m + 1.0), (double)n * m);
-    DLA_LAUNCH(diag_precnd_kernel, dim3(grid_blocks(env(), n, 256)), dim3(256), 0, st, n, m, fac, ops[dla::SPMM_A].diagonal(), x, px);
-    HIPCHK(hipGetLastError());
-    return DLA_OK;
+    return launch_diag_precnd("", n, m, fac, ops[dla::SPMM_A].diagonal(), x, px);
   }
   // ---- ... of the pencil A - lambda B of a generalised problem (the metric B: bvec of reference diaglib.f90:1855)
   int spmm_precnd_pencil(int n, int m, double fac, const double* x, double* px) override
@@ -6767,28 +6793,50 @@ struct HipEngine : dla::Engine {
     if (ops[dla::SPMM_B].fmt < 0) { err = "spmm_precnd_pencil: no metric has been set up (dla_spmm_setup_metric_csr)"; return DLA_ERR_ARG; }
     if (ops[dla::SPMM_A].n != ops[dla::SPMM_B].n) { err = "spmm_precnd_pencil: the operator has " + std::to_string(ops[dla::SPMM_A].n) + " rows and the metric " + std::to_string(ops[dla::SPMM_B].n); return DLA_ERR_ARG; }
     if (n != ops[dla::SPMM_A].n) { err = "spmm_precnd_pencil: n differs from setup"; return DLA_ERR_ARG; }
-    Scope s(this, DLA_OP_PRECND, 16.0 * (double)n * m + 16.0 * (double)n, 2.0 * (double)n * m);
-    DLA_LAUNCH(pencil_precnd_kernel, dim3(grid_blocks(env(), n, 256)), dim3(256), 0, st, n, m, fac, ops[dla::SPMM_A].diagonal(), ops[dla::SPMM_B].diagonal(), x, px);
-    HIPCHK(hipGetLastError());
-    return DLA_OK;
+    return launch_pencil_precnd("", n, m, fac, ops[dla::SPMM_A].diagonal(), ops[dla::SPMM_B].diagonal(), x, px);
   }
 
   // ---- the stored dense matrices (the contract: include/diaglib_amd.h, dla_dense_setup and dla_dense_setup_lr; the kernels: beside
   // dense_mfma_kernel).  Six slots -- the operator, the metric and the four parts A+B, A-B, S+D, S-D of the linear-response pencil
-  // (slot DENSE_LR0 + part) -- each the packed copy, its diagonal and the workspace of a split product.  The blocks only grow: a
+  // (dla::DenseSlot) -- each the packed copy, its diagonal and the workspace of a split product.  The blocks only grow: a
   // smaller matrix after a larger one keeps the larger blocks (the kernels go by n / n_pad).
-  static constexpr int DENSE_LR0 = 2, DENSE_SLOTS = 6;
   struct DenseOp {
     int n = 0;                       // 0: nothing stored
     int last_m = 1;                  // width of the first pass of the most recent product (what dense_info describes)
     DeviceBuffer<double> a, diag, ws;
     void drop() { a.reset(); diag.reset(); ws.reset(); n = 0; last_m = 1; }
-  } dense[DENSE_SLOTS];
-  static const char* dense_noun(int slot)
+  } dense[dla::DENSE_SLOTS];
+  // The words a message about a dense slot needs: what the slot is called, the name of each public entry that reaches it (setup is
+  // also the set-up a callback names while the slot is empty) and the rule quoted for a public number out of range.
+  struct DenseWords { const char *noun, *setup, *setup_dev, *info, *mul, *range; };
+  static const DenseWords& dense_words(int slot)
   {
-    static const char* const nouns[DENSE_SLOTS] = {"dense operator", "dense metric", "dense part apb (A+B)", "dense part amb (A-B)",
-                                                   "dense part spd (S+D)", "dense part smd (S-D)"};
-    return nouns[slot];
+    static constexpr const char* which_rule = "which must be 0 (the operator) or 1 (the metric)";
+    static constexpr const char* part_rule = "part must be 0 (A+B), 1 (A-B), 2 (S+D) or 3 (S-D)";
+#define LR_WORDS(P, SUM) {"dense part " P " (" SUM ")", "dla_dense_setup_lr", "dla_dense_setup_lr_dev", "dla_dense_lr_info", "dense_" P "mul", part_rule}
+    static const DenseWords table[dla::DENSE_SLOTS] = {
+      {"dense operator", "dla_dense_setup", "dla_dense_setup_dev", "dla_dense_info", "dense_matvec", which_rule},
+      {"dense metric", "dla_dense_setup", "dla_dense_setup_dev", "dla_dense_info", "dense_bvec", which_rule},
+      LR_WORDS("apb", "A+B"), LR_WORDS("amb", "A-B"), LR_WORDS("spd", "S+D"), LR_WORDS("smd", "S-D")};
+#undef LR_WORDS
+    // (a number out of range is refused in the words of the entries that take such a number)
+    return table[slot == dla::DENSE_NO_PART ? dla::DENSE_APB : (slot < 0 || slot >= dla::DENSE_SLOTS) ? dla::DENSE_A : slot];
+  }
+  // The one place that decides whether a call on a dense slot is admitted; entry: the name of the public entry or of the callback.
+  // A set-up or a drop needs the slot to exist (DENSE_EXISTS), an info needs it to hold a matrix (DENSE_STORED), a callback needs
+  // that matrix to have n rows and names the set-up that is missing (DENSE_ROWS).  Leaves the refusal in err.
+  enum DenseNeed { DENSE_EXISTS, DENSE_STORED, DENSE_ROWS };
+  int dense_admit(int slot, const char* entry, DenseNeed need, int n = 0)
+  {
+    // (an admitted call -- every callback of a solve -- builds no string)
+    const DenseWords& w = dense_words(slot);
+    const auto refuse = [&](const std::string& why) { err = std::string(entry) + ": " + why; return (int)DLA_ERR_ARG; };
+    if (slot < 0 || slot >= dla::DENSE_SLOTS) return refuse(w.range);
+    if (need == DENSE_EXISTS) return DLA_OK;
+    const DenseOp& op = dense[slot];
+    if (op.n <= 0) return refuse(std::string("no ") + w.noun + " has been set up" + (need == DENSE_ROWS ? std::string(" (") + w.setup + ")" : std::string()));
+    if (need == DENSE_ROWS && n != op.n) return refuse("n = " + std::to_string(n) + " differs from the " + std::to_string(op.n) + " rows of the " + w.noun);
+    return DLA_OK;
   }
   // what every dense set-up refuses of one array; who: the entry's name with ": ", what: the array's name in the message
   int dense_array_ok(const std::string& who, const char* what, const char* ld, int n, const double* a, int lda)
@@ -6831,34 +6879,25 @@ struct HipEngine : dla::Engine {
     op.n = n;
     return DLA_OK;
   }
-  int dense_setup(int which, int via, int n, const double* a, int lda) override
+  int dense_setup(int slot, int via, int n, const double* a, int lda) override
   {
     const bool dev = via == dla::SPMM_VIA_DEVICE;
-    const std::string who = dev ? "dla_dense_setup_dev: " : "dla_dense_setup: ";
-    if (which != 0 && which != 1) { err = who + "which must be 0 (the operator) or 1 (the metric)"; return DLA_ERR_ARG; }
+    const char* entry = dev ? dense_words(slot).setup_dev : dense_words(slot).setup;
+    const std::string who = std::string(entry) + ": ";
+    { const int stc = dense_admit(slot, entry, DENSE_EXISTS); if (stc) return stc; }
     { const int stc = dense_array_ok(who, "matrix", "lda", n, a, lda); if (stc) return stc; }
-    return dense_store(who, dense[which], dev, n, a, lda);
-  }
-  static bool dense_part_ok(int part) { return part >= 0 && part < DENSE_SLOTS - DENSE_LR0; }
-  static constexpr const char* DENSE_PART_RULE = "part must be 0 (A+B), 1 (A-B), 2 (S+D) or 3 (S-D)";
-  int dense_setup_lr(int part, int via, int n, const double* a, int lda) override
-  {
-    const bool dev = via == dla::SPMM_VIA_DEVICE;
-    const std::string who = dev ? "dla_dense_setup_lr_dev: " : "dla_dense_setup_lr: ";
-    if (!dense_part_ok(part)) { err = who + DENSE_PART_RULE; return DLA_ERR_ARG; }
-    { const int stc = dense_array_ok(who, "matrix", "lda", n, a, lda); if (stc) return stc; }
-    return dense_store(who, dense[DENSE_LR0 + part], dev, n, a, lda);
+    return dense_store(who, dense[slot], dev, n, a, lda);
   }
   // p + q and p - q into the two slots of a pair, both or neither: every check and both allocations come before the first write.
   // A slot whose blocks have to grow gets new ones while it still holds the old, so a failed allocation leaves both slots as they were.
-  int dense_setup_lr_pair(int pair, int via, int n, const double* p, int ldp, const double* q, int ldq) override
+  int dense_setup_pair(int pair, int via, int n, const double* p, int ldp, const double* q, int ldq) override
   {
     const bool dev = via == dla::SPMM_VIA_DEVICE;
     const std::string who = dev ? "dla_dense_setup_lr_pair_dev: " : "dla_dense_setup_lr_pair: ";
     if (pair != 0 && pair != 1) { err = who + "pair must be 0 (A and B: fills A+B, A-B) or 1 (S and D: fills S+D, S-D)"; return DLA_ERR_ARG; }
     { const int stc = dense_array_ok(who, "first matrix (p)", "ldp", n, p, ldp); if (stc) return stc; }
     { const int stc = dense_array_ok(who, "second matrix (q)", "ldq", n, q, ldq); if (stc) return stc; }
-    DenseOp* op[2] = {&dense[DENSE_LR0 + 2 * pair], &dense[DENSE_LR0 + 2 * pair + 1]};
+    DenseOp* op[2] = {&dense[dla::DENSE_APB + 2 * pair], &dense[dla::DENSE_APB + 2 * pair + 1]};
     const int n_pad = dense_n_pad(n);
     const size_t total = (size_t)n_pad * n_pad;
     std::vector<double> packed[2], diag[2];
@@ -6897,70 +6936,36 @@ struct HipEngine : dla::Engine {
     op[0]->n = op[1]->n = n;
     return DLA_OK;
   }
-  int dense_info_of(const char* who, int slot, struct dla_dense_info* out)
+  int dense_info(int slot, struct dla_dense_info* out) override
   {
-    if (!out) { err = std::string(who) + ": out is a null pointer"; return DLA_ERR_ARG; }
+    const char* entry = dense_words(slot).info;
+    { const int stc = dense_admit(slot, entry, DENSE_EXISTS); if (stc) return stc; }
+    if (!out) { err = std::string(entry) + ": out is a null pointer"; return DLA_ERR_ARG; }
+    { const int stc = dense_admit(slot, entry, DENSE_STORED); if (stc) return stc; }
     const DenseOp& op = dense[slot];
-    if (op.n <= 0) { err = std::string(who) + ": no " + dense_noun(slot) + " has been set up"; return DLA_ERR_ARG; }
     const DensePlan p = dense_plan(ncu, op.n, op.last_m);
     out->n = op.n; out->n_pad = p.n_pad; out->row_tile = DENSE_TILE * DENSE_WAVE_TILES; out->k_chunks = p.k_chunks;
     out->device_bytes = 8LL * p.n_pad * p.n_pad + 8LL * op.n;
     out->workspace_bytes = 8LL * (long long)p.ws_doubles;
     return DLA_OK;
   }
-  int dense_info(int which, struct dla_dense_info* out) override
+  // (nothing stored: neither the device nor the stream is touched; a number out of range comes from dla_dense_drop alone)
+  int dense_drop(int first, int last) override
   {
-    if (which != 0 && which != 1) { err = "dla_dense_info: which must be 0 (the operator) or 1 (the metric)"; return DLA_ERR_ARG; }
-    return dense_info_of("dla_dense_info", which, out);
-  }
-  int dense_lr_info(int part, struct dla_dense_info* out) override
-  {
-    if (!dense_part_ok(part)) { err = std::string("dla_dense_lr_info: ") + DENSE_PART_RULE; return DLA_ERR_ARG; }
-    return dense_info_of("dla_dense_lr_info", DENSE_LR0 + part, out);
-  }
-  // (nothing stored: neither the device nor the stream is touched)
-  int dense_drop(int which) override
-  {
-    if (which != 0 && which != 1) { err = "dla_dense_drop: which must be 0 (the operator) or 1 (the metric)"; return DLA_ERR_ARG; }
-    if (dense[which].n <= 0 && !dense[which].a) return DLA_OK;
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipStreamSynchronize(st));     // (products of this slot may still be queued)
-    dense[which].drop();
-    return DLA_OK;
-  }
-  int dense_drop_lr() override
-  {
+    { const int stc = dense_admit(first, "dla_dense_drop", DENSE_EXISTS); if (stc) return stc; }
     bool any = false;
-    for (int s = DENSE_LR0; s < DENSE_SLOTS; ++s) any = any || dense[s].n > 0 || dense[s].a;
+    for (int s = first; s <= last; ++s) any = any || dense[s].n > 0 || dense[s].a;
     if (!any) return DLA_OK;
     HIPCHK(hipSetDevice(device));
-    HIPCHK(hipStreamSynchronize(st));     // (products of the parts may still be queued)
-    for (int s = DENSE_LR0; s < DENSE_SLOTS; ++s) dense[s].drop();
+    HIPCHK(hipStreamSynchronize(st));     // (products of these slots may still be queued)
+    for (int s = first; s <= last; ++s) dense[s].drop();
     return DLA_OK;
   }
-  // what a dense callback needs of its slot; who: the callback's name
-  int dense_admit(const std::string& who, int slot, int n)
+  // y = (slot) x: the passes of one product on the slot's copy and the slot's own workspace; the words of a refusal are the
+  // callback's (DenseWords::mul).  (The callbacks of host_logic.cpp pass their own DenseSlot: no number out of range gets here.)
+  int dense_mul(int slot, int n, int m, const double* x, double* y) override
   {
-    const DenseOp& op = dense[slot];
-    if (op.n <= 0) { err = who + ": no " + dense_noun(slot) + " has been set up (" + (slot < DENSE_LR0 ? "dla_dense_setup" : "dla_dense_setup_lr") + ")"; return DLA_ERR_ARG; }
-    if (n != op.n) { err = who + ": n = " + std::to_string(n) + " differs from the " + std::to_string(op.n) + " rows of the " + dense_noun(slot); return DLA_ERR_ARG; }
-    return DLA_OK;
-  }
-  int dense_mul(int which, int n, int m, const double* x, double* y) override
-  {
-    if (which != 0 && which != 1) { err = "dense product: no such slot"; return DLA_ERR_ARG; }
-    return dense_multiply(which ? "dense_bvec" : "dense_matvec", which, n, m, x, y);
-  }
-  int dense_lr_mul(int part, int n, int m, const double* x, double* y) override
-  {
-    static const char* const names[DENSE_SLOTS - DENSE_LR0] = {"dense_apbmul", "dense_ambmul", "dense_spdmul", "dense_smdmul"};
-    if (!dense_part_ok(part)) { err = "dense product: no such part"; return DLA_ERR_ARG; }
-    return dense_multiply(names[part], DENSE_LR0 + part, n, m, x, y);
-  }
-  // y = (slot) x: the passes of one product on the slot's copy and the slot's own workspace
-  int dense_multiply(const char* who, int slot, int n, int m, const double* x, double* y)
-  {
-    { const int stc = dense_admit(who, slot, n); if (stc) return stc; }
+    { const int stc = dense_admit(slot, dense_words(slot).mul, DENSE_ROWS, n); if (stc) return stc; }
     if (m <= 0) return DLA_OK;
     DenseOp& op = dense[slot];
     op.last_m = std::min(m, DENSE_MAX_COLS);
@@ -6999,42 +7004,26 @@ struct HipEngine : dla::Engine {
   // the diagonal kernels of the sparse operator on the stored dense diagonals
   int dense_precnd(bool pencil, int n, int m, double fac, const double* x, double* px) override
   {
-    const std::string who = pencil ? "dense_precnd_pencil" : "dense_precnd";
-    { const int stc = dense_admit(who, 0, n); if (stc) return stc; }
+    const char* who = pencil ? "dense_precnd_pencil" : "dense_precnd";
+    const DenseOp &a = dense[dla::DENSE_A], &b = dense[dla::DENSE_B];
+    { const int stc = dense_admit(dla::DENSE_A, who, DENSE_ROWS, n); if (stc) return stc; }
     if (pencil) {
-      if (dense[1].n <= 0) { err = who + ": no dense metric has been set up (dla_dense_setup with which = 1)"; return DLA_ERR_ARG; }
-      if (dense[1].n != dense[0].n) { err = who + ": the operator has " + std::to_string(dense[0].n) + " rows and the metric " + std::to_string(dense[1].n); return DLA_ERR_ARG; }
+      if (b.n <= 0) { err = std::string(who) + ": no dense metric has been set up (dla_dense_setup with which = 1)"; return DLA_ERR_ARG; }
+      if (b.n != a.n) { err = std::string(who) + ": the operator has " + std::to_string(a.n) + " rows and the metric " + std::to_string(b.n); return DLA_ERR_ARG; }
     }
     if (m <= 0) return DLA_OK;
-    const dim3 grid(grid_blocks(env(), n, 256));
-    if (pencil) {
-      Scope s(this, DLA_OP_PRECND, 16.0 * (double)n * m + 16.0 * (double)n, 2.0 * (double)n * m, "pencil_precnd_kernel");
-      DLA_LAUNCH(pencil_precnd_kernel, grid, dim3(256), 0, st, n, m, fac, (const double*)dense[0].diag, (const double*)dense[1].diag, x, px);
-    } else {
-      Scope s(this, DLA_OP_PRECND, 8.0 * n * (2.0 * m + 1.0), (double)n * m, "diag_precnd_kernel");
-      DLA_LAUNCH(diag_precnd_kernel, grid, dim3(256), 0, st, n, m, fac, (const double*)dense[0].diag, x, px);
-    }
-    HIPCHK(hipGetLastError());
-    return DLA_OK;
+    return pencil ? launch_pencil_precnd("pencil_precnd_kernel", n, m, fac, a.diag, b.diag, x, px)
+                  : launch_diag_precnd("diag_precnd_kernel", n, m, fac, a.diag, x, px);
   }
-  // lr_precnd_kernel, as spmm_lrprec launches it, on the stored diagonals of the dense parts A+B, A-B and S+D (S-D is not read)
+  // lr_precnd_kernel on the stored diagonals of the dense parts A+B, A-B and S+D (S-D is not read)
   int dense_lrprec(int variant, int n, int m, double fac, const double* xp, const double* xm, double* yp, double* ym) override
   {
-    const std::string who = variant == 1 ? "dense_lrprec1" : "dense_lrprec2";
-    for (int part : {(int)DLA_DENSE_LR_APB, (int)DLA_DENSE_LR_AMB, (int)DLA_DENSE_LR_SPD}) {
-      const int stc = dense_admit(who, DENSE_LR0 + part, n);
+    for (int slot : {(int)dla::DENSE_APB, (int)dla::DENSE_AMB, (int)dla::DENSE_SPD}) {
+      const int stc = dense_admit(slot, variant == 1 ? "dense_lrprec1" : "dense_lrprec2", DENSE_ROWS, n);
       if (stc) return stc;
     }
     if (m <= 0) return DLA_OK;
-    Scope s(this, DLA_OP_PRECND, 32.0 * (double)n * m + 24.0 * (double)n, 8.0 * (double)n * m);
-    const bool vec2 = even_rows(n) && (((uintptr_t)xp | (uintptr_t)xm | (uintptr_t)yp | (uintptr_t)ym) % 16 == 0);
-    const size_t nv = (size_t)n / (vec2 ? 2 : 1);
-    const int blocks = grid_blocks(env(), (long long)nv, 256);
-    const double *da = dense[DENSE_LR0 + DLA_DENSE_LR_APB].diag, *dm = dense[DENSE_LR0 + DLA_DENSE_LR_AMB].diag, *ds = dense[DENSE_LR0 + DLA_DENSE_LR_SPD].diag;
-    if (vec2) DLA_LAUNCH(lr_precnd_kernel<2>, dim3(blocks), dim3(256), 0, st, n, m, variant, fac, da, dm, ds, xp, xm, yp, ym);
-    else      DLA_LAUNCH(lr_precnd_kernel<1>, dim3(blocks), dim3(256), 0, st, n, m, variant, fac, da, dm, ds, xp, xm, yp, ym);
-    HIPCHK(hipGetLastError());
-    return DLA_OK;
+    return launch_lr_precnd("", variant, n, m, fac, dense[dla::DENSE_APB].diag, dense[dla::DENSE_AMB].diag, dense[dla::DENSE_SPD].diag, xp, xm, yp, ym);
   }
 
   // ---- the Chebyshev polynomial of A + fac I as a preconditioner (the contract: include/diaglib_amd.h, dla_spmm_precnd_cheb; the
@@ -7409,15 +7398,7 @@ struct HipEngine : dla::Engine {
       if (op.fmt < 0 || !op.diag) { err = who + ": " + words(slot).missing + " (dla_spmm_setup_lr_csr)"; return DLA_ERR_ARG; }
       if (n != op.n) { err = who + ": n = " + std::to_string(n) + " differs from the " + std::to_string(op.n) + " rows of " + words(slot).noun; return DLA_ERR_ARG; }
     }
-    Scope s(this, DLA_OP_PRECND, 32.0 * (double)n * m + 24.0 * (double)n, 8.0 * (double)n * m);
-    const bool vec2 = even_rows(n) && (((uintptr_t)xp | (uintptr_t)xm | (uintptr_t)yp | (uintptr_t)ym) % 16 == 0);
-    const size_t nv = (size_t)n / (vec2 ? 2 : 1);
-    const int blocks = grid_blocks(env(), (long long)nv, 256);
-    const double *da = ops[dla::SPMM_APB].diag, *dm = ops[dla::SPMM_AMB].diag, *ds = ops[dla::SPMM_SPD].diag;
-    if (vec2) DLA_LAUNCH(lr_precnd_kernel<2>, dim3(blocks), dim3(256), 0, st, n, m, variant, fac, da, dm, ds, xp, xm, yp, ym);
-    else      DLA_LAUNCH(lr_precnd_kernel<1>, dim3(blocks), dim3(256), 0, st, n, m, variant, fac, da, dm, ds, xp, xm, yp, ym);
-    HIPCHK(hipGetLastError());
-    return DLA_OK;
+    return launch_lr_precnd("", variant, n, m, fac, ops[dla::SPMM_APB].diag, ops[dla::SPMM_AMB].diag, ops[dla::SPMM_SPD].diag, xp, xm, yp, ym);
   }
 
   // ---- built-in operator

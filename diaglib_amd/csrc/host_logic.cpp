@@ -2033,123 +2033,100 @@ void dla_spmm_smdmul(const int* n, const int* m, const double* x, double* y) { s
 void dla_spmm_lrprec1(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { spmm_precondition(2, n, m, fac, xp, xm, yp, ym); }
 void dla_spmm_lrprec2(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { spmm_precondition(3, n, m, fac, xp, xm, yp, ym); }
 
-// ------------------------------------------------------------------ the stored dense matrices (include/diaglib_amd.h, dla_dense_setup)
-// which = 0 the operator A, 1 the metric B.  An accepted set-up binds its context to the calling thread's dense callbacks
-// (g_dense_ctx); info and drop never do.
-static int dense_set_up(dla_ctx* c, int which, int via, int n, const double* a, int lda)
-{
-  if (!c) return DLA_ERR_ARG;
-  const int st = engfail(c, c->eng->dense_setup(which, via, n, a, lda));
-  if (st == DLA_OK) g_dense_ctx = c;
-  return st;
-}
-int dla_dense_setup(dla_ctx* c, int which, int n, const double* a_host, int lda)
-{
-  DLA_T("dla_dense_setup");
-  return dense_set_up(c, which, dla::SPMM_VIA_HOST, n, a_host, lda);
-}
-int dla_dense_setup_dev(dla_ctx* c, int which, int n, const double* a_dev, int lda)
-{
-  DLA_T("dla_dense_setup_dev");
-  return dense_set_up(c, which, dla::SPMM_VIA_DEVICE, n, a_dev, lda);
-}
-int dla_dense_info(dla_ctx* c, int which, struct dla_dense_info* out)
-{
-  if (!c) return DLA_ERR_ARG;
-  return engfail(c, c->eng->dense_info(which, out));
-}
-int dla_dense_drop(dla_ctx* c, int which)
-{
-  if (!c) return DLA_ERR_ARG;
-  return engfail(c, c->eng->dense_drop(which));
-}
-static void dense_product(int which, const int* n, const int* m, const double* x, double* y)
-{
-  static const SpmmCallback words[2] = {{"dla_dense_matvec before dla_dense_setup: no dense operator has been set up", "dla_dense_matvec failed: "},
-                                        {"dla_dense_bvec before dla_dense_setup: no dense metric has been set up", "dla_dense_bvec failed: "}};
-  dla_ctx* c = g_dense_ctx;
-  if (!c) { callback_failed(DLA_ERR_ARG, words[which].unbound); return; }
-  if (int st = c->eng->dense_mul(which, *n, *m, x, y)) callback_failed(st, words[which].failed + c->eng->err);
-}
-static void dense_precondition(bool pencil, const int* n, const int* m, const double* fac, const double* x, double* px)
-{
-  static const SpmmCallback words[2] = {{"dla_dense_precnd before dla_dense_setup: no dense operator has been set up", "dla_dense_precnd failed: "},
-                                        {"dla_dense_precnd_pencil before dla_dense_setup: no dense operator has been set up", "dla_dense_precnd_pencil failed: "}};
-  dla_ctx* c = g_dense_ctx;
-  if (!c) { callback_failed(DLA_ERR_ARG, words[pencil].unbound); return; }
-  if (int st = c->eng->dense_precnd(pencil, *n, *m, *fac, x, px)) callback_failed(st, words[pencil].failed + c->eng->err);
-}
-void dla_dense_matvec(const int* n, const int* m, const double* x, double* ax) { dense_product(0, n, m, x, ax); }
-void dla_dense_bvec(const int* n, const int* m, const double* x, double* bx) { dense_product(1, n, m, x, bx); }
-void dla_dense_precnd(const int* n, const int* m, const double* fac, const double* x, double* px) { dense_precondition(false, n, m, fac, x, px); }
-void dla_dense_precnd_pencil(const int* n, const int* m, const double* fac, const double* x, double* px) { dense_precondition(true, n, m, fac, x, px); }
-
-// ... and the four dense parts of the linear-response pencil (include/diaglib_amd.h, dla_dense_setup_lr).  An accepted set-up of a
-// part or of a pair binds its context to the thread's dense callbacks like dla_dense_setup does; info and drop never do.
-static int dense_bound(dla_ctx* c, int st)
+// ------------------------------------------------------------------ the stored dense matrices (include/diaglib_amd.h, dla_dense_setup
+// and dla_dense_setup_lr): the operator A, the metric B and the four parts of the linear-response pencil, six slots (dla::DenseSlot)
+// reached like the sparse ones above.  An accepted set-up -- of a slot or of a pair -- binds its context to the calling thread's dense
+// callbacks (g_dense_ctx); info and drop never do.  dla_dense_info and dla_dense_lr_info pass a null `out` on: the engine words it.
+using dla::DENSE_A; using dla::DENSE_B; using dla::DENSE_APB; using dla::DENSE_SMD;
+static int dense_set_up(dla_ctx* c, int st)
 {
   st = engfail(c, st);
   if (st == DLA_OK) g_dense_ctx = c;
   return st;
 }
+static int dense_slot_info(dla_ctx* c, int slot, struct dla_dense_info* out)
+{
+  if (!c) return DLA_ERR_ARG;
+  return engfail(c, c->eng->dense_info(slot, out));
+}
+static int dense_slot_drop(dla_ctx* c, int first, int last)
+{
+  if (!c) return DLA_ERR_ARG;
+  return engfail(c, c->eng->dense_drop(first, last));
+}
+static const SpmmCallback dense_mul_words[dla::DENSE_SLOTS] = {
+  {"dla_dense_matvec before dla_dense_setup: no dense operator has been set up", "dla_dense_matvec failed: "},
+  {"dla_dense_bvec before dla_dense_setup: no dense metric has been set up", "dla_dense_bvec failed: "},
+  {"dla_dense_apbmul before dla_dense_setup_lr: no dense part apb (A+B) has been set up", "dla_dense_apbmul failed: "},
+  {"dla_dense_ambmul before dla_dense_setup_lr: no dense part amb (A-B) has been set up", "dla_dense_ambmul failed: "},
+  {"dla_dense_spdmul before dla_dense_setup_lr: no dense part spd (S+D) has been set up", "dla_dense_spdmul failed: "},
+  {"dla_dense_smdmul before dla_dense_setup_lr: no dense part smd (S-D) has been set up", "dla_dense_smdmul failed: "}};
+static void dense_product(int slot, const int* n, const int* m, const double* x, double* y)
+{
+  dla_ctx* c = g_dense_ctx;
+  if (!c) { callback_failed(DLA_ERR_ARG, dense_mul_words[slot].unbound); return; }
+  if (int st = c->eng->dense_mul(slot, *n, *m, x, y)) callback_failed(st, dense_mul_words[slot].failed + c->eng->err);
+}
+// kind 0: dla_dense_precnd, 1: dla_dense_precnd_pencil, 2 / 3: dla_dense_lrprec1 / 2 (xm, ym: the second pair of the latter two)
+static void dense_precondition(int kind, const int* n, const int* m, const double* fac, const double* x, const double* xm, double* y, double* ym)
+{
+  static const SpmmCallback words[4] = {
+    {"dla_dense_precnd before dla_dense_setup: no dense operator has been set up", "dla_dense_precnd failed: "},
+    {"dla_dense_precnd_pencil before dla_dense_setup: no dense operator has been set up", "dla_dense_precnd_pencil failed: "},
+    {"dla_dense_lrprec1 before dla_dense_setup_lr: no dense part has been set up", "dla_dense_lrprec1 failed: "},
+    {"dla_dense_lrprec2 before dla_dense_setup_lr: no dense part has been set up", "dla_dense_lrprec2 failed: "}};
+  dla_ctx* c = g_dense_ctx;
+  if (!c) { callback_failed(DLA_ERR_ARG, words[kind].unbound); return; }
+  const int st = kind < 2 ? c->eng->dense_precnd(kind == 1, *n, *m, *fac, x, y) : c->eng->dense_lrprec(kind - 1, *n, *m, *fac, x, xm, y, ym);
+  if (st) callback_failed(st, words[kind].failed + c->eng->err);
+}
+
+// ---- the operator A and the metric B ...
+int dla_dense_setup(dla_ctx* c, int which, int n, const double* a_host, int lda)
+{
+  DLA_T("dla_dense_setup");
+  return c ? dense_set_up(c, c->eng->dense_setup(dla::dense_slot_of_which(which), dla::SPMM_VIA_HOST, n, a_host, lda)) : DLA_ERR_ARG;
+}
+int dla_dense_setup_dev(dla_ctx* c, int which, int n, const double* a_dev, int lda)
+{
+  DLA_T("dla_dense_setup_dev");
+  return c ? dense_set_up(c, c->eng->dense_setup(dla::dense_slot_of_which(which), dla::SPMM_VIA_DEVICE, n, a_dev, lda)) : DLA_ERR_ARG;
+}
+int dla_dense_info(dla_ctx* c, int which, struct dla_dense_info* out) { return dense_slot_info(c, dla::dense_slot_of_which(which), out); }
+int dla_dense_drop(dla_ctx* c, int which) { const int slot = dla::dense_slot_of_which(which); return dense_slot_drop(c, slot, slot); }
+void dla_dense_matvec(const int* n, const int* m, const double* x, double* ax) { dense_product(DENSE_A, n, m, x, ax); }
+void dla_dense_bvec(const int* n, const int* m, const double* x, double* bx) { dense_product(DENSE_B, n, m, x, bx); }
+void dla_dense_precnd(const int* n, const int* m, const double* fac, const double* x, double* px) { dense_precondition(0, n, m, fac, x, nullptr, px, nullptr); }
+void dla_dense_precnd_pencil(const int* n, const int* m, const double* fac, const double* x, double* px) { dense_precondition(1, n, m, fac, x, nullptr, px, nullptr); }
+
+// ---- ... and the four parts of a linear-response pencil, one at a time or two from a pair
 int dla_dense_setup_lr(dla_ctx* c, int part, int n, const double* a_host, int lda)
 {
   DLA_T("dla_dense_setup_lr");
-  if (!c) return DLA_ERR_ARG;
-  return dense_bound(c, c->eng->dense_setup_lr(part, dla::SPMM_VIA_HOST, n, a_host, lda));
+  return c ? dense_set_up(c, c->eng->dense_setup(dla::dense_slot_of_part(part), dla::SPMM_VIA_HOST, n, a_host, lda)) : DLA_ERR_ARG;
 }
 int dla_dense_setup_lr_dev(dla_ctx* c, int part, int n, const double* a_dev, int lda)
 {
   DLA_T("dla_dense_setup_lr_dev");
-  if (!c) return DLA_ERR_ARG;
-  return dense_bound(c, c->eng->dense_setup_lr(part, dla::SPMM_VIA_DEVICE, n, a_dev, lda));
+  return c ? dense_set_up(c, c->eng->dense_setup(dla::dense_slot_of_part(part), dla::SPMM_VIA_DEVICE, n, a_dev, lda)) : DLA_ERR_ARG;
 }
 int dla_dense_setup_lr_pair(dla_ctx* c, int pair, int n, const double* p_host, int ldp, const double* q_host, int ldq)
 {
   DLA_T("dla_dense_setup_lr_pair");
-  if (!c) return DLA_ERR_ARG;
-  return dense_bound(c, c->eng->dense_setup_lr_pair(pair, dla::SPMM_VIA_HOST, n, p_host, ldp, q_host, ldq));
+  return c ? dense_set_up(c, c->eng->dense_setup_pair(pair, dla::SPMM_VIA_HOST, n, p_host, ldp, q_host, ldq)) : DLA_ERR_ARG;
 }
 int dla_dense_setup_lr_pair_dev(dla_ctx* c, int pair, int n, const double* p_dev, int ldp, const double* q_dev, int ldq)
 {
   DLA_T("dla_dense_setup_lr_pair_dev");
-  if (!c) return DLA_ERR_ARG;
-  return dense_bound(c, c->eng->dense_setup_lr_pair(pair, dla::SPMM_VIA_DEVICE, n, p_dev, ldp, q_dev, ldq));
+  return c ? dense_set_up(c, c->eng->dense_setup_pair(pair, dla::SPMM_VIA_DEVICE, n, p_dev, ldp, q_dev, ldq)) : DLA_ERR_ARG;
 }
-int dla_dense_lr_info(dla_ctx* c, int part, struct dla_dense_info* out)
-{
-  if (!c) return DLA_ERR_ARG;
-  return engfail(c, c->eng->dense_lr_info(part, out));
-}
-int dla_dense_drop_lr(dla_ctx* c)
-{
-  if (!c) return DLA_ERR_ARG;
-  return engfail(c, c->eng->dense_drop_lr());
-}
-static void dense_lr_product(int part, const int* n, const int* m, const double* x, double* y)
-{
-  static const SpmmCallback words[4] = {
-    {"dla_dense_apbmul before dla_dense_setup_lr: no dense part apb (A+B) has been set up", "dla_dense_apbmul failed: "},
-    {"dla_dense_ambmul before dla_dense_setup_lr: no dense part amb (A-B) has been set up", "dla_dense_ambmul failed: "},
-    {"dla_dense_spdmul before dla_dense_setup_lr: no dense part spd (S+D) has been set up", "dla_dense_spdmul failed: "},
-    {"dla_dense_smdmul before dla_dense_setup_lr: no dense part smd (S-D) has been set up", "dla_dense_smdmul failed: "}};
-  dla_ctx* c = g_dense_ctx;
-  if (!c) { callback_failed(DLA_ERR_ARG, words[part].unbound); return; }
-  if (int st = c->eng->dense_lr_mul(part, *n, *m, x, y)) callback_failed(st, words[part].failed + c->eng->err);
-}
-static void dense_lr_precondition(int variant, const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym)
-{
-  static const SpmmCallback words[2] = {{"dla_dense_lrprec1 before dla_dense_setup_lr: no dense part has been set up", "dla_dense_lrprec1 failed: "},
-                                        {"dla_dense_lrprec2 before dla_dense_setup_lr: no dense part has been set up", "dla_dense_lrprec2 failed: "}};
-  dla_ctx* c = g_dense_ctx;
-  if (!c) { callback_failed(DLA_ERR_ARG, words[variant - 1].unbound); return; }
-  if (int st = c->eng->dense_lrprec(variant, *n, *m, *fac, xp, xm, yp, ym)) callback_failed(st, words[variant - 1].failed + c->eng->err);
-}
-void dla_dense_apbmul(const int* n, const int* m, const double* x, double* y) { dense_lr_product(DLA_DENSE_LR_APB, n, m, x, y); }
-void dla_dense_ambmul(const int* n, const int* m, const double* x, double* y) { dense_lr_product(DLA_DENSE_LR_AMB, n, m, x, y); }
-void dla_dense_spdmul(const int* n, const int* m, const double* x, double* y) { dense_lr_product(DLA_DENSE_LR_SPD, n, m, x, y); }
-void dla_dense_smdmul(const int* n, const int* m, const double* x, double* y) { dense_lr_product(DLA_DENSE_LR_SMD, n, m, x, y); }
-void dla_dense_lrprec1(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { dense_lr_precondition(1, n, m, fac, xp, xm, yp, ym); }
-void dla_dense_lrprec2(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { dense_lr_precondition(2, n, m, fac, xp, xm, yp, ym); }
+int dla_dense_lr_info(dla_ctx* c, int part, struct dla_dense_info* out) { return dense_slot_info(c, dla::dense_slot_of_part(part), out); }
+int dla_dense_drop_lr(dla_ctx* c) { return dense_slot_drop(c, DENSE_APB, DENSE_SMD); }
+void dla_dense_apbmul(const int* n, const int* m, const double* x, double* y) { dense_product(dla::DENSE_APB, n, m, x, y); }
+void dla_dense_ambmul(const int* n, const int* m, const double* x, double* y) { dense_product(dla::DENSE_AMB, n, m, x, y); }
+void dla_dense_spdmul(const int* n, const int* m, const double* x, double* y) { dense_product(dla::DENSE_SPD, n, m, x, y); }
+void dla_dense_smdmul(const int* n, const int* m, const double* x, double* y) { dense_product(dla::DENSE_SMD, n, m, x, y); }
+void dla_dense_lrprec1(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { dense_precondition(2, n, m, fac, xp, xm, yp, ym); }
+void dla_dense_lrprec2(const int* n, const int* m, const double* fac, const double* xp, const double* xm, double* yp, double* ym) { dense_precondition(3, n, m, fac, xp, xm, yp, ym); }
 
 }  // extern "C"

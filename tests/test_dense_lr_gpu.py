@@ -423,6 +423,7 @@ def test_lrprec_against_numpy_bit_for_bit(dev, n, m):
         np.fill_diagonal(a, diag)
         (setup_device if k == 1 else setup_host)(dev, part, a, n + k)
     xp, xm = (np.asfortranarray(rng.standard_normal((n, m))) for _ in range(2))
+    dev.reset_stats()
     launches = dev.stats()["precnd"]["launches"]
     for variant in (1, 2):
         for fac in (0.3, -1.7):
@@ -431,6 +432,10 @@ def test_lrprec_against_numpy_bit_for_bit(dev, n, m):
             assert same_bits(yp, wp), f"lrprec{variant} fac={fac}: yp differs in {int((yp != wp).sum())} places, max {np.abs(yp - wp).max():.3e}"
             assert same_bits(ym, wm), f"lrprec{variant} fac={fac}: ym differs in {int((ym != wm).sum())} places, max {np.abs(ym - wm).max():.3e}"
     assert dev.stats()["precnd"]["launches"] == launches + 4
+    # booked as spmm_lrprec books its launches: under no kernel name, 32 n m + 24 n bytes and 8 n m flops each
+    pc = dev.stats()["precnd"]
+    assert (pc["launches"], pc["alg_bytes"], pc["flops"]) == (4, 4 * (32.0 * n * m + 24.0 * n), 4 * 8.0 * n * m), pc
+    assert not any(v["launches"] for v in dev.kernel_stats().values()), dev.kernel_stats()
 
 
 def test_lrprec_on_the_diagonals_a_pair_set_up_formed(dev):

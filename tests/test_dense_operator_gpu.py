@@ -204,6 +204,18 @@ def test_the_preconditioners_give_the_bits_of_the_numpy_expressions(ctx):
     pre = ctx.stats()["precnd"]["launches"]
     precondition(ctx, "dla_dense_precnd", fac, x)
     assert ctx.stats()["precnd"]["launches"] == pre + 1
+    # booked: one launch each under the kernel's name, with the bytes and flops the sparse preconditioners book for theirs
+    px, py = ctx.panel(x), ctx.panel(n, m)
+    for name, kernel, nbytes, flops in (("dla_dense_precnd", "diag_precnd_kernel", 8.0 * n * (2.0 * m + 1.0), 1.0 * n * m),
+                                        ("dla_dense_precnd_pencil", "pencil_precnd_kernel", 16.0 * n * m + 16.0 * n, 2.0 * n * m)):
+        ctx.reset_stats()
+        ctx._chk(ctx.lib.dla_call_precnd(ctx.h, capi.fn_address(name), n, m, fac, px.ptr, py.ptr))
+        ctx.sync()
+        ks = {k: (v["launches"], v["alg_bytes"], v["flops"]) for k, v in ctx.kernel_stats().items() if v["launches"]}
+        assert ks == {kernel: (1, nbytes, flops)}, ks
+        pc = ctx.stats()["precnd"]
+        assert (pc["launches"], pc["alg_bytes"], pc["flops"]) == (1, nbytes, flops), pc
+    px.free(); py.free()
 
 
 # ------------------------------------------------------------------ 5. independence and refusals

@@ -314,6 +314,7 @@ def test_lrprec_against_numpy_bit_for_bit(dev, rng, n, m, offsets):
     d = _diagonal_parts(dev, n, rng)
     xp, xm = (np.asfortranarray(rng.standard_normal((n, m))) for _ in range(2))
     aa = 0.5 * (d["apb"] + d["amb"])
+    dev.reset_stats()
     for variant in (1, 2):
         for fac in (0.3, -1.7):
             pole = aa * aa - fac * fac * d["spd"] ** 2 if variant == 1 else fac * fac * aa * aa - d["spd"] ** 2
@@ -323,6 +324,10 @@ def test_lrprec_against_numpy_bit_for_bit(dev, rng, n, m, offsets):
             wp, wm = lrprec_numpy(variant, fac, d["apb"], d["amb"], d["spd"], xp, xm)
             assert same_bits(yp, wp), f"lrprec{variant} fac={fac}: yp differs in {int((yp != wp).sum())} places, max {np.abs(yp - wp).max():.3e}"
             assert same_bits(ym, wm), f"lrprec{variant} fac={fac}: ym differs in {int((ym != wm).sum())} places, max {np.abs(ym - wm).max():.3e}"
+    # booked: four launches under no kernel name, 32 n m + 24 n bytes and 8 n m flops each
+    pc = dev.stats()["precnd"]
+    assert (pc["launches"], pc["alg_bytes"], pc["flops"]) == (4, 4 * (32.0 * n * m + 24.0 * n), 4 * 8.0 * n * m), pc
+    assert not any(v["launches"] for v in dev.kernel_stats().values()), dev.kernel_stats()
 
 
 def test_lrprec_takes_a_second_stride_trip(dev, rng):

@@ -160,6 +160,14 @@ def test_pencil_preconditioner(dev, rng, n, m, fmt_b):
     den = a.diagonal() + fac
     wantp = np.where(np.abs(den)[:, None] > 1e-5, x / den[:, None], x)
     assert np.abs(gp.body() - wantp).max() <= 4 * EPS * np.abs(wantp).max()
+    # booked: one launch each under no kernel name, with the bytes and flops of the elementwise pass
+    for name, nbytes, flops in (("dla_spmm_precnd_pencil", 16.0 * n * m + 16.0 * n, 2.0 * n * m), ("dla_spmm_precnd", 8.0 * n * (2.0 * m + 1.0), 1.0 * n * m)):
+        dev.reset_stats()
+        call_precnd(dev, name, n, m, fac, gx.ptr, gp.ptr)
+        dev.sync()
+        assert not any(v["launches"] for v in dev.kernel_stats().values()), dev.kernel_stats()
+        pc = dev.stats()["precnd"]
+        assert (pc["launches"], pc["alg_bytes"], pc["flops"]) == (1, nbytes, flops), pc
     gx.free(); gp.free()
 
 

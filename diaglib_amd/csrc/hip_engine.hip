@@ -7461,8 +7461,9 @@ struct HipEngine : dla::Engine {
   int synth_precnd(int n, int m, double fac, const double* x, double* px) override
   {
     if (n != syn_n) { err = "synth_precnd: n differs from setup"; return DLA_ERR_ARG; }
-    Scope s(this, DLA_OP_PRECND, 8.0 * n * (2.0 * m + 1.0), (double)n * m);
     const bool vec2 = even_rows(n) && (((uintptr_t)x | (uintptr_t)px) % 16 == 0);
+    // (booked under the instance's name: which of the two ran is a decision of the alignment and of the peers' shards)
+    Scope s(this, DLA_OP_PRECND, 8.0 * n * (2.0 * m + 1.0), (double)n * m, vec2 ? "synth_precnd_kernel<2>" : "synth_precnd_kernel<1>");
     const size_t nv = (size_t)n / (vec2 ? 2 : 1);
     const int blocks = (int)std::max((size_t)1, std::min((size_t)ncu * 8, (nv + 255) / 256));
     if (vec2) DLA_LAUNCH(synth_precnd_kernel<2>, dim3(blocks), dim3(256), 0, st, n, m, fac, d_diag, x, px);

@@ -36,7 +36,7 @@ EXPORTS = [
     "dla_backend_name", "dla_get_stats", "dla_reset_stats", "dla_get_kernel_stats", "dla_stream",
     "dla_comm_unique_id", "dla_comm_init", "dla_comm_finalize", "dla_comm_info", "dla_p2p_export", "dla_p2p_attach", "dla_p2p_detach", "dla_set_allreduce_hook", "dla_set_shard",
     "dla_alloc", "dla_free", "dla_trim", "dla_zero", "dla_upload", "dla_download", "dla_copy", "dla_sync",
-    "dla_gram", "dla_gram_lower", "dla_panel_gemm", "dla_panel_update", "dla_trmm_linvt", "dla_trmm_gram", "dla_update_gram", "dla_combo_gram", "dla_ritz_residual", "dla_ritz_residual_p", "dla_ritz_residual2", "dla_axpy",
+    "dla_gram", "dla_gram_lower", "dla_panel_gemm", "dla_panel_update", "dla_trmm_linvt", "dla_trmm_gram", "dla_update_gram", "dla_combo_gram", "dla_ritz_residual", "dla_ritz_residual_p", "dla_ritz_residual2", "dla_ritz_expand", "dla_ritz_expand_counts", "dla_ritz_expand_measured", "dla_axpy",
     "dla_nrm2", "dla_stream_triad", "dla_random_fill", "dla_fill_guess",
     "dla_ortho_cd", "dla_ortho_qr", "dla_ortho_vs_x", "dla_b_ortho", "dla_b_ortho_vs_x", "dla_check_guess", "dla_get_coeffs",
     "dla_call_matvec", "dla_call_precnd", "dla_expand_project", "dla_expand_project_metric",
@@ -150,6 +150,9 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dla_ritz_residual": (i, [vp, i, i, i, vp, vp, c_dp, i, c_dp, i, c_ip, vp, vp, vp, c_dp]),
         "dla_ritz_residual_p": (i, [vp, i, i, i, vp, vp, c_dp, i, c_dp, i, c_ip, vp, vp, vp, c_dp, i, c_dp, i, vp, vp]),
         "dla_ritz_residual2": (i, [vp, i, i, i, vp, vp, c_dp, i, c_dp, i, c_dp, i, c_ip, vp, vp, vp, vp, c_dp]),
+        "dla_ritz_expand": (i, [vp, i, i, i, vp, vp, c_dp, i, c_dp, i, c_ip, vp, vp, vp, c_dp, vp, d, i, i, vp, c_ip]),
+        "dla_ritz_expand_counts": (i, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+        "dla_ritz_expand_measured": (i, [vp, i, i, c_dp, i]),
         "dla_axpy": (i, [vp, sz, d, vp, vp]), "dla_nrm2": (i, [vp, sz, vp, c_dp]),
         "dla_stream_triad": (i, [vp, sz, i, c_dp]),
         "dla_random_fill": (i, [vp, i, i, vp]), "dla_fill_guess": (i, [vp, i, i, vp, C.c_ulonglong, C.c_longlong]),
@@ -445,6 +448,34 @@ class Context:
                                              n_res, skip.ctypes.data_as(c_ip), evec.ptr if evec is not None else None, r.ptr,
                                              avy.ptr if avy is not None else None, _dp(rn)))
         return rn
+
+    def ritz_expand(self, v: DevPanel, av: DevPanel, y: np.ndarray, eig: np.ndarray, n_res: int, skip: np.ndarray,
+                    evec: Optional[DevPanel], r: DevPanel, precnd: int, fac: float, first: int, u0: DevPanel,
+                    m: Optional[int] = None) -> tuple:
+        """dla_ritz_expand: the Ritz sweep that may also form u0 = precnd(r(:, first:), fac) (first is 1-based, u0 has m - first + 1
+        columns) and measure [v | u0]^T u0.  Returns (rnorm, fused)."""
+        y = np.asfortranarray(y, dtype=np.float64)
+        m = evec.m if evec is not None else (y.shape[1] if m is None else int(m))
+        eig = np.ascontiguousarray(eig, dtype=np.float64)
+        skip = np.ascontiguousarray(skip, dtype=np.int32)
+        rn = np.zeros((2, max(1, n_res)), order="F")
+        fused = C.c_int(0)
+        self._chk(self.lib.dla_ritz_expand(self.h, v.n, v.m, m, v.ptr, av.ptr, _dp(y), y.shape[0], _dp(eig), n_res,
+                                           skip.ctypes.data_as(c_ip), evec.ptr if evec is not None else None, r.ptr, None, _dp(rn),
+                                           precnd, float(fac), int(first), u0.m, u0.ptr, C.byref(fused)))
+        return rn, bool(fused.value)
+
+    def ritz_expand_counts(self) -> tuple:
+        """(fused sweeps that ran, fused sweeps whose measurement nobody took) on this context"""
+        run, dropped = C.c_longlong(0), C.c_longlong(0)
+        self._chk(self.lib.dla_ritz_expand_counts(self.h, C.byref(run), C.byref(dropped)))
+        return int(run.value), int(dropped.value)
+
+    def ritz_expand_measured(self, m: int, k: int) -> np.ndarray:
+        """[v | u0]^T u0 ((m + k) x k) of the fused sweep on record"""
+        out = np.zeros((m + k, k), order="F")
+        self._chk(self.lib.dla_ritz_expand_measured(self.h, m, k, _dp(out), m + k))
+        return out
 
     def ritz_residual_p(self, v: DevPanel, av: DevPanel, y: np.ndarray, eig: np.ndarray, n_res: int, skip: np.ndarray,
                         evec: Optional[DevPanel], r: DevPanel, avy: Optional[DevPanel], c2: np.ndarray, p: DevPanel,

@@ -228,6 +228,22 @@ struct Engine : BlockOps {
                             const double* eig, int n_res, const int* skip, double* evec, double* r,
                             double* avy /* optional n x m: uncorrected AV*Y */,
                             double* sumsq_max /* 2*n_res: sum r^2, max|r| */) = 0;
+  // The Ritz sweep without Ritz vectors that also forms the next Davidson block from a PREDICTED first open root (dla_ritz_expand):
+  // u0 = precnd(r(:, first0 ..), fac) with the device-resident diagonal of the library's preconditioner `precnd_kind` (0: sample
+  // operator, 1: stored sparse, 2: stored dense), k = m - first0 columns, and [V | u0]^T u0 measured for the orthogonalisation chain
+  // that follows (the engine remembers it until ortho_chain_begin on the same block, or until anything else is launched).
+  // *ran = 0: the engine does not take the shape and NOTHING has been done -- the caller runs ritz_residual.  Default: never.
+  virtual int ritz_expand(int /*n*/, int /*l*/, int /*m*/, const double* /*v*/, const double* /*av*/, const double* /*y_host*/, int /*ldy*/,
+                          const double* /*eig*/, int /*n_res*/, const int* /*skip*/, double* /*r*/, double* /*sumsq_max*/,
+                          int /*precnd_kind*/, double /*fac*/, int /*first0*/, int /*k*/, double* /*u0*/, int* ran)
+  {
+    *ran = 0;
+    return 0;
+  }
+  // fused sweeps that ran, and records of them that were dropped unused (the prediction missed, or something else came between)
+  virtual void ritz_expand_counts(long long* run, long long* discarded) { *run = 0; *discarded = 0; }
+  // the measured matrices of the fused sweep on record, [V | u0]^T u0 ((m + k) x k, host), reduced as the chain would reduce them
+  virtual int ritz_expand_measured(int /*m*/, int /*k*/, double* /*c_host*/, int /*ldc*/) { return DLA_ERR_ARG; }
   // the same sweep also forms P = V C2 and AP = AV C2 (k2 columns; LOBPCG's new P block, reference diaglib.f90:495-501,
   // whose products read the same two panels as the Ritz step).  Default: the Ritz step, then two panel products.
   virtual int ritz_residual_p(int n, int l, int m, const double* v, const double* av, const double* y_host, int ldy,

@@ -1328,6 +1328,202 @@ __global__ __launch_bounds__(256) void ritz_reduce_kernel(const double* red, int
 }
 
 // ======================================================================================
+// Ritz sweep that also forms and measures the next Davidson block
+// ======================================================================================
+// The residual block R = AV Y - (V Y) Lambda of a Davidson iteration, its norms, the preconditioned block U0 = R(:, first:) / (d + fac)
+// and the two matrices the orthogonalisation chain measures first, V^T U0 and U0^T U0, in ONE sweep over V and AV -- on the data
+// flow of gram_lds_kernel WP == 2: a wave stages 16 rows of ALL columns of V, then of AV, in its LDS image ([column][18]); the
+// tiles of V Y and AV Y are 4 TX MFMAs each away (D^T = Y^T V^T, the coefficients in registers for the whole sweep, two independent
+// chains side by side).  The two products and the correction r - theta e are ritz_kernel's, step by step: the same MFMA per four
+// columns in the same order, the same expression -- R comes out bit for bit as from the plain sweep, its norms to the rounding of
+// another order of summation (the one-sweep form R = [V | AV] [-Y Lambda ; Y] would save nothing and round differently: on the
+// benchmark, whose tolerance sits at rounding level, a root then locked one sweep later).  Every lane then holds R[row c][g + 4 r] and
+//   * adds r^2 and max |r| of the columns whose norm is wanted (RitzExpandArgs::act) to its partials -- ritz_reduce_kernel's layout,
+//   * stores R (16 consecutive rows of a column per 16 lanes: full 128-byte segments),
+//   * scales by the library's diagonal rule (the expression of synth_precnd_kernel / diag_precnd_kernel: a division), stores
+//     columns f0 .. nb-1 as U0 and puts the stored values into the image's output tile, columns 0 .. k-1,
+//   * forms V^T U0 (the AV tiles take no part) and U0^T U0 from that tile, as gram_lds_kernel WP does.
+// The block partials go out as a one-pass WP sweep's: [block][TX + 1][256], slot t = V tile t, slot TX = U0^T U0 -- and they ARE that
+// sweep's, bit for bit, when the grid is its grid (ritz_expand_plan takes wp_plan's): the same rows go to the same wave in the same
+// order (RitzExpandArgs::pair where that sweep stages 32 rows), the same MFMAs in the same order, the same sum over the waves.  A
+// solve with the fused sweep therefore differs from one without only through the order in which the norms are summed.
+// Even n, 16-byte aligned panels (the callers decline everything else); rows >= n are staged as zeros and add nothing.
+struct RitzExpandArgs {
+  const double* v;     // n x m
+  const double* av;    // n x m
+  const double* cpk;   // packed coefficients Y, [16 TX][16], zero padded: both products take them
+  const double* diag;  // n
+  double fac;
+  double* r;           // n x nb
+  double* u0;          // n x k, k = nb - f0
+  double* red;         // norm partials [nblk][16][2]
+  double* partial;     // Gram partials [nblk][TX + 1][256]
+  long long n;
+  int m, nb, f0;
+  int pair;            // 1: a wave takes its 16-row tiles in consecutive pairs (the 32-row tiles of the measuring sweep it stands in for)
+  unsigned act;        // bit j: column j of R is an open wanted root (it is corrected and its norms are formed)
+  double theta[16];    // Ritz values of the columns
+};
+
+template <int TX>
+__global__ __launch_bounds__(256) void davidson_expand_kernel(RitzExpandArgs a)
+{
+  constexpr int RS = 18;                   // doubles per staged column (16 rows + 2: 16-byte alignment, conflict-free fragment reads)
+  constexpr int NC = 16 * (2 * TX + 1);    // staged columns: V tiles, AV tiles, the output tile
+  constexpr int OOFF = 32 * TX;            // where the output tile sits
+  constexpr int NI = 4 * TX;               // load instructions per row tile: 8 columns of 16 rows each
+  extern __shared__ __attribute__((aligned(16))) double glds[];   // [4][NC][RS]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double* my = glds + (size_t)wave * NC * RS;
+  const int c = lane & 15, g = lane >> 4;
+  const int li = lane & 7, lc = lane >> 3;
+  const long long n = a.n;
+  const int k = a.nb - a.f0;
+
+  // (the output tile's columns k .. 15 are never written by a row tile: zero once)
+  for (int idx = lane; idx < 16 * RS; idx += 64) my[(size_t)OOFF * RS + idx] = 0.0;
+  double ca[4 * TX];
+#pragma unroll
+  for (int s = 0; s < 4 * TX; ++s) ca[s] = a.cpk[(size_t)(4 * s + g) * 16 + c];
+  double th[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) th[r] = a.theta[g + 4 * r];
+  v4d acc[TX];
+#pragma unroll
+  for (int t = 0; t < TX; ++t) acc[t] = (v4d){0.0, 0.0, 0.0, 0.0};
+  v4d accuu = (v4d){0.0, 0.0, 0.0, 0.0};
+  double ssq[4], smx[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) { ssq[r] = 0.0; smx[r] = 0.0; }
+
+  typedef VecOf<2>::type vec_t;
+  vec_t stg[NI];
+  double dnext = 1.0;
+  // (the 2 NI address registers are recomputed per tile, as gram_lds_kernel LOW does; instructions whose eight columns all lie
+  //  beyond the basis read one fixed word, and a column beyond it inside a live instruction re-reads the last one: both meet
+  //  zero coefficients and unused rows of V^T U0 only)
+  auto load_tile = [&](long long tile) {
+    const long long r0 = tile * 16;
+    // (a tile that reaches beyond n: rows >= n are staged as zeros; n is even, so a 16-byte row pair is all-in or all-out)
+    const bool rows_ok = r0 + 16 <= n || r0 + 2 * li < n;
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+      const bool isv = j < 2 * TX;
+      int col = 8 * (isv ? j : j - 2 * TX) + lc;
+      col = col < a.m ? col : a.m - 1;
+      const bool pin = 8 * (isv ? j : j - 2 * TX) >= a.m;
+      const double* p = pin ? a.v : (isv ? a.v : a.av) + (size_t)col * (size_t)n + 2 * li + r0;
+      stg[j] = vzero<2>();
+      if (rows_ok) stg[j] = pload<2, 1>(p);
+    }
+    dnext = 1.0;
+    if (r0 + c < n) dnext = a.diag[r0 + c];
+  };
+  auto stage_tile = [&]() {
+#pragma unroll
+    for (int j = 0; j < NI; ++j) lds_store2(my + (size_t)(8 * j + lc) * RS + 2 * li, stg[j]);
+  };
+  auto do_tile = [&](long long r0, double dg) {
+    // (V Y)[row c][g + 4 r] and (AV Y)[row c][g + 4 r]: sums over the staged columns j of V / AV [row c][j] Y(j, g + 4 r)
+    v4d dv = (v4d){0.0, 0.0, 0.0, 0.0}, da = (v4d){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < 4 * TX; ++s) {
+      dv = __builtin_amdgcn_mfma_f64_16x16x4f64(ca[s], lds_load1(my + (size_t)(4 * s + g) * RS + c), dv, 0, 0, 0);
+      da = __builtin_amdgcn_mfma_f64_16x16x4f64(ca[s], lds_load1(my + (size_t)(16 * TX + 4 * s + g) * RS + c), da, 0, 0, 0);
+    }
+    const long long row = r0 + c;
+    const bool rok = row < n;
+    const double den = dg + a.fac;
+    const bool use = fabs(den) > 1.0e-5;                         // mprec, main.f90:161-169 (see synth_precnd_kernel)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int j = g + 4 * r;
+      double val = da[r];
+      if ((a.act >> j) & 1u) {
+        val = val - th[r] * dv[r];       // daxpy(-eig), reference diaglib.f90:1729 (ritz_kernel's expression)
+        ssq[r] += val * val;
+        smx[r] = fmax(smx[r], fabs(val));
+      }
+      if (rok && j < a.nb) __builtin_nontemporal_store(val, a.r + (size_t)j * (size_t)n + row);
+      const double u = use ? val / den : val;
+      const int jj = j - a.f0;
+      if (jj >= 0) {
+        lds_store1(my + (size_t)(OOFF + jj) * RS + c, u);
+        if (rok && jj < k) a.u0[(size_t)jj * (size_t)n + row] = u;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) {
+      const double uf = lds_load1(my + (size_t)(OOFF + c) * RS + 4 * s4 + g);
+      accuu = __builtin_amdgcn_mfma_f64_16x16x4f64(uf, uf, accuu, 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < TX; ++t) {
+        const double xf = lds_load1(my + (size_t)(16 * t + c) * RS + 4 * s4 + g);
+        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(xf, uf, acc[t], 0, 0, 0);
+      }
+    }
+  };
+  // the wave's 16-row tiles: every (4 gridDim.x)-th, or -- pair -- every (4 gridDim.x)-th pair of consecutive ones
+  const long long ntiles = (n + 15) / 16;
+  const int ps = a.pair ? 1 : 0;
+  const long long stride = (long long)gridDim.x * 4;
+  long long tile = ((long long)blockIdx.x * 4 + wave) << ps;
+  __builtin_amdgcn_wave_barrier();
+  if (tile < ntiles) {
+    load_tile(tile);
+    for (;;) {
+      stage_tile();
+      const double dg = dnext;
+      __builtin_amdgcn_wave_barrier();
+      const long long next = (ps && !(tile & 1)) ? tile + 1 : ((tile >> ps) + stride) << ps;
+      if (next < ntiles) load_tile(next);
+      do_tile(tile * 16, dg);
+      __builtin_amdgcn_wave_barrier();
+      tile = next;
+      if (next >= ntiles) break;
+    }
+  }
+
+  // norms: over the 16 lanes that share g, then over the waves; Gram tiles: over the waves, one slot at a time
+  __syncthreads();
+  double* red = glds;   // [4][256] (the staging area is free now); the norms behind it, [4][16][2]
+  double* nred = glds + 1024;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    double s = ssq[r], m = smx[r];
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) {
+      s += __shfl_xor(s, off, 64);
+      m = fmax(m, __shfl_xor(m, off, 64));
+    }
+    if (c == 0) {
+      nred[(wave * 16 + g + 4 * r) * 2 + 0] = s;
+      nred[(wave * 16 + g + 4 * r) * 2 + 1] = m;
+    }
+  }
+  double* pout = a.partial + (size_t)blockIdx.x * (size_t)(TX + 1) * 256;
+#pragma unroll
+  for (int t = 0; t <= TX; ++t) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[wave * 256 + r * 64 + lane] = t < TX ? acc[t < TX ? t : 0][r] : accuu[r];
+    __syncthreads();
+    pout[(size_t)t * 256 + threadIdx.x] = ((red[threadIdx.x] + red[256 + threadIdx.x]) + red[512 + threadIdx.x]) + red[768 + threadIdx.x];
+    __syncthreads();
+  }
+  if (threadIdx.x < 16) {
+    const int j = threadIdx.x;
+    double s = 0.0, m = 0.0;
+    for (int w = 0; w < 4; ++w) {
+      s += nred[(w * 16 + j) * 2 + 0];
+      m = fmax(m, nred[(w * 16 + j) * 2 + 1]);
+    }
+    a.red[((size_t)blockIdx.x * 16 + j) * 2 + 0] = s;
+    a.red[((size_t)blockIdx.x * 16 + j) * 2 + 1] = m;
+  }
+}
+
+// ======================================================================================
 // Elementwise
 // ======================================================================================
 // small host matrix (pinned, device-mapped) -> device, 16 bytes per lane (HipEngine::stage_commit)
@@ -4090,7 +4286,7 @@ struct HipEngine : dla::Engine {
   ncclComm_t comm = nullptr;
   void set_tune(int i, int v) override { knobs.set(i, v); }
   int get_tune(int i) override { return knobs.get(i); }
-  void begin_solve() override { x3_cooldown = X3_COOLDOWN_START; }
+  void begin_solve() override { x3_cooldown = X3_COOLDOWN_START; drop_measured(); }
   // per-kernel statistics (names as rocprofv3 prints them, without namespace / argument list)
   struct KStat { long long launches = 0; double alg_bytes = 0.0, ms = 0.0, flops = 0.0; };
   std::map<std::string, KStat> kstats;
@@ -4223,6 +4419,7 @@ struct HipEngine : dla::Engine {
     {
       e->bind();
       if (e->lc.dry) return;
+      e->drop_measured();              // (whatever is launched now may rewrite the block a fused Ritz sweep measured: see ritz_expand)
       if (e->lc.rec) {
         // speculative launch of a device-driven chain: counted after the read-back, if the device executed it
         e->lc.rec->push_back({e->lc.tag, cls_, kname_, bytes, flops});
@@ -4386,6 +4583,7 @@ struct HipEngine : dla::Engine {
   }
   int h2d(void* dev, const void* host, size_t bytes) override
   {
+    drop_measured();
     HIPCHK(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
     return DLA_OK;
@@ -4408,6 +4606,7 @@ struct HipEngine : dla::Engine {
   Event ev_cb, ev_cb2;
   int callback_begin(int mode) override
   {
+    if (mode != 2) drop_measured();    // (a caller's own routine may write anywhere)
     if (mode == 2) return DLA_OK;
     if (mode == 1) { int stw = wait_stream(); if (stw) return stw; stats.host_syncs++; return DLA_OK; }
     HIPCHK(ev_cb.ensure(hipEventDisableTiming));
@@ -4891,8 +5090,9 @@ struct HipEngine : dla::Engine {
   }
   // Second stage of every Gram: the per-block partials in d_partial -> c (l x k, leading dimension ldc, 0 = l; `extra`: see
   // GramReduceArgs), then the cross-rank sum of c unless the kernel carried it or the result is a column chunk of one rank.
+  // (partial: the block partials of a sweep that left them elsewhere -- the fused Ritz sweep, ritz_expand -- nullptr: d_partial)
   int reduce_and_sum(int cls, double* c, double* c_host, int nblk, int l, int k, int tlw, int kt, int px, int n_out, int extra, int ldc,
-                     StepOut& out)
+                     StepOut& out, const double* partial = nullptr)
   {
     Rode rode;
     {
@@ -4900,7 +5100,7 @@ struct HipEngine : dla::Engine {
       const int groups = reduce_groups(nblk);
       { const int stl = ensure_lvl2(sizeof(double) * (size_t)n_out * groups * 256); if (stl) return stl; }
       if (n_out > 4096) { err = "gram: too many output tiles"; return DLA_ERR_ARG; }     // (d_ticket holds one word per output tile)
-      GramReduceArgs ra{d_partial, d_lvl2, d_ticket, c, c_host, nblk, l, k, tlw, kt, px,
+      GramReduceArgs ra{partial ? partial : (const double*)d_partial, d_lvl2, d_ticket, c, c_host, nblk, l, k, tlw, kt, px,
                         lc.phase, lc.want, 0, n_out, d_ticket + 4096, OrthoTailArgs{}, P2PArgs{}, extra, ldc};
       rode = launch_reduce(ra, dim3(n_out, groups));
     }
@@ -5021,6 +5221,16 @@ struct HipEngine : dla::Engine {
     const bool self = (m == 0);
     if (cx != nullptr && (self || uw == nullptr || wp != nullptr || k > 16)) { err = "gram_wp: bad projection sweep"; return DLA_ERR_ARG; }
     if (k > 48 || (self && k > 16)) { err = "gram_wp: block too wide"; return DLA_ERR_ARG; }
+    if (!lc.dry && rx_keep && measured.valid && !self && wp == nullptr && uw == nullptr && cx == nullptr && x == measured.x && u == measured.u &&
+        n == measured.n && m == measured.m && k == measured.k) {
+      // the measuring sweep of this block has run already, inside the Ritz sweep that formed it (ritz_expand): its partials are reduced
+      // in the sweep's place -- same layout, same reduction, same tail
+      measured.valid = false;
+      if (m * k + k * k > XUG_DOUBLES) { err = "gram_wp: basis too wide for the chain's buffer"; return DLA_ERR_ARG; }
+      int stm = ensure_small(sizeof(double) * (size_t)k * k);
+      if (stm) return stm;
+      return reduce_and_sum(DLA_OP_GRAM, d_xug, nullptr, measured.blocks, m, k, measured.tx, 1, 1, measured.tx + 1, 1, m + k, out, d_rxpart);
+    }
     const WpPlan p = wp_plan(env(), n, m, k, cx != nullptr);
     const int tlw = p.tlw, kt = p.kt, passes = p.passes, blocks = p.blocks, extra = p.extra, slots = p.slots;
     int stc = ensure_partial(sizeof(double) * (size_t)passes * blocks * slots * 256);
@@ -5167,6 +5377,13 @@ struct HipEngine : dla::Engine {
   {
     rep->handled = 0;
     t_pending_k = 0;                 // (whatever an earlier chain left: nobody fetched it, it belongs to no later call)
+    // A block that the Ritz sweep in front of this call formed and measured (ritz_expand): the record is kept while this call's own
+    // launches go out -- the first of them, the planned OP_GRAMX, takes it (gram_wp_once) -- and dropped on every way out that did not
+    struct TakeMeasured {
+      HipEngine* e;
+      TakeMeasured(HipEngine* e_, bool match) : e(e_) { e->rx_keep = match; if (!match) e->drop_measured(); }
+      ~TakeMeasured() { e->rx_keep = false; e->drop_measured(); }
+    } take_measured(this, measured.valid && x == measured.x && bx == x && u == measured.u && n == measured.n && m == measured.m && k == measured.k);
     if (run.active) { err = "ortho_chain: a chain is already in flight"; return DLA_ERR_RUNTIME; }
     // (policy.basis_exact: the stored columns are not orthonormal, only the device chain projects with the caller's D -- the host-driven
     //  loop, which ends on the reference's growth test, must not take such a block)
@@ -6037,6 +6254,126 @@ struct HipEngine : dla::Engine {
       for (int r = 0; r < nslots; ++r) mx = std::max(mx, h_small[ncol + r * ncol + j]);
       out[2 * j] = h_small[j]; out[2 * j + 1] = mx;
     }
+    return DLA_OK;
+  }
+
+  // ---- the Ritz sweep that also forms and measures the next block (davidson_expand_kernel, Engine::ritz_expand)
+  // What it measured is remembered until the chain that orthogonalises the block starts: ortho_chain_begin on the same panel, block
+  // and widths takes the partials in d_rxpart in the place of its OP_GRAMX sweep (gram_wp_once).  Any launch in between -- another
+  // Ritz sweep, a preconditioner, a product, a copy -- drops the record (Scope, zero, d2d, h2d): the block may have been rewritten.
+  DeviceBuffer<double> d_rxpart;     // the Gram partials of the last fused sweep: nothing else writes here
+  struct Measured {
+    bool valid = false;
+    const double *x = nullptr, *u = nullptr;
+    int n = 0, m = 0, k = 0, blocks = 0, tx = 0;
+    double fac = 0.0;
+  } measured;
+  bool rx_keep = false;              // the launches of the moment belong to the fused sweep itself or to the chain that takes the record
+  long long rx_run = 0, rx_discarded = 0;
+  void drop_measured() { if (measured.valid && !rx_keep) { measured.valid = false; ++rx_discarded; } }
+  void ritz_expand_counts(long long* run, long long* discarded) override { *run = rx_run; *discarded = rx_discarded; }
+  // what the record holds, reduced as the chain would reduce it: [V | U0]^T U0, (m + k) x k; the record stays (tests)
+  int ritz_expand_measured(int m, int k, double* c_host, int ldc) override
+  {
+    if (!measured.valid || m != measured.m || k != measured.k) { err = "ritz_expand_measured: no fused sweep of this shape is on record"; return DLA_ERR_ARG; }
+    int stc = ensure_small(sizeof(double) * (size_t)(m + k) * k);
+    if (stc) return stc;
+    rx_keep = true;
+    struct Unkeep { bool& f; ~Unkeep() { f = false; } } unkeep{rx_keep};
+    StepOut out;
+    stc = reduce_and_sum(DLA_OP_GRAM, d_small, h_small.dev(), measured.blocks, m, k, measured.tx, 1, 1, measured.tx + 1, 1, m + k, out, d_rxpart);
+    if (stc) return stc;
+    stc = small_to_host((size_t)(m + k) * k, out.mirror_fresh);
+    if (stc) return stc;
+    for (int j = 0; j < k; ++j) std::memcpy(c_host + (size_t)j * ldc, h_small + (size_t)j * (m + k), sizeof(double) * (m + k));
+    return DLA_OK;
+  }
+  // the device-resident diagonal of one of the library's diagonal preconditioners (kind 0 / 1 / 2: the sample operator, the stored
+  // sparse operator, the stored dense operator); nullptr: none of n rows has been set up
+  const double* precnd_diagonal(int kind, int n)
+  {
+    if (kind == 0) return (n == syn_n && d_diag) ? (const double*)d_diag : nullptr;
+    if (kind == 1) return (n == ops[dla::SPMM_A].n && ops[dla::SPMM_A].diag) ? ops[dla::SPMM_A].diagonal() : nullptr;
+    if (kind == 2) return (dense[dla::DENSE_A].n == n && dense[dla::DENSE_A].diag) ? (const double*)dense[dla::DENSE_A].diag : nullptr;
+    return nullptr;
+  }
+  int ritz_expand(int n, int l, int m, const double* v, const double* av, const double* y_host, int ldy, const double* eig, int n_res,
+                  const int* skip, double* r, double* out, int precnd_kind, double fac, int first0, int k, double* u0, int* ran) override
+  {
+    *ran = 0;
+    drop_measured();
+    if (nranks > 1 || comm || local_only || hook || p2p.on) return DLA_OK;        // (sharded runs keep the plain sweep)
+    const double* dg = precnd_diagonal(precnd_kind, n);
+    if (!dg || !u0 || !r || k <= 0 || k != m - first0) return DLA_OK;
+    const uintptr_t al = (uintptr_t)v | (uintptr_t)av | (uintptr_t)r | (uintptr_t)u0;
+    const RitzExpandPlan p = ritz_expand_plan(env(), n, l, m, first0, even_rows(n) && (al % 16 == 0));
+    if (!p.fits || (size_t)p.blocks * p.gram_slots * 256 == 0) return DLA_OK;
+    const int tx = p.tx;
+    bind();
+    // (a refused request for LDS lowers the engine's limit, like everywhere; nothing has run, the caller takes the plain sweep)
+    bool raised = false;
+    first_instance<std::size(RITZ_EXPAND_TILES)>([&](auto i) {
+      constexpr int TX = RITZ_EXPAND_TILES[decltype(i)::value];
+      if (tx != TX) return false;
+      raised = raise_lds((const void*)davidson_expand_kernel<TX>, p.lds);
+      return true;
+    });
+    if (!raised) { lds_retry = false; return DLA_OK; }
+    // coefficients Y, [16 tx][16]
+    const size_t cnt = (size_t)16 * tx * 16;
+    if (cnt > d_cpk.capacity()) {
+      HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(d_cpk.reserve(std::max(cnt, doubles((size_t)1 << 16))));
+    }
+    int stc = ensure_partial(sizeof(double) * (size_t)p.blocks * 16 * 2);
+    if (stc) return stc;
+    stc = ensure_small(sizeof(double) * p.small_doubles());
+    if (stc) return stc;
+    const size_t gp = (size_t)p.blocks * p.gram_slots * 256;
+    if (gp > d_rxpart.capacity()) {
+      HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(d_rxpart.reserve(gp));
+    }
+    double* pk = nullptr;
+    int slot = 0;
+    stc = stage_slot(sizeof(double) * cnt, &pk, &slot);
+    if (stc) return stc;
+    std::memset(pk, 0, sizeof(double) * cnt);
+    RitzExpandArgs a{v, av, d_cpk, dg, fac, r, u0, d_partial, d_rxpart, (long long)n, l, m, first0, p.rows == 32 ? 1 : 0, 0u, {}};
+    int nact = 0;
+    for (int j = 0; j < m; ++j) {
+      // (open wanted roots only are corrected and measured, as by dla_ritz_residual)
+      if (j < n_res && !(skip && skip[j])) { a.act |= 1u << j; a.theta[j] = eig[j]; ++nact; }
+      const double* yj = y_host + (size_t)j * ldy;
+      for (int q = 0; q < l; ++q) pk[(size_t)q * 16 + j] = yj[q];
+    }
+    stc = stage_commit(slot, sizeof(double) * cnt, d_cpk);
+    if (stc) return stc;
+    rx_keep = true;
+    struct Unkeep { bool& f; ~Unkeep() { f = false; } } unkeep{rx_keep};
+    {
+      // what the sweep moves and what it stands for: the two Ritz products with the correction and the norms, the diagonal scaling,
+      // and X^T U, U^T U of the new block
+      Scope s(this, DLA_OP_RITZ, 8.0 * n * (2.0 * l + m + k + 1.0),
+              4.0 * (double)n * l * m + 5.0 * (double)n * nact + (double)n * k + 2.0 * (double)n * (l + k) * k, p.name());
+      first_instance<std::size(RITZ_EXPAND_TILES)>([&](auto i) {
+        constexpr int TX = RITZ_EXPAND_TILES[decltype(i)::value];
+        if (tx != TX) return false;
+        DLA_LAUNCH(davidson_expand_kernel<TX>, dim3(p.blocks), dim3(256), p.lds, st, a);
+        return true;
+      });
+    }
+    {
+      Scope s2(this, DLA_OP_RITZ, 0.0, 0.0, "ritz_reduce_kernel");
+      DLA_LAUNCH(ritz_reduce_kernel, dim3(p.ncol), dim3(256), 0, st, (const double*)d_partial, p.blocks, p.ncol, d_small, h_small.dev(), 1, 0);
+    }
+    HIPCHK(hipGetLastError());
+    stc = sum_to_host((int)p.small_doubles(), 0);
+    if (stc) return stc;
+    for (int j = 0; j < n_res; ++j) { out[2 * j] = h_small[j]; out[2 * j + 1] = h_small[p.ncol + j]; }
+    measured = Measured{true, v, u0, n, l, k, p.blocks, tx, fac};
+    ++rx_run;
+    *ran = 1;
     return DLA_OK;
   }
 

@@ -33,6 +33,11 @@ struct Knobs {
   bool ritz_p_separate() const { return tune[0] == 5; }
   // 6: the two-coefficient sweep ritz2_kernel off, three sweeps instead (A/B switch, no record kept)
   bool no_ritz2() const { return tune[0] == 6; }
+  // 16: the Ritz sweep that also forms and measures the next block (davidson_expand_kernel) off: dla_ritz_expand is dla_ritz_residual
+  // (A/B and parity switch, tests/test_ritz_expand_solves_gpu.py)
+  bool no_ritz_expand() const { return tune[0] == 16; }
+  // 17: the Davidson driver predicts one lock more than its rule says, so that fused sweeps are discarded (same test)
+  bool ritz_expand_overpredict() const { return tune[0] == 17; }
   // ---- knob 1: blocks of a Ritz sweep, as a multiple of the built-in count (tools/tune_ab.py)
   int ritz_grid_factor() const { return tune[1] > 0 ? tune[1] : 1; }
   // ---- knob 2: the plain panel product (gemm_chunk)
@@ -174,6 +179,8 @@ constexpr RitzInstance RITZ_INSTANCES[] = {
   {1, 2, 0, 0, false}, {2, 2, 2, 0, false}, {3, 2, 3, 0, false},
   // plain, 8-byte path
   {1, 1, 0, 0, false}, {2, 1, 2, 0, false}, {3, 1, 3, 0, false}};
+// davidson_expand_kernel<tx>: the Ritz sweep that also forms and measures the next block, tx column tiles of the basis
+constexpr int RITZ_EXPAND_TILES[] = {1, 2, 3, 4, 5, 6, 7};
 // "round up to an instantiated width": the narrowest listed pass of kt U-tiles that holds `want` X-tiles and that `ok` admits; null
 // when the list has none (the planner keeps its width, and the ladder reports that there is no kernel instance)
 template <typename Tile, size_t N, typename Ok>
@@ -444,6 +451,48 @@ inline Ritz2Plan ritz2_plan(const PlanEnv& env, int n, int l, int m, bool vec2, 
   p.fits = m > 0 && m <= 48 && l > 0 && p.lds_c <= std::min((size_t)150 * 1024, env.lds_limit > 2048 ? env.lds_limit - 2048 : (size_t)0) &&
            !env.knobs.no_ritz2();
   static_cast<RitzGrid&>(p) = ritz_grid(env, n, vec2, p.kt, p.lds_c, 1, nranks_slots);
+  return p;
+}
+
+// The Ritz sweep that also forms the next Davidson block and measures it against the basis (davidson_expand_kernel): a wave stages 16
+// rows of the tx tiles of V, the tx tiles of AV and one output tile, 18 doubles per column.  16-byte path only, one output tile
+// (block <= 16 columns), the whole of V in one pass; anything else, or an image beyond the LDS limit, does not fit and the caller
+// runs the plain sweep.  m: columns of the basis, nb: columns of the Ritz block, first0: first predicted column (0-based), so the
+// new block has nb - first0 columns.
+constexpr size_t ritz_expand_lds_bytes(int tx) { return sizeof(double) * 4 * 16 * (size_t)(2 * tx + 1) * 18; }
+struct RitzExpandPlan {
+  int tx;                // column tiles of the basis (and of its operator image)
+  int staged_tiles;      // 2 tx + 1
+  size_t lds;
+  bool fits;
+  int blocks;
+  int rows;              // rows a wave takes at a time: 16, or 32 (two consecutive tiles) where the measuring sweep stages 32
+  int ncol, nslots;      // the norm reduction behind it (ritz_reduce_kernel): 16 columns, one slot of maxima
+  int gram_slots;        // output tiles of [V | U0]^T U0: tx + 1, in the layout of a one-pass gram_lds_kernel WP sweep
+  size_t small_doubles() const { return (size_t)ncol * (1 + nslots); }
+  // (not a name of the `ritz` family: the statistics' consumers key that family by ritz_kernel's seven template arguments and hold
+  //  every booked name that starts with `ritz` to them, tests/test_knobs_gpu.py; the launch is booked in the class DLA_OP_RITZ)
+  std::string name() const { return plan_name("davidson_expand_kernel<%d>", tx); }
+};
+inline RitzExpandPlan ritz_expand_plan(const PlanEnv& env, int n, int m, int nb, int first0, bool vec2)
+{
+  RitzExpandPlan p{};
+  p.tx = (m + 15) / 16;
+  p.staged_tiles = 2 * p.tx + 1;
+  p.lds = ritz_expand_lds_bytes(p.tx);
+  bool listed = false;
+  for (int t : RITZ_EXPAND_TILES) listed = listed || t == p.tx;
+  p.fits = vec2 && n > 0 && n % 2 == 0 && m > 0 && nb > 0 && nb <= 16 && first0 >= 0 && first0 < nb && listed && p.lds <= env.lds_limit &&
+           !env.knobs.no_ritz_expand();
+  // The grid and the rows per step are those of the measuring sweep the chain would otherwise run on the stored block (wp_plan, OP_GRAMX):
+  // the same rows then go through the same wave in the same order, and the block partials are that sweep's bit for bit.  (Two blocks
+  // per CU up to five basis tiles: from three tiles on this kernel needs more than 256 registers, so the second block runs behind the
+  // first, each over half the rows.)
+  const WpPlan w = wp_plan(env, n, m, std::min(16, std::max(1, nb - first0)), false);     // (a one-tile block: wider ones do not fit)
+  p.blocks = w.blocks;
+  p.rows = w.R;
+  p.ncol = 16; p.nslots = 1;
+  p.gram_slots = p.tx + 1;
   return p;
 }
 

@@ -1259,6 +1259,59 @@ static int callback_order_of(dla_ctx* c, void* fn)
   return r && r->on_engine_stream ? 2 : c->callback_order;
 }
 
+// which of the library's diagonal preconditioners on a device-resident diagonal fn is (Engine::ritz_expand); -1: none of them
+static int diagonal_precnd_kind(dla_precnd_fn fn)
+{
+  if (!own_callback((void*)fn)) return -1;
+  return fn == &dla_synth_precnd ? 0 : fn == &dla_spmm_precnd ? 1 : fn == &dla_dense_precnd ? 2 : -1;
+}
+
+int dla_ritz_expand(dla_ctx* c, int n, int l, int m, const double* v, const double* av, const double* y, int ldy,
+                    const double* eig, int n_res, const int* skip, double* evec, double* r, double* avy, double* rnorm,
+                    dla_precnd_fn precnd, double fac, int first, int k, double* u0, int* fused)
+{
+  if (fused) *fused = 0;
+  const int kind = precnd ? diagonal_precnd_kind(precnd) : -1;
+  const bool may_fuse = c && fused && kind >= 0 && c->callbacks_on_device && !evec && !avy && u0 && r && v && av && y && eig && rnorm &&
+                        n > 0 && l > 0 && m > 0 && m <= 16 && ldy >= l && n_res >= 0 && n_res <= m && first >= 1 && first <= m && k == m - first + 1;
+  if (may_fuse) {
+    DLA_T("dla_ritz_expand");
+    std::vector<double> sm((size_t)2 * (n_res > 0 ? n_res : 1), 0.0);
+    int ran = 0;
+    const int st = c->eng->ritz_expand(n, l, m, v, av, y, ldy, eig, n_res, skip, r, sm.data(), kind, fac, first - 1, k, u0, &ran);
+    if (st) return engfail(c, st);
+    if (ran) {
+      int act = 0;
+      for (int i = 0; i < n_res; ++i) if (!(skip && skip[i])) ++act;
+      // (the logical operation is dla_ritz_residual's: the block's diagonal scaling and its measurement belong to the calls that
+      //  the caller leaves out or that find their first sweep done, and those book themselves)
+      { RefFlops rf(c, 4.0 * n * (double)l * m + 5.0 * n * (double)act); }
+      const double sqrtn = std::sqrt((double)global_rows(c, n));
+      for (int i = 0; i < n_res; ++i) {
+        if (skip && skip[i]) continue;
+        rnorm[2 * i] = std::sqrt(sm[2 * i]) / sqrtn;
+        rnorm[2 * i + 1] = sm[2 * i + 1];
+      }
+      *fused = 1;
+      return DLA_OK;
+    }
+  }
+  return dla_ritz_residual(c, n, l, m, v, av, y, ldy, eig, n_res, skip, evec, r, avy, rnorm);
+}
+
+int dla_ritz_expand_counts(dla_ctx* c, long long* run, long long* discarded)
+{
+  if (!c || !run || !discarded) return fail(c, DLA_ERR_ARG, "dla_ritz_expand_counts: bad argument");
+  c->eng->ritz_expand_counts(run, discarded);
+  return DLA_OK;
+}
+
+int dla_ritz_expand_measured(dla_ctx* c, int m, int k, double* xug, int ld)
+{
+  if (!c || !xug || m <= 0 || k <= 0 || ld < m + k) return fail(c, DLA_ERR_ARG, "dla_ritz_expand_measured: bad argument");
+  return engfail(c, c->eng->ritz_expand_measured(m, k, xug, ld));
+}
+
 int dla_call_matvec(dla_ctx* c, dla_matvec_fn fn, int n, int m, const double* x, double* ax)
 {
   DLA_T("dla_call_matvec");

@@ -36,6 +36,8 @@ module diaglib
 ! option ids of include/diaglib_amd.h
 !
   integer(c_int), parameter :: opt_cb_dev = 1, opt_evec_dev = 2, opt_lr_alg = 7
+! experiment knob 0 of the engine (include/diaglib_amd.h DLA_OPT_TUNE0) and its value "predict one lock more than the rule says"
+  integer(c_int), parameter :: opt_tune0 = 100, tune0_overpredict = 17
 !
 ! ---------------------------------------------------------------------------------------
 ! bookkeeping of a basis that grows block by block (all Davidson-type drivers)
@@ -170,6 +172,18 @@ module diaglib
       integer(c_int), value :: n, l, m, ldy, n_res
       real(c_double) :: y(*), eig(*), rnorm(*)
       integer(c_int) :: skip(*)
+      integer(c_int) :: st
+    end function
+    function dla_ritz_expand(ctx,n,l,m,v,av,y,ldy,eig,n_res,skip,evec,r,avy,rnorm,prec,fac,first,k,u0,fused) &
+             bind(C,name='dla_ritz_expand') result(st)
+      import :: c_ptr, c_funptr, c_int, c_double
+      type(c_ptr), value :: ctx, v, av, evec, r, avy, u0
+      type(c_funptr), value :: prec
+      integer(c_int), value :: n, l, m, ldy, n_res, first, k
+      real(c_double), value :: fac
+      real(c_double) :: y(*), eig(*), rnorm(*)
+      integer(c_int) :: skip(*)
+      integer(c_int) :: fused
       integer(c_int) :: st
     end function
     function dla_ritz_residual_p(ctx,n,l,m,v,av,y,ldy,eig,n_res,skip,evec,r,avy,rnorm,k2,c2,ldc2,p,ap) &
@@ -751,9 +765,18 @@ contains
     logical         :: exact_basis          ! the pending blocks are kept on the device as well (dla_expand_project mode 5)
     integer         :: synced               ! columns of dmat the device knows
     integer(c_int)  :: applied
+!   the next block is formed inside the Ritz sweep for a PREDICTED first open root (dla_ritz_expand, predicted_first below)
+    real(dp), allocatable :: seen(:,:,:)    ! the norms of the last two sweeps: (measure, root, 1 = the one before, 2 = the last)
+    integer         :: nseen, bet           ! sweeps recorded; the first open root the sweep of this iteration was run for
+    integer(c_int)  :: fused                ! ... and whether that sweep formed the block at all
+    logical         :: overpredict
 !
     call env_open(e, n, n_max, evec)
     ritz_cols = 0
+    allocate (seen(2,n_max,2))
+    seen  = zero
+    nseen = 0
+    overpredict = dla_get_option(e%ctx, opt_tune0) .eq. tune0_overpredict
 !
 !   the basis holds at least min_dav blocks whatever the caller asks for (reference :1595-1596)
 !
@@ -805,6 +828,8 @@ contains
 !
     do it = 1, max_iter
       call sub_admit(s)
+      fused = 0_c_int
+      bet   = 0
 !
 !     operator on the new block.  Right after a restart the block starts behind the kept (locked) vectors and runs
 !     `kept` zero columns past the Ritz block, exactly like the reference's offsets (:1685, SURVEY App. B 4).
@@ -873,11 +898,22 @@ contains
                                             e%ritz, resid, c_null_ptr, s%rnorm), 'ritz/residual')
           ritz_cols = 0
         else
-          call chk(e%ctx, dla_ritz_residual(e%ctx, n, s%cols, n_max, basis, abasis, y, s%ld, eig, n_targ, s%mask, &
-                                            c_null_ptr, resid, c_null_ptr, s%rnorm), 'ritz/residual')
+!
+!         ... and forms the next block on the way, for the root that the norms of the last two sweeps predict to be the first open
+!         one: the preconditioned residuals go to the block's place behind the basis, and what the orthogonalisation measures
+!         first, [basis | block]^T block, is taken from the same rows.  The engine declines what it does not take (a caller's own
+!         preconditioner, host-mode callbacks, a sharded run, a basis beyond its staged image) and is then dla_ritz_residual.
+!
+          bet = predicted_first()
+          call chk(e%ctx, dla_ritz_expand(e%ctx, n, s%cols, n_max, basis, abasis, y, s%ld, eig, n_targ, s%mask, &
+                                          c_null_ptr, resid, c_null_ptr, s%rnorm, prec, -eig(bet), bet, n_max - bet + 1, &
+                                          colp(basis,n,s%head+s%act), fused), 'ritz/residual + next block')
           ritz_cols = s%cols
         end if
       end if
+      seen(:,:,1) = seen(:,:,2)
+      seen(:,:,2) = s%rnorm
+      nseen = nseen + 1
 !
       call sub_lock(s, it, n_targ)
       if (verbose) call print_table_rows(s, it, eig - shift)     ! the shift is cosmetic here (SURVEY App. B 1)
@@ -892,8 +928,11 @@ contains
 !       expand with the preconditioned open residuals, orthogonalised against the basis (:1773-1794)
 !
         call sub_open_block(s, first)
-        call chk(e%ctx, dla_call_precnd(e%ctx, prec, n, s%act, -eig(first), colp(resid,n,first), &
-                                        colp(basis,n,s%head)), 'precnd')
+!       (the sweep has formed this very block already when its bet on the first open root was right)
+        if (fused.eq.0 .or. first.ne.bet) then
+          call chk(e%ctx, dla_call_precnd(e%ctx, prec, n, s%act, -eig(first), colp(resid,n,first), &
+                                          colp(basis,n,s%head)), 'precnd')
+        end if
         call lap_start(w)
         if (with_metric) then
 !
@@ -1064,6 +1103,32 @@ contains
         error stop 1
       end if
     end subroutine need_ok
+!
+!   The first root that will be open after the sweep that is about to run: the locking rule (sub_lock) applied to the norms
+!   extrapolated from the last two sweeps, prev * min(1, prev / the one before) for either measure.  Roots lock in order, so the
+!   walk stops at the first one predicted open; the first sweep locks nothing (sub_lock), and one sweep of history predicts no new
+!   lock.  Only a bet: sub_lock decides from the sweep's own norms, and a lost bet costs the block's columns of the sweep.  The norms
+!   are global on sharded runs, so every rank bets alike.  (Knob 0 = 17, tests: one lock more than the rule says, so that bets are lost.)
+!
+    function predicted_first() result(first_open)
+      integer  :: first_open, r, front
+      real(dp) :: guess(2)
+      front = sub_leading(s)
+      if (it.gt.1 .and. nseen.ge.2) then
+        do r = front + 1, s%want
+          if (seen(1,r,1).le.zero .or. seen(2,r,1).le.zero) exit
+          guess(1) = seen(1,r,2)*min(one, seen(1,r,2)/seen(1,r,1))
+          guess(2) = seen(2,r,2)*min(one, seen(2,r,2)/seen(2,r,1))
+          if (guess(1).lt.s%tol_rms .and. guess(2).lt.s%tol_max) then
+            front = front + 1
+          else
+            exit
+          end if
+        end do
+      end if
+      if (overpredict) front = front + 1
+      first_open = min(front + 1, s%blk)
+    end function predicted_first
   end subroutine davidson_core
 !
   subroutine davidson_driver(verbose,n,n_targ,n_max,max_iter,tol,max_dav,shift,matvec,precnd,eig,evec,ok)

@@ -245,6 +245,28 @@ int  dla_ritz_residual_p(dla_ctx* ctx, int n, int l, int m, const double* v_dev,
 int  dla_ritz_residual2(dla_ctx* ctx, int n, int l, int m, const double* v_dev, const double* av_dev,
                         const double* y1_host, int ldy1, const double* y2_host, int ldy2, const double* eig, int n_res,
                         const int* skip, double* e_dev, double* r_dev, double* t_work_dev, double* junk_dev, double* rnorm);
+/* dla_ritz_residual that may also form the next Davidson block inside the same sweep, from a PREDICTION of the first open root:
+ * u0_dev(:, 1:k) = precnd(r(:, first:m), fac) with k = m - first + 1 (first is 1-based), and [V | u0]^T u0 measured for the
+ * orthogonalisation of that block.  The sweep runs fused (*fused = 1) only when precnd is one of the library's diagonal
+ * preconditioners on a device-resident diagonal (dla_synth_precnd, dla_spmm_precnd, dla_dense_precnd), callbacks are in device
+ * mode, no Ritz vectors and no AV Y are asked for (evec_dev = avy_dev = NULL), the context is not sharded and the shape fits the
+ * kernel (even n, 16-byte aligned panels, m <= 16, l <= 112 under the full LDS limit).  r_dev and rnorm come out as from
+ * dla_ritz_residual (the same products and the same correction, step by step), u0_dev
+ * holds EXACTLY the library's diagonal rule applied to the stored r_dev, and a dla_expand_project / dla_ortho_vs_x that follows on
+ * the panel [v_dev | u0_dev] with the same widths, with nothing launched in between, starts from the measured matrices instead of
+ * sweeping the basis again.  A caller whose prediction was wrong simply goes on as after dla_ritz_residual (dla_call_precnd on
+ * r_dev overwrites the block).  In every other case (*fused = 0) the call is exactly dla_ritz_residual and u0_dev is not
+ * touched. */
+int  dla_ritz_expand(dla_ctx* ctx, int n, int l, int m, const double* v_dev, const double* av_dev,
+                     const double* y_host, int ldy, const double* eig, int n_res, const int* skip,
+                     double* evec_dev, double* r_dev, double* avy_dev, double* rnorm,
+                     dla_precnd_fn precnd, double fac, int first, int k, double* u0_dev, int* fused);
+/* fused sweeps of dla_ritz_expand that ran on this context, and how many of them were discarded (nobody took what they measured:
+ * the prediction missed, or another call came between the sweep and the orthogonalisation) */
+int  dla_ritz_expand_counts(dla_ctx* ctx, long long* run, long long* discarded);
+/* What the last fused sweep measured, while it is still on record: xug(1:m, 1:k) = V^T u0 and xug(m+1:m+k, 1:k) = u0^T u0 (host,
+ * leading dimension ld >= m + k), reduced exactly as the orthogonalisation chain reduces them.  The record stays.  For tests. */
+int  dla_ritz_expand_measured(dla_ctx* ctx, int m, int k, double* xug, int ld);
 /* Expansion step of the Davidson and LOBPCG drivers on the contiguous panels basis = [X | U] (n x (m+k)) and
  * abasis = [AX | AU]:   ortho_vs_x(X, U)  (diaglib.f90:1790, 358-366, 523-529),  AU = A U [+ shift U]  (the caller's matvec,
  * :1685, 394-397; daxpy :397)  and the projection --

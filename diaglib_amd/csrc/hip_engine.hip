@@ -4697,6 +4697,9 @@ struct HipEngine : dla::Engine {
     HIPCHK(h_small.reserve(doubles(bytes)));
     return DLA_OK;
   }
+  // the 16-byte path of a sweep over n rows: every rank's row count is even and every panel starts on 16 bytes (null pointers are
+  // aligned).  (gram_dev_once goes by peers_even alone, on purpose: gram_plan tests n itself.)
+  template <typename... P> bool on_16_bytes(long long n, const P*... p) const { return even_rows(n) && (((uintptr_t)p | ...) % 16 == 0); }
   // first allocation of a buffer that starts zeroed (on the engine's stream): both or nothing, so that a later call retries
   template <class T> int reserve_zeroed(DeviceBuffer<T>& b, size_t count)
   {
@@ -4754,6 +4757,19 @@ struct HipEngine : dla::Engine {
     int stw = wait_stream();
     if (stw) return stw;
     stats.host_syncs++;
+    return DLA_OK;
+  }
+  // ... and on into the caller's matrix: the l x k result stands densely in h_small (leading dimension l).  lower_only: a symmetric
+  // matrix of which only the lower triangle of 16 x 16 blocks was formed; the rest is mirrored from it
+  int small_result_home(int l, int k, bool mirror_fresh, double* c_host, int ldc, bool lower_only = false)
+  {
+    const int stc = small_to_host((size_t)l * k, mirror_fresh);
+    if (stc) return stc;
+    for (int j = 0; j < k; ++j) {
+      double* cj = c_host + (size_t)j * ldc;
+      if (!lower_only) { std::memcpy(cj, h_small + (size_t)j * l, sizeof(double) * l); continue; }
+      for (int i2 = 0; i2 < l; ++i2) cj[i2] = (i2 / 16) >= (j / 16) ? h_small[(size_t)i2 + (size_t)j * l] : h_small[(size_t)j + (size_t)i2 * l];
+    }
     return DLA_OK;
   }
 
@@ -5396,7 +5412,7 @@ struct HipEngine : dla::Engine {
     const bool vsx = m > 0;
     ChainIn in{};
     in.m = m; in.k = k;
-    in.vec2 = even_rows(n) && (((uintptr_t)u | (uintptr_t)x | (uintptr_t)bx) % 16 == 0);
+    in.vec2 = on_16_bytes(n, u, x, bx);
     in.bx_is_x = bx == x;
     in.combo_ok = vsx && u == x + (size_t)n * m && can_combo(m, k);
     in.host_between = hook || local_only;
@@ -5800,41 +5816,22 @@ struct HipEngine : dla::Engine {
   }
   int gram_chunks_collect(int l, int k, double* c_host, int ldc) override
   {
-    int stc = small_to_host((size_t)l * k, false);       // (one rank: no cross-rank sum has written the mirror)
-    if (stc) return stc;
-    for (int j = 0; j < k; ++j) std::memcpy(c_host + (size_t)j * ldc, h_small + (size_t)j * l, sizeof(double) * l);
-    return DLA_OK;
+    return small_result_home(l, k, false, c_host, ldc);   // (one rank: no cross-rank sum has written the mirror)
   }
 
   int gram_lower(int n, int l, const double* x, const double* u, double* c_host, int ldc) override
   {
     StepOut out;
-    int stc = gram_dev(n, l, x, l, u, out, DLA_OP_GRAM, true);
-    if (stc) return stc;
-    stc = small_to_host((size_t)l * l, out.mirror_fresh);
-    if (stc) return stc;
-    for (int j = 0; j < l; ++j) std::memcpy(c_host + (size_t)j * ldc, h_small + (size_t)j * l, sizeof(double) * l);
-    return DLA_OK;
+    const int stc = gram_dev(n, l, x, l, u, out, DLA_OP_GRAM, true);
+    return stc ? stc : small_result_home(l, l, out.mirror_fresh, c_host, ldc);
   }
 
   int gram(int n, int l, const double* x, int k, const double* u, double* c_host, int ldc) override
   {
     StepOut out;
-    int stc = gram_dev(n, l, x, k, u, out);
-    if (stc) return stc;
-    stc = small_to_host((size_t)l * k, out.mirror_fresh);
-    if (stc) return stc;
-    if (out.lower_only) {
-      // only the lower block triangle was formed: mirror it (the Gram matrix of a block is symmetric)
-      for (int j = 0; j < k; ++j)
-        for (int i2 = 0; i2 < k; ++i2) {
-          const bool low = (i2 / 16) >= (j / 16);
-          c_host[(size_t)i2 + (size_t)j * ldc] = low ? h_small[(size_t)i2 + (size_t)j * l] : h_small[(size_t)j + (size_t)i2 * l];
-        }
-      return DLA_OK;
-    }
-    for (int j = 0; j < k; ++j) std::memcpy(c_host + (size_t)j * ldc, h_small + (size_t)j * l, sizeof(double) * l);
-    return DLA_OK;
+    const int stc = gram_dev(n, l, x, k, u, out);
+    // (lower_only: a block against itself, l == k -- the Gram matrix of a block is symmetric)
+    return stc ? stc : small_result_home(l, k, out.mirror_fresh, c_host, ldc, out.lower_only);
   }
 
   // second stage of a Gram whose per-block partials a fused kernel left in d_partial (`blocks` of them: gemm_chunk): result in
@@ -5852,17 +5849,9 @@ struct HipEngine : dla::Engine {
   int finish_fused_gram(int k, int blocks, double* g_host, int ldg)
   {
     StepOut out;
-    int stc = fused_reduce(k, blocks, out);
-    if (stc) return stc;
-    stc = small_to_host((size_t)k * k, out.mirror_fresh);
-    if (stc) return stc;
-    // the kernel formed the lower block triangle; mirror it (G is symmetric)
-    for (int j = 0; j < k; ++j)
-      for (int i2 = 0; i2 < k; ++i2) {
-        const bool low = (i2 / 16) >= (j / 16);
-        g_host[(size_t)i2 + (size_t)j * ldg] = low ? h_small[(size_t)i2 + (size_t)j * k] : h_small[(size_t)j + (size_t)i2 * k];
-      }
-    return DLA_OK;
+    const int stc = fused_reduce(k, blocks, out);
+    // (the kernel formed the lower block triangle; G is symmetric)
+    return stc ? stc : small_result_home(k, k, out.mirror_fresh, g_host, ldg, true);
   }
 
   // U <- U W and G = U^T U of the result, one sweep (k <= 48); otherwise two sweeps
@@ -6018,7 +6007,7 @@ struct HipEngine : dla::Engine {
                  int* fused_blocks = nullptr, const double* cpk_dev = nullptr)
   {
     const bool fuse = fused_blocks != nullptr;
-    const bool vec2 = even_rows(n) && (((uintptr_t)x | (uintptr_t)z) % 16 == 0);
+    const bool vec2 = on_16_bytes(n, x, z);
     const GemmPlan p = gemm_plan(env(), n, l, k, mode, fuse, cpk_dev != nullptr, vec2);
     const int kt = p.kt, l4 = p.l4, qt = p.qt, rtp = p.rtp, pipe = p.pipe, blocks = p.blocks;
     const bool inl = p.inl;
@@ -6128,6 +6117,48 @@ struct HipEngine : dla::Engine {
     return stc;
   }
 
+  // ---- what the three Ritz sweeps (ritz_kernel, ritz2_kernel, davidson_expand_kernel) share on the host
+  // the open wanted roots: f(j) for every j < min(n_res, cap) that `skip` does not close; returns their number
+  template <typename F> static int for_open_roots(int n_res, int cap, const int* skip, F&& f)
+  {
+    int nact = 0;
+    for (int j = 0; j < n_res && j < cap; ++j)
+      if (!(skip && skip[j])) { f(j); ++nact; }
+    return nact;
+  }
+  // Everything behind the pack step.  p: the sweep's plan (blocks, ncol, nslots, small_doubles(), name()); a: its arguments, which
+  // get their block partials here; bytes, flops: what the sweep is booked with; ladder: launches the plan's instance of a (under the
+  // sweep's Scope) and returns a status.  out[2 j], out[2 j + 1]: sum and maximum over the rows of column j < n_res -- the sums and
+  // all ranks' maxima come home in one collective (reference :1730-1731 are two reductions).
+  template <typename PLAN, typename ARGS, typename LADDER>
+  int ritz_sweep_tail(const PLAN& p, ARGS& a, double bytes, double flops, int n_res, double* out, LADDER&& ladder)
+  {
+    int stc = ensure_partial(sizeof(double) * (size_t)p.blocks * p.ncol * 2);
+    if (stc) return stc;
+    stc = ensure_small(sizeof(double) * p.small_doubles());
+    if (stc) return stc;
+    a.red = d_partial;
+    {
+      Scope s(this, DLA_OP_RITZ, bytes, flops, p.name());
+      stc = ladder();
+      if (stc) return stc;
+    }
+    {
+      Scope s2(this, DLA_OP_RITZ, 0.0, 0.0, "ritz_reduce_kernel");
+      DLA_LAUNCH(ritz_reduce_kernel, dim3(p.ncol), dim3(256), 0, st, (const double*)d_partial, p.blocks, p.ncol, d_small,
+                         h_small.dev(), p.nslots, local_only ? 0 : rank);
+    }
+    HIPCHK(hipGetLastError());
+    stc = sum_to_host((int)p.small_doubles(), 0);
+    if (stc) return stc;
+    for (int j = 0; j < n_res; ++j) {
+      double mx = 0.0;
+      for (int s = 0; s < p.nslots; ++s) mx = std::max(mx, h_small[p.ncol + s * p.ncol + j]);
+      out[2 * j] = h_small[j]; out[2 * j + 1] = mx;
+    }
+    return DLA_OK;
+  }
+
   int ritz_residual(int n, int l, int m, const double* v, const double* av, const double* y_host, int ldy,
                     const double* eig, int n_res, const int* skip, double* evec, double* r, double* avy,
                     double* out) override
@@ -6142,9 +6173,8 @@ struct HipEngine : dla::Engine {
                       double* out, int k2, const double* c2_host, int ldc2, double* p2, double* ap2) override
   {
     if (k2 <= 0) return ritz_residual(n, l, m, v, av, y_host, ldy, eig, n_res, skip, evec, r, avy, out);
-    const uintptr_t al = (uintptr_t)v | (uintptr_t)av | (uintptr_t)evec | (uintptr_t)r | (uintptr_t)avy | (uintptr_t)p2 | (uintptr_t)ap2;
     const int ktot = (m + k2 + 15) / 16, l4 = ((l + 3) / 4) * 4;
-    const bool one_pass = even_rows(n) && (al % 16 == 0) && m <= 48 && ktot <= 5 && !knobs.ritz_p_separate() &&
+    const bool one_pass = on_16_bytes(n, v, av, evec, r, avy, p2, ap2) && m <= 48 && ktot <= 5 && !knobs.ritz_p_separate() &&
                           sizeof(double) * (size_t)l4 * 16 * ktot <= ritz_dyn_limit(env(), ktot);
     if (!one_pass) return Engine::ritz_residual_p(n, l, m, v, av, y_host, ldy, eig, n_res, skip, evec, r, avy, out, k2, c2_host, ldc2, p2, ap2);
     // [Y | C2] as one coefficient block
@@ -6174,12 +6204,8 @@ struct HipEngine : dla::Engine {
       }
       return DLA_OK;
     }
-    const uintptr_t al = (uintptr_t)v | (uintptr_t)av | (uintptr_t)evec | (uintptr_t)r | (uintptr_t)avy | (uintptr_t)p2 | (uintptr_t)ap2;   // (null pointers are aligned)
     const int nslots = (local_only || nranks < 1) ? 1 : nranks;
-    const RitzPlan p = ritz_plan(env(), n, l, m, k2, even_rows(n) && (al % 16 == 0), nslots);
-    const int kt = p.kt, l4 = p.l4, qt = p.qt, pipe = p.pipe, blocks = p.blocks, ncol = p.ncol;
-    const bool vec2 = p.vec2, xp = p.xp;
-    const size_t lds = p.lds;
+    const RitzPlan p = ritz_plan(env(), n, l, m, k2, on_16_bytes(n, v, av, evec, r, avy, p2, ap2), nslots);
     if (!p.fits) {
       if (k2 > 0) { ritz_p_declined = true; err = "ritz sweep with extra products: coefficient block beyond the LDS limit"; return DLA_ERR_RUNTIME; }
       // Y does not fit the LDS copy in one piece (wide block times deep subspace, e.g. 37 columns x 20 blocks): form the
@@ -6206,55 +6232,30 @@ struct HipEngine : dla::Engine {
       if (ev_tmp) { const int stq2 = free_(ev_tmp); if (!stq) stq = stq2; }
       return stf ? stf : stq;
     }
-    int stc = upload_packed(y_host, ldy, 0, l, m + k2, kt, l4);
+    const int stc = upload_packed(y_host, ldy, 0, l, m + k2, p.kt, p.l4);
     if (stc) return stc;
     RitzArgs a{};
-    a.p2 = p2; a.ap2 = ap2; a.k2 = k2;
-    int nact = 0;
-    for (int j = 0; j < n_res && j < 48; ++j) {
-      if (skip && skip[j]) continue;
-      a.theta[j] = eig[j]; a.active[j] = 1; ++nact;
-    }
-    stc = ensure_partial(sizeof(double) * (size_t)blocks * 16 * kt * 2);
-    if (stc) return stc;
-    stc = ensure_small(sizeof(double) * p.small_doubles());
-    if (stc) return stc;
-    a.v = v; a.av = av; a.cpk = d_cpk; a.evec = evec; a.r = r; a.avy = avy; a.red = d_partial;
-    a.n = n; a.l = l; a.l4 = l4; a.k = m;
-    {
-      // (flops: the two Ritz products and, with extra columns, the two panel products they replace)
-      Scope s(this, DLA_OP_RITZ, 8.0 * n * (2.0 * l + ((avy ? 2.0 : 1.0) + (evec ? 1.0 : 0.0)) * m + 2.0 * k2),
-              4.0 * (double)n * l * (m + k2) + 5.0 * (double)n * nact, p.name());
+    a.v = v; a.av = av; a.cpk = d_cpk; a.evec = evec; a.r = r; a.avy = avy; a.p2 = p2; a.ap2 = ap2; a.k2 = k2;
+    a.n = n; a.l = l; a.l4 = p.l4; a.k = m;
+    const int nact = for_open_roots(n_res, 48, skip, [&](int j) { a.theta[j] = eig[j]; a.active[j] = 1; });
+    // (flops: the two Ritz products and, with extra columns, the two panel products they replace)
+    return ritz_sweep_tail(p, a, 8.0 * n * (2.0 * l + ((avy ? 2.0 : 1.0) + (evec ? 1.0 : 0.0)) * m + 2.0 * k2),
+                           4.0 * (double)n * l * (m + k2) + 5.0 * (double)n * nact, n_res, out, [&]() {
       // (with extra products the 16-byte path is guaranteed by the caller, ritz_residual_p)
       int r_ = DLA_OK;
       if (!first_instance<std::size(RITZ_INSTANCES)>([&](auto i) {
             constexpr RitzInstance s = RITZ_INSTANCES[decltype(i)::value];
-            if (kt != s.kt || (vec2 ? 2 : 1) != s.vec || pipe != s.pipe || qt != s.qt || xp != s.xp) return false;
+            if (p.kt != s.kt || (p.vec2 ? 2 : 1) != s.vec || p.pipe != s.pipe || p.qt != s.qt || p.xp != s.xp) return false;
             auto kfn = ritz_kernel<s.kt, s.vec, 3, s.pipe, s.qt, s.xp>;
-            if (!raise_lds((const void*)kfn, lds, ritz_static_lds(kt))) r_ = DLA_ERR_RUNTIME;
-            else DLA_LAUNCH(kfn, dim3(blocks), dim3(256), lds, st, a);
+            if (!raise_lds((const void*)kfn, p.lds, ritz_static_lds(p.kt))) r_ = DLA_ERR_RUNTIME;
+            else DLA_LAUNCH(kfn, dim3(p.blocks), dim3(256), p.lds, st, a);
             return true;
           })) {
         err = "ritz: no kernel instance";
-        return DLA_ERR_RUNTIME;
+        return (int)DLA_ERR_RUNTIME;
       }
-      if (r_) return r_;
-    }
-    {
-      Scope s2(this, DLA_OP_RITZ, 0.0, 0.0, "ritz_reduce_kernel");
-      DLA_LAUNCH(ritz_reduce_kernel, dim3(ncol), dim3(256), 0, st, (const double*)d_partial, blocks, ncol, d_small,
-                         h_small.dev(), nslots, local_only ? 0 : rank);
-    }
-    HIPCHK(hipGetLastError());
-    // sums and all ranks' maxima in one collective (reference :1730-1731 are two reductions)
-    stc = sum_to_host((int)p.small_doubles(), 0);
-    if (stc) return stc;
-    for (int j = 0; j < n_res; ++j) {
-      double mx = 0.0;
-      for (int r = 0; r < nslots; ++r) mx = std::max(mx, h_small[ncol + r * ncol + j]);
-      out[2 * j] = h_small[j]; out[2 * j + 1] = mx;
-    }
-    return DLA_OK;
+      return r_;
+    });
   }
 
   // ---- the Ritz sweep that also forms and measures the next block (davidson_expand_kernel, Engine::ritz_expand)
@@ -6269,6 +6270,11 @@ struct HipEngine : dla::Engine {
     double fac = 0.0;
   } measured;
   bool rx_keep = false;              // the launches of the moment belong to the fused sweep itself or to the chain that takes the record
+  struct KeepMeasured {              // ... for the life of this guard
+    bool& f;
+    explicit KeepMeasured(bool& f_) : f(f_) { f = true; }
+    ~KeepMeasured() { f = false; }
+  };
   long long rx_run = 0, rx_discarded = 0;
   void drop_measured() { if (measured.valid && !rx_keep) { measured.valid = false; ++rx_discarded; } }
   void ritz_expand_counts(long long* run, long long* discarded) override { *run = rx_run; *discarded = rx_discarded; }
@@ -6278,15 +6284,10 @@ struct HipEngine : dla::Engine {
     if (!measured.valid || m != measured.m || k != measured.k) { err = "ritz_expand_measured: no fused sweep of this shape is on record"; return DLA_ERR_ARG; }
     int stc = ensure_small(sizeof(double) * (size_t)(m + k) * k);
     if (stc) return stc;
-    rx_keep = true;
-    struct Unkeep { bool& f; ~Unkeep() { f = false; } } unkeep{rx_keep};
+    KeepMeasured keep{rx_keep};
     StepOut out;
     stc = reduce_and_sum(DLA_OP_GRAM, d_small, h_small.dev(), measured.blocks, m, k, measured.tx, 1, 1, measured.tx + 1, 1, m + k, out, d_rxpart);
-    if (stc) return stc;
-    stc = small_to_host((size_t)(m + k) * k, out.mirror_fresh);
-    if (stc) return stc;
-    for (int j = 0; j < k; ++j) std::memcpy(c_host + (size_t)j * ldc, h_small + (size_t)j * (m + k), sizeof(double) * (m + k));
-    return DLA_OK;
+    return stc ? stc : small_result_home(m + k, k, out.mirror_fresh, c_host, ldc);
   }
   // the device-resident diagonal of one of the library's diagonal preconditioners (kind 0 / 1 / 2: the sample operator, the stored
   // sparse operator, the stored dense operator); nullptr: none of n rows has been set up
@@ -6305,8 +6306,7 @@ struct HipEngine : dla::Engine {
     if (nranks > 1 || comm || local_only || hook || p2p.on) return DLA_OK;        // (sharded runs keep the plain sweep)
     const double* dg = precnd_diagonal(precnd_kind, n);
     if (!dg || !u0 || !r || k <= 0 || k != m - first0) return DLA_OK;
-    const uintptr_t al = (uintptr_t)v | (uintptr_t)av | (uintptr_t)r | (uintptr_t)u0;
-    const RitzExpandPlan p = ritz_expand_plan(env(), n, l, m, first0, even_rows(n) && (al % 16 == 0));
+    const RitzExpandPlan p = ritz_expand_plan(env(), n, l, m, first0, on_16_bytes(n, v, av, r, u0));
     if (!p.fits || (size_t)p.blocks * p.gram_slots * 256 == 0) return DLA_OK;
     const int tx = p.tx;
     bind();
@@ -6319,58 +6319,31 @@ struct HipEngine : dla::Engine {
       return true;
     });
     if (!raised) { lds_retry = false; return DLA_OK; }
-    // coefficients Y, [16 tx][16]
-    const size_t cnt = (size_t)16 * tx * 16;
-    if (cnt > d_cpk.capacity()) {
-      HIPCHK(hipStreamSynchronize(st));
-      HIPCHK(d_cpk.reserve(std::max(cnt, doubles((size_t)1 << 16))));
-    }
-    int stc = ensure_partial(sizeof(double) * (size_t)p.blocks * 16 * 2);
-    if (stc) return stc;
-    stc = ensure_small(sizeof(double) * p.small_doubles());
-    if (stc) return stc;
     const size_t gp = (size_t)p.blocks * p.gram_slots * 256;
     if (gp > d_rxpart.capacity()) {
       HIPCHK(hipStreamSynchronize(st));
       HIPCHK(d_rxpart.reserve(gp));
     }
-    double* pk = nullptr;
-    int slot = 0;
-    stc = stage_slot(sizeof(double) * cnt, &pk, &slot);
+    // coefficients Y, [16 tx][16] (one column tile: the plan fits no block beyond 16 columns)
+    int stc = upload_packed(y_host, ldy, 0, l, m, 1, 16 * tx);
     if (stc) return stc;
-    std::memset(pk, 0, sizeof(double) * cnt);
-    RitzExpandArgs a{v, av, d_cpk, dg, fac, r, u0, d_partial, d_rxpart, (long long)n, l, m, first0, p.rows == 32 ? 1 : 0, 0u, {}};
-    int nact = 0;
-    for (int j = 0; j < m; ++j) {
-      // (open wanted roots only are corrected and measured, as by dla_ritz_residual)
-      if (j < n_res && !(skip && skip[j])) { a.act |= 1u << j; a.theta[j] = eig[j]; ++nact; }
-      const double* yj = y_host + (size_t)j * ldy;
-      for (int q = 0; q < l; ++q) pk[(size_t)q * 16 + j] = yj[q];
-    }
-    stc = stage_commit(slot, sizeof(double) * cnt, d_cpk);
-    if (stc) return stc;
-    rx_keep = true;
-    struct Unkeep { bool& f; ~Unkeep() { f = false; } } unkeep{rx_keep};
-    {
-      // what the sweep moves and what it stands for: the two Ritz products with the correction and the norms, the diagonal scaling,
-      // and X^T U, U^T U of the new block
-      Scope s(this, DLA_OP_RITZ, 8.0 * n * (2.0 * l + m + k + 1.0),
-              4.0 * (double)n * l * m + 5.0 * (double)n * nact + (double)n * k + 2.0 * (double)n * (l + k) * k, p.name());
+    RitzExpandArgs a{v, av, d_cpk, dg, fac, r, u0, nullptr, d_rxpart, (long long)n, l, m, first0, p.rows == 32 ? 1 : 0, 0u, {}};
+    // (open wanted roots only are corrected and measured, as by dla_ritz_residual)
+    const int nact = for_open_roots(n_res, m, skip, [&](int j) { a.act |= 1u << j; a.theta[j] = eig[j]; });
+    KeepMeasured keep{rx_keep};
+    // what the sweep moves and what it stands for: the two Ritz products with the correction and the norms, the diagonal scaling,
+    // and X^T U, U^T U of the new block
+    stc = ritz_sweep_tail(p, a, 8.0 * n * (2.0 * l + m + k + 1.0),
+                          4.0 * (double)n * l * m + 5.0 * (double)n * nact + (double)n * k + 2.0 * (double)n * (l + k) * k, n_res, out, [&]() {
       first_instance<std::size(RITZ_EXPAND_TILES)>([&](auto i) {
         constexpr int TX = RITZ_EXPAND_TILES[decltype(i)::value];
         if (tx != TX) return false;
         DLA_LAUNCH(davidson_expand_kernel<TX>, dim3(p.blocks), dim3(256), p.lds, st, a);
         return true;
       });
-    }
-    {
-      Scope s2(this, DLA_OP_RITZ, 0.0, 0.0, "ritz_reduce_kernel");
-      DLA_LAUNCH(ritz_reduce_kernel, dim3(p.ncol), dim3(256), 0, st, (const double*)d_partial, p.blocks, p.ncol, d_small, h_small.dev(), 1, 0);
-    }
-    HIPCHK(hipGetLastError());
-    stc = sum_to_host((int)p.small_doubles(), 0);
+      return (int)DLA_OK;
+    });
     if (stc) return stc;
-    for (int j = 0; j < n_res; ++j) { out[2 * j] = h_small[j]; out[2 * j + 1] = h_small[p.ncol + j]; }
     measured = Measured{true, v, u0, n, l, k, p.blocks, tx, fac};
     ++rx_run;
     *ran = 1;
@@ -6382,12 +6355,9 @@ struct HipEngine : dla::Engine {
                      const double* y2_host, int ldy2, const double* eig, int n_res, const int* skip,
                      double* e, double* r, double* t_work, double* junk, double* out) override
   {
-    const uintptr_t al = (uintptr_t)v | (uintptr_t)av | (uintptr_t)e | (uintptr_t)r;
     const int nslots = (local_only || nranks < 1) ? 1 : nranks;
-    const Ritz2Plan p = ritz2_plan(env(), n, l, m, even_rows(n) && (al % 16 == 0), nslots);
-    const int kt = p.kt, l4 = p.l4, blocks = p.blocks, ncol = p.ncol;
-    const bool vec2 = p.vec2;
-    const size_t lds = p.lds;
+    const Ritz2Plan p = ritz2_plan(env(), n, l, m, on_16_bytes(n, v, av, e, r), nslots);
+    const int kt = p.kt;
     if (!p.fits)
       return Engine::ritz_residual2(n, l, m, v, av, y1_host, ldy1, y2_host, ldy2, eig, n_res, skip, e, r, t_work, junk, out);
     // [Y1 | Y2] packed as 2 kt tiles: Y2 starts at tile kt
@@ -6396,48 +6366,34 @@ struct HipEngine : dla::Engine {
       std::memcpy(&yy[(size_t)j * l], y1_host + (size_t)j * ldy1, sizeof(double) * l);
       std::memcpy(&yy[(size_t)(16 * kt + j) * l], y2_host + (size_t)j * ldy2, sizeof(double) * l);
     }
-    int stc = upload_packed(yy.data(), l, 0, l, 16 * kt + m, 2 * kt, l4);
+    const int stc = upload_packed(yy.data(), l, 0, l, 16 * kt + m, 2 * kt, p.l4);
     if (stc) return stc;
     RitzArgs a{};
-    int nact = 0;
-    for (int j = 0; j < n_res && j < 48; ++j) {
-      if (skip && skip[j]) continue;
-      a.theta[j] = eig[j]; a.active[j] = 1; ++nact;
-    }
-    stc = ensure_partial(sizeof(double) * (size_t)blocks * 16 * kt * 2);
-    if (stc) return stc;
-    stc = ensure_small(sizeof(double) * p.small_doubles());
-    if (stc) return stc;
-    a.v = v; a.av = av; a.cpk = d_cpk; a.evec = e; a.r = r; a.avy = nullptr; a.red = d_partial;
-    a.n = n; a.l = l; a.l4 = l4; a.k = m;
-    {
-      // (flops: the two products and the residual correction, as the reference's dgemm pair + daxpy / dnrm2 loop)
-      Scope s(this, DLA_OP_RITZ, 8.0 * n * (2.0 * l + 2.0 * m), 4.0 * (double)n * l * m + 5.0 * (double)n * nact, p.name());
-#define RZ2(K) do { auto kfn = K; if (!raise_lds((const void*)kfn, lds, 1024)) return DLA_ERR_RUNTIME; DLA_LAUNCH(kfn, dim3(blocks), dim3(256), lds, st, a); } while (0)
-      if (vec2) { if (kt == 1) RZ2((ritz2_kernel<1, 2>)); else if (kt == 2) RZ2((ritz2_kernel<2, 2>)); else RZ2((ritz2_kernel<3, 2>)); }
-      else { if (kt == 1) RZ2((ritz2_kernel<1, 1>)); else if (kt == 2) RZ2((ritz2_kernel<2, 1>)); else RZ2((ritz2_kernel<3, 1>)); }
-#undef RZ2
-    }
-    {
-      Scope s2(this, DLA_OP_RITZ, 0.0, 0.0, "ritz_reduce_kernel");
-      DLA_LAUNCH(ritz_reduce_kernel, dim3(ncol), dim3(256), 0, st, (const double*)d_partial, blocks, ncol, d_small,
-                         h_small.dev(), nslots, local_only ? 0 : rank);
-    }
-    HIPCHK(hipGetLastError());
-    stc = sum_to_host((int)p.small_doubles(), 0);
-    if (stc) return stc;
-    for (int j = 0; j < n_res; ++j) {
-      double mx = 0.0;
-      for (int rr = 0; rr < nslots; ++rr) mx = std::max(mx, h_small[ncol + rr * ncol + j]);
-      out[2 * j] = h_small[j]; out[2 * j + 1] = mx;
-    }
-    return DLA_OK;
+    a.v = v; a.av = av; a.cpk = d_cpk; a.evec = e; a.r = r;
+    a.n = n; a.l = l; a.l4 = p.l4; a.k = m;
+    const int nact = for_open_roots(n_res, 48, skip, [&](int j) { a.theta[j] = eig[j]; a.active[j] = 1; });
+    // (flops: the two products and the residual correction, as the reference's dgemm pair + daxpy / dnrm2 loop)
+    return ritz_sweep_tail(p, a, 8.0 * n * (2.0 * l + 2.0 * m), 4.0 * (double)n * l * m + 5.0 * (double)n * nact, n_res, out, [&]() {
+      int r_ = DLA_OK;
+      if (!first_instance<std::size(RITZ2_INSTANCES)>([&](auto i) {
+            constexpr Ritz2Instance s = RITZ2_INSTANCES[decltype(i)::value];
+            if (kt != s.kt || (p.vec2 ? 2 : 1) != s.vec) return false;
+            auto kfn = ritz2_kernel<s.kt, s.vec>;
+            if (!raise_lds((const void*)kfn, p.lds, 1024)) r_ = DLA_ERR_RUNTIME;
+            else DLA_LAUNCH(kfn, dim3(p.blocks), dim3(256), p.lds, st, a);
+            return true;
+          })) {
+        err = "ritz2: no kernel instance";
+        return (int)DLA_ERR_RUNTIME;
+      }
+      return r_;
+    });
   }
 
   int axpy(size_t len, double alpha, const double* x, double* y) override
   {
     Scope s(this, DLA_OP_ELEM, 24.0 * (double)len, 2.0 * (double)len);
-    const int blocks = (int)std::max((size_t)1, std::min((size_t)ncu * 8, (len + 255) / 256));
+    const int blocks = grid_blocks(env(), (long long)len, 256);
     DLA_LAUNCH(axpy_kernel, dim3(blocks), dim3(256), 0, st, len, alpha, x, y);
     HIPCHK(hipGetLastError());
     return DLA_OK;
@@ -6498,7 +6454,7 @@ struct HipEngine : dla::Engine {
   {
     Scope s(this, DLA_OP_ELEM, 8.0 * (double)n * m, 0.0);
     const size_t total = (size_t)n * m;
-    const int blocks = (int)std::max((size_t)1, std::min((size_t)ncu * 8, (total + 255) / 256));
+    const int blocks = grid_blocks(env(), (long long)total, 256);
     DLA_LAUNCH(random_fill_kernel, dim3(blocks), dim3(256), 0, st, (long long)n, m, evec, row0, seed, offset, support_rows);
     HIPCHK(hipGetLastError());
     return DLA_OK;
@@ -7110,7 +7066,7 @@ struct HipEngine : dla::Engine {
                        const double* xp, const double* xm, double* yp, double* ym)
   {
     Scope s(this, DLA_OP_PRECND, 32.0 * (double)n * m + 24.0 * (double)n, 8.0 * (double)n * m, kname);
-    const bool vec2 = even_rows(n) && (((uintptr_t)xp | (uintptr_t)xm | (uintptr_t)yp | (uintptr_t)ym) % 16 == 0);
+    const bool vec2 = on_16_bytes(n, xp, xm, yp, ym);
     const size_t nv = (size_t)n / (vec2 ? 2 : 1);
     const int blocks = grid_blocks(env(), (long long)nv, 256);
     if (vec2) DLA_LAUNCH(lr_precnd_kernel<2>, dim3(blocks), dim3(256), 0, st, n, m, variant, fac, da, dm, ds, xp, xm, yp, ym);
@@ -7779,7 +7735,7 @@ struct HipEngine : dla::Engine {
     }
     Scope s(this, DLA_OP_MATVEC, 8.0 * n * (2.0 * m + syn_rw), 2.0 * (double)n * m * (2 * syn_rw + 1));
     // (t = W^T x sits in d_small, reduced over ranks; nothing else touches that buffer before the kernel below has read it)
-    const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
+    const int blocks = grid_blocks(env(), n, 256);
     DLA_LAUNCH((synth_apply_kernel<4>), dim3(blocks), dim3(256), sizeof(double) * 4 * m, st,
                        syn_row0, n, m, kind, cp, d_w, (const double*)d_small, x, ax);
     HIPCHK(hipGetLastError());
@@ -7789,7 +7745,7 @@ struct HipEngine : dla::Engine {
   {
     if (n != syn_n) { err = "synth_lrprec: n differs from setup"; return DLA_ERR_ARG; }
     Scope s(this, DLA_OP_PRECND, 8.0 * n * (4.0 * m + 1.0), 8.0 * (double)n * m);
-    const int blocks = std::max(1, std::min(ncu * 8, (n + 255) / 256));
+    const int blocks = grid_blocks(env(), n, 256);
     DLA_LAUNCH(synth_lrprec_kernel, dim3(blocks), dim3(256), 0, st, syn_row0, n, m, variant, fac, syn_sigma, (const double*)d_wsq, xp, xm, yp, ym);
     HIPCHK(hipGetLastError());
     return DLA_OK;
@@ -7798,11 +7754,11 @@ struct HipEngine : dla::Engine {
   int synth_precnd(int n, int m, double fac, const double* x, double* px) override
   {
     if (n != syn_n) { err = "synth_precnd: n differs from setup"; return DLA_ERR_ARG; }
-    const bool vec2 = even_rows(n) && (((uintptr_t)x | (uintptr_t)px) % 16 == 0);
+    const bool vec2 = on_16_bytes(n, x, px);
     // (booked under the instance's name: which of the two ran is a decision of the alignment and of the peers' shards)
     Scope s(this, DLA_OP_PRECND, 8.0 * n * (2.0 * m + 1.0), (double)n * m, vec2 ? "synth_precnd_kernel<2>" : "synth_precnd_kernel<1>");
     const size_t nv = (size_t)n / (vec2 ? 2 : 1);
-    const int blocks = (int)std::max((size_t)1, std::min((size_t)ncu * 8, (nv + 255) / 256));
+    const int blocks = grid_blocks(env(), (long long)nv, 256);
     if (vec2) DLA_LAUNCH(synth_precnd_kernel<2>, dim3(blocks), dim3(256), 0, st, n, m, fac, d_diag, x, px);
     else      DLA_LAUNCH(synth_precnd_kernel<1>, dim3(blocks), dim3(256), 0, st, n, m, fac, d_diag, x, px);
     HIPCHK(hipGetLastError());

@@ -5,7 +5,7 @@
 // (remembered plans, the cooldown, the LDS limit, pointers) and passes what a decision reads.  hip_engine.hip takes a plan,
 // books plan.name() and dispatches on the plan's fields; tests/plans_driver.cpp calls the same functions on the CPU.
 // Which template instances of the Gram, pending-factor and Ritz kernels exist is spelled once, in the lists below (GRAM_TILES,
-// gram_direct_instance, GRAM_LOW_TILES, WP_TILES, RITZ_INSTANCES): the planners round to a listed width, the engine's ladders
+// gram_direct_instance, GRAM_LOW_TILES, WP_TILES, RITZ_INSTANCES, RITZ2_INSTANCES): the planners round to a listed width, the engine's ladders
 // instantiate and launch exactly the listed rows, and tests/test_plans.py holds its own transcription against what the driver prints.
 #pragma once
 #include <algorithm>
@@ -179,6 +179,9 @@ constexpr RitzInstance RITZ_INSTANCES[] = {
   {1, 2, 0, 0, false}, {2, 2, 2, 0, false}, {3, 2, 3, 0, false},
   // plain, 8-byte path
   {1, 1, 0, 0, false}, {2, 1, 2, 0, false}, {3, 1, 3, 0, false}};
+// ritz2_kernel<kt, vec>: the sweep with two coefficient blocks
+struct Ritz2Instance { int kt, vec; };
+constexpr Ritz2Instance RITZ2_INSTANCES[] = {{1, 1}, {1, 2}, {2, 1}, {2, 2}, {3, 1}, {3, 2}};
 // davidson_expand_kernel<tx>: the Ritz sweep that also forms and measures the next block, tx column tiles of the basis
 constexpr int RITZ_EXPAND_TILES[] = {1, 2, 3, 4, 5, 6, 7};
 // "round up to an instantiated width": the narrowest listed pass of kt U-tiles that holds `want` X-tiles and that `ok` admits; null

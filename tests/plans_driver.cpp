@@ -117,6 +117,8 @@ int main()
       for (const WpTile& t : WP_TILES) std::printf("%d,%d,%d;", t.tlw, t.kt, t.R);
       std::printf(" ritz_instances=");
       for (const RitzInstance& r : RITZ_INSTANCES) std::printf("%d,%d,%d,%d,%d;", r.kt, r.vec, r.pipe, r.qt, r.xp ? 1 : 0);
+      std::printf(" ritz2_instances=");
+      for (const Ritz2Instance& r : RITZ2_INSTANCES) std::printf("%d,%d;", r.kt, r.vec);
       std::printf("\n");
     } else {
       std::fprintf(stderr, "unknown request: %s\n", line.c_str());

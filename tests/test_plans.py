@@ -5,7 +5,7 @@ tests/plans_driver.cpp is compiled with g++ and no ROCm include (tests/_build/, 
 tests/test_sell_layout.py does); it reads shape lines and prints plan fields and names from the product's own planners.  Expected
 values come from outside the planners: the committed rocprofv3 record of the benchmark, the literal names tests/test_knobs_gpu.py
 asserts, the rules the planners' comments state, and the kernels' instance lists.  Those lists live in hip_plans.h (GRAM_TILES,
-gram_direct_instance, GRAM_LOW_TILES, WP_TILES, RITZ_INSTANCES), where the planners and the dispatch ladders of hip_engine.hip both
+gram_direct_instance, GRAM_LOW_TILES, WP_TILES, RITZ_INSTANCES, RITZ2_INSTANCES), where the planners and the dispatch ladders of hip_engine.hip both
 read them; they are transcribed below as literal sets, and test_transcribed_instance_lists_are_the_engines holds each transcription
 against what the driver prints from the header."""
 import csv
@@ -141,6 +141,8 @@ def test_transcribed_instance_lists_are_the_engines():
     ritz |= {(kt, 2, pipe, 0, 0) for kt in (2, 3) for pipe in (0, 4)} | {(kt, 2, own[kt], qt, 0) for kt in (2, 3) for qt in (1, 2)}
     ritz |= {(kt, vec, own[kt], 0, 0) for kt in (1, 2, 3) for vec in (1, 2)}
     assert set(inst["ritz_instances"]) == ritz and len(inst["ritz_instances"]) == 23
+    # ritz2_kernel<kt, vec>
+    assert set(inst["ritz2_instances"]) == {(1, 1), (1, 2), (2, 1), (2, 2), (3, 1), (3, 2)} and len(inst["ritz2_instances"]) == 6
 
 
 @pytest.mark.parametrize("lds_limit", [64 * KIB, 160 * KIB])
@@ -224,6 +226,22 @@ def test_ritz_plans_fit_the_kernels(knob):
             assert rows.count((p["kt"], 2 if v else 1, p["pipe"], p["qt"], p["xp"])) == 1, what
             tiles_that_fit.add((p["kt"], p["xp"]))
     assert tiles_that_fit == {(kt, 0) for kt in (1, 2, 3)} | {(kt, 1) for kt in (1, 2, 3, 4, 5)}
+
+
+@pytest.mark.parametrize("knob", [0, 6])
+def test_ritz2_plans_fit_the_kernels(knob):
+    """the RITZ2_INSTANCES ladder of ritz_residual2; knob 0 = 6 switches the sweep off"""
+    cases = [(l, m, v) for l in (8, 13, 26, 104, 260, 520, 740) for m in range(1, 49) for v in (0, 1)]
+    rows = listed_instances()["ritz2_instances"]
+    res, _ = run_plans([env_line(t0=knob)] + [f"ritz2 {N_BENCH} {l} {m} {v} 1" for l, m, v in cases])
+    tiles_that_fit = set()
+    for (l, m, v), (p, name) in zip(cases, res):
+        what = (l, m, v, p, name)
+        if p["fits"]:
+            # the one instance ritz_residual2 launches for it: no plan that fits may reach "ritz2: no kernel instance"
+            assert p["kt"] == -(-m // 16) and rows.count((p["kt"], 2 if v else 1)) == 1, what
+            tiles_that_fit.add(p["kt"])
+    assert tiles_that_fit == (set() if knob == 6 else {1, 2, 3})
 
 
 def test_pending_factor_sweeps_fit_the_kernels():

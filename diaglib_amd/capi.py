@@ -40,7 +40,7 @@ EXPORTS = [
     "dla_nrm2", "dla_stream_triad", "dla_random_fill", "dla_fill_guess",
     "dla_ortho_cd", "dla_ortho_qr", "dla_ortho_vs_x", "dla_b_ortho", "dla_b_ortho_vs_x", "dla_check_guess", "dla_get_coeffs",
     "dla_call_matvec", "dla_call_precnd", "dla_expand_project", "dla_expand_project_metric",
-    "dla_syev", "dla_syev_lowest", "dla_potrf_lower", "dla_trtri_lower", "dla_norm_est",
+    "dla_syev", "dla_syev_lowest", "dla_potrf_lower", "dla_trtri_lower", "dla_norm_est", "dla_geev",
     "dla_synth_setup", "dla_synth_matvec", "dla_synth_precnd", "dla_synth_apbmul", "dla_synth_ambmul", "dla_synth_spdmul", "dla_synth_smdmul",
     "dla_synth_metric", "dla_synth_lrprec1", "dla_synth_lrprec2", "dla_pending_factor", "dla_pending_block", "dla_basis_admit", "dla_basis_fold", "dla_basis_sync", "dla_spmm_setup_csr", "dla_spmm_setup_csr_fmt", "dla_spmm_info", "dla_spmm_setup_csr_sharded", "dla_spmm_matvec", "dla_spmm_precnd",
     "dla_spmm_setup_metric_csr", "dla_spmm_metric_info", "dla_spmm_drop_metric", "dla_spmm_bvec", "dla_spmm_precnd_pencil",
@@ -51,11 +51,12 @@ EXPORTS = [
     "dla_spmm_setup_lr_csr", "dla_spmm_setup_lr_csr_dev", "dla_spmm_refresh_lr_values_dev", "dla_spmm_lr_info", "dla_spmm_drop_lr",
     "dla_spmm_apbmul", "dla_spmm_ambmul", "dla_spmm_spdmul", "dla_spmm_smdmul", "dla_spmm_lrprec1", "dla_spmm_lrprec2",
     "dla_dense_setup", "dla_dense_setup_dev", "dla_dense_info", "dla_dense_drop",
-    "dla_dense_matvec", "dla_dense_bvec", "dla_dense_precnd", "dla_dense_precnd_pencil",
+    "dla_dense_matvec", "dla_dense_matvec_t", "dla_dense_bvec", "dla_dense_precnd", "dla_dense_precnd_pencil",
     "dla_dense_setup_lr", "dla_dense_setup_lr_dev", "dla_dense_setup_lr_pair", "dla_dense_setup_lr_pair_dev", "dla_dense_lr_info",
     "dla_dense_drop_lr", "dla_dense_apbmul", "dla_dense_ambmul", "dla_dense_spdmul", "dla_dense_smdmul", "dla_dense_lrprec1",
     "dla_dense_lrprec2",
     "dla_davidson_driver", "dla_gen_david_driver", "dla_lobpcg_driver", "dla_caslr_eff_driver", "dla_caslr_driver", "dla_call_lrprec",
+    "dla_nonsym_driver",
     "dla_last_solve_info", "dla_set_solve_info",
 ]
 
@@ -165,6 +166,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dla_call_matvec": (i, [vp, vp, i, i, vp, vp]), "dla_call_precnd": (i, [vp, vp, i, i, d, vp, vp]),
         "dla_syev": (i, [C.c_char, i, c_dp, i, c_dp]), "dla_syev_lowest": (i, [C.c_char, i, c_dp, i, c_dp, i]),
         "dla_potrf_lower": (i, [i, c_dp, i]),
+        "dla_geev": (i, [i, c_dp, i, c_dp, c_dp, c_dp, i, c_dp, i]),
         "dla_trtri_lower": (i, [i, c_dp, i]), "dla_norm_est": (d, [i, c_dp, i]),
         "dla_synth_setup": (i, [vp, C.c_longlong, C.c_longlong, i, i, d]),
         "dla_pending_factor": (i, [vp, i, vp, i]),
@@ -192,6 +194,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dla_dense_setup": (i, [vp, i, i, vp, i]), "dla_dense_setup_dev": (i, [vp, i, i, vp, i]),
         "dla_dense_info": (i, [vp, i, C.POINTER(DenseInfo)]), "dla_dense_drop": (i, [vp, i]),
         "dla_dense_matvec": (None, [c_ip, c_ip, vp, vp]), "dla_dense_bvec": (None, [c_ip, c_ip, vp, vp]),
+        "dla_dense_matvec_t": (None, [c_ip, c_ip, vp, vp]),
         "dla_dense_precnd": (None, [c_ip, c_ip, c_dp, vp, vp]), "dla_dense_precnd_pencil": (None, [c_ip, c_ip, c_dp, vp, vp]),
         "dla_dense_setup_lr": (i, [vp, i, i, vp, i]), "dla_dense_setup_lr_dev": (i, [vp, i, i, vp, i]),
         "dla_dense_setup_lr_pair": (i, [vp, i, i, vp, i, vp, i]), "dla_dense_setup_lr_pair_dev": (i, [vp, i, i, vp, i, vp, i]),
@@ -205,6 +208,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dla_caslr_driver": (None, [i, i, i, i, i, d, i, vp, vp, vp, vp, vp, vp, vp, c_ip]),
         "dla_call_lrprec": (i, [vp, vp, i, i, d, vp, vp, vp, vp]),
         "dla_gen_david_driver": (None, [i, i, i, i, i, d, i, d, vp, vp, vp, vp, vp, c_ip]),
+        "dla_nonsym_driver": (None, [i, i, i, i, i, d, i, d, vp, vp, vp, vp, vp, vp, i, c_ip]),
         "dla_last_solve_info": (None, [c_ip, c_ip, c_ip]),
     }
     for name, (res, args) in sig.items():
@@ -820,6 +824,10 @@ class Context:
         self._chk(self.lib.dla_dense_info(self.h, int(bool(metric)), C.byref(o)))
         return {name: int(getattr(o, name)) for name, _ in DenseInfo._fields_}
 
+    def dense_matvec_t(self, x: DevPanel, y: DevPanel) -> None:
+        """y = A^T x from the stored copy of the dense operator (dla_dense_matvec_t); x and y are n x m panels that do not overlap"""
+        self._chk(self.lib.dla_call_matvec(self.h, fn_address("dla_dense_matvec_t"), x.n, x.m, x.ptr, y.ptr))
+
     def dense_drop(self, metric: bool = False) -> None:
         """free the dense operator's (metric: the metric's) device blocks; nothing happens where nothing is stored"""
         self._chk(self.lib.dla_dense_drop(self.h, int(bool(metric))))
@@ -975,6 +983,29 @@ class Context:
                                    eig.ctypes.data, ev_ptr, C.byref(ok))
         return eig, out, bool(ok.value), self.last_solve_info()
 
+    def nonsym_driver(self, n: int, n_targ: int, n_max: int, max_iter: int, tol: float, max_dav: int, shift: float,
+                      matvec: Callback, matvec_l: Callback, precnd: Callback, evec_r, evec_l, side: str = "c",
+                      verbose: bool = False):
+        """non-symmetric Davidson (reference diaglib.f90:2252-2943): matvec applies A, matvec_l its transpose; side is "r", "l",
+        "c" (right pass, then left pass, then L^T R = I) or "s" (taken as "c").  evec_r, evec_l: numpy (n, n_max) guesses (host
+        mode) or two DevPanels (evec-on-device mode).  Returns (eig, evec_r_out, evec_l_out, ok, info); eig keeps the shift.
+        Any other side ends the process, as in the reference."""
+        mv, mvl, pc = self._wrap_mv(matvec), self._wrap_mv(matvec_l), self._wrap_pc(precnd)
+        eig = np.zeros(n_max); ok = C.c_int(0)
+        if isinstance(evec_r, DevPanel) != isinstance(evec_l, DevPanel):
+            raise ValueError("nonsym_driver: evec_r and evec_l must both be numpy arrays or both DevPanels")
+        if isinstance(evec_r, DevPanel):
+            self.set_option(OPT_EVEC_ON_DEVICE, 1)
+            r_ptr, l_ptr, out_r, out_l = evec_r.ptr, evec_l.ptr, evec_r, evec_l
+        else:
+            self.set_option(OPT_EVEC_ON_DEVICE, 0)
+            out_r = np.asfortranarray(evec_r, dtype=np.float64).copy(order="F")
+            out_l = np.asfortranarray(evec_l, dtype=np.float64).copy(order="F")
+            r_ptr, l_ptr = out_r.ctypes.data, out_l.ctypes.data
+        self.lib.dla_nonsym_driver(int(verbose), n, n_targ, n_max, max_iter, tol, max_dav, shift, mv, mvl, pc,
+                                   eig.ctypes.data, r_ptr, l_ptr, ord(side), C.byref(ok))
+        return eig, out_r, out_l, bool(ok.value), self.last_solve_info()
+
     def caslr_driver(self, *args, **kw):
         """traditional linear-response driver (reference diaglib.f90:558-1022); arguments as caslr_eff_driver"""
         return self.caslr_eff_driver(*args, _entry="dla_caslr_driver", **kw)
@@ -1042,6 +1073,20 @@ def syev_lowest(a: np.ndarray, m: int, uplo: str = "l"):
     if info != 0:
         raise DlaError(f"dla_syev_lowest info={info}")
     return w, a[:, :m]
+
+
+def geev(a: np.ndarray):
+    """all eigenvalues and the left and right eigenvectors of a general real matrix (dla_geev, dgeev's conventions):
+    returns (wr, wi, vl, vr)"""
+    L = load()
+    a = np.asfortranarray(a, dtype=np.float64).copy(order="F")
+    n = a.shape[0]
+    wr, wi = np.zeros(n), np.zeros(n)
+    vl, vr = np.zeros((n, n), order="F"), np.zeros((n, n), order="F")
+    info = L.dla_geev(n, _dp(a), n, _dp(wr), _dp(wi), _dp(vl), n, _dp(vr), n)
+    if info != 0:
+        raise DlaError(f"dla_geev info={info}")
+    return wr, wi, vl, vr
 
 
 def potrf_lower(a: np.ndarray):

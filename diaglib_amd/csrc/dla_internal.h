@@ -354,6 +354,8 @@ struct Engine : BlockOps {
   virtual int dense_info(int /*slot*/, struct dla_dense_info* /*out*/) { return no_dense(); }
   virtual int dense_drop(int /*first*/, int /*last*/) { return no_dense(); }
   virtual int dense_mul(int /*slot*/, int /*n*/, int /*m*/, const double* /*x*/, double* /*y*/) { return no_dense(); }
+  // y = A^T x on the operator slot's copy (dla_dense_matvec_t)
+  virtual int dense_mul_t(int /*n*/, int /*m*/, const double* /*x*/, double* /*y*/) { return no_dense(); }
   virtual int dense_precnd(bool /*pencil*/, int /*n*/, int /*m*/, double /*fac*/, const double* /*x*/, double* /*px*/) { return no_dense(); }
   virtual int dense_lrprec(int /*variant*/, int /*n*/, int /*m*/, double /*fac*/, const double* /*xp*/, const double* /*xm*/,
                            double* /*yp*/, double* /*ym*/) { return no_dense(); }

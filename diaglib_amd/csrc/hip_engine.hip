@@ -2581,6 +2581,97 @@ __global__ __launch_bounds__(256) void dense_mfma_kernel(int n, int m, int n_pad
       }
   }
 }
+// One pass Y(n x m) = A^T X, m <= 16 G, on the same stored copy (plan: hip_plans.h, dense_t_plan).  The contraction now runs over the
+// rows of the matrix, which are lane & 15 of a stored group -- an MFMA output index as the group is loaded -- so every 16 x 16 block
+// of the matrix (two adjacent groups, 2 KB) is turned in LDS: the wavefront stores its loads lane-linearly (16 bytes per lane) into a
+// region of its own and reads them back one double per lane as the B operand of v_mfma_f64_16x16x4, lane (k = lane >> 4,
+// j = lane & 15) taking a(16 t + 4 s + k, 16 b + j) for step s = 0 .. 3 of row tile t.  X is the A operand as in dense_mfma_kernel
+// (lane: column lane & 15 of the group, row 16 t + 4 s + (lane >> 4)), so the accumulator of lane l holds output index (matrix
+// column) 16 b + (l & 15) for the columns (l >> 4) + 4 r of the group, and a store writes 16 consecutive elements of four columns.
+// Block (bx, by): four wavefronts, wavefront w owns the DENSE_T_WAVE_BLOCKS column blocks of strip 4 bx + w -- 8 adjacent groups, 8 KB
+// contiguous per row tile -- and all four walk the row tiles of chunk by, reading the same fragments of X at about the same time.
+// No block-wide barrier: a wavefront touches its own LDS region only, and LDS operations of one wavefront complete in order.
+// A strip that reaches beyond the last column block reads that block again and stores nothing for it; rows of X at or beyond n
+// (where the stored copy holds zeros) and columns at or beyond m are not loaded.
+// row_chunks = 1 (gridDim.y == 1): the result goes to y.  Otherwise chunk by goes to ws[by][m][n], for dense_combine_kernel.
+template <int G>
+__global__ __launch_bounds__(256) void dense_t_mfma_kernel(int n, int m, int n_pad, int chunk_tiles, const double* __restrict__ a,
+                                                            const double* __restrict__ x, double* __restrict__ y, double* __restrict__ ws)
+{
+  constexpr int W = DENSE_T_WAVE_BLOCKS;
+  __shared__ double turn[4][W * 256];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
+  const int row_tiles = n_pad / DENSE_TILE, col_blocks = n_pad / 16, groups = n_pad / DENSE_GROUP;
+  const int b0 = (blockIdx.x * 4 + wave) * W;
+  if (b0 >= col_blocks) return;
+  const int t0 = blockIdx.y * chunk_tiles, t1 = min(row_tiles, t0 + chunk_tiles);
+  double* my = turn[wave];
+  // the lane's 16-byte element of group 2 b + h in a row tile, and the double it reads back for step 0 of block w
+  size_t aoff[W];
+#pragma unroll
+  for (int w = 0; w < W; ++w) aoff[w] = (size_t)(2 * min(b0 + w, col_blocks - 1)) * 64 + lane;
+  const int back = (li >> 3) * 128 + (16 * (li & 3) + lk) * 2 + ((li >> 2) & 1);
+  const double* xp[G];
+  bool xin[G];
+#pragma unroll
+  for (int q = 0; q < G; ++q) {
+    xin[q] = 16 * q + li < m;
+    xp[q] = x + (size_t)(xin[q] ? 16 * q + li : 0) * n + lk;
+  }
+  v4d acc[W][G];
+#pragma unroll
+  for (int w = 0; w < W; ++w)
+#pragma unroll
+    for (int q = 0; q < G; ++q) acc[w][q] = v4d{0.0, 0.0, 0.0, 0.0};
+  v2d av[W][2];
+  {
+    const v2d* at = (const v2d*)a + (size_t)t0 * groups * 64;
+#pragma unroll
+    for (int w = 0; w < W; ++w) { av[w][0] = at[aoff[w]]; av[w][1] = at[aoff[w] + 64]; }
+  }
+  for (int t = t0; t < t1; ++t) {
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      lds_store2(my + (2 * w) * 128 + 2 * lane, av[w][0]);
+      lds_store2(my + (2 * w + 1) * 128 + 2 * lane, av[w][1]);
+    }
+    if (t + 1 < t1) {         // the next row tile's loads travel while this one is multiplied
+      const v2d* at = (const v2d*)a + (size_t)(t + 1) * groups * 64;
+#pragma unroll
+      for (int w = 0; w < W; ++w) { av[w][0] = at[aoff[w]]; av[w][1] = at[aoff[w] + 64]; }
+    }
+    double xv[4][G];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int row = DENSE_TILE * t + 4 * s + lk;
+#pragma unroll
+      for (int q = 0; q < G; ++q) xv[s][q] = (xin[q] && row < n) ? xp[q][DENSE_TILE * t + 4 * s] : 0.0;
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        const double bv = lds_load1(my + w * 256 + back + 8 * s);
+#pragma unroll
+        for (int q = 0; q < G; ++q) acc[w][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(xv[s][q], bv, acc[w][q], 0, 0, 0);
+      }
+    __builtin_amdgcn_wave_barrier();
+  }
+  double* dst = gridDim.y == 1 ? y : ws + (size_t)blockIdx.y * m * n;
+#pragma unroll
+  for (int w = 0; w < W; ++w) {
+    const int col = (b0 + w) * 16 + li;
+    if (b0 + w >= col_blocks || col >= n) continue;
+#pragma unroll
+    for (int q = 0; q < G; ++q)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int c = 16 * q + lk + 4 * r;
+        if (c < m) dst[(size_t)c * n + col] = acc[w][q][r];
+      }
+  }
+}
 // y = ((p_0 + p_1) + p_2) + ... over the chunks of a split pass, in ascending chunk order, one thread per element
 __global__ void dense_combine_kernel(size_t total, int k_chunks, const double* __restrict__ ws, double* __restrict__ y)
 {
@@ -7289,6 +7380,44 @@ struct HipEngine : dla::Engine {
         Scope s(this, DLA_OP_MATVEC, 0.0, 0.0, "dense_combine_kernel");
         const size_t total = (size_t)n * mp;
         DLA_LAUNCH(dense_combine_kernel, dim3(grid_blocks(env(), (long long)total, 256)), dim3(256), 0, st, total, p.k_chunks, (const double*)op.ws, yc);
+        HIPCHK(hipGetLastError());
+      }
+    }
+    return DLA_OK;
+  }
+  // y = A^T x on the copy of the operator slot (dla_dense_matvec_t): the passes of dense_t_plan on the slot's own workspace.  The slot's
+  // description (dense_info: the first pass of the most recent forward product) is left as it is.
+  int dense_mul_t(int n, int m, const double* x, double* y) override
+  {
+    { const int stc = dense_admit(dla::DENSE_A, "dense_matvec_t", DENSE_ROWS, n); if (stc) return stc; }
+    if (m <= 0) return DLA_OK;
+    DenseOp& op = dense[dla::DENSE_A];
+    for (int c0 = 0; c0 < m; c0 += DENSE_MAX_COLS) {
+      const int mp = std::min(DENSE_MAX_COLS, m - c0);
+      const DenseTPlan p = dense_t_plan(ncu, n, mp);
+      if (p.ws_doubles > op.ws.capacity()) {
+        bind();
+        HIPCHK(hipStreamSynchronize(st));       // (queued products may still use the old block)
+        HIPCHK(op.ws.reserve(p.ws_doubles));
+      }
+      const double* xc = x + (size_t)c0 * n;
+      double* yc = y + (size_t)c0 * n;
+      const dim3 grid((p.strips + 3) / 4, p.row_chunks);
+      {
+        Scope s(this, DLA_OP_MATVEC, 8.0 * (double)n * n + 16.0 * (double)n * mp, 2.0 * (double)n * n * mp, p.name());
+        const bool hit = first_instance<DENSE_MAX_COLS / 16>([&](auto i) {
+          constexpr int G = (int)decltype(i)::value + 1;
+          if (p.acc_groups != G) return false;
+          DLA_LAUNCH((dense_t_mfma_kernel<G>), grid, dim3(256), 0, st, n, mp, p.n_pad, p.chunk_tiles, (const double*)op.a, xc, yc, (double*)op.ws);
+          return true;
+        });
+        if (!hit) { err = "dense transposed product: no kernel instance"; return DLA_ERR_RUNTIME; }
+        HIPCHK(hipGetLastError());
+      }
+      if (p.row_chunks > 1) {
+        Scope s(this, DLA_OP_MATVEC, 0.0, 0.0, "dense_combine_kernel");
+        const size_t total = (size_t)n * mp;
+        DLA_LAUNCH(dense_combine_kernel, dim3(grid_blocks(env(), (long long)total, 256)), dim3(256), 0, st, total, p.row_chunks, (const double*)op.ws, yc);
         HIPCHK(hipGetLastError());
       }
     }

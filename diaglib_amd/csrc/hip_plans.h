@@ -763,4 +763,39 @@ inline DensePlan dense_plan(int ncu, int n, int m)
   return p;
 }
 
+// One pass of the transposed product Y(n x m) = A^T X, m <= DENSE_MAX_COLS, on the same stored copy (include/diaglib_amd.h,
+// dla_dense_matvec_t): a pure function of n, m and the CU count.  The output index is now the matrix's column, the contraction runs
+// down its rows.  A wavefront owns a strip of DENSE_T_WAVE_BLOCKS blocks of 16 matrix columns -- 2 DENSE_T_WAVE_BLOCKS adjacent groups,
+// 8 KB contiguous in every row tile -- and one chunk of the row tiles, so there are strips x row_chunks of them.  The rule for
+// row_chunks is dense_plan's for k_chunks: as many as give every SIMD a wavefront (4 ncu / strips, rounded up), but
+//   * the partial sums may move at most 1 / DENSE_WS_SHARE of the matrix's bytes: row_chunks <= n / (2 DENSE_WS_SHARE m);
+//   * a chunk keeps at least DENSE_T_MIN_CHUNK_TILES row tiles: row_chunks <= row_tiles / DENSE_T_MIN_CHUNK_TILES;
+// and never less than 1.  Chunk c covers the row tiles [c chunk_tiles, min(row_tiles, (c + 1) chunk_tiles)), chunk_tiles =
+// ceil(row_tiles / chunks), and row_chunks is the number of chunks that are not empty.  Partial sums: ws[chunk][m][n], added in
+// ascending chunk order by dense_combine_kernel.  Starting values, like dense_plan's.
+constexpr int DENSE_T_WAVE_BLOCKS = 4, DENSE_T_MIN_CHUNK_TILES = 4;
+struct DenseTPlan {
+  int n_pad, row_tiles, col_blocks, strips;   // col_blocks: n_pad / 16; strips: ceil(col_blocks / DENSE_T_WAVE_BLOCKS)
+  int acc_groups;                             // groups of 16 columns of X (the kernel's instance): 1 .. 3
+  int row_chunks, chunk_tiles;
+  size_t ws_doubles;                          // row_chunks x m x n, 0 with one chunk
+  std::string name() const { return plan_name("dense_t_mfma_kernel<%d>", acc_groups); }
+};
+inline DenseTPlan dense_t_plan(int ncu, int n, int m)
+{
+  DenseTPlan p{};
+  p.n_pad = dense_n_pad(n);
+  p.row_tiles = p.n_pad / DENSE_TILE;
+  p.col_blocks = p.n_pad / 16;
+  p.strips = (p.col_blocks + DENSE_T_WAVE_BLOCKS - 1) / DENSE_T_WAVE_BLOCKS;
+  p.acc_groups = (m + 15) / 16;
+  const long long want = (4LL * std::max(1, ncu) + p.strips - 1) / p.strips;
+  const long long traffic = (long long)n / (2LL * DENSE_WS_SHARE * m), length = p.row_tiles / DENSE_T_MIN_CHUNK_TILES;
+  const int chunks = (int)std::max(1LL, std::min(want, std::min(traffic, length)));
+  p.chunk_tiles = (p.row_tiles + chunks - 1) / chunks;
+  p.row_chunks = (p.row_tiles + p.chunk_tiles - 1) / p.chunk_tiles;
+  p.ws_doubles = p.row_chunks > 1 ? (size_t)p.row_chunks * (size_t)m * (size_t)n : 0;
+  return p;
+}
+
 }  // namespace dla_plans

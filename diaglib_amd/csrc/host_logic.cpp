@@ -1238,7 +1238,7 @@ static const OwnCallback* own_callback(void* fn)
     {(void*)&dla_synth_lrprec1, false, true}, {(void*)&dla_synth_lrprec2, false, true}, {(void*)&dla_spmm_lrprec1, false, true},
     {(void*)&dla_spmm_lrprec2, false, true}, {(void*)&dla_spmm_precnd_cheb, false, true},
     {(void*)&dla_spmm_precnd_cheb_jacobi, false, true}, {(void*)&dla_spmm_precnd_cheb_pencil, false, true},
-    {(void*)&dla_dense_matvec, true, true}, {(void*)&dla_dense_bvec, true, true},
+    {(void*)&dla_dense_matvec, true, true}, {(void*)&dla_dense_bvec, true, true}, {(void*)&dla_dense_matvec_t, true, true},
     {(void*)&dla_dense_apbmul, true, true}, {(void*)&dla_dense_ambmul, true, true}, {(void*)&dla_dense_spdmul, true, true},
     {(void*)&dla_dense_smdmul, true, true},
     {(void*)&dla_dense_precnd, false, true}, {(void*)&dla_dense_precnd_pencil, false, true},
@@ -2149,6 +2149,12 @@ int dla_dense_info(dla_ctx* c, int which, struct dla_dense_info* out) { return d
 int dla_dense_drop(dla_ctx* c, int which) { const int slot = dla::dense_slot_of_which(which); return dense_slot_drop(c, slot, slot); }
 void dla_dense_matvec(const int* n, const int* m, const double* x, double* ax) { dense_product(DENSE_A, n, m, x, ax); }
 void dla_dense_bvec(const int* n, const int* m, const double* x, double* bx) { dense_product(DENSE_B, n, m, x, bx); }
+void dla_dense_matvec_t(const int* n, const int* m, const double* x, double* y)
+{
+  dla_ctx* c = g_dense_ctx;
+  if (!c) { callback_failed(DLA_ERR_ARG, "dla_dense_matvec_t before dla_dense_setup: no dense operator has been set up"); return; }
+  if (int st = c->eng->dense_mul_t(*n, *m, x, y)) callback_failed(st, "dla_dense_matvec_t failed: " + c->eng->err);
+}
 void dla_dense_precnd(const int* n, const int* m, const double* fac, const double* x, double* px) { dense_precondition(0, n, m, fac, x, nullptr, px, nullptr); }
 void dla_dense_precnd_pencil(const int* n, const int* m, const double* fac, const double* x, double* px) { dense_precondition(1, n, m, fac, x, nullptr, px, nullptr); }
 

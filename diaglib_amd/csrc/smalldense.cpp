@@ -703,9 +703,469 @@ int sym_eig_lowest(int n, std::vector<double>& s, int m, std::vector<double>& w_
 }
 inline double& at(double* a, int ld, int i, int j) { return a[(size_t)i + (size_t)j * ld]; }
 inline double at(const double* a, int ld, int i, int j) { return a[(size_t)i + (size_t)j * ld]; }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// General real eigenproblem (dla_geev): Householder reduction to Hessenberg form, Francis' double-shift QR on the Hessenberg matrix
+// with every transformation accumulated, eigenvectors of the quasi-triangular factor by back-substitution and back-transformation
+// (Wilkinson & Reinsch, Handbook II/12-15; Golub & Van Loan 7.4-7.6).  Matrices are row-major n x n here: h[i*n + j].
+// ---------------------------------------------------------------------------------------------------------------------------------
+
+// (xr + i xi) / (yr + i yi) without overflow in the denominator (Smith)
+inline void cdivide(double xr, double xi, double yr, double yi, double& cr, double& ci)
+{
+  if (std::fabs(yr) > std::fabs(yi)) {
+    const double r = yi / yr, d = yr + r * yi;
+    cr = (xr + r * xi) / d;
+    ci = (xi - r * xr) / d;
+  } else {
+    const double r = yr / yi, d = yi + r * yr;
+    cr = (r * xr + xi) / d;
+    ci = (r * xi - xr) / d;
+  }
+}
+
+// h <- Q^T h Q upper Hessenberg, v <- Q
+void hessenberg(int n, std::vector<double>& h, std::vector<double>& v)
+{
+  auto H = [&](int i, int j) -> double& { return h[(size_t)i * n + j]; };
+  auto V = [&](int i, int j) -> double& { return v[(size_t)i * n + j]; };
+  std::vector<double> u(n, 0.0);
+  const int hi = n - 1;
+  for (int m = 1; m < hi; ++m) {
+    double scale = 0.0;
+    for (int i = m; i <= hi; ++i) scale += std::fabs(H(i, m - 1));
+    if (scale == 0.0) continue;
+    double hh = 0.0;
+    for (int i = hi; i >= m; --i) {
+      u[i] = H(i, m - 1) / scale;
+      hh += u[i] * u[i];
+    }
+    double g = std::sqrt(hh);
+    if (u[m] > 0.0) g = -g;
+    hh -= u[m] * g;
+    u[m] -= g;
+    for (int j = m; j < n; ++j) {            // (I - u u^T / hh) from the left
+      double f = 0.0;
+      for (int i = hi; i >= m; --i) f += u[i] * H(i, j);
+      f /= hh;
+      for (int i = m; i <= hi; ++i) H(i, j) -= f * u[i];
+    }
+    for (int i = 0; i <= hi; ++i) {          // ... and from the right
+      double f = 0.0;
+      for (int j = hi; j >= m; --j) f += u[j] * H(i, j);
+      f /= hh;
+      for (int j = m; j <= hi; ++j) H(i, j) -= f * u[j];
+    }
+    u[m] *= scale;
+    H(m, m - 1) = scale * g;                 // (column m-1 below row m keeps scale * u: read back when Q is formed)
+  }
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) V(i, j) = (i == j) ? 1.0 : 0.0;
+  // Q = product of the reflectors, last one first (u[m] of step m is still in u: later steps wrote u[m+1..] only)
+  for (int m = hi - 1; m >= 1; --m) {
+    if (H(m, m - 1) == 0.0) continue;
+    for (int i = m + 1; i <= hi; ++i) u[i] = H(i, m - 1);
+    for (int j = m; j <= hi; ++j) {
+      double g = 0.0;
+      for (int i = m; i <= hi; ++i) g += u[i] * V(i, j);
+      g = (g / u[m]) / H(m, m - 1);          // two divisions: no underflow in the product of the two small numbers
+      for (int i = m; i <= hi; ++i) V(i, j) += g * u[i];
+    }
+  }
+  for (int i = 2; i < n; ++i)
+    for (int j = 0; j < i - 1; ++j) H(i, j) = 0.0;
+}
+
+// Real Schur form of the Hessenberg matrix h by shifted double-step QR, then the eigenvectors: on exit d + i e are the eigenvalues
+// (conjugate pairs consecutive, positive imaginary part first) and v holds the eigenvectors in the same order -- column j for a real
+// eigenvalue, columns j and j+1 the real and imaginary parts for the first of a pair.  Not normalised.  Returns non-zero when an
+// eigenvalue has not deflated after 30 n sweeps.
+int hessenberg_qr_vectors(int nn, std::vector<double>& h, std::vector<double>& v, std::vector<double>& d, std::vector<double>& e)
+{
+  auto H = [&](int i, int j) -> double& { return h[(size_t)i * nn + j]; };
+  auto V = [&](int i, int j) -> double& { return v[(size_t)i * nn + j]; };
+  const double eps = 2.220446049250313e-16;
+  const int sweeps_allowed = 30 * nn;
+  int n = nn - 1;
+  double exshift = 0.0, p = 0.0, q = 0.0, r = 0.0, s = 0.0, z = 0.0, t, w, x, y;
+  double norm = 0.0;
+  for (int i = 0; i < nn; ++i)
+    for (int j = std::max(i - 1, 0); j < nn; ++j) norm += std::fabs(H(i, j));
+  int iter = 0;
+  while (n >= 0) {
+    // a negligible sub-diagonal element splits the active block
+    int l = n;
+    while (l > 0) {
+      s = std::fabs(H(l - 1, l - 1)) + std::fabs(H(l, l));
+      if (s == 0.0) s = norm;
+      if (std::fabs(H(l, l - 1)) < eps * s) break;
+      --l;
+    }
+    if (l == n) {                                   // one real root
+      H(n, n) += exshift;
+      d[n] = H(n, n);
+      e[n] = 0.0;
+      --n;
+      iter = 0;
+    } else if (l == n - 1) {                        // a 2 x 2 block: two real roots or a conjugate pair
+      w = H(n, n - 1) * H(n - 1, n);
+      p = (H(n - 1, n - 1) - H(n, n)) / 2.0;
+      q = p * p + w;
+      z = std::sqrt(std::fabs(q));
+      H(n, n) += exshift;
+      H(n - 1, n - 1) += exshift;
+      x = H(n, n);
+      if (q >= 0.0) {
+        z = (p >= 0.0) ? p + z : p - z;
+        d[n - 1] = x + z;
+        d[n] = d[n - 1];
+        if (z != 0.0) d[n] = x - w / z;
+        e[n - 1] = 0.0;
+        e[n] = 0.0;
+        // the rotation that makes the block upper triangular
+        x = H(n, n - 1);
+        s = std::fabs(x) + std::fabs(z);
+        p = x / s;
+        q = z / s;
+        r = std::sqrt(p * p + q * q);
+        p /= r;
+        q /= r;
+        for (int j = n - 1; j < nn; ++j) {
+          z = H(n - 1, j);
+          H(n - 1, j) = q * z + p * H(n, j);
+          H(n, j) = q * H(n, j) - p * z;
+        }
+        for (int i = 0; i <= n; ++i) {
+          z = H(i, n - 1);
+          H(i, n - 1) = q * z + p * H(i, n);
+          H(i, n) = q * H(i, n) - p * z;
+        }
+        for (int i = 0; i < nn; ++i) {
+          z = V(i, n - 1);
+          V(i, n - 1) = q * z + p * V(i, n);
+          V(i, n) = q * V(i, n) - p * z;
+        }
+      } else {
+        d[n - 1] = x + p;
+        d[n] = x + p;
+        e[n - 1] = z;
+        e[n] = -z;
+      }
+      n -= 2;
+      iter = 0;
+    } else {
+      if (iter >= sweeps_allowed) return 1;
+      // shifts: the eigenvalues of the trailing 2 x 2 block, as their sum and product
+      x = H(n, n);
+      y = H(n - 1, n - 1);
+      w = H(n, n - 1) * H(n - 1, n);
+      if (iter > 0 && iter % 20 == 10) {            // stagnation: an exceptional shift from the sub-diagonal
+        exshift += x;
+        for (int i = 0; i <= n; ++i) H(i, i) -= x;
+        s = std::fabs(H(n, n - 1)) + std::fabs(H(n - 1, n - 2));
+        x = y = 0.75 * s;
+        w = -0.4375 * s * s;
+      }
+      if (iter > 0 && iter % 20 == 0) {             // ... and a second kind, from the block's own eigenvalue
+        s = (y - x) / 2.0;
+        s = s * s + w;
+        if (s > 0.0) {
+          s = std::sqrt(s);
+          if (y < x) s = -s;
+          s = x - w / ((y - x) / 2.0 + s);
+          for (int i = 0; i <= n; ++i) H(i, i) -= s;
+          exshift += s;
+          x = y = w = 0.964;
+        }
+      }
+      ++iter;
+      // two consecutive small sub-diagonal elements let the step start further down
+      int m = n - 2;
+      while (m >= l) {
+        z = H(m, m);
+        r = x - z;
+        s = y - z;
+        p = (r * s - w) / H(m + 1, m) + H(m, m + 1);
+        q = H(m + 1, m + 1) - z - r - s;
+        r = H(m + 2, m + 1);
+        s = std::fabs(p) + std::fabs(q) + std::fabs(r);
+        p /= s;
+        q /= s;
+        r /= s;
+        if (m == l) break;
+        if (std::fabs(H(m, m - 1)) * (std::fabs(q) + std::fabs(r)) <
+            eps * (std::fabs(p) * (std::fabs(H(m - 1, m - 1)) + std::fabs(z) + std::fabs(H(m + 1, m + 1))))) break;
+        --m;
+      }
+      for (int i = m + 2; i <= n; ++i) {
+        H(i, i - 2) = 0.0;
+        if (i > m + 2) H(i, i - 3) = 0.0;
+      }
+      // the double step on rows l..n, columns m..n: 3-element reflectors chase the bulge down
+      for (int k = m; k <= n - 1; ++k) {
+        const bool notlast = (k != n - 1);
+        if (k != m) {
+          p = H(k, k - 1);
+          q = H(k + 1, k - 1);
+          r = notlast ? H(k + 2, k - 1) : 0.0;
+          x = std::fabs(p) + std::fabs(q) + std::fabs(r);
+          if (x == 0.0) continue;
+          p /= x;
+          q /= x;
+          r /= x;
+        }
+        s = std::sqrt(p * p + q * q + r * r);
+        if (p < 0.0) s = -s;
+        if (s == 0.0) continue;
+        if (k != m) H(k, k - 1) = -s * x;
+        else if (l != m) H(k, k - 1) = -H(k, k - 1);
+        p += s;
+        x = p / s;
+        y = q / s;
+        z = r / s;
+        q /= p;
+        r /= p;
+        for (int j = k; j < nn; ++j) {
+          p = H(k, j) + q * H(k + 1, j);
+          if (notlast) {
+            p += r * H(k + 2, j);
+            H(k + 2, j) -= p * z;
+          }
+          H(k, j) -= p * x;
+          H(k + 1, j) -= p * y;
+        }
+        const int last = std::min(n, k + 3);
+        for (int i = 0; i <= last; ++i) {
+          p = x * H(i, k) + y * H(i, k + 1);
+          if (notlast) {
+            p += z * H(i, k + 2);
+            H(i, k + 2) -= p * r;
+          }
+          H(i, k) -= p;
+          H(i, k + 1) -= p * q;
+        }
+        for (int i = 0; i < nn; ++i) {
+          p = x * V(i, k) + y * V(i, k + 1);
+          if (notlast) {
+            p += z * V(i, k + 2);
+            V(i, k + 2) -= p * r;
+          }
+          V(i, k) -= p;
+          V(i, k + 1) -= p * q;
+        }
+      }
+    }
+  }
+  if (norm == 0.0) return 0;          // the zero matrix: v is the identity, every eigenvalue 0
+  // eigenvectors of the quasi-triangular matrix, column by column from the right, written over its upper part
+  for (n = nn - 1; n >= 0; --n) {
+    p = d[n];
+    q = e[n];
+    if (q == 0.0) {
+      int l = n;
+      H(n, n) = 1.0;
+      for (int i = n - 1; i >= 0; --i) {
+        w = H(i, i) - p;
+        r = 0.0;
+        for (int j = l; j <= n; ++j) r += H(i, j) * H(j, n);
+        if (e[i] < 0.0) {               // lower row of a 2 x 2 block: solved together with the row above
+          z = w;
+          s = r;
+        } else {
+          l = i;
+          if (e[i] == 0.0) {
+            H(i, n) = (w != 0.0) ? -r / w : -r / (eps * norm);
+          } else {
+            x = H(i, i + 1);
+            y = H(i + 1, i);
+            q = (d[i] - p) * (d[i] - p) + e[i] * e[i];
+            t = (x * s - z * r) / q;
+            H(i, n) = t;
+            H(i + 1, n) = (std::fabs(x) > std::fabs(z)) ? (-r - w * t) / x : (-s - y * t) / z;
+          }
+          t = std::fabs(H(i, n));
+          if (eps * t * t > 1.0)
+            for (int j = i; j <= n; ++j) H(j, n) /= t;
+        }
+      }
+    } else if (q < 0.0) {               // second member of a pair: columns n-1, n get the vector of d[n-1] + i e[n-1]
+      int l = n - 1;
+      if (std::fabs(H(n, n - 1)) > std::fabs(H(n - 1, n))) {
+        H(n - 1, n - 1) = q / H(n, n - 1);
+        H(n - 1, n) = -(H(n, n) - p) / H(n, n - 1);
+      } else {
+        cdivide(0.0, -H(n - 1, n), H(n - 1, n - 1) - p, q, H(n - 1, n - 1), H(n - 1, n));
+      }
+      H(n, n - 1) = 0.0;
+      H(n, n) = 1.0;
+      for (int i = n - 2; i >= 0; --i) {
+        double ra = 0.0, sa = 0.0;
+        for (int j = l; j <= n; ++j) {
+          ra += H(i, j) * H(j, n - 1);
+          sa += H(i, j) * H(j, n);
+        }
+        w = H(i, i) - p;
+        if (e[i] < 0.0) {
+          z = w;
+          r = ra;
+          s = sa;
+        } else {
+          l = i;
+          if (e[i] == 0.0) {
+            cdivide(-ra, -sa, w, q, H(i, n - 1), H(i, n));
+          } else {
+            x = H(i, i + 1);
+            y = H(i + 1, i);
+            double vr = (d[i] - p) * (d[i] - p) + e[i] * e[i] - q * q;
+            const double vi = (d[i] - p) * 2.0 * q;
+            if (vr == 0.0 && vi == 0.0)
+              vr = eps * norm * (std::fabs(w) + std::fabs(q) + std::fabs(x) + std::fabs(y) + std::fabs(z));
+            cdivide(x * r - z * ra + q * sa, x * s - z * sa - q * ra, vr, vi, H(i, n - 1), H(i, n));
+            if (std::fabs(x) > std::fabs(z) + std::fabs(q)) {
+              H(i + 1, n - 1) = (-ra - w * H(i, n - 1) + q * H(i, n)) / x;
+              H(i + 1, n) = (-sa - w * H(i, n) - q * H(i, n - 1)) / x;
+            } else {
+              cdivide(-r - y * H(i, n - 1), -s - y * H(i, n), z, q, H(i + 1, n - 1), H(i + 1, n));
+            }
+          }
+          t = std::max(std::fabs(H(i, n - 1)), std::fabs(H(i, n)));
+          if (eps * t * t > 1.0)
+            for (int j = i; j <= n; ++j) {
+              H(j, n - 1) /= t;
+              H(j, n) /= t;
+            }
+        }
+      }
+    }
+  }
+  // back to the original basis: v <- v * (upper triangle of h)
+  for (int j = nn - 1; j >= 0; --j)
+    for (int i = 0; i < nn; ++i) {
+      z = 0.0;
+      for (int k = 0; k <= j; ++k) z += V(i, k) * H(k, j);
+      V(i, j) = z;
+    }
+  return 0;
+}
+
+// eigenvalues and unnormalised eigenvectors of the row-major n x n matrix h (destroyed)
+int general_eig(int n, std::vector<double>& h, std::vector<double>& v, std::vector<double>& d, std::vector<double>& e)
+{
+  v.assign((size_t)n * n, 0.0);
+  d.assign(n, 0.0);
+  e.assign(n, 0.0);
+  hessenberg(n, h, v);
+  return hessenberg_qr_vectors(n, h, v, d, e);
+}
+
+// dgeev's scaling of one eigenvector (re, im: columns of a column-major array; im null for a real vector): Euclidean norm 1 and the
+// component of largest magnitude real -- and positive, so that the result does not depend on reflector signs
+void normalise_vector(int n, double* re, double* im)
+{
+  double nrm = 0.0;
+  for (int i = 0; i < n; ++i) nrm += re[i] * re[i] + (im ? im[i] * im[i] : 0.0);
+  nrm = std::sqrt(nrm);
+  if (!(nrm > 0.0)) return;
+  int imax = 0;
+  double big = -1.0;
+  for (int i = 0; i < n; ++i) {
+    const double m2 = re[i] * re[i] + (im ? im[i] * im[i] : 0.0);
+    if (m2 > big) {
+      big = m2;
+      imax = i;
+    }
+  }
+  if (!im) {
+    const double sc = (re[imax] < 0.0 ? -1.0 : 1.0) / nrm;
+    for (int i = 0; i < n; ++i) re[i] *= sc;
+    return;
+  }
+  // multiply by conj(c) / (|c| nrm), c the largest component
+  const double cm = std::sqrt(big), cr = re[imax] / cm / nrm, ci = -im[imax] / cm / nrm;
+  for (int i = 0; i < n; ++i) {
+    const double a = re[i], b = im[i];
+    re[i] = a * cr - b * ci;
+    im[i] = a * ci + b * cr;
+  }
+  im[imax] = 0.0;
+}
 }  // namespace
 
 extern "C" {
+
+// dgeev('v','v') of reference diaglib.f90:2499 (see include/diaglib_amd.h).  The left vectors come from a second run on the transpose;
+// its eigenvalues are matched to those of the first run, nearest first, conjugate pairs with pairs while the two runs count alike.
+int dla_geev(int n, double* a, int lda, double* wr, double* wi, double* vl, int ldvl, double* vr, int ldvr)
+{
+  DLA_T("dla_geev");
+  if (n <= 0) return 0;
+  if (lda < n || ldvl < n || ldvr < n || !a || !wr || !wi || !vl || !vr) return -1;
+  std::vector<double> h((size_t)n * n), ht((size_t)n * n), v, vt, d, e, dt, et;
+  for (int j = 0; j < n; ++j)
+    for (int i = 0; i < n; ++i) {
+      h[(size_t)i * n + j] = at(a, lda, i, j);
+      ht[(size_t)j * n + i] = at(a, lda, i, j);
+    }
+  if (general_eig(n, h, v, d, e) != 0) return DLA_ERR_LAPACK;
+  if (general_eig(n, ht, vt, dt, et) != 0) return DLA_ERR_LAPACK;
+  for (int j = 0; j < n; ++j) {
+    wr[j] = d[j];
+    wi[j] = e[j];
+    for (int i = 0; i < n; ++i) at(vr, ldvr, i, j) = v[(size_t)i * n + j];
+  }
+  // partner[j]: the position in the transposed run that serves position j (first members of pairs and real eigenvalues only)
+  int pairs = 0, pairs_t = 0;
+  for (int j = 0; j < n; ++j) {
+    pairs += (e[j] > 0.0);
+    pairs_t += (et[j] > 0.0);
+  }
+  const bool by_kind = (pairs == pairs_t);
+  std::vector<char> used(n, 0);
+  for (int j = 0; j < n; ++j) {
+    if (e[j] < 0.0) continue;
+    int best = -1;
+    double bd = 0.0;
+    for (int k = 0; k < n; ++k) {
+      if (used[k] || et[k] < 0.0) continue;
+      if (by_kind && ((e[j] > 0.0) != (et[k] > 0.0))) continue;
+      const double dist = std::hypot(d[j] - dt[k], e[j] - et[k]);
+      if (best < 0 || dist < bd) {
+        best = k;
+        bd = dist;
+      }
+    }
+    if (best < 0) return DLA_ERR_LAPACK;
+    used[best] = 1;
+    if (e[j] > 0.0 && et[best] > 0.0) {
+      // A^T w = lambda w  =>  u = conj(w) satisfies u^H A = lambda u^H
+      for (int i = 0; i < n; ++i) {
+        at(vl, ldvl, i, j) = vt[(size_t)i * n + best];
+        at(vl, ldvl, i, j + 1) = -vt[(size_t)i * n + best + 1];
+      }
+    } else if (e[j] > 0.0) {
+      // (the runs disagree on whether this nearly double eigenvalue is a pair: a real vector of the transpose serves both members)
+      for (int i = 0; i < n; ++i) {
+        at(vl, ldvl, i, j) = vt[(size_t)i * n + best];
+        at(vl, ldvl, i, j + 1) = 0.0;
+      }
+    } else {
+      for (int i = 0; i < n; ++i) at(vl, ldvl, i, j) = vt[(size_t)i * n + best];
+    }
+  }
+  for (int j = 0; j < n; ++j) {
+    if (wi[j] > 0.0 && j + 1 < n) {
+      normalise_vector(n, &at(vr, ldvr, 0, j), &at(vr, ldvr, 0, j + 1));
+      normalise_vector(n, &at(vl, ldvl, 0, j), &at(vl, ldvl, 0, j + 1));
+      ++j;
+    } else {
+      normalise_vector(n, &at(vr, ldvr, 0, j), nullptr);
+      normalise_vector(n, &at(vl, ldvl, 0, j), nullptr);
+    }
+  }
+  for (int j = 0; j < n; ++j)
+    for (int i = 0; i < n; ++i) at(a, lda, i, j) = h[(size_t)i * n + j];   // destroyed, like dgeev's
+  return 0;
+}
 
 int dla_syev(char uplo, int n, double* a, int lda, double* w)
 {

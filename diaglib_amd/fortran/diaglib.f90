@@ -18,7 +18,8 @@
 ! default they receive HOST arrays (the engine stages blocks through pinned memory); after
 ! `call diaglib_amd_config(callbacks_on_device=.true.)` they receive DEVICE addresses under the same signature.
 !
-! Not provided (SURVEY.md 2 row 5): nonsym_driver.
+! nonsym_driver (reference :2252-2943) runs what the reference runs -- its simultaneous two-sided mode is switched off in its
+! source -- as consecutive one-sided passes on an orthonormal basis; see the routine and INTEGRATION.md for the differences.
 !
 module diaglib
   use real_precision
@@ -27,7 +28,7 @@ module diaglib
   private
 !
   public :: lobpcg_driver, davidson_driver, gen_david_driver, ortho, b_ortho, ortho_cd, ortho_vs_x, b_ortho_vs_x
-  public :: caslr_eff_driver, caslr_driver
+  public :: caslr_eff_driver, caslr_driver, nonsym_driver
   public :: diaglib_amd_config, diaglib_amd_timings
 !
   real(dp), parameter :: zero = 0.0_dp, one = 1.0_dp, ten = 10.0_dp
@@ -365,6 +366,12 @@ module diaglib
       character(kind=c_char), value :: uplo
       integer(c_int), value :: n, lda, m
       real(c_double) :: a(*), w(*)
+      integer(c_int) :: info
+    end function
+    function dla_geev(n,a,lda,wr,wi,vl,ldvl,vr,ldvr) bind(C,name='dla_geev') result(info)
+      import :: c_int, c_double
+      integer(c_int), value :: n, lda, ldvl, ldvr
+      real(c_double) :: a(*), wr(*), wi(*), vl(*), vr(*)
       integer(c_int) :: info
     end function
     subroutine dla_set_solve_info(iters,cols,restarts) bind(C,name='dla_set_solve_info')
@@ -1154,6 +1161,335 @@ contains
     call davidson_core(verbose, n, n_targ, n_max, max_iter, tol, max_dav, shift, c_funloc(matvec), c_funloc(precnd), &
                        c_funloc(bvec), .true., eig, evec, ok)
   end subroutine gen_david_driver
+!
+! ---------------------------------------------------------------------------------------
+! Non-symmetric Davidson (reference diaglib.f90:2252-2943).
+!
+! What the reference runs: its simultaneous mode is switched off in the source (side = 's' sets `right` and `consecutive`,
+! :2398-2406), so every pass is a block Davidson on ONE orthonormal basis V with the non-symmetric reduced matrix V^T A V; the
+! left pass is the same iteration with matvec_l = A^T.  side = 'r' / 'l': one pass.  side = 'c': the right pass, its
+! orthonormalised vectors as the left guess (:2899-2900), the left pass, the eigenvalues of the two compared (:2887-2890), and
+! the closing biorthogonalisation L^T R = I (:2908-2911, :3395-3445) -- after which the columns span the two invariant subspaces
+! but are no longer individual eigenvectors.  side = 's' is taken as 'c'.
+!
+! Deliberate differences (INTEGRATION.md): the reduced matrix grows by its new rows and columns (the reference recomputes all of
+! it every iteration, :2491); the eigenpairs are sorted completely, real ones by ascending real part, those with |imag| > 1e-12
+! behind them (the intent of sort_eigenpairs, :2945-3017); root-following is done by intent (follow_roots below), not by the text
+! of :2539-2697, which indexes (2,n_max) arrays as (j,1) and reads overlap_idx_l(k,6); after 'c' ok means that BOTH passes
+! converged (the reference's ok is overwritten by its ortho_cd calls); the consistency check takes |eig_r - eig_l| of the
+! n_targ wanted roots.  eig keeps the shift, like the reference's (it only prints eig - shift).
+! ---------------------------------------------------------------------------------------
+  subroutine nonsym_driver(verbose,n,n_targ,n_max,max_iter,tol,max_dav,shift,matvec,matvec_l,precnd,eig,evec_r,evec_l,side,ok)
+    logical,          intent(in)            :: verbose
+    integer,          intent(in)            :: n, n_targ, n_max, max_iter, max_dav
+    real(dp),         intent(in)            :: tol, shift
+    character(len=1), intent(in)            :: side
+    real(dp),         intent(inout)         :: eig(n_max)
+    real(dp),         intent(inout), target :: evec_r(n,n_max), evec_l(n,n_max)
+    logical,          intent(inout)         :: ok
+    external                                :: matvec, matvec_l, precnd
+!
+    type(solve_env) :: e
+    type(c_ptr)     :: other                ! 'c': the left block on the device (e%ritz is the right one)
+    real(dp), allocatable :: eig_r(:)
+    logical  :: ok_r, ok_l
+    integer  :: sweeps, sweeps_l
+    real(dp) :: growth
+    integer(c_int) :: flag
+!
+    ok = .false.
+    select case (side)
+    case ('r')
+      call env_open(e, n, n_max, evec_r)
+      call nonsym_pass(verbose, .false., n, n_targ, n_max, max_iter, tol, max_dav, shift, c_funloc(matvec), c_funloc(precnd), &
+                       e, e%ritz, eig, ok, sweeps)
+      call env_close(e, evec_r, sweeps)
+    case ('l')
+      call env_open(e, n, n_max, evec_l)
+      call nonsym_pass(verbose, .true., n, n_targ, n_max, max_iter, tol, max_dav, shift, c_funloc(matvec_l), c_funloc(precnd), &
+                       e, e%ritz, eig, ok, sweeps)
+      call env_close(e, evec_l, sweeps)
+    case ('c','s')
+      call env_open(e, n, n_max, evec_r)
+      if (e%ritz_is_callers) then
+        other = c_loc(evec_l)
+      else
+        other = dev_panel(e%ctx, n, n_max, 'evec_l')
+      end if
+      call nonsym_pass(verbose, .false., n, n_targ, n_max, max_iter, tol, max_dav, shift, c_funloc(matvec), c_funloc(precnd), &
+                       e, e%ritz, eig, ok_r, sweeps)
+      allocate (eig_r(n_targ))
+      eig_r = eig(1:n_targ)
+!     the right vectors, orthonormalised, are the guess of the left pass (:2899-2900)
+      call chk(e%ctx, dla_ortho_cd(e%ctx, n, n_max, e%ritz, growth, flag), 'ortho_cd')
+      call chk(e%ctx, dla_copy(e%ctx, other, e%ritz, nbytes(n,n_max)), 'copy')
+      call nonsym_pass(verbose, .true., n, n_targ, n_max, max_iter, tol, max_dav, shift, c_funloc(matvec_l), c_funloc(precnd), &
+                       e, other, eig, ok_l, sweeps_l)
+      if (maxval(abs(eig_r - eig(1:n_targ))) .gt. tol) then
+        write(6,*) 'eigenvalues in the consecutive computation of right and left eigenpairs do not match.'
+        error stop 1
+      end if
+      ok = ok_r .and. ok_l
+      call biorthonormalise(e%ctx, n, n_max, other, e%ritz)
+      if (.not.e%ritz_is_callers) then
+        call chk(e%ctx, dla_download(e%ctx, c_loc(evec_l), other, nbytes(n,n_max)), 'download of evec_l')
+        call drop_panel(e%ctx, other)
+      end if
+      call env_close(e, evec_r, sweeps + sweeps_l)
+      deallocate (eig_r)
+    case default
+      write(6,*) 'choice for side is not correct. can be r,l,s,c.'
+      error stop 1
+    end select
+  end subroutine nonsym_driver
+!
+! One pass: block Davidson for the lowest real eigenvalues of a non-symmetric operator on an orthonormal basis.  `ritz` (device,
+! n x n_max) holds the guess on entry and the Ritz vectors of the last sweep on exit.  With `left` the operator is A^T: the
+! eigenvectors of the pass' reduced matrix V^T A^T V are the left eigenvectors of the reference's a_red = V^T A V (:2493).
+!
+  subroutine nonsym_pass(verbose,left,n,n_targ,n_max,max_iter,tol,max_dav,shift,op,prec,e,ritz,eig,ok,sweeps)
+    logical,         intent(in)    :: verbose, left
+    integer,         intent(in)    :: n, n_targ, n_max, max_iter, max_dav
+    real(dp),        intent(in)    :: tol, shift
+    type(c_funptr),  intent(in)    :: op, prec
+    type(solve_env), intent(inout) :: e
+    type(c_ptr),     intent(in)    :: ritz
+    real(dp),        intent(inout) :: eig(n_max)
+    logical,         intent(out)   :: ok
+    integer,         intent(out)   :: sweeps
+!
+    real(dp), parameter :: tol_im = 1.0e-12_dp           ! (:2377)
+    type(subspace)  :: s
+    type(stopwatch) :: w
+    type(c_ptr)     :: basis, abasis, resid
+    real(dp), allocatable :: h(:,:), hw(:,:), wr(:), wi(:), vl(:,:), vr(:,:), y(:,:), theta(:), prev(:,:), idle(:,:)
+    integer,  allocatable :: ord(:)
+    real(dp)        :: t_begin(2), t_end(2), growth
+    integer         :: it, col, first, j, r, nk, nk_prev
+    logical         :: fresh                              ! first sweep, or first after a restart: nothing to follow
+    integer(c_int)  :: info, flag
+!
+    call sub_setup(s, n_targ, n_max, max(min_dav,max_dav), tol)
+    basis  = dev_panel(e%ctx, n, s%ld, 'space')
+    abasis = dev_panel(e%ctx, n, s%ld, 'aspace')
+    resid  = dev_panel(e%ctx, n, n_max, 'r')
+    allocate (h(s%ld,s%ld), hw(s%ld,s%ld), wr(s%ld), wi(s%ld), vl(s%ld,s%ld), vr(s%ld,s%ld), y(s%ld,2*n_max), theta(2*n_max), &
+              prev(s%ld,2*n_max), ord(s%ld), idle(2,n_max))
+    h       = zero
+    idle    = zero
+    nk_prev = 0
+    fresh   = .true.
+    ok      = .false.
+    sweeps  = max_iter
+    call clock_now(t_begin)
+!
+    call chk(e%ctx, dla_check_guess(e%ctx, n, n_max, ritz), 'check_guess')
+    call chk(e%ctx, dla_copy(e%ctx, basis, ritz, nbytes(n,n_max)), 'copy')
+    if (verbose) write(6,'(t5,a,d10.2,a,l2,a,l2,a,/,t5,a,/,t7,a,a,/,t5,a)') 'Davidson-nonsym iterations (tol=', tol, &
+          ', right =', .not.left, ', left =', left, '):', repeat('-',96), '  iter  root              eigenvalue', &
+          '         rms(right)              rms(left)     max ok', repeat('-',96)
+!
+    do it = 1, max_iter
+      call sub_admit(s)
+      col = s%head
+      call lap_start(w)
+      call chk(e%ctx, dla_call_matvec(e%ctx, op, n, s%act, colp(basis,n,col), colp(abasis,n,col)), 'matvec')
+      call lap_charge(w, w%mv)
+      e%op_cols = e%op_cols + s%act
+!
+!     the reduced matrix V^T (op V) grows by its new columns [X | U]^T (op U) and its new rows U^T (op X): the reference
+!     recomputes all of it (:2491), 16 n ldu bytes more per iteration
+!
+      call chk(e%ctx, dla_gram(e%ctx, n, s%cols, basis, s%act, colp(abasis,n,col), h(1,col), s%ld), 'projection (columns)')
+      if (col.gt.1) call chk(e%ctx, dla_gram(e%ctx, n, s%act, colp(basis,n,col), col-1, abasis, h(col,1), s%ld), &
+                             'projection (rows)')
+!
+!     all eigenpairs of the reduced matrix (:2499), sorted: real ones by ascending real part, then the complex ones
+!
+      hw(1:s%cols,1:s%cols) = h(1:s%cols,1:s%cols)
+      call lap_start(w)
+      info = dla_geev(int(s%cols,c_int), hw, int(s%ld,c_int), wr, wi, vl, int(s%ld,c_int), vr, int(s%ld,c_int))
+      call lap_charge(w, w%diag)
+      if (info.ne.0) then
+        write(6,*) 'diagonalization of reduced space failed.'
+        error stop 1
+      end if
+      call sort_pairs(s%cols, wr, wi, ord)
+      nk = min(2*n_max, s%cols)
+      y  = zero
+      do j = 1, nk
+        theta(j)      = wr(ord(j))
+        y(1:s%cols,j) = vr(1:s%cols,ord(j))
+      end do
+      if (verbose .and. any(abs(wi(ord(1:n_max))).gt.tol_im)) then
+        write(6,*)
+        write(6,*) 'complex contribution in sought eigenvalues'
+        write(6,*)
+      end if
+!
+!     keep every root at the place it had in the last sweep (:2539-2697)
+!
+      if (.not.fresh) call follow_roots()
+      fresh   = .false.
+      prev    = y
+      nk_prev = nk
+      eig     = theta(1:n_max)
+!
+!     Ritz vectors, residuals of the open wanted roots and their norms: one sweep (:2711-2736)
+!
+      call sub_refresh_mask(s)
+      call chk(e%ctx, dla_ritz_residual(e%ctx, n, s%cols, n_max, basis, abasis, y, s%ld, eig, n_targ, s%mask, &
+                                        ritz, resid, c_null_ptr, s%rnorm), 'ritz/residual')
+      call sub_lock(s, it, n_targ)                          ! (:2741-2752)
+      if (verbose) then
+        do r = 1, n_targ
+          if (left) then
+            write(6,'(t9,i4,2x,i4,f24.12,2d12.4,2d12.4,l3)') it, r, eig(r) - shift, s%rnorm(:,r), idle(:,r), s%locked(r)
+          else
+            write(6,'(t9,i4,2x,i4,f24.12,2d12.4,2d12.4,l3)') it, r, eig(r) - shift, idle(:,r), s%rnorm(:,r), s%locked(r)
+          end if
+        end do
+        write(6,*)
+      end if
+      if (sub_finished(s)) then
+        ok = .true.
+        sweeps = it
+        exit
+      end if
+!
+      if (sub_has_room(s)) then
+!
+!       expand with the preconditioned open residuals, orthogonalised against the basis (:2779-2807)
+!
+        call sub_open_block(s, first)
+        call chk(e%ctx, dla_call_precnd(e%ctx, prec, n, s%act, -eig(first), colp(resid,n,first), colp(basis,n,s%head)), 'precnd')
+        call lap_start(w)
+        call chk(e%ctx, dla_ortho_vs_x(e%ctx, n, s%cols, s%act, basis, colp(basis,n,s%head)), 'ortho_vs_x')
+        call lap_charge(w, w%ortho)
+      else
+!
+!       basis full: restart from the orthonormalised Ritz vectors (:2815-2860); every column meets the operator again
+!
+        if (verbose) write(6,'(t7,a)') 'Restarting davidson.'
+        e%restarts = e%restarts + 1
+        call chk(e%ctx, dla_copy(e%ctx, basis, ritz, nbytes(n,n_max)), 'copy')
+        call lap_start(w)
+        call chk(e%ctx, dla_ortho_cd(e%ctx, n, n_max, basis, growth, flag), 'ortho_cd')
+        call lap_charge(w, w%ortho)
+        h = zero
+        call sub_collapse(s)
+        s%frozen = sub_leading(s)
+        fresh = .true.
+      end if
+      if (verbose) call print_block_report(s)
+    end do
+!
+    call clock_now(t_end)
+    w%total = t_end - t_begin
+    if (verbose) call print_timings('timings for davidson (cpu/wall): ', w)
+    call drop_panel(e%ctx, basis)
+    call drop_panel(e%ctx, abasis)
+    call drop_panel(e%ctx, resid)
+    deallocate (h, hw, wr, wi, vl, vr, y, theta, prev, ord, idle)
+!
+  contains
+!
+!   Root-following, by intent: each of the first n_max new reduced eigenvectors is given to the old one it overlaps most (the old
+!   vectors have zeros in the rows the basis has gained since).  When those choices are a permutation of 1 .. n_max, new pair j
+!   moves to the place of its old partner; otherwise the sorted order stands.
+!
+    subroutine follow_roots()
+      integer  :: to(n_max), jj, kk, best
+      logical  :: taken(n_max)
+      real(dp) :: ov, top, ysave(s%ld,n_max), tsave(n_max)
+      taken = .false.
+      do jj = 1, n_max
+        best = 0
+        top  = -one
+        do kk = 1, nk_prev
+          ov = abs(dot_product(prev(1:s%cols,kk), y(1:s%cols,jj)))
+          if (ov.gt.top) then
+            top  = ov
+            best = kk
+          end if
+        end do
+        if (best.lt.1 .or. best.gt.n_max) return
+        if (taken(best)) return
+        taken(best) = .true.
+        to(jj) = best
+      end do
+      ysave = y(:,1:n_max)
+      tsave = theta(1:n_max)
+      do jj = 1, n_max
+        y(:,to(jj))  = ysave(:,jj)
+        theta(to(jj)) = tsave(jj)
+      end do
+    end subroutine follow_roots
+  end subroutine nonsym_pass
+!
+! order of the eigenvalues wr + i wi: the real ones (|wi| <= 1e-12) by ascending wr, behind them the others, again by ascending wr
+! (stable: equal keys keep the solver's order, so a conjugate pair stays together, positive imaginary part first)
+!
+  subroutine sort_pairs(m, wr, wi, ord)
+    integer,  intent(in)  :: m
+    real(dp), intent(in)  :: wr(m), wi(m)
+    integer,  intent(out) :: ord(m)
+    integer :: i, j, k
+    do i = 1, m
+      k = i
+      j = i - 1
+      do while (j.ge.1)
+        if (.not.before(i, ord(j))) exit
+        ord(j+1) = ord(j)
+        j = j - 1
+      end do
+      ord(j+1) = k
+    end do
+  contains
+    logical function before(a, b)
+      integer, intent(in) :: a, b
+      logical :: ca, cb
+      ca = abs(wi(a)).gt.1.0e-12_dp
+      cb = abs(wi(b)).gt.1.0e-12_dp
+      if (ca.neqv.cb) then
+        before = cb
+      else
+        before = wr(a).lt.wr(b)
+      end if
+    end function before
+  end subroutine sort_pairs
+!
+! L <- L U S^-1/2, R <- R V S^-1/2 for L^T R = U S V^T (reference svd_biortho, :3395-3445): L^T R = I afterwards.  The scaling is
+! folded into the coefficients; a panel is rotated in place where dla_panel_gemm allows it and through a temporary otherwise.
+!
+  subroutine biorthonormalise(ctx, n, m, lvec, rvec)
+    type(c_ptr), intent(in) :: ctx, lvec, rvec
+    integer,     intent(in) :: n, m
+    real(dp), allocatable :: over(:,:), u(:,:), sv(:), v(:,:)
+    type(c_ptr) :: tmp
+    integer     :: i
+    logical     :: in_place
+    allocate (over(m,m), u(m,m), sv(m), v(m,m))
+    call chk(ctx, dla_gram(ctx, n, m, lvec, m, rvec, over, m), 'overlap')
+    call small_svd(m, over, u, sv, v)
+    do i = 1, m
+      u(:,i) = u(:,i)/sqrt(sv(i))
+      v(:,i) = v(:,i)/sqrt(sv(i))
+    end do
+    in_place = m.le.48 .and. 128*m*((m+15)/16).le.65536
+    if (in_place) then
+      call chk(ctx, dla_panel_gemm(ctx, n, m, lvec, m, u, m, lvec), 'rotation of evec_l')
+      call chk(ctx, dla_panel_gemm(ctx, n, m, rvec, m, v, m, rvec), 'rotation of evec_r')
+    else
+      tmp = dev_panel(ctx, n, m, 'rotation')
+      call chk(ctx, dla_panel_gemm(ctx, n, m, lvec, m, u, m, tmp), 'rotation of evec_l')
+      call chk(ctx, dla_copy(ctx, lvec, tmp, nbytes(n,m)), 'copy')
+      call chk(ctx, dla_panel_gemm(ctx, n, m, rvec, m, v, m, tmp), 'rotation of evec_r')
+      call chk(ctx, dla_copy(ctx, rvec, tmp, nbytes(n,m)), 'copy')
+      call drop_panel(ctx, tmp)
+    end if
+    deallocate (over, u, sv, v)
+  end subroutine biorthonormalise
 !
 ! ---------------------------------------------------------------------------------------
 ! LOBPCG (reference diaglib.f90:171-556), standard and generalised (gen_eig) problem.

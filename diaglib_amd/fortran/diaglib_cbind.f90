@@ -6,7 +6,7 @@
 !
 module diaglib_cbind
   use iso_c_binding
-  use diaglib, only : davidson_driver, lobpcg_driver, gen_david_driver, caslr_eff_driver, caslr_driver
+  use diaglib, only : davidson_driver, lobpcg_driver, gen_david_driver, caslr_eff_driver, caslr_driver, nonsym_driver
   implicit none
 !
   abstract interface
@@ -123,5 +123,25 @@ contains
     call caslr_driver(verbose.ne.0,n,2*n,n_targ,n_max,max_iter,tol,max_dav,f1,f2,f3,f4,f5,eig,evec,lok)
     ok = merge(1_c_int, 0_c_int, lok)
   end subroutine dla_caslr_driver
+!
+! reference diaglib.f90:2252-2253; side travels as the character's code
+!
+  subroutine dla_nonsym_driver(verbose,n,n_targ,n_max,max_iter,tol,max_dav,shift, &
+                               matvec,matvec_l,precnd,eig,evec_r,evec_l,side,ok) bind(C,name='dla_nonsym_driver')
+    integer(c_int), value :: verbose, n, n_targ, n_max, max_iter, max_dav, side
+    real(c_double), value :: tol, shift
+    type(c_funptr), value :: matvec, matvec_l, precnd
+    real(c_double)        :: eig(n_max), evec_r(n,n_max), evec_l(n,n_max)
+    integer(c_int)        :: ok
+    procedure(mv_iface), pointer :: mv, mvl
+    procedure(pc_iface), pointer :: pc
+    logical :: lok
+    call c_f_procpointer(matvec, mv)
+    call c_f_procpointer(matvec_l, mvl)
+    call c_f_procpointer(precnd, pc)
+    lok = .false.
+    call nonsym_driver(verbose.ne.0,n,n_targ,n_max,max_iter,tol,max_dav,shift,mv,mvl,pc,eig,evec_r,evec_l,achar(side),lok)
+    ok = merge(1_c_int, 0_c_int, lok)
+  end subroutine dla_nonsym_driver
 !
 end module diaglib_cbind

@@ -90,7 +90,7 @@ enum {
                                       takes another route than planned the operator is called a SECOND time on the finished
                                       block and its first output is dropped -- the reference calls matvec exactly once per
                                       block (diaglib.f90:1685, 394-397), so:
-                                      1 (default): only for the library's own device operators (dla_synth_*, dla_spmm_matvec, dla_spmm_bvec, dla_spmm_apbmul .. _smdmul, dla_dense_matvec, dla_dense_bvec, dla_dense_apbmul .. _smdmul),
+                                      1 (default): only for the library's own device operators (dla_synth_*, dla_spmm_matvec, dla_spmm_bvec, dla_spmm_apbmul .. _smdmul, dla_dense_matvec, dla_dense_matvec_t, dla_dense_bvec, dla_dense_apbmul .. _smdmul),
                                          which are pure functions of their input; a caller's callback is called once, in order;
                                       2: also for the caller's device-mode callbacks (ordering contract 0 or 2) -- the caller
                                          states that the operator keeps no state between calls;
@@ -410,6 +410,14 @@ int    dla_syev_lowest(char uplo, int n, double* a, int lda, double* w, int m); 
 int    dla_potrf_lower(int m, double* a, int lda);                  /* dpotrf('l'): :3261             */
 int    dla_trtri_lower(int m, double* a, int lda);                  /* dtrtri('l','n'): :3310         */
 double dla_norm_est(int m, const double* a, int lda);               /* norm_est: :3447-3479           */
+/* dgeev('v','v') of the non-symmetric driver (:2499): all eigenvalues wr + i wi and the right (vr) and left (vl, u^H A = lambda u^H)
+ * eigenvectors of the general n x n matrix a, which is destroyed.  dgeev's conventions: conjugate pairs are consecutive, the one
+ * with positive imaginary part first; column j is the vector of a real eigenvalue, columns j and j+1 are the real and imaginary
+ * parts of the vector of the first member of a pair (the second member's is its conjugate); every vector has Euclidean norm 1
+ * and its component of largest magnitude is real (and, here, positive).  Hessenberg reduction, shifted double-step QR, vectors
+ * by back-substitution; no balancing; the left vectors come from a second run on the transpose, its eigenvalues matched to the
+ * first run's.  Returns DLA_ERR_LAPACK when an eigenvalue has not deflated after 30 n sweeps, -1 for a bad argument. */
+int    dla_geev(int n, double* a, int lda, double* wr, double* wi, double* vl, int ldvl, double* vr, int ldvr);
 
 /* ---------------------------------------------------------------- built-in device operator (bench / tests)
  * A = diag(i+1) + sigma W W^T, W(i,j) = (2 u01(1,i,j)-1)/sqrt(i), i = 1-based global row;
@@ -452,6 +460,13 @@ void dla_caslr_eff_driver(int verbose, int n, int n_targ, int n_max, int max_ite
 void dla_caslr_driver(int verbose, int n, int n_targ, int n_max, int max_iter, double tol, int max_dav,
                       dla_matvec_fn apbmul, dla_matvec_fn ambmul, dla_matvec_fn spdmul, dla_matvec_fn smdmul,
                       dla_lrprec_fn lrprec, double* eig, double* evec, int* ok);
+/* non-symmetric Davidson: reference diaglib.f90:2252-2943 (nonsym_driver).  matvec applies A, matvec_l its transpose; side is the
+ * character code of 'r' (right eigenvectors), 'l' (left), 'c' (right, then left from the right ones; 's' is taken as 'c'); eig is
+ * returned with the shift in it; after 'c' the columns of evec_l and evec_r are biorthonormal bases of the two invariant subspaces
+ * (L^T R = I), not individual eigenvectors.  The solve report counts both passes. */
+void dla_nonsym_driver(int verbose, int n, int n_targ, int n_max, int max_iter, double tol, int max_dav, double shift,
+                       dla_matvec_fn matvec, dla_matvec_fn matvec_l, dla_precnd_fn precnd,
+                       double* eig, double* evec_r, double* evec_l, int side, int* ok);
 /* iteration report of the last driver call (iterations, matvec columns, restarts) */
 void dla_last_solve_info(int* iters, int* matvec_cols, int* restarts);
 void dla_set_solve_info(int iters, int matvec_cols, int restarts);   /* used by the Fortran drivers */
@@ -791,6 +806,21 @@ int  dla_dense_info     (dla_ctx* ctx, int which, struct dla_dense_info* out);
 int  dla_dense_drop     (dla_ctx* ctx, int which);                                        /* no-op where nothing is stored */
 void dla_dense_matvec(const int* n, const int* m, const double* x_dev, double* ax_dev);           /* ax = A x */
 void dla_dense_bvec  (const int* n, const int* m, const double* x_dev, double* bx_dev);           /* bx = B x */
+/* y = A^T x from the same stored copy of the operator (which = 0): the matvec_l of nonsym_driver, so that a device-mode caller does
+ * not store the matrix twice.  Everything dla_dense_matvec says about itself holds with A^T for A: the callback shape, the context
+ * it acts on, dla_stream, up to 48 columns per pass with the matrix read once, any n >= 1 and m >= 1, x unchanged and not
+ * overlapping y, nothing written outside the n x m result, no atomics, one writer per element, bit-identical repeats, a pure
+ * function of its input (DLA_OPT_RUN_AHEAD = 1 covers it).  It reads the existing copy: device_bytes, the set-up entries and what
+ * dla_dense_info answers are unchanged by it.  The contraction runs down the rows of the matrix, which are an MFMA output index in
+ * the stored order, so a wavefront turns every 16 x 16 block in LDS before it multiplies (dense_t_mfma_kernel<G>).  A wavefront owns
+ * 64 output indices and one chunk of whole row tiles (boundaries are multiples of 16) and sums it in ascending row order by one MFMA
+ * chain; dense_t_plan in diaglib_amd/csrc/hip_plans.h states how many chunks a pass has.  With more than one, the partials go to
+ * the slot's workspace (row_chunks x m x n doubles, grown on demand, not counted in device_bytes) and are added in ascending chunk
+ * order, ((p_0 + p_1) + p_2) + ..., by one thread per element (dense_combine_kernel).
+ * Accuracy: every element stays within (n + 2) eps (|A|^T |x|)_i of the exact product; exact on small-integer data.
+ * Refusals go through the status of dla_call_matvec with a message naming dla_dense_matvec_t and the cause (no dense operator, or
+ * another n); a refused call writes nothing.  Statistics: as dla_dense_matvec, under dense_t_mfma_kernel<G>. */
+void dla_dense_matvec_t(const int* n, const int* m, const double* x_dev, double* y_dev);         /* y = A^T x */
 void dla_dense_precnd(const int* n, const int* m, const double* fac, const double* x_dev, double* px_dev);         /* x / (a_ii + fac), guard 1e-5: mprec */
 void dla_dense_precnd_pencil(const int* n, const int* m, const double* fac, const double* x_dev, double* px_dev);  /* x / (a_ii + fac b_ii), same guard */
 

@@ -19,10 +19,17 @@ users' sizes, beside torch.matmul and the triad rate of the same process.
    call, in ms and in GB/s of its 16 n^2 + 16 n_pad^2 bytes (two sources read, two copies written), beside the triad rate of the
    process.  Recorded figures, no thresholds.
 
+4. With --transpose, the transposed product instead (record: profiles/dense_operator_t.txt): dla_dense_matvec_t beside
+   dla_dense_matvec on the SAME stored matrix at n = 2048, 8192 and 32768, m = 8, 13 and 37, alternating call by call as in 1. --
+   medians, spreads, TB/s of the booked bytes and the ratio transposed / forward -- and one nonsym_driver solve (side c, 4 roots,
+   n_max 8, tol 1e-9, max_dav 10) of the matrix of examples/fortran_nonsym_caller at n = 2000 in device mode (dla_dense_matvec,
+   dla_dense_matvec_t, dla_dense_precnd) beside host callbacks (numpy products with a and its transposed copy).
+
 Every leg is a process of its own under `timeout`; the first leg that fails ends the run.
 
     python tools/dense_operator_bench.py [rounds] [record]          (defaults 10, profiles/dense_operator.txt)
     python tools/dense_operator_bench.py --lr [rounds] [record]     (defaults 10, profiles/dense_lr_operator.txt)
+    python tools/dense_operator_bench.py --transpose [rounds] [record]   (defaults 10, profiles/dense_operator_t.txt)
 """
 import os
 import subprocess
@@ -37,6 +44,8 @@ import numpy as np  # noqa: E402
 CALLS_PER_ROUND, WIDTHS = 5, (1, 8, 13, 37)
 LEGS = [("product 2048", 300), ("product 8192", 300), ("product 32768", 420), ("solve 2000", 420)]
 LR_LEGS = [("lrsolve 2000", 420), ("lrpair 8192", 300)]
+T_LEGS = [("tproduct 2048", 300), ("tproduct 8192", 300), ("tproduct 32768", 420), ("nsolve 2000", 420)]
+T_WIDTHS = (8, 13, 37)
 
 
 def leg_product(n, rounds):
@@ -89,6 +98,99 @@ def leg_product(n, rounds):
               f"{med['dense'] / med['torch']:5.2f}   max |difference| {diff:.2e}", flush=True)
         x.free(); y.free()
     print(f"  triad after the products {ctx.stream_triad(max(1 << 24, n * n // 4)):.0f} GB/s")
+    ctx.dense_drop()
+
+
+def leg_tproduct(n, rounds):
+    import torch
+    from diaglib_amd import capi
+    ctx = capi.Context()
+    ctx.set_option(capi.OPT_CALLBACKS_ON_DEVICE, 1)
+    stream = torch.cuda.ExternalStream(ctx.lib.dla_stream(ctx.h))
+    gen = torch.Generator(device="cuda").manual_seed(n)
+    a = torch.rand((n, n), dtype=torch.float64, device="cuda", generator=gen).T      # column-major: a(i, k) at i + k n
+    ctx.dense_setup(a)
+    triad = ctx.stream_triad(max(1 << 24, n * n // 4))
+    fns = {"forward": capi.fn_address("dla_dense_matvec"), "transposed": capi.fn_address("dla_dense_matvec_t")}
+    print(f"n = {n}: stored copy {ctx.dense_info()['device_bytes'] / 1e6:.0f} MB, triad {triad:.0f} GB/s")
+    for m in T_WIDTHS:
+        x, y = ctx.panel(n, m), ctx.panel(n, m)
+        ctx.random_fill(x)
+        xt = ctx._dev_tensor(x.ptr, n, m)
+
+        def call(which):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            ctx._chk(ctx.lib.dla_call_matvec(ctx.h, fns[which], n, m, x.ptr, y.ptr))
+            e1.record(stream)
+            return e0, e1
+
+        for which in ("forward", "transposed") * 3:
+            call(which)
+        ctx.sync()
+        with torch.cuda.stream(stream):
+            want = torch.matmul(a.T, xt)
+        stream.synchronize()
+        diff = float((ctx._dev_tensor(y.ptr, n, m) - want).abs().max())      # (y holds the last call's result: the transposed one)
+        ms = {"forward": [], "transposed": []}
+        for _ in range(rounds):
+            pairs = [(which, call(which)) for _ in range(CALLS_PER_ROUND) for which in ("forward", "transposed")]
+            ctx.sync()
+            for which in ms:
+                ms[which].append([e0.elapsed_time(e1) for k, (e0, e1) in pairs if k == which])
+        med, spread = {}, {}
+        for which in ms:
+            t = np.array(ms[which])
+            per_round = np.median(t, axis=1)
+            med[which], spread[which] = float(np.median(t)), float(per_round.max() - per_round.min())
+        rate = {w: (8.0 * n * n + 16.0 * n * m) / (med[w] * 1e-3) / 1e12 for w in med}
+        print(f"  m = {m:2d}  forward {med['forward']:8.4f} ms (spread {spread['forward']:.4f}) {rate['forward']:5.2f} TB/s   transposed "
+              f"{med['transposed']:8.4f} ms (spread {spread['transposed']:.4f}) {rate['transposed']:5.2f} TB/s   transposed / forward = "
+              f"{med['transposed'] / med['forward']:5.2f}   max |A^T x - torch| {diff:.2e}", flush=True)
+        x.free(); y.free()
+    print(f"  triad after the products {ctx.stream_triad(max(1 << 24, n * n // 4)):.0f} GB/s")
+    ctx.dense_drop()
+
+
+def leg_nsolve(n):
+    from diaglib_amd import capi
+    ctx = capi.Context()
+    t, m, tol, max_dav = 4, 8, 1e-9, 10
+    # the matrix of examples/fortran_nonsym_caller: exp(-T) A0 exp(T), T = alpha u v^T of Frobenius norm 0.01
+    idx = np.arange(1, n + 1.0)
+    a0 = 1.0 / (idx[:, None] + idx[None, :])
+    np.fill_diagonal(a0, idx + 1.0)
+    u, v = np.sin(1.3 * idx), np.cos(0.7 * idx)
+    alpha = 0.01 / (np.linalg.norm(u) * np.linalg.norm(v))
+    s = alpha * (v @ u)
+    a = (np.eye(n) - alpha * np.expm1(-s) / -s * np.outer(u, v)) @ a0 @ (np.eye(n) + alpha * np.expm1(s) / s * np.outer(u, v))
+    a, at, diag = np.asfortranarray(a), np.asfortranarray(a.T), np.diag(a).copy()
+
+    def mprec(fac, x):
+        d = diag + fac
+        safe = np.abs(d) > 1.0e-5
+        return np.where(safe[:, None], x / np.where(safe, d, 1.0)[:, None], x)
+
+    g = np.zeros((n, m), order="F")
+    g[np.arange(m), np.arange(m)] = 1.0
+    ctx.dense_setup(a)
+    out = {}
+    for mode, device, fns in (("host callbacks (numpy, a and its transposed copy)", 0, (lambda x: a @ x, lambda x: at @ x, mprec)),
+                              ("device callbacks (dla_dense_matvec, dla_dense_matvec_t)", 1,
+                               tuple(capi.fn_address(f) for f in ("dla_dense_matvec", "dla_dense_matvec_t", "dla_dense_precnd")))):
+        ctx.set_option(capi.OPT_CALLBACKS_ON_DEVICE, device)
+        times = []
+        for _ in range(5):
+            ctx.sync()
+            t0 = time.perf_counter()
+            eig, _, _, ok, info = ctx.nonsym_driver(n, t, m, 200, tol, max_dav, 0.0, *fns, g, g, "c")
+            times.append((time.perf_counter() - t0) * 1e3)
+        out[mode] = eig[:t].copy()
+        print(f"n = {n} nonsym_driver side c, {mode}: median {np.median(times[1:]):8.2f} ms per solve (min {min(times[1:]):.2f}), {info['iters']} iterations, "
+              f"{info['matvec_cols']} matvec columns, ok = {ok}", flush=True)
+    e0, e1 = out.values()
+    print(f"  largest relative eigenvalue difference between the two modes: {float(np.abs(e0 / e1 - 1.0).max()):.2e}")
+    ctx.set_option(capi.OPT_CALLBACKS_ON_DEVICE, 0)
     ctx.dense_drop()
 
 
@@ -180,18 +282,21 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--leg":
         kind, n, rounds = sys.argv[2], int(sys.argv[3]), int(sys.argv[4])
         {"product": lambda: leg_product(n, rounds), "solve": lambda: leg_solve(n), "lrsolve": lambda: leg_lr_solve(n),
-         "lrpair": lambda: leg_lr_pair(n, rounds)}[kind]()
+         "lrpair": lambda: leg_lr_pair(n, rounds), "tproduct": lambda: leg_tproduct(n, rounds), "nsolve": lambda: leg_nsolve(n)}[kind]()
         return 0
-    args = [a for a in sys.argv[1:] if a != "--lr"]
-    lr = "--lr" in sys.argv[1:]
+    args = [a for a in sys.argv[1:] if a not in ("--lr", "--transpose")]
+    lr, tr = "--lr" in sys.argv[1:], "--transpose" in sys.argv[1:]
     rounds = int(args[0]) if args else 10
-    record = args[1] if len(args) > 1 else os.path.join(ROOT, "profiles", "dense_lr_operator.txt" if lr else "dense_operator.txt")
-    if lr:
+    record = args[1] if len(args) > 1 else os.path.join(ROOT, "profiles", "dense_operator_t.txt" if tr else "dense_lr_operator.txt" if lr else "dense_operator.txt")
+    if tr:
+        text = [f"tools/dense_operator_bench.py --transpose {rounds}: dla_dense_matvec_t beside dla_dense_matvec on the same stored matrix, "
+                f"{rounds * CALLS_PER_ROUND} timed calls each per shape; nonsym_driver in device mode beside host callbacks (4 timed solves each)"]
+    elif lr:
         text = [f"tools/dense_operator_bench.py --lr {rounds}: the linear-response drivers on dense parts in device mode beside host callbacks (4 timed solves "
                 f"each), and the pair set-up ({rounds} timed calls) beside the triad rate"]
     else:
         text = [f"tools/dense_operator_bench.py {rounds}: dla_dense_matvec beside torch.matmul and the triad rate; {rounds * CALLS_PER_ROUND} timed calls each per shape"]
-    for leg, limit in (LR_LEGS if lr else LEGS):
+    for leg, limit in (T_LEGS if tr else LR_LEGS if lr else LEGS):
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg"] + leg.split() + [str(rounds)]
         p = subprocess.Popen(cmd, stdout=subprocess.PIPE, text=True)
         for line in p.stdout:                             # (as it comes: a long leg is not silent)

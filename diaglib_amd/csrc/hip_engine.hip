@@ -4355,7 +4355,6 @@ template <typename F, size_t... I>
 bool first_instance(std::index_sequence<I...>, F&& f) { return (f(std::integral_constant<size_t, I>{}) || ...); }
 template <size_t N, typename F>
 bool first_instance(F&& f) { return first_instance(std::make_index_sequence<N>{}, f); }
-
 struct HipEngine : dla::Engine {
   int device = 0;
   int ncu = 256;
@@ -5794,23 +5793,21 @@ struct HipEngine : dla::Engine {
   template <int TLW, int KT, int R>
   int launch_gram_lds(const GramArgs& a, dim3 grid, const GramPlan& p)
   {
-#define GLK(SELF_, Q)                                                                                          \
-    do {                                                                                                      \
-      auto kfn = gram_lds_kernel<TLW, KT, 1, R, SELF_, Q>;                                                    \
-      const size_t lds = gram_lds_bytes(TLW, KT, R, SELF_, false);                                            \
-      if (!raise_lds((const void*)kfn, lds)) return DLA_ERR_RUNTIME;                                          \
-      DLA_LAUNCH(kfn, grid, dim3(256), lds, st, a);                                                   \
-      return DLA_OK;                                                                                          \
-    } while (0)
-    if constexpr (TLW == KT) {
-      if (p.self) {
-        if constexpr (KT >= 2) { if (p.qt == 1) GLK(1, 1); if (p.qt == 2) GLK(1, 2); }
-        GLK(1, 0);
+    int r_ = DLA_OK;
+    const bool hit = first_instance<std::size(GRAM_LDS_FORMS)>([&](auto i) {
+      constexpr GramLdsForm f = GRAM_LDS_FORMS[decltype(i)::value];
+      if constexpr (!gram_lds_form(TLW, KT, f)) return false;
+      else {
+        if ((p.self ? 1 : 0) != f.self || p.qt != f.qt) return false;
+        auto kfn = gram_lds_kernel<TLW, KT, 1, R, f.self, f.qt>;
+        const size_t lds = gram_lds_bytes(TLW, KT, R, f.self, false);
+        if (!raise_lds((const void*)kfn, lds)) r_ = DLA_ERR_RUNTIME;
+        else DLA_LAUNCH(kfn, grid, dim3(256), lds, st, a);
+        return true;
       }
-    }
-    if constexpr (KT >= 2) { if (p.qt == 1) GLK(0, 1); if (p.qt == 2) GLK(0, 2); }
-    GLK(0, 0);
-#undef GLK
+    });
+    if (!hit) { err = "gram: no kernel instance"; return DLA_ERR_RUNTIME; }
+    return r_;
   }
   // single-pass lower triangle (gram_lds_kernel LOW): T x T tiles, 16-row wave tiles
   template <int T>
@@ -6040,55 +6037,26 @@ struct HipEngine : dla::Engine {
     return stage_commit(slot, sizeof(double) * cnt, d_cpk);
   }
 
-  // (The gemm_kernel ladders keep their macros and have no instance list in hip_plans.h: their instances are a product of independent
-  //  flags -- argument type x KT x VEC x MODE x fuse x depth x quarter tiles x row groups -- and a list of rows would be longer.)
-  template <int KT, typename ARGS>
-  int launch_gemm_gram(const ARGS& a, int blocks, size_t lds, bool vec2, int mode, int qt, int rtp)
+  // The one launch of gemm_kernel: the row of GEMM_INSTANCES (hip_plans.h) whose template arguments equal the plan's fields, and nothing
+  // else selects an instance.  The rows are what a predicate admits of the product argument type x KT x VEC x MODE x fuse x depth x
+  // quarter tiles x row groups, and exactly they are instantiated; a plan that names none launches nothing.  ARGS is the plan's `inl`.
+  template <typename ARGS>
+  int launch_gemm(const GemmPlan& p, const ARGS& a)
   {
-#define GGQRP(V, M, Q, R, P)                                                                                  \
-    do {                                                                                                      \
-      auto kfn = gemm_kernel<KT, V, M, ARGS, true, (M == 2 ? 0 : 1), P, 9, Q, R>;                             \
-      if (!raise_lds((const void*)kfn, lds)) return DLA_ERR_RUNTIME;                                          \
-      DLA_LAUNCH(kfn, dim3(blocks), dim3(256), lds, st, a);                                           \
-    } while (0)
-#define GGQR(V, M, Q, R) GGQRP(V, M, Q, R, (KT >= 3 ? 3 : KT >= 2 ? 2 : 0))
-#define GGQ(V, M, Q) do { if (KT == 3 && V == 2 && rtp == 1) GGQR(V, M, Q, 1); else GGQR(V, M, Q, 2); } while (0)
-#define GG(V, M) GGQ(V, M, 0)
-    if constexpr (KT >= 2) {
-      if (vec2 && qt == 1) { if (mode == 1) GGQ(2, 1, 1); else if (mode == 2) GGQ(2, 2, 1); else GGQ(2, 0, 1); return DLA_OK; }
-      if (vec2 && qt == 2) { if (mode == 1) GGQ(2, 1, 2); else if (mode == 2) GGQ(2, 2, 2); else GGQ(2, 0, 2); return DLA_OK; }
-    }
-    if (vec2) { if (mode == 1) GG(2, 1); else if (mode == 2) GG(2, 2); else GG(2, 0); }
-    else      { if (mode == 1) GG(1, 1); else if (mode == 2) GG(1, 2); else GG(1, 0); }
-#undef GG
-#undef GGQ
-#undef GGQR
-#undef GGQRP
-    return DLA_OK;
-  }
-
-  template <int KT, typename ARGS>
-  void launch_gemm(const ARGS& a, int blocks, size_t lds, bool vec2, int mode, int qt, int pipe)
-  {
-#define GM(V, M) DLA_LAUNCH((gemm_kernel<KT, V, M, ARGS>), dim3(blocks), dim3(256), lds, st, a)
-#define GMQP(M, Q, P) DLA_LAUNCH((gemm_kernel<KT, 2, M, ARGS, false, (M == 2 ? 0 : 1), P, 9, Q>), dim3(blocks), dim3(256), lds, st, a)
-#define GMQ(M, Q) GMQP(M, Q, 2)      /* (a third step per stage costs these kernels their second wave per SIMD: update -22 %) */
-#define GMP(M, P) DLA_LAUNCH((gemm_kernel<KT, 2, M, ARGS, false, 1, P>), dim3(blocks), dim3(256), lds, st, a)
-    if (vec2 && KT >= 2 && pipe != 2) {   // (a depth other than these kernels' own: Knobs::gemm_pipe_depth -- mode 0 / 1, no quarter tiles)
-      if (pipe == 0) { if (mode == 0) GMP(0, 0); else GMP(1, 0); }
-      else           { if (mode == 0) GMP(0, 4); else GMP(1, 4); }
-      return;
-    }
-    if constexpr (KT >= 2) {
-      if (vec2 && qt == 1) { if (mode == 0) GMQ(0, 1); else if (mode == 1) GMQ(1, 1); else if (mode == 2) GMQ(2, 1); else GMQ(3, 1); return; }
-      if (vec2 && qt == 2) { if (mode == 0) GMQ(0, 2); else if (mode == 1) GMQ(1, 2); else if (mode == 2) GMQ(2, 2); else GMQ(3, 2); return; }
-    }
-#undef GMQ
-#undef GMQP
-    if (vec2) { if (mode == 0) GM(2, 0); else if (mode == 1) GM(2, 1); else if (mode == 2) GM(2, 2); else GM(2, 3); }
-    else      { if (mode == 0) GM(1, 0); else if (mode == 1) GM(1, 1); else if (mode == 2) GM(1, 2); else GM(1, 3); }
-#undef GM
-#undef GMP
+    int r_ = DLA_OK;
+    const bool hit = first_instance<std::size(GEMM_INSTANCES.row)>([&](auto i) {
+      constexpr GemmInstance s = GEMM_INSTANCES.row[decltype(i)::value];
+      if constexpr (s.inl != std::is_same_v<ARGS, GemmArgsInl>) return false;
+      else {
+        if (!p.names(s)) return false;
+        auto kfn = gemm_kernel<s.kt, s.vec, s.mode, ARGS, s.fuse, (s.mode == 2 ? 0 : 1), s.pipe, 9, s.qt, s.rtp>;
+        if (s.fuse && !raise_lds((const void*)kfn, p.lds)) r_ = DLA_ERR_RUNTIME;
+        else DLA_LAUNCH(kfn, dim3(p.blocks), dim3(256), p.lds, st, a);
+        return true;
+      }
+    });
+    if (!hit) { err = "gemm: no kernel instance"; return DLA_ERR_RUNTIME; }
+    return r_;
   }
 
   // cpk_dev != nullptr: the coefficient block is already packed in device memory (ortho_tail_kernel wrote it)
@@ -6100,10 +6068,8 @@ struct HipEngine : dla::Engine {
     const bool fuse = fused_blocks != nullptr;
     const bool vec2 = on_16_bytes(n, x, z);
     const GemmPlan p = gemm_plan(env(), n, l, k, mode, fuse, cpk_dev != nullptr, vec2);
-    const int kt = p.kt, l4 = p.l4, qt = p.qt, rtp = p.rtp, pipe = p.pipe, blocks = p.blocks;
-    const bool inl = p.inl;
-    const size_t lds = p.lds;
-    if (!inl && cpk_dev == nullptr) {
+    const int kt = p.kt, l4 = p.l4, blocks = p.blocks;
+    if (!p.inl && cpk_dev == nullptr) {
       int stc = upload_packed(c_host, ldc, l0, l, k, kt, l4);
       if (stc) return stc;
     }
@@ -6117,33 +6083,17 @@ struct HipEngine : dla::Engine {
     a.phase = lc.phase; a.want = lc.want; a.xpf = knobs.no_next_tile_prefetch() ? 0 : 1;
     const double rd = (mode == 0) ? 8.0 * n * (double)l : (mode == 2 ? 8.0 * n * (double)k : 8.0 * n * (double)(l + k));
     Scope s(this, cls, rd + 8.0 * n * (double)k, (cls == DLA_OP_TRMM ? 1.0 : 2.0) * (double)n * l * k, p.name());
-    if (inl) {
+    int stl;
+    if (p.inl) {
       GemmArgsInl ai{};
       ai.x = a.x; ai.z = z; ai.n = n; ai.l = l; ai.l4 = l4; ai.k = k; ai.gpart = d_partial;
       for (int j = 0; j < k; ++j)
-        for (int p = 0; p < l; ++p) ai.cin[p * 16 + j] = c_host[(size_t)(l0 + p) + (size_t)j * ldc];
-      int stl = DLA_OK;
-      if (fuse) stl = launch_gemm_gram<1>(ai, blocks, lds, vec2, mode, 0, 2);
-      else launch_gemm<1>(ai, blocks, lds, vec2, mode, 0, pipe);
-      if (stl) return stl;
-      HIPCHK(hipGetLastError());
-      return DLA_OK;
+        for (int r = 0; r < l; ++r) ai.cin[r * 16 + j] = c_host[(size_t)(l0 + r) + (size_t)j * ldc];
+      stl = launch_gemm(p, ai);
+    } else {
+      stl = launch_gemm(p, a);
     }
-    if (fuse) {
-      int stl;
-      if (kt == 1) stl = launch_gemm_gram<1>(a, blocks, lds, vec2, mode, 0, 2);
-      else if (kt == 2) stl = launch_gemm_gram<2>(a, blocks, lds, vec2, mode, qt, 2);
-      else stl = launch_gemm_gram<3>(a, blocks, lds, vec2, mode, qt, rtp);
-      if (stl) return stl;
-      HIPCHK(hipGetLastError());
-      return DLA_OK;
-    }
-    switch (kt) {
-      case 1: launch_gemm<1>(a, blocks, lds, vec2, mode, 0, pipe); break;
-      case 2: launch_gemm<2>(a, blocks, lds, vec2, mode, qt, pipe); break;
-      case 3: launch_gemm<3>(a, blocks, lds, vec2, mode, qt, pipe); break;
-      default: err = "gemm: k > 48 not supported in one call"; return DLA_ERR_ARG;
-    }
+    if (stl) return stl;
     HIPCHK(hipGetLastError());
     return DLA_OK;
   }

@@ -4,9 +4,10 @@
 // knobs and the chain policy.  The planners have no members and touch no global; the engine owns every piece of state
 // (remembered plans, the cooldown, the LDS limit, pointers) and passes what a decision reads.  hip_engine.hip takes a plan,
 // books plan.name() and dispatches on the plan's fields; tests/plans_driver.cpp calls the same functions on the CPU.
-// Which template instances of the Gram, pending-factor and Ritz kernels exist is spelled once, in the lists below (GRAM_TILES,
-// gram_direct_instance, GRAM_LOW_TILES, WP_TILES, RITZ_INSTANCES, RITZ2_INSTANCES): the planners round to a listed width, the engine's ladders
-// instantiate and launch exactly the listed rows, and tests/test_plans.py holds its own transcription against what the driver prints.
+// Which template instances of the Gram, pending-factor, panel-product and Ritz kernels exist is spelled once, in the lists below
+// (GRAM_TILES, gram_direct_instance, GRAM_LOW_TILES, GRAM_LDS_FORMS, WP_TILES, GEMM_INSTANCES, RITZ_INSTANCES, RITZ2_INSTANCES): the
+// planners round to a listed width, the engine's ladders instantiate exactly the listed instances and launch the one whose template
+// arguments equal the plan's fields, or none, and tests/test_plans.py holds its own transcription against what the driver prints.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -144,7 +145,8 @@ inline int quarter_tiles(const PlanEnv& env, int k, bool vec2)
 // resident blocks per CU that the dynamic LDS of a panel-product or Ritz sweep leaves room for
 inline int blocks_per_cu(size_t lds) { return lds > 80 * 1024 ? 1 : lds > 40 * 1024 ? 2 : 4; }
 
-// ---- the instance lists: one row per template instance the engine's ladders can launch (plain integers, compile-time)
+// ---- the instance lists: one row per template instance the engine's ladders can launch (plain integers, compile-time); for a family
+// that is a product of flags, the rows that a predicate over the flags admits
 // gram_kernel / gram_lds_kernel passes of kt U-tiles x tlw X-tiles
 struct GramTile { int tlw, kt; };
 constexpr GramTile GRAM_TILES[] = {
@@ -158,6 +160,11 @@ constexpr bool gram_direct_instance(int tlw, int kt)
   return !(tlw == 5 || tlw == 7 || tlw == 10 || (tlw == 12 && kt > 1) || (tlw == 3 && kt >= 2 && kt <= 3) || (tlw >= 5 && kt == 3) ||
            (tlw >= 7 && kt == 2));
 }
+// gram_lds_kernel<tlw, kt, 1, R, self, qt> of a listed pass: SELF (a block against itself, staged once) only where both sides have the
+// same tiles, quarter tiles of the last U tile only behind a full one
+struct GramLdsForm { int self, qt; };
+constexpr GramLdsForm GRAM_LDS_FORMS[] = {{0, 0}, {0, 1}, {0, 2}, {1, 0}, {1, 1}, {1, 2}};
+constexpr bool gram_lds_form(int tlw, int kt, const GramLdsForm& f) { return !(f.self && tlw != kt) && !(f.qt > 0 && kt < 2); }
 // tiles per side of the single-pass lower triangle (gram_lds_kernel LOW)
 constexpr int GRAM_LOW_TILES[] = {4, 5, 6, 7};
 // sweeps of the pending-factor schedule (gram_lds_kernel WP), with the rows R of a staged tile
@@ -184,6 +191,45 @@ struct Ritz2Instance { int kt, vec; };
 constexpr Ritz2Instance RITZ2_INSTANCES[] = {{1, 1}, {1, 2}, {2, 1}, {2, 2}, {3, 1}, {3, 2}};
 // davidson_expand_kernel<tx>: the Ritz sweep that also forms and measures the next block, tx column tiles of the basis
 constexpr int RITZ_EXPAND_TILES[] = {1, 2, 3, 4, 5, 6, 7};
+// gemm_kernel<kt, vec, mode, inl ? GemmArgsInl : GemmArgs, fuse, mode == 2 ? 0 : 1, pipe, 9, qt, rtp>: a product of independent flags, so the
+// set is a predicate over them; GEMM_INSTANCES below is the same set as rows, for the ladder
+struct GemmInstance { int kt, vec, mode; bool inl, fuse; int pipe, qt, rtp; };
+constexpr bool gemm_instance(const GemmInstance& g)
+{
+  if (g.fuse && g.mode == 3) return false;                                       // the fused form: Z = XC, Z -= XC and U <- U W only
+  if (g.inl && g.kt != 1) return false;                                          // 16 x 16 coefficients fit the kernel arguments
+  if (g.qt > 0 && !(g.vec == 2 && g.kt >= 2)) return false;                      // quarter tiles: the 16-byte path, behind a full tile
+  if (g.qt > 0 && !g.fuse && g.mode == 1 && g.kt == 2) return false;             // ... and never the plain two-tile update (gemm_plan)
+  if (g.rtp == 1 && !(g.fuse && g.kt == 3 && g.vec == 2)) return false;          // one row group: the fused three-tile sweep only
+  if (g.pipe == ((g.fuse && g.kt >= 3) ? 3 : g.kt >= 2 ? 2 : 0)) return true;    // the kernel's own depth: 0 / 2 / 2 plain, 0 / 2 / 3 fused
+  // the depths of Knobs::gemm_pipe_depth: the plain product and update of two and three tiles, no quarter tiles
+  return (g.pipe == 0 || g.pipe == 4) && !g.fuse && g.vec == 2 && g.kt >= 2 && g.mode <= 1 && g.qt == 0;
+}
+// candidate c of the box kt 1 .. 3 x vec 1 .. 2 x mode 0 .. 3 x inl x fuse x depth 0 .. 4 x qt 0 .. 2 x rtp 1 .. 2
+constexpr int GEMM_CANDIDATES = 3 * 2 * 4 * 2 * 2 * 5 * 3 * 2;
+constexpr GemmInstance gemm_candidate(int c)
+{
+  GemmInstance g{};
+  g.rtp = 1 + c % 2; c /= 2;  g.qt = c % 3; c /= 3;  g.pipe = c % 5; c /= 5;  g.fuse = c % 2; c /= 2;  g.inl = c % 2; c /= 2;
+  g.mode = c % 4; c /= 4;  g.vec = 1 + c % 2; c /= 2;  g.kt = 1 + c;
+  return g;
+}
+constexpr int gemm_instance_count()
+{
+  int n = 0;
+  for (int c = 0; c < GEMM_CANDIDATES; ++c) n += gemm_instance(gemm_candidate(c)) ? 1 : 0;
+  return n;
+}
+struct GemmInstanceList { GemmInstance row[gemm_instance_count()]; };
+constexpr GemmInstanceList gemm_instances()
+{
+  GemmInstanceList list{};
+  int n = 0;
+  for (int c = 0; c < GEMM_CANDIDATES; ++c)
+    if (gemm_instance(gemm_candidate(c))) list.row[n++] = gemm_candidate(c);
+  return list;
+}
+constexpr GemmInstanceList GEMM_INSTANCES = gemm_instances();
 // "round up to an instantiated width": the narrowest listed pass of kt U-tiles that holds `want` X-tiles and that `ok` admits; null
 // when the list has none (the planner keeps its width, and the ladder reports that there is no kernel instance)
 template <typename Tile, size_t N, typename Ok>
@@ -337,6 +383,11 @@ struct GemmPlan {
   int per_cu, rtp, pipe, blocks;
   bool vec2, fuse;
   int mode;
+  // whether g is the instance this plan names
+  bool names(const GemmInstance& g) const
+  {
+    return kt == g.kt && (vec2 ? 2 : 1) == g.vec && mode == g.mode && inl == g.inl && fuse == g.fuse && pipe == g.pipe && qt == g.qt && rtp == g.rtp;
+  }
   std::string name() const
   {
     return plan_name("gemm_kernel<%d, %d, %d, %s, %s, %d, %d, 9, %d, %d>", kt, vec2 ? 2 : 1, mode, inl ? "GemmArgsInl" : "GemmArgs",

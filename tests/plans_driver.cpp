@@ -13,7 +13,7 @@
 //   lean M K P2P_ON NRANKS COMM
 //   close LEAN X3 OP ...
 //   fused L K                          fused_lds
-//   instances                          the instance lists, one line per list, and gram_direct_instance over tlw 1..12 x kt 1..4
+//   instances                          the instance lists on one line, and gram_direct_instance over tlw 1..12 x kt 1..4
 #include <cstdio>
 #include <iostream>
 #include <sstream>
@@ -115,6 +115,10 @@ int main()
       for (int t : GRAM_LOW_TILES) std::printf("%d;", t);
       std::printf(" wp_tiles=");
       for (const WpTile& t : WP_TILES) std::printf("%d,%d,%d;", t.tlw, t.kt, t.R);
+      std::printf(" gram_lds_forms=");
+      for (const GramLdsForm& f : GRAM_LDS_FORMS) std::printf("%d,%d;", f.self, f.qt);
+      std::printf(" gemm=");
+      for (const GemmInstance& g : GEMM_INSTANCES.row) std::printf("%d,%d,%d,%d,%d,%d,%d,%d;", g.kt, g.vec, g.mode, g.inl, g.fuse, g.pipe, g.qt, g.rtp);
       std::printf(" ritz_instances=");
       for (const RitzInstance& r : RITZ_INSTANCES) std::printf("%d,%d,%d,%d,%d;", r.kt, r.vec, r.pipe, r.qt, r.xp ? 1 : 0);
       std::printf(" ritz2_instances=");

@@ -3,7 +3,7 @@ dla_trmm_gram, dla_update_gram, dla_combo_gram), ritz_kernel (dla_ritz_residual,
 (dla_ritz_residual2) and dla_gram's alignment dispatch and leading dimensions -- through the guarded checkers of tests/dense_ref.py:
 long-double references, sentinel columns around every output, NaN columns around every input.
 
-  a. the gemm_kernel ladder: launch_gemm and launch_gemm_gram have no instance list, so every call a small request can reach without
+  a. the gemm_kernel ladder (launch_gemm over GEMM_INSTANCES of hip_plans.h): every call a small request can reach without
      knobs is made once and must book the name(s) the CPU planner (tests/plans_driver.cpp) prints for the request line(s) of that shape;
      the names of the grid are all the planner gives on an exhaustive walk of the requests a dense entry can make (k <= 48)
   b. tails: n = 1 .. 257 around every wave-tile and block boundary, for every writer
@@ -168,7 +168,7 @@ def test_gemm_ladder_books_the_planned_instance(ctx, n, family):
 @pytest.mark.parametrize("n", [N_EVEN, N_ODD])
 def test_gemm_ladder_is_covered(ctx, n):
     """the instances seen by test_gemm_ladder_books_the_planned_instance are all the planner can name over the grid, and the grid's
-    are all it can name for any request of a dense entry: no arm of launch_gemm / launch_gemm_gram that a request without knobs reaches
+    are all it can name for any request of a dense entry: no instance of launch_gemm that a request without knobs reaches
     is left out"""
     want = set()
     for family in LADDER_FAMILIES:

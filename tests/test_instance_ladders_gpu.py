@@ -1,17 +1,22 @@
 """GPU: the dispatch ladders of hip_engine.hip launch the instance the planners name, for every row of the instance lists of
-hip_plans.h (GRAM_TILES, GRAM_LOW_TILES, WP_TILES, RITZ_INSTANCES) that a small call can reach.
+hip_plans.h (GRAM_TILES, GRAM_LOW_TILES, WP_TILES, RITZ_INSTANCES) that a small call can reach, and for the gemm_kernel instances
+(GEMM_INSTANCES) of one to three column tiles: plain and fused, in the kernel arguments and packed, with quarter tiles, accumulating,
+and at the pipeline depths of knob 2.
 
 Each call must succeed (a plan without a row is "no kernel instance"), give the right numbers, and book the name that the CPU
 planners (tests/plans_driver.cpp, through tests/test_plans.py) print for the request line of exactly that shape.  n = 1000 is even
 with a partial last wave tile (the 16-byte path, the LDS-staged kernels); n = 999 is odd (the 8-byte path, the direct-load kernels).
 Bounds are the neighbours': tests/test_kernels_gpu.py for the Gram matrices and the Ritz sweep, test_chain_ortho_vs_x_vs_oracle of
-tests/test_ortho_chain_gpu.py for the chains.  Nothing here forces a failure path (tests/test_lds_refusal_gpu.py does)."""
+tests/test_ortho_chain_gpu.py for the chains, tests/test_dense_sweeps_gpu.py (the checkers of tests/dense_ref.py) for the panel
+products.  Nothing here forces a failure path (tests/test_lds_refusal_gpu.py does)."""
 import re
+import zlib
 
 import numpy as np
 import pytest
 
-from test_plans import env_line, run_plans
+import dense_ref
+from test_plans import LDS, env_line, run_plans
 
 pytestmark = pytest.mark.gpu
 EPS = np.finfo(np.float64).eps
@@ -158,3 +163,71 @@ def test_ritz_ladder_with_extra_products(ctx, panels):
         check_ritz(v, av, y, eig, skip, pe.download(), pr.download(), pa.download(), rn, n)
         assert np.all(np.abs(pp.download() - v @ c2) <= 64 * EPS * (np.abs(v) @ np.abs(c2)) + 1e-300)
         assert np.all(np.abs(pap.download() - av @ c2) <= 64 * EPS * (np.abs(av) @ np.abs(c2)) + 1e-300)
+
+
+TUNE_GEMM = 100 + 2
+GEMM_K = (13, 21, 29, 37, 45)              # one to three column tiles; quarter tiles of 2 at 21 and 37
+GEMM_L = (13, 42, 104)                     # l = 13 under k = 13 travels in the kernel arguments
+
+
+class PanelDraws:
+    """the generator the checkers of tests/dense_ref.py draw from: a block of n rows is the leading columns of the module's panels (the
+    first one a checker asks for of X, the second of U), the coefficient blocks are drawn from a seed"""
+
+    def __init__(self, panels, n, seed):
+        self.n, self.blocks, self.rng = n, [panels[0][:n], panels[1][:n]], np.random.default_rng(seed)
+
+    def standard_normal(self, shape):
+        return self.blocks.pop(0)[:, :shape[1]] if shape[0] == self.n else self.rng.standard_normal(shape)
+
+
+def fuses(depth, k):
+    """what update_gram_once, trmm_gram_once and can_combo ask of a contraction of `depth` rows: the packed coefficients and three spare
+    rows in 64 KiB, and the LDS of the sweep (fused_lds) within the limit"""
+    kt, l4 = -(-k // 16), -(-depth // 4) * 4
+    return k <= 48 and 128 * (depth + 3) * kt <= 65536 and 8 * (kt * l4 * 16 + 64 * (16 * kt + 9)) <= LDS
+
+
+def gemm_cases(n):
+    """[(checker, its shape, knob 2, the planner's request lines)]"""
+    v = 1 - n % 2
+
+    def line(l, k, mode, fuse):
+        return f"gemm {n} {l} {k} {mode} {fuse} 0 {v}"
+
+    out = []
+    for k in GEMM_K:
+        # (a shape the engine does not fuse: the triangular update, or the update, as a sweep of its own and the Gram matrix behind it)
+        out += [("check_product", (n, k, k, "trmm"), 0, [line(k, k, 2, 0)]),
+                ("check_fused", (n, k, k, "trmm_gram"), 0, [line(k, k, 2, 1 if fuses(k, k) else 0)])]
+        for l in GEMM_L:
+            assert fuses(l + k, k), (l, k)                                                # (dla_combo_gram has no other form)
+            out += [("check_product", (n, l, k, "gemm"), 0, [line(l, k, 0, 0)]), ("check_product", (n, l, k, "update"), 0, [line(l, k, 1, 0)]),
+                    ("check_fused", (n, l, k, "update_gram"), 0, [line(l, k, 1, 1 if fuses(l, k) else 0)]),
+                    ("check_fused", (n, l, k, "combo_gram"), 0, [line(l + k, k, 0, 1)])]
+    # 208 rows of three-tile coefficients are two LDS chunks of at most 168: the second one accumulates (mode 3)
+    out.append(("check_product", (n, 208, 45, "gemm"), 0, [line(168, 45, 0, 0), line(40, 45, 3, 0)]))
+    for knob in (1, 4):                                                                    # pipeline depth 0 / 4 (16-byte path)
+        out += [("check_product", (n, l, 29, mode), knob, [line(l, 29, m, 0)]) for l in GEMM_L for m, mode in enumerate(("gemm", "update"))]
+    return out
+
+
+@pytest.mark.parametrize("n", [N_EVEN, N_ODD])
+def test_gemm_ladder(ctx, panels, n):
+    """dla_panel_gemm, dla_panel_update, dla_trmm_linvt and the fused dla_trmm_gram, dla_update_gram, dla_combo_gram on k columns and a
+    contraction of l: launch_gemm launches the instance the plan names, or none"""
+    cases = gemm_cases(n)
+    want = {knob: iter(run_plans([env_line(t2=knob)] + [ln for _, _, kn, lines in cases if kn == knob for ln in lines])[0]) for knob in (0, 1, 4)}
+    seen = set()
+    for fn, shape, knob, lines in cases:
+        names = sorted(next(want[knob])[1] for _ in lines)
+        ctx.set_option(TUNE_GEMM, knob)
+        ctx.reset_stats()
+        try:
+            getattr(dense_ref, fn)(ctx, PanelDraws(panels, n, zlib.crc32(repr((fn, shape, knob)).encode())), *shape)      # (raises unless DLA_OK)
+        finally:
+            ctx.set_option(TUNE_GEMM, 0)
+        assert booked(ctx, r"gemm_kernel<") == names, (fn, shape, knob, lines, names, booked(ctx, r"gemm_kernel<"))
+        assert all(st["launches"] == 1 for name, st in ctx.kernel_stats().items() if name in names), (fn, shape, knob)
+        seen |= set(names)
+    print(n, len(seen), sorted(seen))

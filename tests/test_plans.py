@@ -5,9 +5,9 @@ tests/plans_driver.cpp is compiled with g++ and no ROCm include (tests/_build/, 
 tests/test_sell_layout.py does); it reads shape lines and prints plan fields and names from the product's own planners.  Expected
 values come from outside the planners: the committed rocprofv3 record of the benchmark, the literal names tests/test_knobs_gpu.py
 asserts, the rules the planners' comments state, and the kernels' instance lists.  Those lists live in hip_plans.h (GRAM_TILES,
-gram_direct_instance, GRAM_LOW_TILES, WP_TILES, RITZ_INSTANCES, RITZ2_INSTANCES), where the planners and the dispatch ladders of hip_engine.hip both
-read them; they are transcribed below as literal sets, and test_transcribed_instance_lists_are_the_engines holds each transcription
-against what the driver prints from the header."""
+gram_direct_instance, GRAM_LOW_TILES, GRAM_LDS_FORMS, WP_TILES, GEMM_INSTANCES, RITZ_INSTANCES, RITZ2_INSTANCES), where the planners
+and the dispatch ladders of hip_engine.hip both read them; they are transcribed below as literal sets (the gemm_kernel set as its rules),
+and test_transcribed_instance_lists_are_the_engines holds each transcription against what the driver prints from the header."""
 import csv
 import itertools
 import os
@@ -121,6 +121,26 @@ def direct_load_instance(t, k):
 GWP = {(t, 1, 32) for t in (1, 2)} | {(t, 1, 16) for t in (3, 4, 5, 6, 7, 8, 10, 12)} | {(t, 2, 16) for t in range(1, 9)} | {(t, 3, 16) for t in range(1, 6)}
 
 
+def gemm_kernel_instance(kt, vec, mode, inl, fuse, pipe, qt, rtp):
+    """the gemm_kernel instances launch_gemm can launch (GEMM_INSTANCES), rule by rule"""
+    if fuse and mode == 3:
+        return False                                  # the fused form: modes 0 .. 2
+    if inl and kt != 1:
+        return False                                  # coefficients in the kernel arguments: one tile
+    if qt and not (vec == 2 and kt >= 2):
+        return False                                  # quarter tiles: the 16-byte path, two and three tiles
+    if qt and not fuse and mode == 1 and kt == 2:
+        return False                                  # ... which the plain two-tile update never takes
+    if rtp == 1 and not (fuse and kt == 3 and vec == 2):
+        return False                                  # one row group: the fused three-tile sweep on the 16-byte path
+    own = {1: 0, 2: 2, 3: 3 if fuse else 2}[kt]       # the kernel's own depth
+    return pipe == own or (pipe in (0, 4) and not fuse and vec == 2 and kt >= 2 and mode in (0, 1) and not qt)
+
+
+# (kt, vec, mode, inl, fuse, pipe, qt, rtp) of gemm_kernel<kt, vec, mode, GemmArgsInl / GemmArgs, fuse, mode != 2, pipe, 9, qt, rtp>
+GEMM = {r for r in itertools.product((1, 2, 3), (1, 2), (0, 1, 2, 3), (0, 1), (0, 1), (0, 2, 3, 4), (0, 1, 2), (1, 2)) if gemm_kernel_instance(*r)}
+
+
 def listed_instances():
     """what the driver prints of hip_plans.h: each list as a list of integer tuples, in the header's order"""
     res, _ = run_plans(["instances"])
@@ -143,6 +163,10 @@ def test_transcribed_instance_lists_are_the_engines():
     assert set(inst["ritz_instances"]) == ritz and len(inst["ritz_instances"]) == 23
     # ritz2_kernel<kt, vec>
     assert set(inst["ritz2_instances"]) == {(1, 1), (1, 2), (2, 1), (2, 2), (3, 1), (3, 2)} and len(inst["ritz2_instances"]) == 6
+    # gram_lds_kernel<tlw, kt, 1, R, self, qt> of a listed pass: (self, qt)
+    assert set(inst["gram_lds_forms"]) == {(s, q) for s in (0, 1) for q in (0, 1, 2)} and len(inst["gram_lds_forms"]) == 6
+    assert set(inst["gemm"]) == GEMM and len(inst["gemm"]) == 99
+    assert sum(1 for r in GEMM if r[4]) == 45 and sum(1 for r in GEMM if r[3]) == 14              # fused; coefficients in the arguments
 
 
 @pytest.mark.parametrize("lds_limit", [64 * KIB, 160 * KIB])
@@ -177,23 +201,31 @@ def per_cu_steps(lds):
     return 1 if lds > 80 * KIB else 2 if lds > 40 * KIB else 4
 
 
-@pytest.mark.parametrize("knob", [0, 1, 4])
+@pytest.mark.parametrize("knob", [0, 1, 4, "no_quarter_tiles", "fused3_two_row_groups"])
 def test_gemm_plans_fit_the_kernels(knob):
+    """knob 2 at 0 / 1 / 4 (Knobs::gemm_pipe_depth), and knob 7 at 1 (no_quarter_tiles) and 5 (fused3_two_row_groups)"""
+    tune = {"no_quarter_tiles": {"t7": 1}, "fused3_two_row_groups": {"t7": 5}}.get(knob, {"t2": knob})
+    depth = {1: 0, 4: 4}.get(knob)                                       # the depth knob 2 asks for, if any
     cases = [(l, k, mode, fuse, packed, v) for l in (1, 4, 13, 16, 17, 42, 63, 104, 208, 320, 512) for k in range(1, 49) for mode in range(4)
              for fuse in (0, 1) for packed in (0, 1) for v in (0, 1) if not (fuse and mode == 3)]
-    res, _ = run_plans([env_line(t2=knob)] + [f"gemm {N_BENCH} {l} {k} {m} {f} {pk} {v}" for l, k, m, f, pk, v in cases])
+    rows = listed_instances()["gemm"]
+    res, _ = run_plans([env_line(**tune)] + [f"gemm {N_BENCH} {l} {k} {m} {f} {pk} {v}" for l, k, m, f, pk, v in cases])
     for (l, k, mode, fuse, packed, v), (p, name) in zip(cases, res):
         what = (l, k, mode, fuse, packed, v, p, name)
         kt = -(-k // 16)
         assert p["kt"] == kt and p["l4"] == -(-l // 4) * 4 and p["l4"] >= l, what
         assert p["per_cu"] == per_cu_steps(p["lds"]), what
-        assert (p["rtp"] == 1) == bool(fuse and kt == 3 and v and p["per_cu"] >= 2) and p["rtp"] in (1, 2), what
-        own = 3 if (fuse and kt >= 3) else 2 if kt >= 2 else 0           # GGQR / GM, GMQ: the kernels' own depth
-        if not fuse and knob and v and kt >= 2 and mode in (0, 1):
-            assert p["pipe"] == {1: 0, 4: 4}[knob] and p["qt"] == 0, what   # GMP
+        one_group = bool(fuse and kt == 3 and v and p["per_cu"] >= 2 and knob != "fused3_two_row_groups")
+        assert (p["rtp"] == 1) == one_group and p["rtp"] in (1, 2), what
+        own = 3 if (fuse and kt >= 3) else 2 if kt >= 2 else 0           # the kernels' own depth: 0 / 2 / 2 plain, 0 / 2 / 3 fused
+        if not fuse and depth is not None and v and kt >= 2 and mode in (0, 1):
+            assert p["pipe"] == depth and p["qt"] == 0, what             # another depth: plain, 16-byte path, modes 0 / 1, no quarter tiles
         else:
             assert p["pipe"] == own, what
         assert p["qt"] in (0, 1, 2) and (not p["qt"] or (1 <= k % 16 <= 8 and kt in (2, 3) and v)), what
+        assert not (p["qt"] and knob == "no_quarter_tiles"), what
+        # the one instance launch_gemm launches for it: no plan of the grid may reach "gemm: no kernel instance"
+        assert rows.count((kt, 2 if v else 1, mode, p["inl"], fuse, p["pipe"], p["qt"], p["rtp"])) == 1, what
         assert p["inl"] == int(not packed and kt == 1 and p["l4"] <= 16), what
         assert 1 <= p["blocks"] <= NCU * p["per_cu"], what
         floor = 8 * p["l4"] * (16 * (kt - 1) + 8 if p["qt"] else 16 * kt)           # the LDS copy of C

@@ -24,7 +24,7 @@ ARCH = "gfx950"
 
 CXX_SOURCES = ["csrc/host_logic.cpp", "csrc/smalldense.cpp"]
 WIDE_SIMD_SOURCES = ["csrc/smalldense.cpp"]
-HIP_SOURCES = ["csrc/hip_engine.hip"]
+HIP_SOURCES = ["csrc/hip_engine.hip", "csrc/spmm_transpose_sort.hip"]
 F90_SOURCES = ["fortran/real_precision.f90", "fortran/diaglib.f90", "fortran/diaglib_cbind.f90"]  # order matters
 HEADERS = ["csrc/dla_internal.h", "csrc/hip_owned.h", "csrc/hip_plans.h", os.path.join(ROOT, "include", "diaglib_amd.h")]
 

@@ -45,6 +45,7 @@ EXPORTS = [
     "dla_synth_metric", "dla_synth_lrprec1", "dla_synth_lrprec2", "dla_pending_factor", "dla_pending_block", "dla_basis_admit", "dla_basis_fold", "dla_basis_sync", "dla_spmm_setup_csr", "dla_spmm_setup_csr_fmt", "dla_spmm_info", "dla_spmm_setup_csr_sharded", "dla_spmm_matvec", "dla_spmm_precnd",
     "dla_spmm_setup_metric_csr", "dla_spmm_metric_info", "dla_spmm_drop_metric", "dla_spmm_bvec", "dla_spmm_precnd_pencil",
     "dla_spmm_setup_csr_dev", "dla_spmm_refresh_values_dev",
+    "dla_spmm_transpose_prepare", "dla_spmm_transpose_info", "dla_spmm_drop_transpose", "dla_spmm_matvec_t",
     "dla_spmm_cheb_config", "dla_spmm_cheb_info", "dla_spmm_precnd_cheb",
     "dla_spmm_cheb_jacobi_upper", "dla_spmm_precnd_cheb_jacobi",
     "dla_spmm_cheb_pencil_upper", "dla_spmm_precnd_cheb_pencil",
@@ -179,6 +180,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dla_spmm_setup_csr_sharded": (i, [vp, i, C.c_longlong, C.c_longlong, vp, vp, vp]),
         "dla_spmm_setup_metric_csr": (i, [vp, i, vp, vp, vp, i]), "dla_spmm_metric_info": (i, [vp, C.POINTER(SpmmInfo)]),
         "dla_spmm_drop_metric": (i, [vp]),
+        "dla_spmm_transpose_prepare": (i, [vp, i]), "dla_spmm_transpose_info": (i, [vp, C.POINTER(SpmmInfo)]),
+        "dla_spmm_drop_transpose": (i, [vp]), "dla_spmm_matvec_t": (None, [c_ip, c_ip, vp, vp]),
         "dla_spmm_bvec": (None, [c_ip, c_ip, vp, vp]), "dla_spmm_precnd_pencil": (None, [c_ip, c_ip, c_dp, vp, vp]),
         "dla_spmm_setup_csr_dev": (i, [vp, i, i, vp, vp, vp, i]), "dla_spmm_refresh_values_dev": (i, [vp, i, i, vp, vp, vp]),
         "dla_spmm_cheb_config": (i, [vp, i, d]), "dla_spmm_cheb_info": (i, [vp, C.POINTER(SpmmChebInfo)]),
@@ -651,6 +654,27 @@ class Context:
         o = SpmmInfo()
         self._chk(self.lib.dla_spmm_info(self.h, C.byref(o)))
         return self._spmm_info_dict(o)
+
+    def spmm_transpose_prepare(self, fmt: str = "auto") -> None:
+        """build the transposed index of the stored operator (dla_spmm_transpose_prepare): dla_spmm_matvec_t then forms A^T x from
+        the operator's one stored copy.  fmt lays out the TRANSPOSED pattern ("ell", "sell" or "auto"); a new set-up of the operator
+        drops the index, a refresh of its values keeps it"""
+        self._chk(self.lib.dla_spmm_transpose_prepare(self.h, self._spmm_format("spmm_transpose_prepare", fmt)))
+
+    def spmm_transpose_info(self) -> dict:
+        """spmm_info of the transposed index (device_bytes: the index arrays only); raises while none is prepared"""
+        o = SpmmInfo()
+        self._chk(self.lib.dla_spmm_transpose_info(self.h, C.byref(o)))
+        return self._spmm_info_dict(o)
+
+    def spmm_drop_transpose(self) -> None:
+        """free the transposed index (nothing happens without one); the operator stays as it is"""
+        self._chk(self.lib.dla_spmm_drop_transpose(self.h))
+
+    def spmm_matvec_t(self, x: DevPanel, y: DevPanel) -> None:
+        """y = A^T x through the transposed index of the stored sparse operator (dla_spmm_matvec_t); x and y are n x m panels that
+        do not overlap"""
+        self._chk(self.lib.dla_call_matvec(self.h, fn_address("dla_spmm_matvec_t"), x.n, x.m, x.ptr, y.ptr))
 
     def spmm_setup_metric(self, b, fmt: str = "ell") -> None:
         """hand a scipy.sparse matrix (symmetric positive definite, square) to this context as the metric B of A x = lambda B x,

@@ -314,6 +314,13 @@ struct Engine : BlockOps {
   // (an engine that stores no sparse matrix but A overrides the product of A alone)
   virtual int spmm_mul(int slot, int n, int m, const double* x, double* y) { return slot == SPMM_A ? spmm_matvec(n, m, x, y) : DLA_ERR_ARG; }
   virtual int spmm_matvec(int /*n*/, int /*m*/, const double* /*x*/, double* /*ax*/) { return DLA_ERR_ARG; }
+  // the transposed index of A (TransposeIndex below; the contract: include/diaglib_amd.h, dla_spmm_transpose_prepare) and y = A^T x
+  // through it.  An engine without one (the host-memory test engine) refuses every call.
+  int no_transpose(const char* entry) { err = std::string(entry) + ": this engine keeps no transposed index"; return DLA_ERR_ARG; }
+  virtual int spmm_transpose_prepare(int /*format*/) { return no_transpose("spmm_transpose_prepare"); }
+  virtual int spmm_transpose_info(struct dla_spmm_info* /*out*/) { return no_transpose("spmm_transpose_info"); }
+  virtual int spmm_transpose_drop() { return DLA_OK; }
+  virtual int spmm_mul_t(int /*n*/, int /*m*/, const double* /*x*/, double* /*y*/) { return no_transpose("spmm_matvec_t"); }
   // A on a row shard: rows row0 .. row0 + n_local - 1 of A with GLOBAL column indices.  Columns outside the shard must lie within
   // `halo` rows of it (a banded matrix); every rank publishes its first and last `halo` rows of x through the all-reduce of the
   // small-product transport (disjoint slots: a sum that gathers), see sharded_ell_* below.  Collective: every rank calls it (the
@@ -624,6 +631,128 @@ inline void sell_build(int n, const long long* rowptr, const int* colind, const 
 {
   sell_layout(n, rowptr, s);
   sell_fill(n, rowptr, colind, values, s);
+}
+
+// ---- the transposed index of the stored operator (include/diaglib_amd.h, dla_spmm_transpose_prepare): y = A^T x from the one stored
+// copy of A's values.  The index is a sparse layout of its own -- ELLPACK, or slices with a tail, decided by the code above on the
+// COLUMN lengths of A -- whose entries are two int32 instead of a column and a value: the source row, and the position of the value
+// in A's stored val array (the tail of a sliced A lies behind its `stored` padded entries).  Padding has position -1 and takes part
+// in no arithmetic.  The entries of column j stand in ascending order of the caller's CSR arrays, so the product walks them exactly
+// as the forward product walks the rows of the explicitly (stably) transposed matrix stored in the index's format.
+// The host twin below builds from host arrays what the engine builds on the device from A's stored blocks.
+struct TransposeIndex {
+  int n = 0, fmt = -1, w = 0;       // fmt: DLA_SPMM_ELL (w: the longest column) or DLA_SPMM_SELL (lay); -1: none
+  long long nnz = 0;
+  std::vector<long long> colptr;    // [n + 1], from 0: the column pointers of A, which are the row pointers of A^T
+  SellLayout lay;                   // DLA_SPMM_SELL: sell_layout of colptr (col / val / diag stay empty)
+  std::vector<int> row, pos;        // [entries()]
+  long long entries() const { return fmt == DLA_SPMM_SELL ? lay.stored + lay.long_entries : (long long)w * n; }
+};
+// the stored position of every entry of a matrix in its val array, in the order of the caller's CSR arrays (entry p - rowptr[0]);
+// L: sell_layout of the same row pointers for DLA_SPMM_SELL, else the matrix is ELLPACK
+inline void spmm_stored_positions(int n, const long long* rowptr, int fmt, const SellLayout* L, std::vector<long long>& apos)
+{
+  const long long p0 = rowptr[0];
+  apos.assign((size_t)(rowptr[n] - p0), -1);
+  if (fmt != DLA_SPMM_SELL) {
+    for (int i = 0; i < n; ++i)
+      for (long long p = rowptr[i]; p < rowptr[i + 1]; ++p) apos[(size_t)(p - p0)] = (p - rowptr[i]) * n + i;
+    return;
+  }
+  for (int slot = 0; slot < n; ++slot) {
+    if (L->perm[slot] < 0) continue;
+    const int i = L->perm[slot];
+    const long long base = L->slice_ptr[slot / SELL_C] + slot % SELL_C;
+    for (long long p = rowptr[i]; p < rowptr[i + 1]; ++p) apos[(size_t)(p - p0)] = base + (p - rowptr[i]) * SELL_C;
+  }
+  for (size_t r = 0; r < L->long_row.size(); ++r) {
+    const int i = L->long_row[r];
+    for (long long p = rowptr[i]; p < rowptr[i + 1]; ++p) apos[(size_t)(p - p0)] = L->stored + L->long_ptr[r] + (p - rowptr[i]);
+  }
+}
+// the layout of the index from the column pointers: format, width or slices and tail.  a_entries: what A stores (w n, or stored +
+// long_entries), the range of the positions
+inline int spmm_transpose_layout(int n, const long long* colptr, int format, long long a_entries, TransposeIndex& t, std::string& err)
+{
+  if (format != DLA_SPMM_ELL && format != DLA_SPMM_SELL && format != DLA_SPMM_AUTO) { err = "spmm_transpose_prepare: unknown format"; return DLA_ERR_ARG; }
+  if (a_entries > 2147483647LL) {
+    err = "spmm_transpose_prepare: the operator stores " + std::to_string(a_entries) + " entries, and positions beyond 2147483647 do not fit the index";
+    return DLA_ERR_ARG;
+  }
+  t.n = n; t.nnz = colptr[n] - colptr[0];
+  t.colptr.assign(colptr, colptr + n + 1);
+  long long w = 0;
+  for (int j = 0; j < n; ++j) w = std::max(w, colptr[j + 1] - colptr[j]);
+  t.fmt = spmm_pick_format(format, (int)std::min<long long>(w, 2147483647LL), n, t.nnz);
+  t.w = t.fmt == DLA_SPMM_ELL ? (int)w : 0;
+  t.lay = SellLayout();
+  if (t.fmt == DLA_SPMM_SELL) sell_layout(n, t.colptr.data(), t.lay);
+  t.row.clear(); t.pos.clear();
+  return DLA_OK;
+}
+// fills row / pos of a laid-out index: src(k, &row, &pos) gives the k-th entry in transposed order (column by column, each in the
+// caller's order).  Where each entry goes is what sell_fill and the ELLPACK set-up do with a column and a value.
+template <class Src>
+inline void spmm_transpose_fill(TransposeIndex& t, Src src)
+{
+  const int n = t.n;
+  t.row.assign((size_t)t.entries(), 0); t.pos.assign((size_t)t.entries(), -1);
+  const std::vector<long long>& cp = t.colptr;
+  if (t.fmt != DLA_SPMM_SELL) {
+    for (int j = 0; j < n; ++j)
+      for (int q = 0; q < t.w; ++q) {
+        const size_t d = (size_t)q * n + j;
+        if (cp[j] + q < cp[j + 1]) src(cp[j] + q, &t.row[d], &t.pos[d]);
+        else t.row[d] = j;
+      }
+    return;
+  }
+  const SellLayout& s = t.lay;
+  for (int sl = 0; sl < s.slices; ++sl) {
+    const long long base = s.slice_ptr[sl];
+    const int width = (int)((s.slice_ptr[sl + 1] - base) / SELL_C);
+    for (int lane = 0; lane < SELL_C; ++lane) {
+      const int slot = sl * SELL_C + lane;
+      const bool tail = slot < n && s.perm[slot] < 0;
+      const int j = slot < n ? (tail ? ~s.perm[slot] : s.perm[slot]) : 0;
+      const int lj = (slot < n && !tail) ? (int)(cp[j + 1] - cp[j]) : 0;
+      for (int q = 0; q < width; ++q) {
+        const size_t d = (size_t)(base + (long long)q * SELL_C + lane);
+        if (q < lj) src(cp[j] + q, &t.row[d], &t.pos[d]);
+        else t.row[d] = j;
+      }
+    }
+  }
+  for (size_t r = 0; r < s.long_row.size(); ++r) {
+    const int j = s.long_row[r];
+    for (long long e = s.long_ptr[r]; e < s.long_ptr[r + 1]; ++e) {
+      const size_t d = (size_t)(s.stored + e);
+      src(cp[j] + (e - s.long_ptr[r]), &t.row[d], &t.pos[d]);
+    }
+  }
+}
+// the whole index from host CSR arrays that have passed spmm_csr_check; a_fmt / a_layout: how A is stored (spmm_stored_positions)
+inline int spmm_transpose_build(int n, const long long* rowptr, const int* colind, int a_fmt, int a_w, const SellLayout* a_layout, int format,
+                                TransposeIndex& t, std::string& err)
+{
+  const long long p0 = rowptr[0], nnz = rowptr[n] - p0;
+  const long long a_entries = a_fmt == DLA_SPMM_SELL ? a_layout->stored + a_layout->long_entries : (long long)a_w * n;
+  std::vector<long long> colptr((size_t)n + 1, 0);
+  for (long long p = p0; p < p0 + nnz; ++p) ++colptr[(size_t)colind[p] + 1];
+  for (int j = 0; j < n; ++j) colptr[(size_t)j + 1] += colptr[j];
+  { const int stc = spmm_transpose_layout(n, colptr.data(), format, a_entries, t, err); if (stc) return stc; }
+  std::vector<long long> apos;
+  spmm_stored_positions(n, rowptr, a_fmt, a_layout, apos);
+  // a stable counting sort of the entries by column: ascending position in the caller's arrays inside every column
+  std::vector<long long> next(colptr.begin(), colptr.end() - 1);
+  std::vector<int> srow((size_t)nnz), spos((size_t)nnz);
+  for (int i = 0; i < n; ++i)
+    for (long long p = rowptr[i]; p < rowptr[i + 1]; ++p) {
+      const size_t k = (size_t)next[(size_t)colind[p]]++;
+      srow[k] = i; spos[k] = (int)apos[(size_t)(p - p0)];
+    }
+  spmm_transpose_fill(t, [&](long long k, int* row, int* pos) { *row = srow[(size_t)k]; *pos = spos[(size_t)k]; });
+  return DLA_OK;
 }
 
 // ---- the scalars of the Chebyshev preconditioner (include/diaglib_amd.h, dla_spmm_precnd_cheb; Saad, Iterative Methods, Algorithm

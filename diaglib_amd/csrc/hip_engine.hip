@@ -80,6 +80,12 @@ template <int V, int NT> __device__ __forceinline__ void pstore(double* p, typen
     }                                                                                 \
   } while (0)
 
+// spmm_transpose_sort.hip: the stable sort of (key, value) pairs behind dla_spmm_transpose_prepare
+namespace dla {
+hipError_t sort_pairs_by_key(void* temp, size_t* temp_bytes, const int* key_in, int* key_out, const int* val_in, int* val_out,
+                             size_t count, int key_bits, hipStream_t st);
+}
+
 namespace {
 
 // ======================================================================================
@@ -1927,6 +1933,130 @@ __global__ __launch_bounds__(256) void long_rows_combine_kernel(int n, int m, in
   }
 }
 
+// ---- y = A^T x through the transposed index of the stored operator (dla::TransposeIndex; the contract: include/diaglib_amd.h,
+// dla_spmm_transpose_prepare).  The three kernels above with the value fetched through a position: where they read (col, val) the
+// index gives (row, pos) -- the row of x to gather, and where A's stored value array holds the entry -- so per entry 8 bytes of
+// index stream coalesced and the 8 bytes of the value are a second gather (into val, beside the one into x).  pos < 0 is padding:
+// it is skipped, so y_j = fma over the entries of column j in stored order from 0.0 and nothing else.  Padding only follows a
+// column's entries, never precedes them.
+// ELLPACK: the thread keeps its w (row, fetched value) pairs in registers across the m right-hand sides as ell_rows does, and the
+// count of real entries beside them.
+template <int W>
+__global__ __launch_bounds__(256) void ell_spmm_t_kernel(int n, int m, int w, const int* __restrict__ trow, const int* __restrict__ tpos,
+                                                         const double* __restrict__ val, const double* __restrict__ x,
+                                                         double* __restrict__ y)
+{
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    if constexpr (W > 0) {
+      int rj[W]; double vj[W];
+      int cnt = 0;
+#pragma unroll
+      for (int q = 0; q < W; ++q) {
+        const int p = q < w ? tpos[(size_t)q * n + i] : -1;
+        const bool in = p >= 0;
+        rj[q] = in ? trow[(size_t)q * n + i] : i;
+        vj[q] = in ? val[p] : 0.0;
+        cnt += in ? 1 : 0;
+      }
+      for (int c = 0; c < m; ++c) {
+        const double* xc = x + (size_t)c * n;
+        double s = 0.0;
+#pragma unroll
+        for (int q = 0; q < W; ++q) s = q < cnt ? fma(vj[q], xc[rj[q]], s) : s;
+        __builtin_nontemporal_store(s, y + (size_t)c * n + i);
+      }
+    } else {
+      for (int c = 0; c < m; ++c) {
+        const double* xc = x + (size_t)c * n;
+        double s = 0.0;
+        for (int q = 0; q < w; ++q) {
+          const int p = tpos[(size_t)q * n + i];
+          if (p < 0) break;
+          s = fma(val[p], xc[trow[(size_t)q * n + i]], s);
+        }
+        __builtin_nontemporal_store(s, y + (size_t)c * n + i);
+      }
+    }
+  }
+}
+// sliced: sell_spmm_kernel<MC> with the fetch; perm[slot] is the COLUMN of A a slot computes
+template <int MC>
+__global__ __launch_bounds__(256) void sell_spmm_t_kernel(int n, int m, int slices, const long long* __restrict__ slice_ptr,
+                                                          const int* __restrict__ perm, const int* __restrict__ trow,
+                                                          const int* __restrict__ tpos, const double* __restrict__ val,
+                                                          const double* __restrict__ x, double* __restrict__ y)
+{
+  const int lane = threadIdx.x & 63;
+  for (int s = blockIdx.x * 4 + (threadIdx.x >> 6); s < slices; s += gridDim.x * 4) {
+    const long long p0 = slice_ptr[s];
+    const int width = (int)((slice_ptr[s + 1] - p0) >> 6);
+    const int slot = s * 64 + lane;
+    const int out = slot < n ? perm[slot] : -1;
+    const int* rs = trow + p0 + lane;
+    const int* ps = tpos + p0 + lane;
+    for (int c0 = 0; c0 < m; c0 += MC) {
+      const double* xc = x + (size_t)c0 * n;
+      const int mc = min(MC, m - c0);
+      double acc[MC];
+#pragma unroll
+      for (int k = 0; k < MC; ++k) acc[k] = 0.0;
+      for (int q = 0; q < width; ++q) {
+        const int pj = ps[(size_t)q * 64];
+        if (pj < 0) continue;
+        const int rj = rs[(size_t)q * 64];
+        const double vj = val[pj];
+#pragma unroll
+        for (int k = 0; k < MC; ++k) if (k < mc) acc[k] = fma(vj, xc[(size_t)k * n + rj], acc[k]);
+      }
+      if (out >= 0) {
+#pragma unroll
+        for (int k = 0; k < MC; ++k) if (k < mc) __builtin_nontemporal_store(acc[k], y + (size_t)(c0 + k) * n + out);
+      }
+    }
+  }
+}
+// the tail of the index: csr_long_segments_kernel<MC> with the fetch (a tail holds no padding); long_rows_combine_kernel adds the
+// partial sums of the columns of more than one segment
+template <int MC>
+__global__ __launch_bounds__(256) void csr_long_segments_t_kernel(int n, int m, int nseg, const long long* __restrict__ seg_ptr,
+                                                                  const int* __restrict__ seg_row, const int* __restrict__ seg_part,
+                                                                  const int* __restrict__ long_row, const int* __restrict__ trow,
+                                                                  const int* __restrict__ tpos, const double* __restrict__ val,
+                                                                  const double* __restrict__ x, double* __restrict__ y,
+                                                                  double* __restrict__ part)
+{
+  const int lane = threadIdx.x & 63;
+  for (int g = blockIdx.x * 4 + (threadIdx.x >> 6); g < nseg; g += gridDim.x * 4) {
+    const int out = long_row[seg_row[g]];
+    const int slot = seg_part[g];
+    const long long p0 = seg_ptr[g], p1 = seg_ptr[g + 1];
+    for (int c0 = 0; c0 < m; c0 += MC) {
+      const double* xc = x + (size_t)c0 * n;
+      const int mc = min(MC, m - c0);
+      double acc[MC];
+#pragma unroll
+      for (int k = 0; k < MC; ++k) acc[k] = 0.0;
+      for (long long p = p0 + lane; p < p1; p += 64) {
+        const int rj = trow[p];
+        const double vj = val[tpos[p]];
+#pragma unroll
+        for (int k = 0; k < MC; ++k) if (k < mc) acc[k] = fma(vj, xc[(size_t)k * n + rj], acc[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < MC; ++k)
+        for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
+      if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < MC; ++k)
+          if (k < mc) {
+            if (slot < 0) y[(size_t)(c0 + k) * n + out] = acc[k];
+            else part[(size_t)slot * m + (c0 + k)] = acc[k];
+          }
+      }
+    }
+  }
+}
+
 // ---- the Chebyshev polynomial preconditioner on the stored operator (the contract: include/diaglib_amd.h, dla_spmm_precnd_cheb).
 // One step is z_{k+1} = alpha u + beta v + gamma x + eta (A u) with u = z_k, v = z_{k-1} (dla::cheb_coefficients): the product
 // kernels above with the combination as their epilogue, so that A u never travels to HBM.  Per step 12 w n bytes of matrix, the
@@ -2329,7 +2459,7 @@ __device__ __forceinline__ void tail_walk(int nseg, long long stored, const long
   for (int g = blockIdx.x * 4 + (threadIdx.x >> 6); g < nseg; g += gridDim.x * 4) {
     const int r = seg_row[g];
     const long long src0 = rowptr[long_row[r]] + shift - long_ptr[r];
-    for (long long t = seg_ptr[g] + lane; t < seg_ptr[g + 1]; t += 64) f((size_t)(stored + t), src0 + t, 0);
+    for (long long t = seg_ptr[g] + lane; t < seg_ptr[g + 1]; t += 64) f((size_t)(stored + t), src0 + t, long_row[r]);
   }
 }
 
@@ -2438,6 +2568,68 @@ __global__ __launch_bounds__(256) void pattern_compare_kernel(int n, int w, int 
     ell_walk(n, w, rowptr, shift, same);
   }
   if (bad) atomicOr(flag, bad);
+}
+
+// ---- building the transposed index of a stored matrix (dla_spmm_transpose_prepare; dla::TransposeIndex is the host twin).  The
+// entries never leave the device, and no result depends on the arrival order of anything: every element below has one writer.
+// Pass 1, over A's own layout through the walkers that filled it (the stored row pointers, shift 0): entry e = p - rowptr[0] of the
+// caller's arrays learns its column (the sort key), its row and the position d of its value in A's blocks; ident[e] = e is the
+// sort's payload.
+template <bool SELL>
+__global__ __launch_bounds__(256) void stored_positions_kernel(int n, int w, int slices, int nseg, long long stored,
+                                                               const long long* __restrict__ slice_ptr, const int* __restrict__ perm,
+                                                               const long long* __restrict__ seg_ptr, const int* __restrict__ seg_row,
+                                                               const int* __restrict__ long_row, const long long* __restrict__ long_ptr,
+                                                               const long long* __restrict__ rowptr, const int* __restrict__ col,
+                                                               int* __restrict__ key, int* __restrict__ ident, int* __restrict__ erow,
+                                                               int* __restrict__ epos)
+{
+  const long long first = rowptr[0];
+  auto note = [&](size_t d, long long p, int i) {
+    if (p < 0) return;
+    const long long e = p - first;
+    key[e] = col[d]; ident[e] = (int)e; erow[e] = i; epos[e] = (int)d;
+  };
+  if constexpr (SELL) {
+    sell_walk(n, slices, slice_ptr, perm, rowptr, 0, note);
+    tail_walk(nseg, stored, seg_ptr, seg_row, long_row, long_ptr, rowptr, 0, note);
+  } else {
+    ell_walk(n, w, rowptr, 0, note);
+  }
+}
+// Pass 2 (behind the stable sort of (key, ident) by key): the column pointers from the sorted keys.  Entry k writes colptr[c] = k for
+// every column c in (key[k - 1], key[k]] -- its own column and the empty ones in front of it -- and the last entry closes the rest.
+__global__ __launch_bounds__(256) void column_pointers_kernel(long long nnz, int n, const int* __restrict__ key, long long* __restrict__ colptr)
+{
+  for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < nnz; k += (long long)gridDim.x * 256) {
+    const int c1 = key[k];
+    for (int c = k > 0 ? key[k - 1] + 1 : 0; c <= c1; ++c) colptr[c] = k;
+    if (k == nnz - 1)
+      for (int c = c1 + 1; c <= n; ++c) colptr[c] = nnz;
+  }
+}
+// Pass 3, over the INDEX's layout through the same walkers, with the column pointers as its row pointers: element d takes the k-th
+// entry in sorted order, or padding (position -1, the column itself as its row)
+template <bool SELL>
+__global__ __launch_bounds__(256) void transpose_fill_kernel(int n, int w, int slices, int nseg, long long stored,
+                                                             const long long* __restrict__ slice_ptr, const int* __restrict__ perm,
+                                                             const long long* __restrict__ seg_ptr, const int* __restrict__ seg_row,
+                                                             const int* __restrict__ long_row, const long long* __restrict__ long_ptr,
+                                                             const long long* __restrict__ colptr, const int* __restrict__ sorted,
+                                                             const int* __restrict__ erow, const int* __restrict__ epos,
+                                                             int* __restrict__ trow, int* __restrict__ tpos)
+{
+  auto place = [&](size_t d, long long k, int j) {
+    const int e = k >= 0 ? sorted[k] : 0;
+    trow[d] = k >= 0 ? erow[e] : j;
+    tpos[d] = k >= 0 ? epos[e] : -1;
+  };
+  if constexpr (SELL) {
+    sell_walk(n, slices, slice_ptr, perm, colptr, 0, place);
+    tail_walk(nseg, stored, seg_ptr, seg_row, long_row, long_ptr, colptr, 0, place);
+  } else {
+    ell_walk(n, w, colptr, 0, place);
+  }
 }
 
 // px = x / (d + fac) where |d + fac| > 1e-5, else x: the harness' diagonal preconditioner (main.f90:161-169) on the
@@ -6656,10 +6848,19 @@ struct HipEngine : dla::Engine {
   static hipError_t up(void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; }
   int place_sell(SparseOp& op, int n, const dla::SellLayout& L, const long long* rowptr)
   {
-    const size_t tot = (size_t)(L.stored + L.long_entries), nl = L.long_row.size(), ns = L.seg_row.size(), nm = L.multi_row.size();
+    const size_t tot = (size_t)(L.stored + L.long_entries);
     HIPCHK(op.col.reserve(tot));
     HIPCHK(op.val.reserve(tot));
     HIPCHK(op.diag.reserve((size_t)n));
+    HIPCHK(op.rowptr.reserve((size_t)n + 1));
+    { const int stc = place_sell_tables(op, n, L); if (stc) return stc; }
+    HIPCHK(up(op.rowptr, rowptr, sizeof(long long) * ((size_t)n + 1)));
+    return DLA_OK;
+  }
+  // ... the tables alone: what a layout consists of besides its entries (the transposed index has a layout and other entries)
+  int place_sell_tables(SparseOp& op, int n, const dla::SellLayout& L)
+  {
+    const size_t nl = L.long_row.size(), ns = L.seg_row.size(), nm = L.multi_row.size();
     HIPCHK(op.sell_ptr.reserve(L.slice_ptr.size()));
     HIPCHK(op.sell_perm.reserve((size_t)n));
     HIPCHK(op.long_row.reserve(std::max<size_t>(1, nl)));
@@ -6668,7 +6869,6 @@ struct HipEngine : dla::Engine {
     HIPCHK(op.seg_part.reserve(std::max<size_t>(1, ns)));
     HIPCHK(op.multi_row.reserve(std::max<size_t>(1, nm)));
     HIPCHK(op.part_ptr.reserve(nm + 1));
-    HIPCHK(op.rowptr.reserve((size_t)n + 1));
     HIPCHK(op.long_ptr.reserve(nl + 1));
     HIPCHK(up(op.sell_ptr, L.slice_ptr.data(), sizeof(long long) * L.slice_ptr.size()));
     HIPCHK(up(op.sell_perm, L.perm.data(), sizeof(int) * (size_t)n));
@@ -6678,7 +6878,6 @@ struct HipEngine : dla::Engine {
     HIPCHK(up(op.seg_part, L.seg_part.data(), sizeof(int) * ns));
     HIPCHK(up(op.multi_row, L.multi_row.data(), sizeof(int) * nm));
     HIPCHK(up(op.part_ptr, L.part_ptr.data(), sizeof(int) * (nm + 1)));
-    HIPCHK(up(op.rowptr, rowptr, sizeof(long long) * ((size_t)n + 1)));
     HIPCHK(up(op.long_ptr, L.long_ptr.data(), sizeof(long long) * (nl + 1)));
     return DLA_OK;
   }
@@ -6866,7 +7065,7 @@ struct HipEngine : dla::Engine {
     if (stc == DLA_ERR_ARG && quoted) err = quote(slot, entry) + err;
     if (slot == dla::SPMM_A) cheb.upper_valid = cheb.off_valid = false;
     if (slot == dla::SPMM_B) cheb.offb_valid = false;
-    if (!stc && slot == dla::SPMM_A) shard.drop();
+    if (!stc && slot == dla::SPMM_A) { shard.drop(); tidx.drop(); }     // (a new pattern: the transposed index of the old one goes)
     return stc;
   }
   int op_info(const SparseOp& op, struct dla_spmm_info* out) const
@@ -6901,6 +7100,7 @@ struct HipEngine : dla::Engine {
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamSynchronize(st));     // (products of these slots may still be queued)
     for (int s = first; s <= last; ++s) ops[s].drop();
+    if (first <= dla::SPMM_A && dla::SPMM_A <= last) tidx.drop();
     if (first <= dla::SPMM_A && dla::SPMM_A <= last) cheb.upper_valid = cheb.off_valid = false;
     if (first <= dla::SPMM_B && dla::SPMM_B <= last) cheb.offb_valid = false;
     return DLA_OK;
@@ -6959,6 +7159,154 @@ struct HipEngine : dla::Engine {
     HIPCHK(hipGetLastError());
     return DLA_OK;
   }
+  // ---- y = A^T x through the transposed index of slot A (the contract: include/diaglib_amd.h, dla_spmm_transpose_prepare; the
+  // kernels: beside ell_spmm_t_kernel and stored_positions_kernel).  The index is a layout of its own over the COLUMN lengths of A --
+  // the tables of a SparseOp without its entries -- plus (row, pos) per stored entry and its own workspace of partial sums.  It
+  // belongs to A's stored pattern: spmm_setup, spmm_setup_csr_sharded and spmm_drop give it up, a refresh of the values keeps it.
+  struct TransposeIdx {
+    // the index's own layout over the column lengths of A: the tables and counts of a stored matrix, with the source rows where a matrix
+    // has its columns (lay.col) and the workspace of partial sums; lay.val, lay.diag and lay.rowptr stay empty
+    SparseOp lay;
+    DeviceBuffer<int> pos;             // [entries], beside lay.col: where A's stored values hold the entry; -1: padding
+    bool held() const { return lay.fmt >= 0; }
+    // (the caller has waited for the stream)
+    void drop() { lay.drop(); pos.reset(); }
+  };
+  TransposeIdx tidx;
+  int spmm_transpose_prepare(int format) override
+  {
+    const char* who = "spmm_transpose_prepare: ";
+    SparseOp& op = ops[dla::SPMM_A];
+    if (op.fmt < 0) { err = std::string(who) + "no operator has been set up"; return DLA_ERR_ARG; }
+    if (shard.on) { err = std::string(who) + "the operator of this context is row-sharded, and a transposed index of a row shard is not supported"; return DLA_ERR_ARG; }
+    if (format != DLA_SPMM_ELL && format != DLA_SPMM_SELL && format != DLA_SPMM_AUTO) { err = std::string(who) + "unknown format"; return DLA_ERR_ARG; }
+    const bool a_sell = op.fmt == DLA_SPMM_SELL;
+    const int n = op.n;
+    const long long nnz = op.nnz, a_entries = a_sell ? op.sell_stored + op.sell_long_entries : (long long)op.w * n;
+    if (a_entries > 2147483647LL) {
+      err = std::string(who) + "the operator stores " + std::to_string(a_entries) + " entries, and positions beyond 2147483647 do not fit the index";
+      return DLA_ERR_ARG;
+    }
+    bind();
+    HIPCHK(hipStreamSynchronize(st));
+    // the temporaries, 24 bytes per entry and the sort's own: released when this function returns
+    DeviceBuffer<int> key, ident, erow, epos, key_sorted, sorted;
+    DeviceBuffer<long long> colptr;
+    DeviceBuffer<char> sort_temp;
+    for (DeviceBuffer<int>* b : {&key, &ident, &erow, &epos, &key_sorted, &sorted}) HIPCHK(b->reserve((size_t)nnz));
+    HIPCHK(colptr.reserve((size_t)n + 1));
+    int key_bits = 1;
+    while (key_bits < 31 && (1LL << key_bits) < (long long)n) ++key_bits;
+    size_t temp_bytes = 0;
+    HIPCHK(dla::sort_pairs_by_key(nullptr, &temp_bytes, key, key_sorted, ident, sorted, (size_t)nnz, key_bits, st));
+    HIPCHK(sort_temp.reserve(std::max<size_t>(1, temp_bytes)));
+    // one launch over a layout's rows, slices and tail segments at once
+    auto walk_blocks = [&](const SparseOp& o) {
+      const bool sell = o.fmt == DLA_SPMM_SELL;
+      const SpmmSetupPlan p = spmm_setup_plan(env(), n, nnz, sell ? o.sell_slices : 0, sell ? o.sell_long_segments : 0);
+      return dim3(std::max(p.row_blocks, std::max(p.slice_blocks, p.seg_blocks)));
+    };
+#define LAYOUT_OF(O) n, (O).w, (O).sell_slices, (O).sell_long_segments, (O).sell_stored, (const long long*)(O).sell_ptr, (const int*)(O).sell_perm, \
+                     (const long long*)(O).seg_ptr, (const int*)(O).seg_row, (const int*)(O).long_row, (const long long*)(O).long_ptr
+    if (a_sell) DLA_LAUNCH((stored_positions_kernel<true>), walk_blocks(op), dim3(256), 0, st, LAYOUT_OF(op), (const long long*)op.rowptr, (const int*)op.col,
+                           (int*)key, (int*)ident, (int*)erow, (int*)epos);
+    else DLA_LAUNCH((stored_positions_kernel<false>), walk_blocks(op), dim3(256), 0, st, LAYOUT_OF(op), (const long long*)op.rowptr, (const int*)op.col,
+                    (int*)key, (int*)ident, (int*)erow, (int*)epos);
+    HIPCHK(hipGetLastError());
+    HIPCHK(dla::sort_pairs_by_key((char*)sort_temp, &temp_bytes, key, key_sorted, ident, sorted, (size_t)nnz, key_bits, st));
+    DLA_LAUNCH(column_pointers_kernel, dim3(grid_blocks(env(), nnz, 256)), dim3(256), 0, st, nnz, n, (const int*)key_sorted, (long long*)colptr);
+    HIPCHK(hipGetLastError());
+    std::vector<long long> cp((size_t)n + 1);
+    HIPCHK(hipMemcpyAsync(cp.data(), (const long long*)colptr, sizeof(long long) * cp.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    // the host lays the index out (dla::spmm_transpose_layout: the format rule and dla::sell_layout on the column lengths)
+    dla::TransposeIndex T;
+    { const int stc = dla::spmm_transpose_layout(n, cp.data(), format, a_entries, T, err); if (stc) return stc; }
+    // everything is allocated in a fresh index; the one in use is given up only when the new one is complete
+    TransposeIdx fresh;
+    SparseOp& lay = fresh.lay;
+    HIPCHK(lay.col.reserve((size_t)T.entries()));
+    HIPCHK(fresh.pos.reserve((size_t)T.entries()));
+    if (T.fmt == DLA_SPMM_SELL) {
+      { const int stc = place_sell_tables(lay, n, T.lay); if (stc) return stc; }
+      hold_sell(lay, n, T.lay);
+    } else {
+      lay.n = n; lay.w = T.w; lay.fmt = DLA_SPMM_ELL; lay.nnz = nnz;
+    }
+    if (T.fmt == DLA_SPMM_SELL) DLA_LAUNCH((transpose_fill_kernel<true>), walk_blocks(lay), dim3(256), 0, st, LAYOUT_OF(lay), (const long long*)colptr,
+                                           (const int*)sorted, (const int*)erow, (const int*)epos, (int*)lay.col, (int*)fresh.pos);
+    else DLA_LAUNCH((transpose_fill_kernel<false>), walk_blocks(lay), dim3(256), 0, st, LAYOUT_OF(lay), (const long long*)colptr, (const int*)sorted,
+                    (const int*)erow, (const int*)epos, (int*)lay.col, (int*)fresh.pos);
+#undef LAYOUT_OF
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    tidx = std::move(fresh);
+    return DLA_OK;
+  }
+  int spmm_transpose_info(struct dla_spmm_info* out) override
+  {
+    if (!tidx.held()) { err = "spmm_transpose_info: no transposed index has been prepared (dla_spmm_transpose_prepare)"; return DLA_ERR_ARG; }
+    const int stc = op_info(tidx.lay, out);
+    // (the index arrays only: 8 bytes per entry where a matrix has 12, and no diagonal)
+    out->device_bytes -= 4 * (out->stored + out->long_entries) + 8 * (long long)out->n;
+    return stc;
+  }
+  // (no index: neither the device nor the stream is touched)
+  int spmm_transpose_drop() override
+  {
+    if (!tidx.held()) return DLA_OK;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipStreamSynchronize(st));     // (products may still be queued)
+    tidx.drop();
+    return DLA_OK;
+  }
+  int spmm_mul_t(int n, int m, const double* x, double* y) override
+  {
+    const SparseOp& op = ops[dla::SPMM_A];
+    SparseOp& t = tidx.lay;
+    if (op.fmt < 0) { err = "spmm_matvec_t: no operator has been set up"; return DLA_ERR_ARG; }
+    if (!tidx.held()) { err = "spmm_matvec_t: no transposed index (dla_spmm_matvec_t before dla_spmm_transpose_prepare)"; return DLA_ERR_ARG; }
+    if (n != op.n) { err = "spmm_matvec_t: n differs from setup"; return DLA_ERR_ARG; }
+    const double* val = op.val;
+    const int *row = t.col, *pos = tidx.pos;
+    const double flops = 2.0 * (double)t.nnz * m;
+    if (t.fmt == DLA_SPMM_SELL) {
+      const LongRowsPlan p = long_rows_plan(env(), t.sell_long_segments, t.sell_multi_rows, t.sell_multi_segments, m, LONG_MC);
+      if (p.part_doubles > t.long_part.capacity()) {
+        bind();
+        HIPCHK(hipStreamSynchronize(st));       // (queued products may still use the old block)
+        HIPCHK(t.long_part.reserve(p.part_doubles));
+      }
+      {
+        Scope s(this, DLA_OP_MATVEC, 8.0 * (double)(t.sell_stored + t.sell_long_entries) + 8.0 * (double)t.nnz + 4.0 * n + 16.0 * (double)n * m + 16.0 * (double)p.part_doubles,
+                flops, plan_name("sell_spmm_t_kernel<%d>", SELL_MC));
+        DLA_LAUNCH((sell_spmm_t_kernel<SELL_MC>), dim3(grid_blocks(env(), t.sell_slices, 4)), dim3(256), 0, st, n, m, t.sell_slices, (const long long*)t.sell_ptr,
+                   (const int*)t.sell_perm, row, pos, val, x, y);
+        HIPCHK(hipGetLastError());
+      }
+      if (t.sell_long_segments > 0) {
+        Scope s(this, DLA_OP_MATVEC, 0.0, 0.0, plan_name("csr_long_segments_t_kernel<%d>", LONG_MC));
+        DLA_LAUNCH((csr_long_segments_t_kernel<LONG_MC>), dim3(p.seg_blocks), dim3(256), 0, st, n, m, t.sell_long_segments, (const long long*)t.seg_ptr,
+                   (const int*)t.seg_row, (const int*)t.seg_part, (const int*)t.long_row, row + t.sell_stored, pos + t.sell_stored, val, x, y, (double*)t.long_part);
+        HIPCHK(hipGetLastError());
+      }
+      if (p.combine_blocks > 0) {
+        Scope s(this, DLA_OP_MATVEC, 0.0, 0.0, "long_rows_combine_kernel");
+        DLA_LAUNCH(long_rows_combine_kernel, dim3(p.combine_blocks), dim3(256), 0, st, n, m, t.sell_multi_rows, (const int*)t.multi_row, (const int*)t.part_ptr,
+                   (const double*)t.long_part, y);
+        HIPCHK(hipGetLastError());
+      }
+      return DLA_OK;
+    }
+    const dim3 grid(grid_blocks(env(), n, 256));
+    ell_width(t.w, [&](auto W) {
+      Scope s(this, DLA_OP_MATVEC, 8.0 * (double)t.w * n + 8.0 * (double)t.nnz + 16.0 * (double)n * m, flops, plan_name("ell_spmm_t_kernel<%d>", decltype(W)::value));
+      DLA_LAUNCH((ell_spmm_t_kernel<decltype(W)::value>), grid, dim3(256), 0, st, n, m, t.w, row, pos, val, x, y);
+    });
+    HIPCHK(hipGetLastError());
+    return DLA_OK;
+  }
+
   // ---- ... on a row shard (banded matrices: the columns of a shard reach at most `halo` rows into its neighbours); A only
   // all-reduce of a few host values through the engine's small-product transport (setup-time agreement between the ranks)
   bool has_transport() const override { return hook != nullptr || comm != nullptr || p2p.on; }
@@ -7024,6 +7372,7 @@ struct HipEngine : dla::Engine {
     cheb.upper_valid = cheb.off_valid = false;
     stc = upload_ell(ops[dla::SPMM_A], e.col, e.val, e.diag);
     if (stc) return stc;
+    tidx.drop();
     ops[dla::SPMM_A].n = n; ops[dla::SPMM_A].w = e.w; shard.halo = (int)halo; shard.on = true;
     ops[dla::SPMM_A].fmt = DLA_SPMM_ELL; ops[dla::SPMM_A].nnz = rowptr[n] - rowptr[0];
     return DLA_OK;

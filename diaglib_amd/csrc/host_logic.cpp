@@ -1239,6 +1239,7 @@ static const OwnCallback* own_callback(void* fn)
     {(void*)&dla_spmm_lrprec2, false, true}, {(void*)&dla_spmm_precnd_cheb, false, true},
     {(void*)&dla_spmm_precnd_cheb_jacobi, false, true}, {(void*)&dla_spmm_precnd_cheb_pencil, false, true},
     {(void*)&dla_dense_matvec, true, true}, {(void*)&dla_dense_bvec, true, true}, {(void*)&dla_dense_matvec_t, true, true},
+    {(void*)&dla_spmm_matvec_t, true, true},
     {(void*)&dla_dense_apbmul, true, true}, {(void*)&dla_dense_ambmul, true, true}, {(void*)&dla_dense_spdmul, true, true},
     {(void*)&dla_dense_smdmul, true, true},
     {(void*)&dla_dense_precnd, false, true}, {(void*)&dla_dense_precnd_pencil, false, true},
@@ -2002,6 +2003,29 @@ int dla_spmm_setup_csr_sharded(dla_ctx* c, int n_local, long long row0, long lon
 }
 void dla_spmm_matvec(const int* n, const int* m, const double* x, double* ax) { spmm_product(SPMM_A, n, m, x, ax); }
 void dla_spmm_precnd(const int* n, const int* m, const double* fac, const double* x, double* px) { spmm_precondition(0, n, m, fac, x, nullptr, px, nullptr); }
+// ... and its transposed index: y = A^T x from the stored values of A (the engine drops the index with every accepted set-up of A)
+int dla_spmm_transpose_prepare(dla_ctx* c, int format)
+{
+  DLA_T("dla_spmm_transpose_prepare");
+  if (!c) return DLA_ERR_ARG;
+  return engfail(c, c->eng->spmm_transpose_prepare(format));
+}
+int dla_spmm_transpose_info(dla_ctx* c, struct dla_spmm_info* out)
+{
+  if (!c || !out) return DLA_ERR_ARG;
+  return engfail(c, c->eng->spmm_transpose_info(out));
+}
+int dla_spmm_drop_transpose(dla_ctx* c)
+{
+  if (!c) return DLA_ERR_ARG;
+  return engfail(c, c->eng->spmm_transpose_drop());
+}
+void dla_spmm_matvec_t(const int* n, const int* m, const double* x, double* y)
+{
+  dla_ctx* c = g_spmm_ctx;
+  if (!c) { callback_failed(DLA_ERR_ARG, "dla_spmm_matvec_t before dla_spmm_setup_csr: no operator has been set up"); return; }
+  if (int st = c->eng->spmm_mul_t(*n, *m, x, y)) callback_failed(st, "dla_spmm_matvec_t failed: " + c->eng->err);
+}
 // ... and the Chebyshev polynomial of A + fac I as its preconditioner.  The configuration is the context's and binds nothing: like
 // info, refresh and drop it leaves the thread's callbacks on the context they act on.
 int dla_spmm_cheb_config(dla_ctx* c, int steps, double lo_fraction)

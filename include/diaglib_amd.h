@@ -90,7 +90,7 @@ enum {
                                       takes another route than planned the operator is called a SECOND time on the finished
                                       block and its first output is dropped -- the reference calls matvec exactly once per
                                       block (diaglib.f90:1685, 394-397), so:
-                                      1 (default): only for the library's own device operators (dla_synth_*, dla_spmm_matvec, dla_spmm_bvec, dla_spmm_apbmul .. _smdmul, dla_dense_matvec, dla_dense_matvec_t, dla_dense_bvec, dla_dense_apbmul .. _smdmul),
+                                      1 (default): only for the library's own device operators (dla_synth_*, dla_spmm_matvec, dla_spmm_matvec_t, dla_spmm_bvec, dla_spmm_apbmul .. _smdmul, dla_dense_matvec, dla_dense_matvec_t, dla_dense_bvec, dla_dense_apbmul .. _smdmul),
                                          which are pure functions of their input; a caller's callback is called once, in order;
                                       2: also for the caller's device-mode callbacks (ordering contract 0 or 2) -- the caller
                                          states that the operator keeps no state between calls;
@@ -614,6 +614,50 @@ void dla_spmm_spdmul(const int* n, const int* m, const double* x_dev, double* y_
 void dla_spmm_smdmul(const int* n, const int* m, const double* x_dev, double* y_dev);          /* y = (S-D) x */
 void dla_spmm_lrprec1(const int* n, const int* m, const double* fac, const double* xp_dev, const double* xm_dev, double* yp_dev, double* ym_dev);
 void dla_spmm_lrprec2(const int* n, const int* m, const double* fac, const double* xp_dev, const double* xm_dev, double* yp_dev, double* ym_dev);
+
+/* ---------------------------------------------------------------- y = A^T x from the one stored copy of the sparse operator
+ * The left pass of nonsym_driver needs matvec_l = A^T x.  The stored operator keeps its values once: dla_spmm_transpose_prepare
+ * builds a TRANSPOSED INDEX of slot A (single rank, any stored format of A, host and device set-ups alike), and dla_spmm_matvec_t
+ * forms A^T x by fetching A's stored values through it.  The index holds two int32 per stored entry -- the source row, and the
+ * position of the value in A's stored value array (the tail of a sliced A lies behind its `stored` padded entries) -- 8 bytes per
+ * entry where a transposed copy would cost 12 and a second refresh: dla_spmm_refresh_values_dev on A is at once a refresh of A^T,
+ * and nothing can get out of step.
+ * Layout.  The index is laid out by the code that lays out a matrix, applied to the COLUMN lengths of A: `format` is ELL, SELL or
+ * AUTO as in dla_spmm_setup_csr_fmt (AUTO: ELLPACK while longest column x n / nnz is at most 1.25), columns above
+ * long_row_threshold entries go to the index's tail, in segments of long_segment_entries.  A matrix of short rows with one dense
+ * column therefore gets a tail in the index although A itself is ELLPACK, and a matrix with a dense row has positions that point
+ * into A's tail values.  A padding entry has position -1 and takes part in no arithmetic.  dla_spmm_transpose_info describes the
+ * index in the fields of dla_spmm_info: format is never AUTO, nnz equals A's, stored / slices / long_rows / long_entries / the
+ * segment counts describe the index, and device_bytes counts the index arrays only (8 bytes per stored entry plus the tables of a
+ * sliced layout).  A set-up whose stored positions do not fit int32 is refused.
+ * Order of summation.  The entries of column j are taken in ascending index of the caller's CSR arrays -- ascending source row;
+ * duplicates and unsorted columns keep the caller's order.  Outside the index's tail y_j starts from 0.0 and takes one
+ * fma(value, x[row], acc) per entry in that order; a tail column follows the tail-row contract above on that list, word for word
+ * (lanes striding over a segment, the butterfly with off = 32 .. 1, segments added in ascending order by one thread); a column with
+ * no entry gives +0.0.  So dla_spmm_matvec_t returns, bit for bit, what dla_spmm_bvec returns for a metric slot holding the
+ * explicitly (stably) transposed CSR arrays in the index's format.  The other guarantees are the forward product's: no atomics,
+ * one writer per element of the result and of the workspace of partial sums (which belongs to the index), bit-identical repeats,
+ * the same bits from host and device set-ups of A, x unchanged and not overlapping y, nothing outside the n x m result written,
+ * every element within (len_j + 2) eps (|A|^T |x|)_j with len_j the column's length, exact on small-integer data.
+ * Lifecycle.  The index belongs to the stored PATTERN of A: every accepted set-up of slot A through any entry (the sharded one
+ * included) drops it, a refused set-up leaves it and its bits alone, dla_spmm_refresh_values_dev keeps it (the next product uses
+ * the new values without another prepare), and preparing again replaces it -- all or nothing: everything is checked and allocated
+ * before the index in use is given up.  Preparing never changes what dla_spmm_info answers for A, nor the bits of dla_spmm_matvec,
+ * dla_spmm_precnd, the Chebyshev forms or any other slot.  The call is synchronous on dla_stream like the device set-ups; only
+ * n + 1 column pointers travel to the host, the entries are sorted (a stable radix sort by column) and scattered by kernels, and
+ * the temporaries are freed before it returns.
+ * Refusals (DLA_ERR_ARG, the message names the entry and the cause).  dla_spmm_transpose_prepare: no operator stored, a row-sharded
+ * operator, an unknown format.  dla_spmm_transpose_info: no index.  dla_spmm_matvec_t fails through the status of dla_call_matvec
+ * and writes nothing: no operator, no index ("dla_spmm_matvec_t before dla_spmm_transpose_prepare"), another n.
+ * dla_spmm_matvec_t is a pure function of its input (DLA_OPT_RUN_AHEAD = 1 covers it).
+ * Statistics.  A product books under DLA_OP_MATVEC alg_bytes = 8 (stored entries of the index) + 8 nnz + 16 n m -- plus, for a
+ * sliced index, what the forward product adds: 4 n for the permutation and 16 bytes per partial sum -- and flops = 2 nnz m, under
+ * the name of the kernel that walks the ELLPACK or sliced part (ell_spmm_t_kernel<W>, sell_spmm_t_kernel<8>); the tail's kernels
+ * (csr_long_segments_t_kernel<4>, long_rows_combine_kernel) book a launch each under their own names. */
+int  dla_spmm_transpose_prepare(dla_ctx* ctx, int format);            /* ELL / SELL / AUTO, applied to the TRANSPOSED pattern */
+int  dla_spmm_transpose_info(dla_ctx* ctx, struct dla_spmm_info* out); /* layout of the index; DLA_ERR_ARG while none */
+int  dla_spmm_drop_transpose(dla_ctx* ctx);                            /* frees the index; no-op without one */
+void dla_spmm_matvec_t(const int* n, const int* m, const double* x_dev, double* y_dev);          /* y = A^T x */
 
 /* ---------------------------------------------------------------- Chebyshev polynomial preconditioner on the stored operator
  * dla_spmm_precnd and dla_spmm_precnd_pencil divide by a diagonal, which does nothing for a stencil, FEM or graph matrix whose

@@ -52,6 +52,7 @@ EXPORTS = [
     "dla_spmm_setup_lr_csr", "dla_spmm_setup_lr_csr_dev", "dla_spmm_refresh_lr_values_dev", "dla_spmm_lr_info", "dla_spmm_drop_lr",
     "dla_spmm_apbmul", "dla_spmm_ambmul", "dla_spmm_spdmul", "dla_spmm_smdmul", "dla_spmm_lrprec1", "dla_spmm_lrprec2",
     "dla_dense_setup", "dla_dense_setup_dev", "dla_dense_info", "dla_dense_drop",
+    "dla_dense_setup_sym", "dla_dense_setup_sym_dev", "dla_dense_sym_info",
     "dla_dense_matvec", "dla_dense_matvec_t", "dla_dense_bvec", "dla_dense_precnd", "dla_dense_precnd_pencil",
     "dla_dense_setup_lr", "dla_dense_setup_lr_dev", "dla_dense_setup_lr_pair", "dla_dense_setup_lr_pair_dev", "dla_dense_lr_info",
     "dla_dense_drop_lr", "dla_dense_apbmul", "dla_dense_ambmul", "dla_dense_spdmul", "dla_dense_smdmul", "dla_dense_lrprec1",
@@ -100,6 +101,10 @@ class SpmmChebInfo(C.Structure):
 class DenseInfo(C.Structure):
     _fields_ = [("n", C.c_int), ("n_pad", C.c_int), ("row_tile", C.c_int), ("k_chunks", C.c_int), ("device_bytes", C.c_longlong),
                 ("workspace_bytes", C.c_longlong)]
+
+
+class DenseSymInfo(C.Structure):
+    _fields_ = [("uplo", C.c_int), ("panels", C.c_int), ("chunk_blocks", C.c_int), ("max_partials", C.c_int)]
 
 
 class DlaError(RuntimeError):
@@ -196,6 +201,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "dla_spmm_lrprec1": (None, [c_ip, c_ip, c_dp, vp, vp, vp, vp]), "dla_spmm_lrprec2": (None, [c_ip, c_ip, c_dp, vp, vp, vp, vp]),
         "dla_dense_setup": (i, [vp, i, i, vp, i]), "dla_dense_setup_dev": (i, [vp, i, i, vp, i]),
         "dla_dense_info": (i, [vp, i, C.POINTER(DenseInfo)]), "dla_dense_drop": (i, [vp, i]),
+        "dla_dense_setup_sym": (i, [vp, i, i, vp, i, C.c_char]), "dla_dense_setup_sym_dev": (i, [vp, i, i, vp, i, C.c_char]),
+        "dla_dense_sym_info": (i, [vp, i, C.POINTER(DenseSymInfo)]),
         "dla_dense_matvec": (None, [c_ip, c_ip, vp, vp]), "dla_dense_bvec": (None, [c_ip, c_ip, vp, vp]),
         "dla_dense_matvec_t": (None, [c_ip, c_ip, vp, vp]),
         "dla_dense_precnd": (None, [c_ip, c_ip, c_dp, vp, vp]), "dla_dense_precnd_pencil": (None, [c_ip, c_ip, c_dp, vp, vp]),
@@ -807,18 +814,25 @@ class Context:
         self._chk(self.lib.dla_spmm_drop_lr(self.h))
 
     # ---- the dense operator and metric (dla_dense_matvec, dla_dense_bvec, dla_dense_precnd, dla_dense_precnd_pencil)
-    def dense_setup(self, a, metric: bool = False) -> None:
+    def dense_setup(self, a, metric: bool = False, sym=None) -> None:
         """hand a dense n x n matrix to this context as its dense operator (metric: the metric B of A x = lambda B x); the library
         keeps a copy of its own, so ``a`` may be freed or overwritten afterwards.  ``a`` is a NumPy array (made float64 and
         Fortran-ordered) or a two-dimensional float64 torch tensor on the GPU with unit stride along its rows -- a column-major
-        view such as ``buf.T`` of a C-contiguous ``buf`` -- whose other stride is taken as lda; anything else is refused"""
-        self._dense_set_up("dense_setup", int(bool(metric)), a)
+        view such as ``buf.T`` of a C-contiguous ``buf`` -- whose other stride is taken as lda; anything else is refused.
+        sym = "L" or "U": the matrix is symmetric and only that triangle of ``a`` is read; the library stores one triangle
+        (dla_dense_setup_sym: about half the memory).  sym = None stores the matrix in full"""
+        if sym is None:
+            self._dense_set_up("dense_setup", int(bool(metric)), a)
+            return
+        if sym not in ("L", "U"):
+            raise ValueError(f"dense_setup: sym must be None, 'L' or 'U', not {sym!r}")
+        self._dense_set_up("dense_setup_sym", int(bool(metric)), a, sym.encode())
 
-    def _dense_set_up(self, who: str, k: int, a) -> None:
-        """slot number k through dla_<who>, or through dla_<who>_dev where ``a`` is on the device"""
+    def _dense_set_up(self, who: str, k: int, a, *more) -> None:
+        """slot number k through dla_<who>, or through dla_<who>_dev where ``a`` is on the device; more: what the entry takes after lda"""
         dev, a, n, lda = self._dense_array(who, "a", a)
         entry = getattr(self.lib, f"dla_{who}_dev" if dev else f"dla_{who}")
-        self._chk(entry(self.h, k, n, a.data_ptr() if dev else a.ctypes.data, lda))
+        self._chk(entry(self.h, k, n, a.data_ptr() if dev else a.ctypes.data, lda, *more))
 
     @staticmethod
     def _dense_array(who: str, name: str, a):
@@ -847,6 +861,13 @@ class Context:
         o = DenseInfo()
         self._chk(self.lib.dla_dense_info(self.h, int(bool(metric)), C.byref(o)))
         return {name: int(getattr(o, name)) for name, _ in DenseInfo._fields_}
+
+    def dense_sym_info(self, metric: bool = False) -> dict:
+        """how a symmetric dense operator (metric: the metric) is stored and multiplied: uplo ("L" or "U"), panels, chunk_blocks,
+        max_partials (include/diaglib_amd.h, dla_dense_sym_info); raises on an empty slot and on a slot stored in full"""
+        o = DenseSymInfo()
+        self._chk(self.lib.dla_dense_sym_info(self.h, int(bool(metric)), C.byref(o)))
+        return {"uplo": chr(o.uplo), "panels": int(o.panels), "chunk_blocks": int(o.chunk_blocks), "max_partials": int(o.max_partials)}
 
     def dense_matvec_t(self, x: DevPanel, y: DevPanel) -> None:
         """y = A^T x from the stored copy of the dense operator (dla_dense_matvec_t); x and y are n x m panels that do not overlap"""

@@ -359,6 +359,9 @@ struct Engine : BlockOps {
   virtual int dense_setup(int /*slot*/, int /*via*/, int /*n*/, const double* /*a*/, int /*lda*/) { return no_dense(); }
   virtual int dense_setup_pair(int /*pair*/, int /*via*/, int /*n*/, const double* /*p*/, int /*ldp*/, const double* /*q*/, int /*ldq*/) { return no_dense(); }
   virtual int dense_info(int /*slot*/, struct dla_dense_info* /*out*/) { return no_dense(); }
+  // one triangle of a symmetric operator or metric (dla_dense_setup_sym; uplo as the caller gave it) and what dla_dense_sym_info answers
+  virtual int dense_setup_sym(int /*slot*/, int /*via*/, int /*n*/, const double* /*a*/, int /*lda*/, char /*uplo*/) { return no_dense(); }
+  virtual int dense_sym_info(int /*slot*/, struct dla_dense_sym_info* /*out*/) { return no_dense(); }
   virtual int dense_drop(int /*first*/, int /*last*/) { return no_dense(); }
   virtual int dense_mul(int /*slot*/, int /*n*/, int /*m*/, const double* /*x*/, double* /*y*/) { return no_dense(); }
   // y = A^T x on the operator slot's copy (dla_dense_matvec_t)

@@ -2875,6 +2875,204 @@ __global__ void dense_combine_kernel(size_t total, int k_chunks, const double* _
   }
 }
 
+// ---- a symmetric dense matrix stored as one triangle (the contract: include/diaglib_amd.h, dla_dense_setup_sym; layout and plan:
+// hip_plans.h, dense_sym_plan)
+// The triangular copy of a column-major a(lda, n) in device memory of which only the triangle `lower` (or the upper one) is
+// referenced: one thread per STORED element as in dense_pack_kernel, the same map as dense_sym_pack on the host.  Elements of a
+// diagonal block that lie in the other triangle are read at their mirror position; padding gets 0.0.
+__global__ void dense_sym_pack_kernel(int n, int n_pad, bool lower, const double* __restrict__ a, size_t lda, double* __restrict__ stored)
+{
+  const size_t total = dense_sym_doubles(n_pad), stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t d = (size_t)blockIdx.x * blockDim.x + threadIdx.x; d < total; d += stride) {
+    const int i = dense_sym_row_of(d), k = dense_sym_col_of(d);
+    stored[d] = (i < n && k < n) ? a[dense_sym_source(lda, lower, i, k)] : 0.0;
+  }
+}
+// One pass Y(n x m) = A X, m <= 16 G, on the triangular copy (plan and workspace layout: hip_plans.h, dense_sym_plan).  Block
+// (bx, by): panel P = gridDim.y - 1 - by (the long panels start first), chunk bx of its column blocks; a block whose chunk the panel
+// does not have leaves at once.  Wavefront w owns the RT = DENSE_WAVE_TILES row tiles 16 P + 4 w .. + 3, and all four walk the
+// column blocks of the chunk together.  For a stored block (T, b), b <= T, a wavefront loads the two groups once (16 bytes per lane
+// each, no bounds check; a tile beyond the matrix or above the block's diagonal is not loaded at all -- the triangle stores
+// nothing there) and uses them twice:
+//   forward     the MFMAs of dense_mfma_kernel -- the X fragment of block b as the A operand, the loaded pair as the B operand --
+//               into acc_f[tile][q], which stays in registers across the chunk: lane l holds row 16 T + (l & 15), columns (l >> 4) + 4 r;
+//   transposed  for T > b only: the pair goes lane-linearly into the wavefront's own LDS region and comes back through the `back`
+//               index of dense_t_mfma_kernel as the B operand, lane (k, j) taking a(16 T + 4 s + k, 16 b + j), against the X
+//               fragment of row tile T (kept in registers for the whole chunk): acc_t[q] gathers the wavefront's tiles, lane l holding
+//               row 16 b + (l & 15).
+// After the tiles of a column block the four acc_t go to LDS (two buffers, taken in turn: one block-wide barrier per column block)
+// and every thread adds one element per column group in wavefront order ((w0 + w1) + w2) + w3; where the panel has a tile below
+// block b that sum is the panel's transposed partial of block b.  The forward partial of (panel, chunk) is written at the end.
+// Everything goes to the workspace for dense_sym_combine_kernel, each element by one thread -- except a matrix of one tile
+// (nt = 1: one block, nothing transposed), whose workgroup writes y.  Rows of X at or beyond n and columns at or beyond m are not
+// loaded; nothing is stored for rows at or beyond n, columns at or beyond m, or tiles beyond the matrix.
+template <int G>
+__global__ __launch_bounds__(256) void dense_sym_mfma_kernel(int n, int m, int nt, int chunk_panels, size_t t_base, const double* __restrict__ a,
+                                                              const double* __restrict__ x, double* __restrict__ y, double* __restrict__ ws)
+{
+  constexpr int RT = DENSE_WAVE_TILES;
+  __shared__ double turn[4][256];
+  __shared__ double sums[2][4][G * 256];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
+  const int P = (int)gridDim.y - 1 - (int)blockIdx.y, c = blockIdx.x;
+  if (c > P / chunk_panels) return;                       // (block-uniform, before any barrier)
+  const int last = min(DENSE_SYM_PANEL_TILES * P + DENSE_SYM_PANEL_TILES - 1, nt - 1);   // the panel's last tile: its last column block
+  const int b0 = DENSE_SYM_PANEL_TILES * chunk_panels * c, b1 = min(last + 1, b0 + DENSE_SYM_PANEL_TILES * chunk_panels);
+  const int tile0 = DENSE_SYM_PANEL_TILES * P + RT * wave;
+  double* my = turn[wave];
+  const int back = (li >> 3) * 128 + (16 * (li & 3) + lk) * 2 + ((li >> 2) & 1);
+  const double* xp[G];
+  bool xin[G];
+#pragma unroll
+  for (int q = 0; q < G; ++q) {
+    xin[q] = 16 * q + li < m;
+    xp[q] = x + (size_t)(xin[q] ? 16 * q + li : 0) * n + lk;
+  }
+  // the X fragments of the wavefront's own row tiles: the A operand of every transposed step
+  double xt[RT][4][G];
+#pragma unroll
+  for (int t = 0; t < RT; ++t)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int row = DENSE_TILE * (tile0 + t) + 4 * s;
+#pragma unroll
+      for (int q = 0; q < G; ++q) xt[t][s][q] = (xin[q] && row + lk < n) ? xp[q][row] : 0.0;
+    }
+  v4d acc_f[RT][G];
+#pragma unroll
+  for (int t = 0; t < RT; ++t)
+#pragma unroll
+    for (int q = 0; q < G; ++q) acc_f[t][q] = v4d{0.0, 0.0, 0.0, 0.0};
+  // What column block b needs from memory -- the pairs of the wavefront's tiles and the X fragment of the block -- is loaded one
+  // column block ahead, all of it together and before anything of the current block is waited for (loads return in order).  ALL: the
+  // wavefront's four tiles all lie in the matrix and strictly below the blocks b and b + 1, the common case, which then runs without
+  // a branch; otherwise every tile is tested on its own (wavefront-uniform).
+  v2d av[RT][2], nx[RT][2];
+  double xf[2][2][G], nxf[2][2][G];
+#pragma unroll
+  for (int t = 0; t < RT; ++t) nx[t][0] = nx[t][1] = v2d{0.0, 0.0};
+  const auto fetch = [&](auto all, int b) {
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+      const int T = tile0 + t;
+      if (decltype(all)::value || (T <= last && b <= T)) {
+        const v2d* p = (const v2d*)a + ((size_t)T * (size_t)(T + 1) + (size_t)(2 * b)) * 64 + lane;
+        nx[t][0] = p[0];
+        nx[t][1] = p[64];
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const int k = DENSE_TILE * b + DENSE_GROUP * h + 4 * e;
+#pragma unroll
+        for (int q = 0; q < G; ++q) nxf[h][e][q] = (xin[q] && k + lk < n) ? xp[q][k] : 0.0;
+      }
+  };
+  const auto step = [&](auto all, int b) {
+    constexpr bool ALL = decltype(all)::value;
+#pragma unroll
+    for (int t = 0; t < RT; ++t) { av[t][0] = nx[t][0]; av[t][1] = nx[t][1]; }
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int e = 0; e < 2; ++e)
+#pragma unroll
+        for (int q = 0; q < G; ++q) xf[h][e][q] = nxf[h][e][q];
+    // (the last column block of a chunk fetches itself again: no branch, and the lines are in the cache)
+    fetch(all, min(b + 1, b1 - 1));
+    v4d acc_t[G];
+#pragma unroll
+    for (int q = 0; q < G; ++q) acc_t[q] = v4d{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+      const int T = tile0 + t;
+      if (ALL || (T <= last && b <= T)) {
+        // (the turn through LDS is issued first: its latency passes behind the forward MFMAs)
+        const bool turned = ALL || T > b;
+        double bv[4];
+        if (turned) {
+          lds_store2(my + 2 * lane, av[t][0]);
+          lds_store2(my + 128 + 2 * lane, av[t][1]);
+          __builtin_amdgcn_wave_barrier();
+#pragma unroll
+          for (int s = 0; s < 4; ++s) bv[s] = lds_load1(my + back + 8 * s);
+          __builtin_amdgcn_wave_barrier();
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int e = 0; e < 2; ++e)
+#pragma unroll
+            for (int q = 0; q < G; ++q) acc_f[t][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(xf[h][e][q], av[t][h][e], acc_f[t][q], 0, 0, 0);
+        if (turned) {
+#pragma unroll
+          for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int q = 0; q < G; ++q) acc_t[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(xt[t][s][q], bv[s], acc_t[q], 0, 0, 0);
+        }
+      }
+    }
+    // the four wavefronts' sums for column block b, added in wavefront order.  The buffer alternates: this buffer is stored to again
+    // two column blocks on, behind the next block's barrier, which no thread passes before its reads below have completed.
+#pragma unroll
+    for (int q = 0; q < G; ++q)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sums[b & 1][wave][q * 256 + r * 64 + lane] = acc_t[q][r];
+    __syncthreads();
+    if (b < last) {                                       // (block-uniform: the panel has a tile below block b)
+      double* dst = ws + t_base + (size_t)16 * (size_t)m * ((size_t)8 * P * P + (size_t)7 * P + (size_t)b);
+#pragma unroll
+      for (int q = 0; q < G; ++q) {
+        const int e = q * 256 + (int)threadIdx.x;
+        const double s = ((sums[b & 1][0][e] + sums[b & 1][1][e]) + sums[b & 1][2][e]) + sums[b & 1][3][e];
+        const int col = 16 * q + lk + 4 * wave;
+        if (col < m) dst[(size_t)col * 16 + li] = s;
+      }
+    }
+  };
+  fetch(std::false_type{}, b0);
+  // every thread of the block takes the same number of steps (one block-wide barrier each), whichever path its wavefront takes
+  const int b_all = tile0 + RT - 1 <= last ? min(b1, tile0) : b0;     // the blocks [b0, b_all - 1) run the branch-free path
+  int b = b0;
+  for (; b + 1 < b_all; ++b) step(std::true_type{}, b);
+  for (; b < b1; ++b) step(std::false_type{}, b);
+  const bool direct = nt == 1;
+  const int rows = min(256, n - 256 * P);
+  double* dst = direct ? y : ws + (size_t)m * ((size_t)256 * (size_t)dense_sym_chunks_before(P, chunk_panels) + (size_t)c * (size_t)rows);
+  const size_t ld = direct ? (size_t)n : (size_t)rows;
+#pragma unroll
+  for (int t = 0; t < RT; ++t) {
+    const int row = (RT * wave + t) * DENSE_TILE + li;   // within the panel
+    if (tile0 + t > last || 256 * P + row >= n) continue;
+#pragma unroll
+    for (int q = 0; q < G; ++q)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int col = 16 * q + lk + 4 * r;
+        if (col < m) dst[(size_t)col * ld + row] = acc_f[t][q][r];
+      }
+  }
+}
+// y(i, col) of a pass on the triangular copy, one thread per element, in one order: the forward partials of the element's panel
+// by ascending chunk, then the transposed partials of its column block by ascending panel -- ((f_0 + f_1) + ... ) + t_P + t_P+1 ...
+__global__ void dense_sym_combine_kernel(int n, int m, int nt, int chunk_panels, size_t t_base, const double* __restrict__ ws, double* __restrict__ y)
+{
+  const size_t total = (size_t)n * m, stride = (size_t)gridDim.x * blockDim.x;
+  const int panels = (nt + DENSE_SYM_PANEL_TILES - 1) / DENSE_SYM_PANEL_TILES;
+  for (size_t at = (size_t)blockIdx.x * blockDim.x + threadIdx.x; at < total; at += stride) {
+    const int i = (int)(at % (size_t)n), col = (int)(at / (size_t)n);
+    const int P = i / 256, b = i / DENSE_TILE, rows = min(256, n - 256 * P);
+    const double* f = ws + (size_t)m * (size_t)256 * (size_t)dense_sym_chunks_before(P, chunk_panels) + (size_t)col * rows + (i - 256 * P);
+    double s = f[0];
+    for (int c = 1; c <= P / chunk_panels; ++c) s += f[(size_t)c * m * rows];
+    for (int p = dense_sym_first_panel(nt, b); p < panels; ++p)
+      s += ws[t_base + (size_t)16 * (size_t)m * ((size_t)8 * p * p + (size_t)7 * p + (size_t)b) + (size_t)col * 16 + (i & 15)];
+    y[at] = s;
+  }
+}
+
 // The harness' lrprec_1 / lrprec_2 (main.f90:234-281; synth_lrprec_kernel restates them) on the stored diagonals of the sparse
 // linear-response parts (dla_spmm_setup_lr_csr): aa = ((A+B)_ii + (A-B)_ii) / 2, sg = (S+D)_ii (D is antisymmetric: its diagonal
 // is zero, so S+D carries the diagonal of S).  One thread keeps VEC rows of the three diagonals in registers -- read once -- and
@@ -7486,8 +7684,9 @@ struct HipEngine : dla::Engine {
   struct DenseOp {
     int n = 0;                       // 0: nothing stored
     int last_m = 1;                  // width of the first pass of the most recent product (what dense_info describes)
+    char uplo = 0;                   // 0: stored in full; 'L' / 'U': one triangle (dla_dense_setup_sym), the triangle that was referenced
     DeviceBuffer<double> a, diag, ws;
-    void drop() { a.reset(); diag.reset(); ws.reset(); n = 0; last_m = 1; }
+    void drop() { a.reset(); diag.reset(); ws.reset(); n = 0; last_m = 1; uplo = 0; }
   } dense[dla::DENSE_SLOTS];
   // The words a message about a dense slot needs: what the slot is called, the name of each public entry that reaches it (setup is
   // also the set-up a callback names while the slot is empty) and the rule quoted for a public number out of range.
@@ -7529,28 +7728,30 @@ struct HipEngine : dla::Engine {
     if (lda < n) { err = who + ld + " = " + std::to_string(lda) + " is below n = " + std::to_string(n); return DLA_ERR_ARG; }
     return DLA_OK;
   }
-  // the copy and the diagonal of a checked array into one slot
-  int dense_store(const std::string& who, DenseOp& op, bool dev, int n, const double* a, int lda)
+  // the copy and the diagonal of a checked array into one slot; uplo: 0 for the full copy, 'L' / 'U' for the triangular one
+  int dense_store(const std::string& who, DenseOp& op, bool dev, int n, const double* a, int lda, char uplo = 0)
   {
     const int n_pad = dense_n_pad(n);
-    const size_t total = (size_t)n_pad * n_pad;
+    const size_t total = uplo ? dense_sym_doubles(n_pad) : (size_t)n_pad * n_pad;
     std::vector<double> packed, diag;
     if (!dev) {
       try { packed.resize(total); diag.resize((size_t)n); }
       catch (const std::bad_alloc&) { err = who + "no host memory for the packed copy"; return DLA_ERR_ALLOC; }
-      dense_pack(n, a, (size_t)lda, packed.data(), diag.data());
+      if (uplo) dense_sym_pack(n, a, (size_t)lda, uplo, packed.data(), diag.data());
+      else dense_pack(n, a, (size_t)lda, packed.data(), diag.data());
     }
     bind();
     HIPCHK(hipStreamSynchronize(st));      // (queued products may still read the old blocks)
     // (a block that has to grow is released first: from here on a failure leaves the slot empty, not half replaced)
-    op.n = 0; op.last_m = 1;
+    op.n = 0; op.last_m = 1; op.uplo = 0;
     if (op.a.reserve(total) != hipSuccess || op.diag.reserve((size_t)n) != hipSuccess) {
       op.drop();
       err = who + "no device memory for " + std::to_string(8 * total + 8 * (size_t)n) + " bytes";
       return DLA_ERR_ALLOC;
     }
     if (dev) {
-      DLA_LAUNCH(dense_pack_kernel, dim3(grid_blocks(env(), (long long)total, 256)), dim3(256), 0, st, n, n_pad, a, (size_t)lda, (double*)op.a);
+      if (uplo) DLA_LAUNCH(dense_sym_pack_kernel, dim3(grid_blocks(env(), (long long)total, 256)), dim3(256), 0, st, n, n_pad, uplo == 'L', a, (size_t)lda, (double*)op.a);
+      else DLA_LAUNCH(dense_pack_kernel, dim3(grid_blocks(env(), (long long)total, 256)), dim3(256), 0, st, n, n_pad, a, (size_t)lda, (double*)op.a);
       HIPCHK(hipGetLastError());
       DLA_LAUNCH(dense_diag_kernel, dim3(grid_blocks(env(), n, 256)), dim3(256), 0, st, n, a, (size_t)lda, (double*)op.diag);
       HIPCHK(hipGetLastError());
@@ -7560,6 +7761,31 @@ struct HipEngine : dla::Engine {
       HIPCHK(hipMemcpy(op.diag, diag.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
     }
     op.n = n;
+    op.uplo = uplo;
+    return DLA_OK;
+  }
+  // one triangle of a symmetric operator or metric (dla_dense_setup_sym): the checks of dense_setup, then the triangle's letter
+  int dense_setup_sym(int slot, int via, int n, const double* a, int lda, char uplo) override
+  {
+    const bool dev = via == dla::SPMM_VIA_DEVICE;
+    const char* entry = dev ? "dla_dense_setup_sym_dev" : "dla_dense_setup_sym";
+    const std::string who = std::string(entry) + ": ";
+    { const int stc = dense_admit(slot, entry, DENSE_EXISTS); if (stc) return stc; }
+    { const int stc = dense_array_ok(who, "matrix", "lda", n, a, lda); if (stc) return stc; }
+    const char up = uplo == 'l' ? 'L' : uplo == 'u' ? 'U' : uplo;
+    if (up != 'L' && up != 'U') { err = who + "uplo must be 'L' or 'U' (the triangle of the array that is referenced)"; return DLA_ERR_ARG; }
+    return dense_store(who, dense[slot], dev, n, a, lda, up);
+  }
+  int dense_sym_info(int slot, struct dla_dense_sym_info* out) override
+  {
+    const char* entry = "dla_dense_sym_info";
+    { const int stc = dense_admit(slot, entry, DENSE_EXISTS); if (stc) return stc; }
+    if (!out) { err = std::string(entry) + ": out is a null pointer"; return DLA_ERR_ARG; }
+    { const int stc = dense_admit(slot, entry, DENSE_STORED); if (stc) return stc; }
+    const DenseOp& op = dense[slot];
+    if (!op.uplo) { err = std::string(entry) + ": the " + dense_words(slot).noun + " is stored in full (dla_dense_setup), not as a triangle"; return DLA_ERR_ARG; }
+    const DenseSymPlan p = dense_sym_plan(ncu, op.n, op.last_m);
+    out->uplo = op.uplo; out->panels = p.panels; out->chunk_blocks = p.chunk_blocks; out->max_partials = p.max_partials;
     return DLA_OK;
   }
   int dense_setup(int slot, int via, int n, const double* a, int lda) override
@@ -7626,6 +7852,13 @@ struct HipEngine : dla::Engine {
     if (!out) { err = std::string(entry) + ": out is a null pointer"; return DLA_ERR_ARG; }
     { const int stc = dense_admit(slot, entry, DENSE_STORED); if (stc) return stc; }
     const DenseOp& op = dense[slot];
+    if (op.uplo) {
+      const DenseSymPlan p = dense_sym_plan(ncu, op.n, op.last_m);
+      out->n = op.n; out->n_pad = p.n_pad; out->row_tile = DENSE_TILE * DENSE_WAVE_TILES; out->k_chunks = p.max_chunks;
+      out->device_bytes = 8LL * (long long)dense_sym_doubles(p.n_pad) + 8LL * op.n;
+      out->workspace_bytes = 8LL * (long long)p.ws_doubles;
+      return DLA_OK;
+    }
     const DensePlan p = dense_plan(ncu, op.n, op.last_m);
     out->n = op.n; out->n_pad = p.n_pad; out->row_tile = DENSE_TILE * DENSE_WAVE_TILES; out->k_chunks = p.k_chunks;
     out->device_bytes = 8LL * p.n_pad * p.n_pad + 8LL * op.n;
@@ -7652,6 +7885,7 @@ struct HipEngine : dla::Engine {
     if (m <= 0) return DLA_OK;
     DenseOp& op = dense[slot];
     op.last_m = std::min(m, DENSE_MAX_COLS);
+    if (op.uplo) return dense_mul_sym(op, n, m, x, y);
     for (int c0 = 0; c0 < m; c0 += DENSE_MAX_COLS) {
       const int mp = std::min(DENSE_MAX_COLS, m - c0);
       const DensePlan p = dense_plan(ncu, n, mp);
@@ -7684,6 +7918,43 @@ struct HipEngine : dla::Engine {
     }
     return DLA_OK;
   }
+  // y = (slot) x on a triangular copy (dla_dense_setup_sym): the passes of dense_sym_plan on the slot's own workspace.  Booked with
+  // the bytes a pass has to move -- the triangle with its diagonal once, 4 n (n + 1), and x and y -- and the flops of the full product.
+  int dense_mul_sym(DenseOp& op, int n, int m, const double* x, double* y)
+  {
+    for (int c0 = 0; c0 < m; c0 += DENSE_MAX_COLS) {
+      const int mp = std::min(DENSE_MAX_COLS, m - c0);
+      const DenseSymPlan p = dense_sym_plan(ncu, n, mp);
+      if (p.ws_doubles > op.ws.capacity()) {
+        bind();
+        HIPCHK(hipStreamSynchronize(st));       // (queued products may still use the old block)
+        HIPCHK(op.ws.reserve(p.ws_doubles));
+      }
+      const double* xc = x + (size_t)c0 * n;
+      double* yc = y + (size_t)c0 * n;
+      const dim3 grid(p.max_chunks, p.panels);
+      {
+        Scope s(this, DLA_OP_MATVEC, 4.0 * (double)n * (n + 1.0) + 16.0 * (double)n * mp, 2.0 * (double)n * n * mp, p.name());
+        const bool hit = first_instance<DENSE_MAX_COLS / 16>([&](auto i) {
+          constexpr int G = (int)decltype(i)::value + 1;
+          if (p.acc_groups != G) return false;
+          DLA_LAUNCH((dense_sym_mfma_kernel<G>), grid, dim3(256), 0, st, n, mp, p.row_tiles, p.chunk_panels, p.t_base, (const double*)op.a, xc, yc,
+                     (double*)op.ws);
+          return true;
+        });
+        if (!hit) { err = "dense symmetric product: no kernel instance"; return DLA_ERR_RUNTIME; }
+        HIPCHK(hipGetLastError());
+      }
+      if (p.row_tiles > 1) {
+        // (the partial sums are not compulsory traffic: the launch is booked without algorithmic bytes)
+        Scope s(this, DLA_OP_MATVEC, 0.0, 0.0, "dense_sym_combine_kernel");
+        DLA_LAUNCH(dense_sym_combine_kernel, dim3(grid_blocks(env(), (long long)n * mp, 256)), dim3(256), 0, st, n, mp, p.row_tiles, p.chunk_panels, p.t_base,
+                   (const double*)op.ws, yc);
+        HIPCHK(hipGetLastError());
+      }
+    }
+    return DLA_OK;
+  }
   // y = A^T x on the copy of the operator slot (dla_dense_matvec_t): the passes of dense_t_plan on the slot's own workspace.  The slot's
   // description (dense_info: the first pass of the most recent forward product) is left as it is.
   int dense_mul_t(int n, int m, const double* x, double* y) override
@@ -7691,6 +7962,7 @@ struct HipEngine : dla::Engine {
     { const int stc = dense_admit(dla::DENSE_A, "dense_matvec_t", DENSE_ROWS, n); if (stc) return stc; }
     if (m <= 0) return DLA_OK;
     DenseOp& op = dense[dla::DENSE_A];
+    if (op.uplo) return dense_mul_sym(op, n, m, x, y);    // (A^T = A: the symmetric product, the slot's description left as it is)
     for (int c0 = 0; c0 < m; c0 += DENSE_MAX_COLS) {
       const int mp = std::min(DENSE_MAX_COLS, m - c0);
       const DenseTPlan p = dense_t_plan(ncu, n, mp);

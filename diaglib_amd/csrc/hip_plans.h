@@ -849,4 +849,113 @@ inline DenseTPlan dense_t_plan(int ncu, int n, int m)
   return p;
 }
 
+// ---- a symmetric dense operator or metric stored as one triangle (include/diaglib_amd.h, dla_dense_setup_sym)
+// The tile and group format of the full copy, but row tile T (16 rows) keeps only its groups 0 .. 2 T + 1, that is the 16 x 16
+// blocks of the column blocks 0 .. T.  Groups of a tile are consecutive and tiles follow each other: tile T starts at group
+// T (T + 1), the two groups of a block stay adjacent (2 KB), and the copy holds 128 nt (nt + 1) doubles, nt = n_pad / 16 --
+// n_pad^2 / 2 + 8 n_pad.  A diagonal block is stored whole, mirrored from the referenced triangle, so it is a plain forward block;
+// padding is 0.0.
+constexpr size_t dense_sym_doubles(int n_pad) { return (size_t)128 * (size_t)(n_pad / DENSE_TILE) * (size_t)(n_pad / DENSE_TILE + 1); }
+// where a(i, k) lives in the triangular copy (0-based, both below n_pad, k / 16 <= i / 16)
+constexpr size_t dense_sym_index(int i, int k)
+{
+  const size_t t = (size_t)(i / DENSE_TILE);
+  return ((t * (t + 1) + (size_t)(k / DENSE_GROUP)) * 64 + (size_t)((k % 4) * 16 + i % DENSE_TILE)) * 2 + (size_t)((k % DENSE_GROUP) / 4);
+}
+// ... and back: the row tile of stored group gi (the largest T with T (T + 1) <= gi, bit by bit: T < 2^16), then the row and the
+// column of stored element d (what the pack kernel runs, one thread per element)
+constexpr int dense_sym_tile_of(size_t gi)
+{
+  size_t t = 0;
+  for (size_t bit = (size_t)1 << 15; bit; bit >>= 1)
+    if ((t | bit) * ((t | bit) + 1) <= gi) t |= bit;
+  return (int)t;
+}
+constexpr int dense_sym_row_of(size_t d) { return dense_sym_tile_of(d / 128) * DENSE_TILE + (int)((d >> 1) & 15); }
+constexpr int dense_sym_col_of(size_t d)
+{
+  const size_t t = (size_t)dense_sym_tile_of(d / 128);
+  return (int)(d / 128 - t * (t + 1)) * DENSE_GROUP + (int)(d & 1) * 4 + (int)((d >> 5) & 3);
+}
+// a(i, k) of a symmetric matrix of which only the triangle uplo ('L' or 'U') of the column-major array is referenced
+constexpr size_t dense_sym_source(size_t lda, bool lower, int i, int k) { return (i >= k) == lower ? (size_t)k * lda + i : (size_t)i * lda + k; }
+// the triangular copy and the diagonal (n doubles) of such an array: what dla_dense_setup_sym uploads.  The other strict triangle
+// is never read, inside diagonal blocks either.
+inline void dense_sym_pack(int n, const double* a, size_t lda, char uplo, double* stored, double* diag)
+{
+  const int n_pad = dense_n_pad(n);
+  const bool lower = uplo == 'L' || uplo == 'l';
+  std::fill(stored, stored + dense_sym_doubles(n_pad), 0.0);
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < std::min(n, (i / DENSE_TILE + 1) * DENSE_TILE); ++k) stored[dense_sym_index(i, k)] = a[dense_sym_source(lda, lower, i, k)];
+  for (int i = 0; i < n; ++i) diag[i] = a[(size_t)i * lda + i];
+}
+
+// One pass of a product Y(n x m) = A X on the triangular copy, m <= DENSE_MAX_COLS: a pure function of n, m and the CU count.
+// A workgroup of four wavefronts owns a panel of DENSE_SYM_PANEL_TILES = 4 DENSE_WAVE_TILES row tiles (256 rows; wavefront w the tiles
+// 16 P + 4 w .. + 3 of panel P) and one chunk of the column blocks 0 .. last tile of the panel.  A stored block (T, b) is loaded once
+// and used twice: A_Tb x_b goes to the forward sums of rows of tile T, and for T > b A_Tb^T x_T to the transposed sums of the rows of
+// block b.  Chunks are chunk_blocks = 16 chunk_panels blocks long, so panel P has P / chunk_panels + 1 of them (the last one ends
+// with the panel's diagonal blocks) and a pass has items = sum over P of that.  The rule for chunk_panels:
+//   * enough items to give every SIMD of the device DENSE_SYM_ITEMS_PER_CU wavefronts: the largest chunk_panels with items >=
+//     DENSE_SYM_ITEMS_PER_CU ncu.  The items are not equal -- the last chunk of a panel ends on the diagonal -- and with one item per
+//     CU the longest one sets the time of the pass; several shorter ones per CU even that out (DESIGN section 3 has both measured),
+//   * but at least 1 (a chunk keeps at least the 16 column blocks of one panel),
+//   * and then the smallest one at or above it for which the forward partial sums, written and read once -- 16 bytes each -- stay
+//     within 1 / DENSE_WS_SHARE of the 8 dense_sym_doubles bytes of the copy, or chunk_panels = panels (one chunk per panel).
+// The transposed partial sums are not the chunking's to decide: one per panel and column block below the panel's last tile,
+// 16 rows x m, about m / 256 of the copy's bytes written and read.  The panel height is a starting value, like the constants above.
+// Workspace (doubles, every one written by one thread of the product kernel and read by one of the combine kernel):
+//   forward, from 0: panel P, chunk c at m (256 F(P) + c rows(P)), [column][row] with rows(P) = min(256, n - 256 P) rows,
+//     F(P) = sum over P' < P of (P' / chunk_panels + 1) (dense_sym_chunks_before);
+//   transposed, from t_base = m (256 F(last panel) + chunks(last panel) rows(last panel)): panel P, block b < min(16 P + 15, nt - 1)
+//     at t_base + 16 m (8 P^2 + 7 P + b), [column][16 rows].
+// A matrix of one tile (n <= 16) has nothing to combine: its one workgroup writes y, ws_doubles = 0.
+// max_partials: the largest number of partial sums added into one element of y.
+constexpr int DENSE_SYM_PANEL_TILES = 4 * DENSE_WAVE_TILES, DENSE_SYM_ITEMS_PER_CU = 4;
+constexpr long long dense_sym_chunks_before(int panel, int chunk_panels)
+{
+  const long long q = panel / chunk_panels, r = panel % chunk_panels;
+  return panel + (long long)chunk_panels * q * (q - 1) / 2 + r * q;
+}
+// the first panel that holds a transposed partial sum for column block b (panels at or above it all do)
+constexpr int dense_sym_first_panel(int nt, int b)
+{
+  return b / DENSE_SYM_PANEL_TILES + ((b % DENSE_SYM_PANEL_TILES == DENSE_SYM_PANEL_TILES - 1 || b == nt - 1) ? 1 : 0);
+}
+struct DenseSymPlan {
+  int n_pad, row_tiles, panels;
+  int acc_groups;                             // groups of 16 columns of X (the kernel's instance): 1 .. 3
+  int chunk_panels, chunk_blocks, max_chunks; // max_chunks: the chunks of the last panel (the launch's grid.x)
+  long long items;
+  int max_partials;
+  size_t t_base, ws_doubles;
+  std::string name() const { return plan_name("dense_sym_mfma_kernel<%d>", acc_groups); }
+};
+inline DenseSymPlan dense_sym_plan(int ncu, int n, int m)
+{
+  DenseSymPlan p{};
+  p.n_pad = dense_n_pad(n);
+  p.row_tiles = p.n_pad / DENSE_TILE;
+  p.panels = (p.row_tiles + DENSE_SYM_PANEL_TILES - 1) / DENSE_SYM_PANEL_TILES;
+  p.acc_groups = (m + 15) / 16;
+  const int last = p.panels - 1, rows_last = n - 256 * last;
+  const auto forward = [&](int cp) { return (size_t)m * ((size_t)256 * (size_t)dense_sym_chunks_before(last, cp) + (size_t)(last / cp + 1) * (size_t)rows_last); };
+  int cp = 1;
+  while (cp < p.panels && dense_sym_chunks_before(p.panels, cp + 1) >= (long long)DENSE_SYM_ITEMS_PER_CU * std::max(1, ncu)) ++cp;
+  while (cp < p.panels && 16 * forward(cp) * DENSE_WS_SHARE > 8 * dense_sym_doubles(p.n_pad)) ++cp;
+  p.chunk_panels = cp;
+  p.chunk_blocks = DENSE_SYM_PANEL_TILES * cp;
+  p.max_chunks = last / cp + 1;
+  p.items = dense_sym_chunks_before(p.panels, cp);
+  p.max_partials = 0;
+  for (int b = 0; b < p.row_tiles; ++b)
+    p.max_partials = std::max(p.max_partials, b / DENSE_SYM_PANEL_TILES / cp + 1 + p.panels - dense_sym_first_panel(p.row_tiles, b));
+  if (p.row_tiles == 1) return p;             // (one block: t_base = ws_doubles = 0)
+  p.t_base = forward(cp);
+  const size_t t_blocks = (size_t)8 * last * last + (size_t)7 * last + (size_t)std::min(16 * last + 15, p.row_tiles - 1);
+  p.ws_doubles = p.t_base + (size_t)16 * (size_t)m * t_blocks;
+  return p;
+}
+
 }  // namespace dla_plans

@@ -2169,6 +2169,21 @@ int dla_dense_setup_dev(dla_ctx* c, int which, int n, const double* a_dev, int l
   DLA_T("dla_dense_setup_dev");
   return c ? dense_set_up(c, c->eng->dense_setup(dla::dense_slot_of_which(which), dla::SPMM_VIA_DEVICE, n, a_dev, lda)) : DLA_ERR_ARG;
 }
+int dla_dense_setup_sym(dla_ctx* c, int which, int n, const double* a_host, int lda, char uplo)
+{
+  DLA_T("dla_dense_setup_sym");
+  return c ? dense_set_up(c, c->eng->dense_setup_sym(dla::dense_slot_of_which(which), dla::SPMM_VIA_HOST, n, a_host, lda, uplo)) : DLA_ERR_ARG;
+}
+int dla_dense_setup_sym_dev(dla_ctx* c, int which, int n, const double* a_dev, int lda, char uplo)
+{
+  DLA_T("dla_dense_setup_sym_dev");
+  return c ? dense_set_up(c, c->eng->dense_setup_sym(dla::dense_slot_of_which(which), dla::SPMM_VIA_DEVICE, n, a_dev, lda, uplo)) : DLA_ERR_ARG;
+}
+int dla_dense_sym_info(dla_ctx* c, int which, struct dla_dense_sym_info* out)
+{
+  if (!c) return DLA_ERR_ARG;
+  return engfail(c, c->eng->dense_sym_info(dla::dense_slot_of_which(which), out));
+}
 int dla_dense_info(dla_ctx* c, int which, struct dla_dense_info* out) { return dense_slot_info(c, dla::dense_slot_of_which(which), out); }
 int dla_dense_drop(dla_ctx* c, int which) { const int slot = dla::dense_slot_of_which(which); return dense_slot_drop(c, slot, slot); }
 void dla_dense_matvec(const int* n, const int* m, const double* x, double* ax) { dense_product(DENSE_A, n, m, x, ax); }

@@ -840,7 +840,7 @@ void dla_spmm_precnd_cheb_pencil(const int* n, const int* m, const double* fac, 
  * under the name of its kernel, dense_mfma_kernel<G> with G accumulator groups of 16 columns; the combining kernel of a split pass
  * books a launch of its own with no algorithmic bytes (the workspace is not compulsory traffic).  The preconditioners book under
  * DLA_OP_PRECND as the sparse ones do.
- * Out of scope (the four linear-response parts as dense matrices: the next block): row shards; halving the traffic through symmetry; aliasing the
+ * Out of scope (the four linear-response parts as dense matrices: the next block): row shards; aliasing the
  * caller's array instead of copying it; sanitizer runs of code loaded into an interpreter (the layout and the planner are host-only
  * code, testable from a stand-alone program); any inspection of kernel assembly. */
 struct dla_dense_info { int n; int n_pad; int row_tile; int k_chunks; long long device_bytes; long long workspace_bytes; };
@@ -867,6 +867,49 @@ void dla_dense_bvec  (const int* n, const int* m, const double* x_dev, double* b
 void dla_dense_matvec_t(const int* n, const int* m, const double* x_dev, double* y_dev);         /* y = A^T x */
 void dla_dense_precnd(const int* n, const int* m, const double* fac, const double* x_dev, double* px_dev);         /* x / (a_ii + fac), guard 1e-5: mprec */
 void dla_dense_precnd_pencil(const int* n, const int* m, const double* fac, const double* x_dev, double* px_dev);  /* x / (a_ii + fac b_ii), same guard */
+/* A symmetric operator or metric stored as ONE TRIANGLE.  Every driver that uses these two slots except nonsym_driver works on
+ * symmetric matrices; dla_dense_setup_sym stores such a matrix in about half the memory and a product streams each stored byte once.
+ * Set-up: the rules of dla_dense_setup -- which = 0 / 1, a column-major with lda >= n, the library's own copy, synchronous, host and
+ * device set-up of the same values store the same bits, allocations only grow, a refused set-up replaces nothing.  uplo = 'L' or 'U'
+ * (or lower case) names the triangle of the array that is REFERENCED: the other strict triangle is never read, neither on the host
+ * nor on the device, inside diagonal blocks either, and may hold anything.  a(i,k) = a(k,i) is assumed, not checked.
+ * A slot remembers how it is stored: dla_dense_matvec, dla_dense_bvec, dla_dense_precnd and dla_dense_precnd_pencil keep their names
+ * and shapes and dispatch on it, so a caller changes its set-up line and nothing else.  dla_dense_matvec_t on a symmetric slot is
+ * the symmetric product (the same bits).  A full set-up of a slot replaces a symmetric one and the reverse; slots stored in full
+ * behave bit for bit as before.
+ * Layout.  The tile and group format of the full copy, but row tile T (16 rows) keeps only its groups 0 .. 2 T + 1, the column
+ * blocks 0 .. T: tile T starts at group T (T + 1) and the copy holds 128 nt (nt + 1) doubles, nt = n_pad / 16 -- n_pad^2 / 2 +
+ * 8 n_pad; device_bytes = 8 * 128 nt (nt + 1) + 8 n (at n = 65536: 17 GB instead of 34 GB).  Diagonal blocks are stored whole,
+ * mirrored from the referenced triangle; padding is 0.0; diag[i] = a(i,i), so the preconditioners return the bits they return on a
+ * full copy.
+ * The product.  One pass takes up to 48 columns and loads every stored byte once.  A workgroup owns a panel of 256 rows and one
+ * chunk of the column blocks up to the panel's last tile (dense_sym_plan in diaglib_amd/csrc/hip_plans.h states the rule for the
+ * chunk length from n, the width of the pass and the number of compute units alone).  A stored 16 x 16 block (T, b) is used twice:
+ * as A_Tb x_b (the MFMAs of dense_mfma_kernel) and, for T > b, turned in LDS as in dense_t_mfma_kernel, as A_Tb^T x_T.  The forward
+ * partial sums of a (panel, chunk) and the transposed ones of a (panel, column block) -- the four wavefronts' added in wavefront
+ * order -- go to the slot's workspace (dense_sym_plan states its layout; it is not counted in device_bytes), and
+ * dense_sym_combine_kernel adds the partials of an element with one thread in one order: forward chunks ascending, then transposed
+ * partials by ascending panel.  No atomics; every element of the result and of the workspace has one writer; repeated products are
+ * bit-identical; 'L' and 'U' of an exactly symmetric array store the same bits.  Accuracy, shapes and callbacks: as dla_dense_matvec
+ * ((n + 2) eps (|A| |x|)_i; any n, m >= 1; nothing outside the n x m result is written).
+ * The transposed partial sums cost about m / 256 of the copy's bytes per pass in workspace and traffic, whatever the chunking: the
+ * format saves memory at every shape and time only where the stored bytes dominate.  Measured against dla_dense_matvec on the full
+ * copy (profiles/dense_sym_operator.txt): 0.86-0.88 of its time at n = 32768 for 8-13 columns, 0.97 at n = 8192; it SAVES MEMORY AND
+ * COSTS TIME at n = 2048 (1.6-2.0 times the full product) and for blocks of 37 columns (1.6-2.4 times at every size measured).  The
+ * panel height and the planner's constants are starting values.
+ * Info.  dla_dense_info on a symmetric slot answers n, n_pad, row_tile, device_bytes as above, the workspace of the first pass of the
+ * most recent product, and in k_chunks the largest number of chunks of a panel.  dla_dense_sym_info adds the triangle that was
+ * referenced ('L' or 'U'), the panels, the chunk length in column blocks and the largest number of partial sums added into one
+ * element; it answers DLA_ERR_ARG on an empty slot and on a slot stored in full.
+ * Refused with DLA_ERR_ARG, the message naming the entry: what dla_dense_setup refuses, and uplo not one of L l U u.
+ * Statistics: a pass books one launch under DLA_OP_MATVEC with alg_bytes = 4 n (n + 1) + 16 n m and flops = 2 n^2 m under
+ * dense_sym_mfma_kernel<G>; the combine books a launch of its own with no algorithmic bytes.
+ * Out of scope: the four linear-response parts and the pair set-up (A +- B are symmetric, S +- D are not); row shards; symmetric
+ * sparse storage. */
+struct dla_dense_sym_info { int uplo; int panels; int chunk_blocks; int max_partials; };   /* uplo: 'L' or 'U' */
+int  dla_dense_setup_sym    (dla_ctx* ctx, int which, int n, const double* a_host, int lda, char uplo);
+int  dla_dense_setup_sym_dev(dla_ctx* ctx, int which, int n, const double* a_dev,  int lda, char uplo);
+int  dla_dense_sym_info     (dla_ctx* ctx, int which, struct dla_dense_sym_info* out);
 
 /* ---------------------------------------------------------------- dense linear-response parts
  * The reference harness' linear-response problems are DENSE (main.f90:528-760): A+B, A-B, S+D and S-D of the pencil

@@ -25,11 +25,19 @@ users' sizes, beside torch.matmul and the triad rate of the same process.
    n_max 8, tol 1e-9, max_dav 10) of the matrix of examples/fortran_nonsym_caller at n = 2000 in device mode (dla_dense_matvec,
    dla_dense_matvec_t, dla_dense_precnd) beside host callbacks (numpy products with a and its transposed copy).
 
+5. With --sym, the symmetric storage instead (record: profiles/dense_sym_operator.txt): the product on the triangular copy
+   (dla_dense_setup_sym, here in the metric slot: dense_sym_mfma_kernel and dense_sym_combine_kernel) beside dla_dense_matvec on the
+   full copy of the SAME symmetric matrix in the same process at n = 2048, 8192 and 32768, m = 8, 13 and 37, alternating call by
+   call as in 1. -- medians, spreads, the device bytes of both copies, the full product's rate over its booked bytes beside the
+   triad rate, the plan of the symmetric pass and the ratio symmetric / full -- and the harness solve of 2. at n = 2000 in device
+   mode with the operator stored in full and as a triangle.
+
 Every leg is a process of its own under `timeout`; the first leg that fails ends the run.
 
     python tools/dense_operator_bench.py [rounds] [record]          (defaults 10, profiles/dense_operator.txt)
     python tools/dense_operator_bench.py --lr [rounds] [record]     (defaults 10, profiles/dense_lr_operator.txt)
     python tools/dense_operator_bench.py --transpose [rounds] [record]   (defaults 10, profiles/dense_operator_t.txt)
+    python tools/dense_operator_bench.py --sym [rounds] [record]         (defaults 10, profiles/dense_sym_operator.txt)
 """
 import os
 import subprocess
@@ -46,6 +54,7 @@ LEGS = [("product 2048", 300), ("product 8192", 300), ("product 32768", 420), ("
 LR_LEGS = [("lrsolve 2000", 420), ("lrpair 8192", 300)]
 T_LEGS = [("tproduct 2048", 300), ("tproduct 8192", 300), ("tproduct 32768", 420), ("nsolve 2000", 420)]
 T_WIDTHS = (8, 13, 37)
+S_LEGS = [("sproduct 2048", 300), ("sproduct 8192", 300), ("sproduct 32768", 420), ("ssolve 2000", 420)]
 
 
 def leg_product(n, rounds):
@@ -149,6 +158,91 @@ def leg_tproduct(n, rounds):
               f"{med['transposed'] / med['forward']:5.2f}   max |A^T x - torch| {diff:.2e}", flush=True)
         x.free(); y.free()
     print(f"  triad after the products {ctx.stream_triad(max(1 << 24, n * n // 4)):.0f} GB/s")
+    ctx.dense_drop()
+
+
+def leg_sproduct(n, rounds):
+    import torch
+    from diaglib_amd import capi
+    ctx = capi.Context()
+    ctx.set_option(capi.OPT_CALLBACKS_ON_DEVICE, 1)
+    stream = torch.cuda.ExternalStream(ctx.lib.dla_stream(ctx.h))
+    gen = torch.Generator(device="cuda").manual_seed(n)
+    a = torch.rand((n, n), dtype=torch.float64, device="cuda", generator=gen)
+    a = torch.tril(a) + torch.tril(a, -1).T                                          # exactly symmetric (and so column-major as it is)
+    ctx.dense_setup(a.T)                                                             # slot 0: the full copy
+    ctx.dense_setup(a.T, metric=True, sym="L")                                       # slot 1: one triangle of the same matrix
+    full, tri = ctx.dense_info()["device_bytes"], ctx.dense_info(True)["device_bytes"]
+    triad = ctx.stream_triad(max(1 << 24, n * n // 4))
+    fns = {"full": capi.fn_address("dla_dense_matvec"), "symmetric": capi.fn_address("dla_dense_bvec")}
+    print(f"n = {n}: full copy {full / 1e6:.0f} MB, triangular copy {tri / 1e6:.0f} MB ({(full - tri) / 1e6:.0f} MB saved, {tri / full:.3f} of the full copy), "
+          f"triad {triad:.0f} GB/s")
+    for m in T_WIDTHS:
+        x, y, ys = ctx.panel(n, m), ctx.panel(n, m), ctx.panel(n, m)
+        ctx.random_fill(x)
+        out = {"full": y, "symmetric": ys}
+
+        def call(which):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            ctx._chk(ctx.lib.dla_call_matvec(ctx.h, fns[which], n, m, x.ptr, out[which].ptr))
+            e1.record(stream)
+            return e0, e1
+
+        for which in ("full", "symmetric") * 3:
+            call(which)
+        ctx.sync()
+        diff = float((ctx._dev_tensor(y.ptr, n, m) - ctx._dev_tensor(ys.ptr, n, m)).abs().max())
+        ms = {"full": [], "symmetric": []}
+        for _ in range(rounds):
+            pairs = [(which, call(which)) for _ in range(CALLS_PER_ROUND) for which in ("full", "symmetric")]
+            ctx.sync()
+            for which in ms:
+                ms[which].append([e0.elapsed_time(e1) for k, (e0, e1) in pairs if k == which])
+        med, spread = {}, {}
+        for which in ms:
+            t = np.array(ms[which])
+            per_round = np.median(t, axis=1)
+            med[which], spread[which] = float(np.median(t)), float(per_round.max() - per_round.min())
+        rate = (8.0 * n * n + 16.0 * n * m) / (med["full"] * 1e-3) / 1e9
+        plan, ws = ctx.dense_sym_info(True), ctx.dense_info(True)["workspace_bytes"]
+        print(f"  m = {m:2d}  full {med['full']:8.4f} ms (spread {spread['full']:.4f}) {rate:6.0f} GB/s = {rate / triad:5.2f} of the triad rate   symmetric "
+              f"{med['symmetric']:8.4f} ms (spread {spread['symmetric']:.4f}; {plan['panels']} panels, chunks of {plan['chunk_blocks']} blocks, at most "
+              f"{plan['max_partials']} partials per element, workspace {ws / 1e6:.1f} MB)   symmetric / full = {med['symmetric'] / med['full']:5.2f}   "
+              f"max |difference| {diff:.2e}", flush=True)
+        x.free(); y.free(); ys.free()
+    print(f"  triad after the products {ctx.stream_triad(max(1 << 24, n * n // 4)):.0f} GB/s")
+    ctx.dense_drop()
+    ctx.dense_drop(True)
+
+
+def leg_ssolve(n):
+    from diaglib_amd import capi
+    ctx = capi.Context()
+    t, m, tol, max_dav = 8, 13, 1e-9, 20
+    idx = np.arange(1, n + 1.0)
+    a = 1.0 / (idx[:, None] + idx[None, :])
+    np.fill_diagonal(a, idx + 1.0)
+    g = np.zeros((n, m), order="F")
+    g[np.arange(m), np.arange(m)] = 1.0
+    ctx.set_option(capi.OPT_CALLBACKS_ON_DEVICE, 1)
+    mv, pc = capi.fn_address("dla_dense_matvec"), capi.fn_address("dla_dense_precnd")
+    times, out = {"stored in full": [], "stored as a triangle": []}, {}
+    for _ in range(5):                                       # (the two storages alternate solve by solve; the first pair is the warm-up)
+        for mode, sym in (("stored in full", None), ("stored as a triangle", "L")):
+            ctx.dense_setup(a, sym=sym)
+            ctx.sync()
+            t0 = time.perf_counter()
+            eig, _, ok, info = ctx.davidson_driver(n, t, m, 300, tol, max_dav, 0.0, mv, pc, g)
+            times[mode].append((time.perf_counter() - t0) * 1e3)
+            out[mode] = (eig[:t].copy(), ok, info["iters"], ctx.dense_info()["device_bytes"])
+    for mode, ts in times.items():
+        eig, ok, iters, nbytes = out[mode]
+        print(f"n = {n} davidson_driver, device callbacks, operator {mode} ({nbytes / 1e6:.1f} MB): median {np.median(ts[1:]):8.2f} ms per solve "
+              f"(min {min(ts[1:]):.2f}), {iters} iterations, ok = {ok}", flush=True)
+    e0, e1 = (v[0] for v in out.values())
+    print(f"  largest relative eigenvalue difference between the two storages: {float(np.abs(e0 / e1 - 1.0).max()):.2e}")
+    ctx.set_option(capi.OPT_CALLBACKS_ON_DEVICE, 0)
     ctx.dense_drop()
 
 
@@ -282,13 +376,18 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--leg":
         kind, n, rounds = sys.argv[2], int(sys.argv[3]), int(sys.argv[4])
         {"product": lambda: leg_product(n, rounds), "solve": lambda: leg_solve(n), "lrsolve": lambda: leg_lr_solve(n),
-         "lrpair": lambda: leg_lr_pair(n, rounds), "tproduct": lambda: leg_tproduct(n, rounds), "nsolve": lambda: leg_nsolve(n)}[kind]()
+         "lrpair": lambda: leg_lr_pair(n, rounds), "tproduct": lambda: leg_tproduct(n, rounds), "nsolve": lambda: leg_nsolve(n),
+         "sproduct": lambda: leg_sproduct(n, rounds), "ssolve": lambda: leg_ssolve(n)}[kind]()
         return 0
-    args = [a for a in sys.argv[1:] if a not in ("--lr", "--transpose")]
-    lr, tr = "--lr" in sys.argv[1:], "--transpose" in sys.argv[1:]
+    args = [a for a in sys.argv[1:] if a not in ("--lr", "--transpose", "--sym")]
+    lr, tr, sy = "--lr" in sys.argv[1:], "--transpose" in sys.argv[1:], "--sym" in sys.argv[1:]
     rounds = int(args[0]) if args else 10
-    record = args[1] if len(args) > 1 else os.path.join(ROOT, "profiles", "dense_operator_t.txt" if tr else "dense_lr_operator.txt" if lr else "dense_operator.txt")
-    if tr:
+    record = args[1] if len(args) > 1 else os.path.join(ROOT, "profiles", "dense_sym_operator.txt" if sy else "dense_operator_t.txt" if tr else "dense_lr_operator.txt" if lr else "dense_operator.txt")
+    if sy:
+        text = [f"tools/dense_operator_bench.py --sym {rounds}: the product on the triangular copy (dla_dense_setup_sym) beside dla_dense_matvec on the full "
+                f"copy of the same symmetric matrix, {rounds * CALLS_PER_ROUND} timed calls each per shape; davidson_driver in device mode on both storages "
+                f"(4 timed solves each)"]
+    elif tr:
         text = [f"tools/dense_operator_bench.py --transpose {rounds}: dla_dense_matvec_t beside dla_dense_matvec on the same stored matrix, "
                 f"{rounds * CALLS_PER_ROUND} timed calls each per shape; nonsym_driver in device mode beside host callbacks (4 timed solves each)"]
     elif lr:
@@ -296,7 +395,7 @@ def main():
                 f"each), and the pair set-up ({rounds} timed calls) beside the triad rate"]
     else:
         text = [f"tools/dense_operator_bench.py {rounds}: dla_dense_matvec beside torch.matmul and the triad rate; {rounds * CALLS_PER_ROUND} timed calls each per shape"]
-    for leg, limit in (T_LEGS if tr else LR_LEGS if lr else LEGS):
+    for leg, limit in (S_LEGS if sy else T_LEGS if tr else LR_LEGS if lr else LEGS):
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg"] + leg.split() + [str(rounds)]
         p = subprocess.Popen(cmd, stdout=subprocess.PIPE, text=True)
         for line in p.stdout:                             # (as it comes: a long leg is not silent)
